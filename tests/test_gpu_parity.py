@@ -425,12 +425,12 @@ def test_second_seed_against_oracle():
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_keys():
-    """bench.py (driver contract): ONE JSON line with the metric keys, the roofline object and, at N=1, the cpu_baseline object."""
+    """bench.py --full (driver contract): ONE JSON line with the metric keys, the roofline object and, at N=1, the cpu_baseline object."""
     import json
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "128", "--cpu-seconds", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "128", "--cpu-seconds", "1", "--full"],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -468,6 +468,38 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     # informational leg at the reference's Ipopt tolerance: fewer iterations, same problems solved, close to the 1e-8 solutions
     rt = d["at_reference_tolerance"]
     assert rt["tol"] == 1e-5 and rt["solved_fraction"] == 1.0 and rt["mean_iters"] < d["config"]["mean_iters"] and rt["joint_rms_vs_tol_1e-8_rad"] < 1e-3
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """bench.py without --full: the headline line only (no side legs), `steps` timed steps, and --dump-outputs writes what the last
+    step returned -- the same as a direct solve of the same seeded batch."""
+    import json
+    import subprocess
+    import sys
+    import torch
+    from boundmpc_amd import BatchedOCPSolver, workload
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "128", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] - 128 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("cpu_baseline", "at_reference_tolerance", "kernel_ms_by_seed", "other_configs"):
+        assert k not in d, k
+    out = {k: np.load(os.path.join(tmp_path, k + ".npy")) for k in ("x", "iters", "status", "kkt")}
+    assert all(v.dtype == np.float64 for v in out.values())
+    P, X, _ = workload.make_batch(128, seed=0)
+    s = BatchedOCPSolver(10, 4, 0.1)
+    o = s.solve_batch(torch.tensor(P, device="cuda"), torch.tensor(X, device="cuda"), want=("iters", "status", "kkt"))
+    torch.cuda.synchronize()
+    assert np.array_equal(out["x"], o["x"].cpu().numpy()) and np.array_equal(out["status"], o["status"].cpu().numpy().astype(np.float64))
+    assert np.array_equal(out["iters"], o["iters"].cpu().numpy().astype(np.float64))
+    s.close()
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -552,7 +584,7 @@ def test_bench_launches_its_own_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--rehearse-one-gpu", "--steps", "2", "--warmup", "1",
-                        "--batch", "128", "--workers", "2", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--batch", "128", "--workers", "2", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
