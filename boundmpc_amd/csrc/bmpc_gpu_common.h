@@ -1,6 +1,9 @@
 // bmpc_gpu_common.h -- what the translation units of libboundmpc_hip.so share: the device math macros the wave program
-// (bmpc_wave.inl) is written in, and the kernel argument records.  bmpc_hip.hip holds the one-wave-per-problem kernels and the C ABI,
-// bmpc_team.hip the team kernels (NW cooperating waves per problem) and their launchers.
+// (bmpc_wave.inl) is written in, its lane and phase macros (one set per BMPC_NW: one wave, or a workgroup of cooperating waves), the phase
+// stamps, the per-problem slicing of a batch kernel's arguments, and the kernel argument records.  The kernel entry texts shared between
+// units are bmpc_multi_batch.inl (the batch kernel of the team and pair units) and bmpc_tick_kernel.inl (the fused tick of the one-wave tick
+// and team units).  bmpc_hip.hip holds the one-wave-per-problem batch kernel and the C ABI, bmpc_team.hip the team kernels (NW cooperating
+// waves per problem), bmpc_pair.hip the pair kernel, bmpc_resto.hip the restoration kernels, bmpc_tick.hip the one-wave fused ticks.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,6 +30,64 @@
 #define BMPC_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define BMPC_NOW() ((long long)wall_clock64())      // constant 100 MHz counter
 #define BMPCS_OPAQUE(x) asm volatile("" : "+v"(x))      // stream functions: keeps a loaded value out of the optimiser's reach (no re-sinking of the load under a branch)
+
+#if BMPC_NW > 1
+// ---- a workgroup of BMPC_NW cooperating waves per problem (bmpc_team.hip, bmpc_pair.hip) ----
+#define BMPC_LANE_ID (threadIdx.x & 63)
+// a phase of ONE wave of the workgroup (lane = 0..63); opaque lane id as in the one-wave build
+#define LANES_BEGIN { int lane_ = threadIdx.x & 63; asm volatile("" : "+v"(lane_)); const int lane = lane_; (void)lane;
+#define LANES_END } __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+// workgroup barrier: s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier with workgroup-scope release / acquire.  The waves of a workgroup sit on
+// one CU and share its L1, so workspace words one wave stored are visible to the others behind it.
+#define TEAM_SYNC() __syncthreads()
+// the same for hand-overs that go through LDS only: LDS operations complete (lgkmcnt(0)), the waves meet, but outstanding vector-memory
+// loads -- a sweep's register prefetch of a later stage -- are NOT waited for (what the vmcnt(0) of __syncthreads() would do: a full
+// round trip to the slab per barrier)
+#define TEAM_SYNC_LDS() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+#define WIDE_BEGIN LANES_BEGIN const int wl = W.wv * 64 + lane; (void)wl;
+#define WIDE_END LANES_END TEAM_SYNC();
+#ifdef BMPC_PAIR_ROLE
+// diagnostic compile only (resource table per wave role, tests/kernel_resources.py --pair-roles): the solo regions of the OTHER role are compiled out
+#define SOLO_BEGIN(w) if (W.wv == (w) && (w) == BMPC_PAIR_ROLE) {
+#else
+#define SOLO_BEGIN(w) if (W.wv == (w)) {
+#endif
+#define SOLO_END }
+// the stream functions run on wave 0 of the workgroup (64 cooperating lanes, as in the one-wave build): their phase boundary is a wavefront fence
+#define BMPCS_SYNC() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+#else
+// ---- one wave per problem (bmpc_hip.hip, bmpc_resto.hip, bmpc_tick.hip); bmpc_wave.inl supplies the one-wave team macros ----
+#define LANES_BEGIN { int lane_ = threadIdx.x; asm volatile("" : "+v"(lane_)); const int lane = lane_; (void)lane;   // opaque per phase: stops LICM from hoisting per-lane address arithmetic out of the solver loops (register pressure)
+// The workgroup is ONE wave: its LDS and vector-memory instructions execute in program order, so a phase boundary needs no
+// s_barrier and no s_waitcnt drain (what __syncthreads() would emit: vmcnt(0) lgkmcnt(0), i.e. a full stall on every
+// outstanding prefetch / store).  A wavefront-scope fence keeps the COMPILER from moving memory operations across it.
+#define LANES_END } __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
+#define BMPCS_SYNC() __syncthreads()
+#endif
+
+// Phase stamps of the wave program (BMPC_PROF), in the batch kernels only: a unit opts in by defining BMPC_STAMPS before this header --
+// 1: the per-phase cycle stamps of lane 0 of a -DBMPC_PROFILE build (diagnostic library libboundmpc_hip_prof.so, never the product);
+// 2: also the textual markers of a -DBMPC_MARKS compile (-S only: static instructions per phase, tests/isa_phase_stats.py).
+#if defined(BMPC_PROFILE) && BMPC_STAMPS >= 1
+#define BMPC_PROF(W, id) { long long now_ = clock64(); if (threadIdx.x == 0) { ((long long *)((W).L + BMPC_NAMESPACE::L_PROF))[id] += now_ - (W).tprev; } (W).tprev = now_; }
+#elif defined(BMPC_MARKS) && BMPC_STAMPS >= 2
+#define BMPC_PROF(W, id) asm volatile("s_nop 0 ; BMPCMARK " #id ::: "memory");
+#endif
+
+// Problem `pr` = problem b of a batch kernel's arguments `a`: its slices of the inputs and of the outputs the caller passed (NULL stays NULL);
+// np, nw, ng: the lengths of a problem's parameter, variable and constraint vectors (computed once, ahead of the kernel's work loop).
+// A macro, expanded in the kernel body: the same lines as a function that takes `a` (by value or by reference) cost the argument loads their
+// no-clobber property, and the register allocation of the whole kernel moves.
+#define BMPC_STRIDES(a) const int np = 141 + 91 * (a).S, nw = (a).N * BMPC_NAMESPACE::NZ, ng = (a).N * BMPC_NAMESPACE::NG
+#define BMPC_PROBLEM(pr, a, b) \
+    BMPC_NAMESPACE::Problem pr; \
+    pr.p = (a).p + (long long)(b) * np; pr.x0 = (a).x0 + (long long)(b) * nw; \
+    pr.x = (a).x ? (a).x + (long long)(b) * nw : nullptr; pr.g = (a).g ? (a).g + (long long)(b) * ng : nullptr; \
+    pr.lam_g = (a).lam_g ? (a).lam_g + (long long)(b) * ng : nullptr; pr.lam_x = (a).lam_x ? (a).lam_x + (long long)(b) * nw : nullptr; \
+    pr.f = (a).f ? (a).f + (b) : nullptr; pr.kkt = (a).kkt ? (a).kkt + (b) : nullptr; \
+    pr.iters = (a).iters ? (a).iters + (b) : nullptr; pr.status = (a).status ? (a).status + (b) : nullptr; \
+    pr.state = (a).state ? (a).state + (long long)(b) * ((a).N * BMPC_NAMESPACE::NI + 2) : nullptr; \
+    pr.resto_from = -1
 
 // kernel arguments of a solve; OPTS = the Opts type of the wave program's namespace (same layout in every instantiation)
 template <class OPTS>

@@ -10,25 +10,9 @@
 
 #include "../../include/boundmpc_hip.h"
 
+#define BMPC_STAMPS 2      // phase stamps: -DBMPC_PROFILE cycle stamps and -DBMPC_MARKS markers (bmpc_gpu_common.h)
 #include "bmpc_gpu_common.h"
-#define LANES_BEGIN { int lane_ = threadIdx.x; asm volatile("" : "+v"(lane_)); const int lane = lane_; (void)lane;   // opaque per phase: stops LICM from hoisting per-lane address arithmetic out of the solver loops (register pressure)
-// The workgroup is ONE wave: its LDS and vector-memory instructions execute in program order, so a phase boundary needs no
-// s_barrier and no s_waitcnt drain (what __syncthreads() would emit: vmcnt(0) lgkmcnt(0), i.e. a full stall on every
-// outstanding prefetch / store).  A wavefront-scope fence keeps the COMPILER from moving memory operations across it.
-#define LANES_END } __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
-
-#ifdef BMPC_MARKS
-// diagnostic compile only (-S): textual markers in the ISA at the phase stamps, to count static instructions per phase
-#define BMPC_PROF(W, id) asm volatile("s_nop 0 ; BMPCMARK " #id ::: "memory");
-#endif
-#ifdef BMPC_PROFILE
-// diagnostic build only (libboundmpc_hip_prof.so): per-phase cycle stamps of lane 0, never in the product library
-#undef BMPC_PROF
-#define BMPC_PROF(W, id) { long long now_ = clock64(); if (threadIdx.x == 0) { ((long long *)((W).L + bmpc::L_PROF))[id] += now_ - (W).tprev; } (W).tprev = now_; }
-#endif
-
 #include "bmpc_wave.inl"
-#define BMPCS_SYNC() __syncthreads()
 #include "bmpc_stream.inl"
 
 typedef KArgsT<bmpc::Opts> KArgs;
@@ -44,7 +28,7 @@ __global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_solve_kernel(KArgs
     __shared__ double lds[bmpc::L_SIZE];
     bmpc::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = bmpc::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride); W.wv = 0;
     W.deadline = 0; W.it_base = 0;
-    const int np = 141 + 91 * a.S, nw = a.N * bmpc::NZ, ng = a.N * bmpc::NG;
+    BMPC_STRIDES(a);
 #ifdef BMPC_PROFILE
     if (threadIdx.x < 32) ((long long *)(lds + bmpc::L_PROF))[threadIdx.x] = 0;
     __syncthreads();
@@ -56,14 +40,7 @@ __global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_solve_kernel(KArgs
         b = __builtin_amdgcn_readfirstlane(b);
         if ((unsigned)b >= (unsigned)a.B) break;      // every wave reaches this exit: the queue is finite (unsigned: a queue word nobody reset ends the wave, it never becomes an address)
         if (a.order) b = __builtin_amdgcn_readfirstlane(a.order[b]);      // longest-expected-first order of a batch larger than the resident waves (queue_order_kernel)
-        bmpc::Problem pr;
-        pr.p = a.p + (long long)b * np; pr.x0 = a.x0 + (long long)b * nw;
-        pr.x = a.x ? a.x + (long long)b * nw : nullptr; pr.g = a.g ? a.g + (long long)b * ng : nullptr;
-        pr.lam_g = a.lam_g ? a.lam_g + (long long)b * ng : nullptr; pr.lam_x = a.lam_x ? a.lam_x + (long long)b * nw : nullptr;
-        pr.f = a.f ? a.f + b : nullptr; pr.kkt = a.kkt ? a.kkt + b : nullptr;
-        pr.iters = a.iters ? a.iters + b : nullptr; pr.status = a.status ? a.status + b : nullptr;
-        pr.state = a.state ? a.state + (long long)b * (a.N * bmpc::NI + 2) : nullptr;
-        pr.resto_from = -1;
+        BMPC_PROBLEM(pr, a, b);
         const long long t0_ = a.latency_us ? (long long)wall_clock64() : 0;
         bmpc::wave_solve_retry<ZLDS>(W, pr);      // (+ the second attempt of a long-horizon solve that ends with status 2)
         __syncthreads();
@@ -95,16 +72,17 @@ __global__ void __launch_bounds__(256) queue_order_kernel(int B, const double *k
     if (i < B) order[r] = i;
 }
 
+// (members without an initialiser start at zero / NULL: bmpc_create value-initialises the handle)
 struct bmpc_handle {
     int N, S; double h; bmpc_options o;
     int dev;                 // device the handle was created on: workspace, work queue, events and streams of the handle live there
-    int refs; bool closed;   // one reference for the creator, one per captured graph (their kernels carry the workspace addresses);
+    int refs = 1; bool closed;   // one reference for the creator, one per captured graph (their kernels carry the workspace addresses);
                              // bmpc_destroy closes the handle, the memory goes when the last reference does
     // launches of one handle share its workspace and work queue, so they are ordered against each other whatever streams the
     // caller uses: every launch records order_ev, a launch on another stream waits for it first
     hipEvent_t order_ev, bridge_ev; bool order_valid; hipStream_t order_stream;
     double rt_row_cap;       // real-time mode: a position tube row (l^2 - w^2, any stage) above this vetoes the iterate (bmpc_stream_set_rt_position_row_cap); 0 = off
-    double rt_viol_tol;      // acceptance threshold of stream_post in real-time mode (flag bit 1); default = the reference's 1e-4
+    double rt_viol_tol = 1e-4;      // acceptance threshold of stream_post in real-time mode (flag bit 1); default = the reference's 1e-4
     double rt_budget_us;     // time budget of a fused tick (bmpc_stream_set_time_budget); 0 = none
     hipStream_t own_stream;  // graph replays requested on the legacy null stream run here, bracketed by events (bmpc_graph_launch)
     int grid; long long scr_stride; double *scratch; int scr_waves; int graphs_alive; int *counter; unsigned long long *prof;
@@ -114,8 +92,8 @@ struct bmpc_handle {
     int hold_mu;            // bmpc_set_barrier_hold: 1 = a solve holds the barrier level it starts on
     int retry_cap;          // bmpc_set_second_attempt: iterations of the second attempt of a stateless solve that ends with status 2 (0 = none; default 100 for N > 11)
     double level_c, level_lo, level_hi;      // bmpc_stream_set_level_rule: stream_pack sets the level of a stream's next tick (level_hi <= 0: off)
-    int start_rollout;      // 1 (default): a stateless solve whose x0 is far off its own dynamics starts from the rollout of x0's jerks (bmpc_set_start_rollout)
-    int resto_on, resto_short, resto_cap;      // restoration phase (bmpc_set_restoration): mode 0 off / 1 full (default N <= 11) / 2 after a numerical breakdown only (default N > 11); jam = resto_short consecutive short steps; iterations per phase
+    int start_rollout = 1;  // 1 (default): a stateless solve whose x0 is far off its own dynamics starts from the rollout of x0's jerks (bmpc_set_start_rollout)
+    int resto_on, resto_short = 6, resto_cap = 40;      // restoration phase (bmpc_set_restoration): mode 0 off / 1 full (default N <= 11) / 2 after a numerical breakdown only (default N > 11); jam = resto_short consecutive short steps; iterations per phase
     int queue_order;         // bmpc_set_queue_order: 1 = a batch beyond the resident waves is solved in the order of decreasing f(x0) (default for N > 11), 0 = natural order
     double *qkey; int *qorder; int q_cap;      // [q_cap] keys and order of the last such batch
     int team_mode;           // bmpc_set_team_waves: 0 automatic (teams when the batch fits into the resident teams), 1 never, BMPC_TEAM_NW whenever possible
@@ -190,13 +168,9 @@ extern "C" int bmpc_create(int N, int S, double dt, const bmpc_options *opts, bm
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return BMPC_ERR_NOGPU;
     bmpc_handle *h = new (std::nothrow) bmpc_handle();
     if (!h) return BMPC_ERR_ARG;
-    h->start_rollout = 1; h->hold_mu = 0; h->retry_cap = N > 11 ? 100 : 0; h->level_c = 0.0; h->level_lo = 0.0; h->level_hi = 0.0;
-    h->resto_on = N <= 11 ? 1 : 2; h->resto_short = 6; h->resto_cap = 40;      // restoration phase: full for short horizons, after a numerical breakdown only for long ones (bmpc_set_restoration)
-    h->N = N; h->S = S; h->h = dt; h->timing = 0; h->ev = nullptr; h->nev = 0; h->n_timed = 0; h->latency_us = nullptr;
-    h->scratch = nullptr; h->scr_waves = 0; h->graphs_alive = 0; h->counter = nullptr; h->aux_int = nullptr; h->aux_cap = 0; h->prof = nullptr; h->stage_d = nullptr; h->stage_h = nullptr; h->stage_cap = 0;
-    h->team_grid = 0; h->pair_grid = 0; h->team_mode = 0;
-    h->queue_order = N > 11 ? 1 : 0; h->qkey = nullptr; h->qorder = nullptr; h->q_cap = 0;
-    h->rt_viol_tol = 1e-4; h->rt_row_cap = 0.0; h->rt_budget_us = 0.0; h->dev = 0; h->refs = 1; h->closed = false; h->order_ev = nullptr; h->bridge_ev = nullptr; h->order_valid = false; h->order_stream = nullptr; h->own_stream = nullptr;
+    h->N = N; h->S = S; h->h = dt;
+    h->retry_cap = N > 11 ? 100 : 0; h->queue_order = N > 11 ? 1 : 0;
+    h->resto_on = N <= 11 ? 1 : 2;      // restoration phase: full for short horizons, after a numerical breakdown only for long ones (bmpc_set_restoration)
     if (opts) h->o = *opts; else bmpc_default_options_for(N, &h->o);
     int dev = 0, per_cu = 0; hipDeviceProp_t prop;
     bool ok = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess;
@@ -399,20 +373,25 @@ static hipError_t reset_queue(bmpc_handle *h, hipStream_t st) {
     hipLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, st, h->counter);
     return hipGetLastError();
 }
+// kernel arguments from the handle's settings; the caller adds its buffers and what its launch shape changes
+static KArgs handle_kargs(const bmpc_handle *h, int B, int max_iter) {
+    KArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h;
+    a.o.tol = h->o.tol; a.o.max_iter = max_iter > 0 ? max_iter : h->o.max_iter; a.o.mu_init = h->o.mu_init; a.o.mu_min_fac = h->o.mu_min_fac;
+    a.o.slack_push = h->o.slack_push; a.o.exact_hessian = h->o.exact_hessian; a.o.verbose = 0; a.o.mu_warm = h->o.mu_warm; a.o.stall_window = h->o.stall_window; a.o.bound_margin = h->o.bound_margin;
+    a.o.restoration = h->resto_on; a.o.resto_short = h->resto_short; a.o.resto_cap = h->resto_cap; a.o.start_rollout = h->start_rollout; a.o.hold_mu = h->hold_mu; a.o.retry_cap = h->retry_cap;
+    a.latency_us = h->latency_us; a.scratch = h->scratch; a.scr_stride = h->scr_stride; a.counter = h->counter; a.prof = h->prof;
+    return a;
+}
 // fills the kernel arguments and enqueues {reset of the work-queue counter, solver kernel} on `st`
 static int enqueue_solve(bmpc_handle *h, int B, const double *p, const double *x0, double *state, int max_iter, double *x, double *g, double *lam_g,
                          double *lam_x, double *f, int *iters, int *status, double *kkt, hipStream_t st, bool timed, bool capturing = false) {
     if (h->closed) return BMPC_ERR_ARG;
     if (!capturing) { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
-    KArgs a; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h;
-    a.o.tol = h->o.tol; a.o.max_iter = max_iter > 0 ? max_iter : h->o.max_iter; a.o.mu_init = h->o.mu_init; a.o.mu_min_fac = h->o.mu_min_fac;
-    a.o.slack_push = h->o.slack_push; a.o.exact_hessian = h->o.exact_hessian; a.o.verbose = 0; a.o.mu_warm = h->o.mu_warm; a.o.stall_window = h->o.stall_window; a.o.bound_margin = h->o.bound_margin;
-    a.o.restoration = h->resto_on; a.o.resto_short = h->resto_short; a.o.resto_cap = h->resto_cap; a.o.start_rollout = h->start_rollout; a.o.hold_mu = h->hold_mu; a.o.retry_cap = state ? 0 : h->retry_cap;
-    a.p = p; a.x0 = x0; a.x = x; a.g = g; a.lam_g = lam_g; a.lam_x = lam_x; a.f = f; a.kkt = kkt; a.iters = iters; a.status = status;
-    a.state = state; a.latency_us = h->latency_us; a.budget_ticks = 0;
+    KArgs a = handle_kargs(h, B, max_iter);
+    if (state) a.o.retry_cap = 0;
+    a.p = p; a.x0 = x0; a.x = x; a.g = g; a.lam_g = lam_g; a.lam_x = lam_x; a.f = f; a.kkt = kkt; a.iters = iters; a.status = status; a.state = state;
     const int grid = launch_grid(h, B);
     if (grid > h->scr_waves) return BMPC_ERR_ARG;      // callers reserve the workspace first (never inside a stream capture)
-    a.scratch = h->scratch; a.scr_stride = h->scr_stride; a.counter = h->counter; a.prof = h->prof;
     // restoration phase: the batch kernels hand a jammed problem over through status[] / iters[] (handle-owned when the caller wants neither)
     const bool resto = h->resto_on != 0;
     a.counter2 = h->counter + 1; a.rcount = resto ? h->counter + 2 : nullptr;
@@ -425,7 +404,6 @@ static int enqueue_solve(bmpc_handle *h, int B, const double *p, const double *x
     const bool zlds = h->N <= 11 && h->S <= bmpc::SMAX_ZLDS;
     hipEvent_t *pair = nullptr;
     if (timed) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
-    a.order = nullptr;
     if (h->queue_order && !state && solve_waves(h, B) == 1 && B > h->grid && B <= h->q_cap && B <= BMPC_QUEUE_ORDER_MAX) {
         // Longest-expected-first: an evaluation pass (the same kernel with max_iter = 0: f at x0, nothing else written), the ranking, then the solve
         // hands the problems out in that order.  Inside the timed region: it is part of what the batch costs.  A result does not depend on which
@@ -477,19 +455,17 @@ extern "C" int bmpc_solve_batch_warm(bmpc_handle *h, int B, const double *p, con
 // ---- hipGraph-captured step: {queue reset, solver kernel, restoration kernel} of one (warm-started) solve, instantiated once, replayed per tick ----
 struct bmpc_graph { bmpc_handle *h; hipGraph_t graph; hipGraphExec_t exec; };
 
-extern "C" int bmpc_graph_create(bmpc_handle *h, int B, const double *p, const double *x0, double *state, int max_iter, double *x, double *g,
-                                 double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt, bmpc_graph **out) {
-    if (!h || !out || B < 1 || max_iter < 0 || !p || !x0 || !x) return BMPC_ERR_ARG;
-    { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
+// captures what enqueue(stream) puts on a capture stream of its own and instantiates it; the graph holds a reference to the handle
+template <class ENQUEUE>
+static int capture_graph(bmpc_handle *h, bmpc_graph **out, ENQUEUE enqueue) {
     hipStream_t cs;
     HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    bmpc_graph *gr = new (std::nothrow) bmpc_graph();
+    bmpc_graph *gr = new (std::nothrow) bmpc_graph{h, nullptr, nullptr};
     if (!gr) { hipStreamDestroy(cs); return BMPC_ERR_ARG; }
-    gr->h = h; gr->graph = nullptr; gr->exec = nullptr;
     int rc = BMPC_OK;
     if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess) rc = BMPC_ERR_HIP;
     if (rc == BMPC_OK) {
-        rc = enqueue_solve(h, B, p, x0, state, max_iter, x, g, lam_g, lam_x, f, iters, status, kkt, cs, false, true);
+        rc = enqueue(cs);
         hipError_t e = hipStreamEndCapture(cs, &gr->graph);       // always end the capture, also after an enqueue error
         if (rc == BMPC_OK && e != hipSuccess) rc = BMPC_ERR_HIP;
     }
@@ -498,6 +474,13 @@ extern "C" int bmpc_graph_create(bmpc_handle *h, int B, const double *p, const d
     if (rc != BMPC_OK) { if (gr->exec) hipGraphExecDestroy(gr->exec); if (gr->graph) hipGraphDestroy(gr->graph); delete gr; return rc; }
     *out = gr; h->graphs_alive++; h->refs++;
     return BMPC_OK;
+}
+
+extern "C" int bmpc_graph_create(bmpc_handle *h, int B, const double *p, const double *x0, double *state, int max_iter, double *x, double *g,
+                                 double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt, bmpc_graph **out) {
+    if (!h || !out || B < 1 || max_iter < 0 || !p || !x0 || !x) return BMPC_ERR_ARG;
+    { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
+    return capture_graph(h, out, [&](hipStream_t cs) { return enqueue_solve(h, B, p, x0, state, max_iter, x, g, lam_g, lam_x, f, iters, status, kkt, cs, false, true); });
 }
 extern "C" int bmpc_graph_launch(bmpc_graph *gr, void *hip_stream) {
     if (!gr || !gr->h || gr->h->closed) return BMPC_ERR_ARG;
@@ -630,14 +613,10 @@ static int enqueue_tick(bmpc_handle *h, int B, const double *path, int path_entr
                         int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags, hipStream_t st, bool capturing) {
     if (h->closed) return BMPC_ERR_ARG;
     if (!capturing) { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
-    KArgs a; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h;
-    a.o.tol = h->o.tol; a.o.max_iter = max_iter > 0 ? max_iter : h->o.max_iter; a.o.mu_init = h->o.mu_init; a.o.mu_min_fac = h->o.mu_min_fac;
-    a.o.slack_push = h->o.slack_push; a.o.exact_hessian = h->o.exact_hessian; a.o.verbose = 0; a.o.mu_warm = h->o.mu_warm; a.o.stall_window = h->o.stall_window; a.o.bound_margin = h->o.bound_margin;
-    a.o.restoration = h->resto_on; a.o.resto_short = h->resto_short; a.o.resto_cap = h->resto_cap; a.o.start_rollout = h->start_rollout; a.o.hold_mu = h->hold_mu; a.o.retry_cap = 0;
-    a.p = p; a.x0 = x0; a.x = x; a.g = g; a.lam_g = nullptr; a.lam_x = nullptr; a.f = nullptr; a.kkt = kkt; a.iters = iters; a.status = status;
-    a.state = dual_state; a.latency_us = h->latency_us; a.budget_ticks = (long long)(h->rt_budget_us * 100.0);
+    KArgs a = handle_kargs(h, B, max_iter);
+    a.o.retry_cap = 0; a.budget_ticks = (long long)(h->rt_budget_us * 100.0);
+    a.p = p; a.x0 = x0; a.x = x; a.g = g; a.kkt = kkt; a.iters = iters; a.status = status; a.state = dual_state;
     if (B > h->scr_waves) return BMPC_ERR_ARG;
-    a.scratch = h->scratch; a.scr_stride = h->scr_stride; a.counter = h->counter; a.prof = h->prof;
     SArgs s; s.path = path; s.path_stride = path_entries * bmpcs::PT_LEN; s.ss = sstate; s.rb = robot; s.traj = traj; s.flags = flags; s.rt_tol = h->rt_viol_tol; s.rt_row_cap = h->rt_row_cap; s.lvl_c = h->level_c; s.lvl_lo = h->level_lo; s.lvl_hi = h->level_hi;
     const bool timed = !capturing && h->timing != 0;
     hipEvent_t *pair = nullptr;
@@ -645,7 +624,7 @@ static int enqueue_tick(bmpc_handle *h, int B, const double *path, int path_entr
     // The post-processing of a fused tick needs the final solution, so here the restoration phase runs INSIDE the kernel (instantiations with
     // RESTO); a time-budgeted real-time tick never gets as far as a jam (six short steps) and runs the lean instantiation with the phase off.
     const bool resto = h->resto_on != 0 && a.budget_ticks == 0;
-    a.o.restoration = resto ? h->resto_on : 0; a.counter2 = nullptr; a.rcount = nullptr; a.order = nullptr;      // (the handle's MODE, not a flag: 2 = after a numerical breakdown only, as every other launch shape runs it)
+    a.o.restoration = resto ? h->resto_on : 0;      // (the handle's MODE, not a flag: 2 = after a numerical breakdown only, as every other launch shape runs it)
     if (use_team(h, B)) HIPCHK(bmpc_team_launch_tick(BMPC_TEAM_NW, resto, &a, &s, B, st));
     else HIPCHK(bmpc_tick_launch(h->N <= 11 && h->S <= bmpc::SMAX_ZLDS, resto, &a, &s, B, st));      // (long horizons, 5 or 6 path segments: iterate in the workspace)
     if (timed) { HIPCHK(hipEventRecord(pair[1], st)); h->n_timed++; }
@@ -653,6 +632,16 @@ static int enqueue_tick(bmpc_handle *h, int B, const double *path, int path_entr
     return BMPC_OK;
 }
 static bool tick_fusable(const bmpc_handle *h, int B) { return B <= (use_team(h, B) ? h->team_grid : h->grid); }      // stream b = workgroup b: every stream needs a resident workgroup
+// enqueues one closed-loop tick on `st`: fused into one launch when every stream has a resident workgroup, else {pack, solve, post}
+static int enqueue_stream_tick(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0, double *dual_state,
+                               int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags, hipStream_t st, bool capturing) {
+    if (tick_fusable(h, B)) return enqueue_tick(h, B, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, st, capturing);
+    // real-time mode: the warm start continues from the iterate of the previous tick on every launch shape (fused or not)
+    int rc = bmpc_stream_pack_rt(h, B, path, path_entries, sstate, robot, p, x0, dual_state, (flags & 2) ? x : nullptr, st);
+    if (rc == BMPC_OK) rc = enqueue_solve(h, B, p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt, st, !capturing && h->timing != 0, capturing);
+    if (rc == BMPC_OK) rc = bmpc_stream_post(h, B, path, path_entries, sstate, robot, x, g, status, traj, flags, st);
+    return rc;
+}
 extern "C" int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
                                 double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
                                 void *hip_stream) {
@@ -660,13 +649,7 @@ extern "C" int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int p
     if (h->N > bmpcs::STREAM_NMAX) return BMPC_ERR_ARG;      // (the solver's own limit)
     if (B == 0) return BMPC_OK;
     { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
-    hipStream_t st = (hipStream_t)hip_stream;
-    if (tick_fusable(h, B)) return enqueue_tick(h, B, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, st, false);
-    // real-time mode: the warm start continues from the iterate of the previous tick on every launch shape (fused or not)
-    int rc = bmpc_stream_pack_rt(h, B, path, path_entries, sstate, robot, p, x0, dual_state, (flags & 2) ? x : nullptr, st);
-    if (rc == BMPC_OK) rc = enqueue_solve(h, B, p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt, st, h->timing != 0);
-    if (rc == BMPC_OK) rc = bmpc_stream_post(h, B, path, path_entries, sstate, robot, x, g, status, traj, flags, st);
-    return rc;
+    return enqueue_stream_tick(h, B, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, (hipStream_t)hip_stream, false);
 }
 
 extern "C" int bmpc_stream_set_rt_feasibility_tol(bmpc_handle *h, double tol) {
@@ -721,34 +704,9 @@ extern "C" int bmpc_stream_graph_create(bmpc_handle *h, int B, const double *pat
     if (!h || !out || B < 1 || max_iter < 0 || path_entries < h->S + 1 || !path || !sstate || !robot || !p || !x0 || !x || !g || !status || !traj) return BMPC_ERR_ARG;
     if (h->N > bmpcs::STREAM_NMAX) return BMPC_ERR_ARG;      // (the solver's own limit)
     { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
-    hipStream_t cs;
-    HIPCHK(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-    bmpc_graph *gr = new (std::nothrow) bmpc_graph();
-    if (!gr) { hipStreamDestroy(cs); return BMPC_ERR_ARG; }
-    gr->h = h; gr->graph = nullptr; gr->exec = nullptr;
-    int rc = BMPC_OK;
-    if (hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal) != hipSuccess) rc = BMPC_ERR_HIP;
-    if (rc == BMPC_OK) {
-        if (tick_fusable(h, B)) rc = enqueue_tick(h, B, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, cs, true);
-        else {
-            rc = bmpc_stream_pack_rt(h, B, path, path_entries, sstate, robot, p, x0, dual_state, (flags & 2) ? x : nullptr, cs);
-            if (rc == BMPC_OK) rc = enqueue_solve(h, B, p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt, cs, false, true);
-            if (rc == BMPC_OK) rc = bmpc_stream_post(h, B, path, path_entries, sstate, robot, x, g, status, traj, flags, cs);
-        }
-        hipError_t e = hipStreamEndCapture(cs, &gr->graph);
-        if (rc == BMPC_OK && e != hipSuccess) rc = BMPC_ERR_HIP;
-    }
-    if (rc == BMPC_OK && hipGraphInstantiate(&gr->exec, gr->graph, nullptr, nullptr, 0) != hipSuccess) rc = BMPC_ERR_HIP;
-    hipStreamDestroy(cs);
-    if (rc != BMPC_OK) { if (gr->exec) hipGraphExecDestroy(gr->exec); if (gr->graph) hipGraphDestroy(gr->graph); delete gr; return rc; }
-    *out = gr; h->graphs_alive++; h->refs++;
-    return BMPC_OK;
+    return capture_graph(h, out, [&](hipStream_t cs) { return enqueue_stream_tick(h, B, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, cs, true); });
 }
 
-#ifdef BMPC_MARKS
-// diagnostic compile only (-S): textual markers in the ISA at the phase stamps, to count static instructions per phase
-#define BMPC_PROF(W, id) asm volatile("s_nop 0 ; BMPCMARK " #id ::: "memory");
-#endif
 #ifdef BMPC_PROFILE
 // diagnostic build only: accumulated lane-0 cycle counts per phase (16 slots), then reset
 extern "C" int bmpc_get_profile(bmpc_handle *h, unsigned long long *out) {

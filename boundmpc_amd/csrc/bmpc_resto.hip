@@ -15,8 +15,6 @@
 #include <cstring>
 
 #include "bmpc_gpu_common.h"
-#define LANES_BEGIN { int lane_ = threadIdx.x; asm volatile("" : "+v"(lane_)); const int lane = lane_; (void)lane;
-#define LANES_END } __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier();
 #include "bmpc_wave.inl"
 
 typedef KArgsT<bmpc::Opts> KArgs;
@@ -32,7 +30,7 @@ __global__ void __launch_bounds__(64, 1) bmpc_resto_kernel(KArgs a) {
     if (!fresh && *(volatile int *)a.rcount == 0) return;      // nothing jammed in this batch (wave-uniform: one word)
     bmpc::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = bmpc::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride); W.wv = 0;
     W.deadline = 0; W.tprev = 0; W.it_base = 0;
-    const int np = 141 + 91 * a.S, nw = a.N * bmpc::NZ, ng = a.N * bmpc::NG;
+    BMPC_STRIDES(a);
     for (;;) {
         int b = 0, st = 0;
         if (threadIdx.x == 0) { b = atomicAdd(fresh ? a.counter : a.counter2, 1); st = (!fresh && (unsigned)b < (unsigned)a.B) ? a.status[b] : 0; }
@@ -40,6 +38,8 @@ __global__ void __launch_bounds__(64, 1) bmpc_resto_kernel(KArgs a) {
         if ((unsigned)b >= (unsigned)a.B) break;             // every wave reaches this exit: the queue is finite
         if (!fresh && st != 4) continue;
         if (fresh && a.order) b = __builtin_amdgcn_readfirstlane(a.order[b]);      // longest-expected-first order (queue_order_kernel)
+        // (its own slicing, not BMPC_PROBLEM: x, iters and status are always there, and a continuation starts from x; the shared lines with
+        // these overrides compile to another kernel)
         bmpc::Problem pr;
         pr.p = a.p + (long long)b * np; pr.x0 = (fresh ? a.x0 : a.x) + (long long)b * nw;      // continuation: the iterate the batch kernel left (read before x is rewritten)
         pr.x = a.x + (long long)b * nw; pr.g = a.g ? a.g + (long long)b * ng : nullptr;

@@ -19,22 +19,7 @@
 #define BMPC_NW 4
 #endif
 #define BMPC_NAMESPACE bmpct
-#define BMPC_EMU 1
-#define BMPC_HD
-#define BMPC_D
-#define BMPC_SINCOS(x, s, c) (*(s) = std::sin(x), *(c) = std::cos(x))
-#define BMPC_EXP(x) std::exp(x)
-#define BMPC_LOG(x) std::log(x)
-#define BMPC_SQRT(x) std::sqrt(x)
-#define BMPC_SIN(x) std::sin(x)
-#define BMPC_COS(x) std::cos(x)
-#define BMPC_ATAN2(y, x) std::atan2(y, x)
-#define BMPC_RSQRT(x) (1.0 / std::sqrt(x))
-#define BMPC_FABS(x) std::fabs(x)
-#define BMPC_FMAX(a, b) std::fmax(a, b)
-#define BMPC_FMIN(a, b) std::fmin(a, b)
-#define BMPC_POW15(x) ((x) * std::sqrt(x))
-#define BMPC_POW(x, y) std::pow(x, y)
+#include "bmpc_emu_host.h"
 #define LANES_BEGIN for (int li_ = 0; li_ < 64; ++li_) { const int lane = W.order[li_]; (void)lane;
 #define LANES_END }
 #define LIDX lane

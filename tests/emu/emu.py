@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libbmpc_emu.so")
 _SRC = [os.path.join(_HERE, "bmpc_emu.cpp"), os.path.join(_HERE, "..", "..", "boundmpc_amd", "csrc", "bmpc_wave.inl"),
-        os.path.join(_HERE, "..", "..", "boundmpc_amd", "csrc", "bmpc_stream.inl")]
+        os.path.join(_HERE, "..", "..", "boundmpc_amd", "csrc", "bmpc_stream.inl"), os.path.join(_HERE, "bmpc_emu_host.h")]
 
 
 class Opts(ctypes.Structure):
@@ -71,7 +71,7 @@ def team_lib(nw=4):
     if nw not in _TLIBS:
         pair = nw == "pair"
         path = os.path.join(_HERE, "libbmpc_emu_pair.so" if pair else f"libbmpc_emu_team{nw}.so")
-        src = [os.path.join(_HERE, "bmpc_emu_team.cpp"), _SRC[1]]
+        src = [os.path.join(_HERE, "bmpc_emu_team.cpp"), _SRC[1], _SRC[3]]
         if not os.path.exists(path) or any(os.path.getmtime(path) < os.path.getmtime(s) for s in src):
             subprocess.check_call(["g++", "-O2", "-fopenmp", "-fPIC", "-shared", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-enum-compare"]
                                   + (["-DBMPC_NW=2", "-DBMPC_WSG"] if pair else [f"-DBMPC_NW={nw}"]) + ["-o", path, src[0]])

@@ -162,7 +162,8 @@ def test_library_carries_the_hash_of_its_sources(tmp_path, monkeypatch):
     assert lib.bmpc_build_hash().decode() == want and lib.bmpc_options_size() == ctypes.sizeof(_lib.Options)
     # every translation unit and every header the kernels include is part of the hash
     names = {os.path.basename(p) for p in build.SOURCES}
-    assert {"bmpc_hip.hip", "bmpc_team.hip", "bmpc_resto.hip", "bmpc_tick.hip", "bmpc_wave.inl", "bmpc_stream.inl", "bmpc_gpu_common.h", "boundmpc_hip.h"} <= names
+    assert {"bmpc_hip.hip", "bmpc_team.hip", "bmpc_resto.hip", "bmpc_tick.hip", "bmpc_wave.inl", "bmpc_stream.inl", "bmpc_gpu_common.h", "boundmpc_hip.h",
+            "bmpc_pair.hip", "bmpc_multi_batch.inl", "bmpc_tick_kernel.inl"} <= names
     # a library from other sources is refused at load time
     monkeypatch.setattr(build, "source_hash", lambda: "0" * 16)
     monkeypatch.setattr(_lib, "_lib", None)
