@@ -127,6 +127,9 @@ class BoundMPC:
         self.prev_solution = None
         self.prev_infeasible_solution = None
         self.lam_g0 = 0; self.lam_x0 = 0
+        # opt-in primal-dual warm start: the solver call gets the multipliers of the last accepted solve, as the reference's commented-out
+        # lam_g0 / lam_x0 arguments would (BoundMPC.py:451-452).  Default off: the reference's call, without multipliers.
+        self.warm_start_duals = bool(getattr(params, "warm_start_duals", False))
         if solver is None:
             # the product path: HIP batched solver behind the nlpsol call convention; raises without a GPU
             from .solver import BatchedOCPSolver, NlpSolverShim
@@ -269,11 +272,15 @@ class BoundMPC:
                    v1=v_1, v2=v_2, v3=v_3, jac_l=jac_l, jac_r=jac_r, a=(a4, a3, a2, a1, a0))
         return w0.tolist(), params, aux
 
+    def _duals(self):
+        """Keyword arguments of the solver call for the multipliers: none by default, lam_g0 / lam_x0 with params.warm_start_duals."""
+        return dict(lam_g0=self.lam_g0, lam_x0=self.lam_x0) if self.warm_start_duals else {}
+
     def solve(self, q0, dq0, ddq0, p0, v0, x_phi_d, jerk_current):
         """Pack + one solver call, no post-processing and no state advance of the path parameter
         (the warm-start bookkeeping of pack() still applies).  Returns (sol, stats)."""
         w0, params, _ = self.pack(q0, dq0, ddq0, p0, v0, x_phi_d, jerk_current)
-        sol = self.solver(x0=w0, lbx=self.lbu, ubx=self.ubu, lbg=self.lbg, ubg=self.ubg, p=params)
+        sol = self.solver(x0=w0, lbx=self.lbu, ubx=self.ubu, lbg=self.lbg, ubg=self.ubg, p=params, **self._duals())
         return sol, self.solver.stats()
 
     def step(self, q0, dq0, ddq0, p0, v0, x_phi_d, jerk_current, x_des=None):
@@ -285,7 +292,7 @@ class BoundMPC:
         After N failures in a row there is nothing left to replay and five Nones go back to the caller."""
         w0, params, aux = self.pack(q0, dq0, ddq0, p0, v0, x_phi_d, jerk_current)
         t0 = time.perf_counter()
-        sol = self.solver(x0=w0, lbx=self.lbu, ubx=self.ubu, lbg=self.lbg, ubg=self.ubg, p=params)
+        sol = self.solver(x0=w0, lbx=self.lbu, ubx=self.ubu, lbg=self.lbg, ubg=self.ubg, p=params, **self._duals())
         candidate = np.asarray(sol['x'], dtype=float).ravel()
         time_elapsed = time.perf_counter() - t0
         stats = self.solver.stats()

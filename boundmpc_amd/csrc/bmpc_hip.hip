@@ -14,6 +14,7 @@
 #include "bmpc_gpu_common.h"
 #include "bmpc_wave.inl"
 #include "bmpc_stream.inl"
+#include "bmpc_dual.inl"
 
 typedef KArgsT<bmpc::Opts> KArgs;
 #ifndef BMPC_TEAM_NW
@@ -72,6 +73,33 @@ __global__ void __launch_bounds__(256) queue_order_kernel(int B, const double *k
     if (i < B) order[r] = i;
 }
 
+// Primal-dual warm start (bmpc_dual.inl): the dual state of a warm solve from multipliers in CasADi's convention.  One wave per problem over the
+// handle's resident waves and workspace slabs; every problem costs one evaluation, so the waves stride over the batch (no work queue).
+struct DualArgs {
+    int N, S, B; double h; bmpc::Opts o;
+    const double *p, *x0, *lam_g, *lam_x; double *state; double mu;
+    double *scratch; long long scr_stride;
+};
+template <bool ZLDS>
+__global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_dual_kernel(DualArgs a) {
+    __shared__ double lds[bmpc::L_SIZE];
+    bmpc::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = bmpc::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride); W.wv = 0;
+    W.deadline = 0; W.it_base = 0;
+#ifdef BMPC_PROFILE
+    if (threadIdx.x < 32) ((long long *)(lds + bmpc::L_PROF))[threadIdx.x] = 0;
+    __syncthreads();
+    W.tprev = clock64();
+#endif
+    const int np = 141 + 91 * a.S, nw = a.N * bmpc::NZ, ng = a.N * bmpc::NG, sl = a.N * bmpc::NI + 2;
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        bmpc::DualIn d;
+        d.p = a.p + (long long)b * np; d.x0 = a.x0 + (long long)b * nw; d.state = a.state + (long long)b * sl; d.mu = a.mu;
+        d.lam_g = a.lam_g ? a.lam_g + (long long)b * ng : nullptr; d.lam_x = a.lam_x ? a.lam_x + (long long)b * nw : nullptr;
+        bmpc::wave_state_from_multipliers<ZLDS>(W, d);
+        __syncthreads();
+    }
+}
+
 // (members without an initialiser start at zero / NULL: bmpc_create value-initialises the handle)
 struct bmpc_handle {
     int N, S; double h; bmpc_options o;
@@ -100,6 +128,7 @@ struct bmpc_handle {
     int timing; hipEvent_t *ev; int nev; long long n_timed;   // timing = number of launches whose {start, stop} event pairs are kept (ring)
     double *latency_us;
     double *stage_d, *stage_h; int stage_cap;   // device and pinned host staging of the host-buffer path (bmpc_solve_batch_host)
+    double *stage_state; int stage_state_cap;   // device dual state of the host-buffer path with multipliers (bmpc_solve_batch_host_dual)
 };
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "boundmpc_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return BMPC_ERR_HIP; } } while (0)
@@ -141,7 +170,7 @@ static void handle_release(bmpc_handle *h) {
     if (h->order_ev) hipEventDestroy(h->order_ev);
     if (h->bridge_ev) hipEventDestroy(h->bridge_ev);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
-    hipFree(h->scratch); hipFree(h->counter); hipFree(h->aux_int); hipFree(h->qkey); hipFree(h->qorder); hipFree(h->prof); hipFree(h->stage_d); if (h->stage_h) hipHostFree(h->stage_h);
+    hipFree(h->scratch); hipFree(h->counter); hipFree(h->aux_int); hipFree(h->qkey); hipFree(h->qorder); hipFree(h->prof); hipFree(h->stage_d); if (h->stage_h) hipHostFree(h->stage_h); hipFree(h->stage_state);
     delete h;
 }
 
@@ -452,6 +481,28 @@ extern "C" int bmpc_solve_batch_warm(bmpc_handle *h, int B, const double *p, con
     return enqueue_solve(h, B, p, x0, state, max_iter, x, g, lam_g, lam_x, f, iters, status, kkt, (hipStream_t)hip_stream, h->timing != 0);
 }
 
+// primal-dual warm start: enqueues the conversion kernel (bmpc_dual.inl) on `st`, ordered against the handle's other launches like enqueue_solve
+static int enqueue_dual(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g, const double *lam_x, double mu0, double *state, hipStream_t st) {
+    if (h->closed) return BMPC_ERR_ARG;
+    const int grid = B < h->grid ? B : h->grid;
+    if (grid > h->scr_waves) return BMPC_ERR_ARG;
+    { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
+    const KArgs k = handle_kargs(h, B, 0);
+    DualArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h; a.o = k.o;
+    a.p = p; a.x0 = x0; a.lam_g = lam_g; a.lam_x = lam_x; a.state = state; a.mu = mu0; a.scratch = h->scratch; a.scr_stride = h->scr_stride;
+    if (h->N <= 11 && h->S <= bmpc::SMAX_ZLDS) hipLaunchKernelGGL(bmpc_dual_kernel<true>, dim3(grid), dim3(64), 0, st, a);      // iterate in LDS
+    else hipLaunchKernelGGL(bmpc_dual_kernel<false>, dim3(grid), dim3(64), 0, st, a);                                          // iterate in the workspace
+    HIPCHK(hipGetLastError());
+    return order_after(h, st);
+}
+extern "C" int bmpc_state_from_multipliers(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g0, const double *lam_x0,
+                                           double mu0, double *state, void *hip_stream) {
+    if (!h || B < 0 || (B > 0 && (!p || !x0 || !state))) return BMPC_ERR_ARG;
+    if (B == 0) return BMPC_OK;
+    { const int rc_ = ensure_scratch(h, B < h->grid ? B : h->grid); if (rc_ != BMPC_OK) return rc_; }
+    return enqueue_dual(h, B, p, x0, lam_g0, lam_x0, mu0, state, (hipStream_t)hip_stream);
+}
+
 // ---- hipGraph-captured step: {queue reset, solver kernel, restoration kernel} of one (warm-started) solve, instantiated once, replayed per tick ----
 struct bmpc_graph { bmpc_handle *h; hipGraph_t graph; hipGraphExec_t exec; };
 
@@ -561,6 +612,56 @@ extern "C" int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, con
     memcpy(hp, p, b * np * sizeof(double)); memcpy(hx0, x0, b * nw * sizeof(double));
     TRY(hipMemcpyAsync(dp, hp, n_in * sizeof(double), hipMemcpyHostToDevice, hs));
     if (rc == BMPC_OK) rc = bmpc_solve_batch(h, B, dp, dx0, dx, dg, dlg, dlx, df, dit, dst, dk, hs);
+    TRY(hipMemcpyAsync(hx, dx, n_out * sizeof(double) + b * 2 * sizeof(int), hipMemcpyDeviceToHost, hs));
+    TRY(hipStreamSynchronize(hs));
+    if (rc == BMPC_OK) {
+        memcpy(x, hx, b * nw * sizeof(double));
+        if (g) memcpy(g, hg, b * ng * sizeof(double));
+        if (lam_g) memcpy(lam_g, hlg, b * ng * sizeof(double));
+        if (lam_x) memcpy(lam_x, hlx, b * nw * sizeof(double));
+        if (f) memcpy(f, hf, b * sizeof(double));
+        if (kkt) memcpy(kkt, hk, b * sizeof(double));
+        if (iters) memcpy(iters, hit, b * sizeof(int));
+        if (status) memcpy(status, hst, b * sizeof(int));
+    }
+#undef TRY
+    return rc;
+}
+
+// host-buffer path with multipliers: the staging record of bmpc_solve_batch_host, with lam_x0 / lam_g0 staged where the outputs lam_x / lam_g will be
+// written (the conversion reads them before the solve behind it overwrites them, in stream order), so the inputs are still ONE host-to-device copy
+extern "C" int bmpc_solve_batch_host_dual(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g0, const double *lam_x0,
+                                          double *x, double *g, double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt) {
+    if (!h || B < 0 || (B > 0 && (!p || !x0 || !x))) return BMPC_ERR_ARG;
+    if (B == 0) return BMPC_OK;
+    if (h->closed) return BMPC_ERR_ARG;
+    int rc = host_stage_reserve(h, B);
+    if (rc != BMPC_OK) return rc;
+    const size_t np = 141 + 91 * h->S, nw = (size_t)h->N * 44, ng = (size_t)h->N * 43, b = (size_t)B, sl = (size_t)h->N * bmpc::NI + 2;
+    if (B > h->stage_state_cap) {
+        DevGuard dg(h->dev);
+        if (h->stage_state) { wait_for_handle(h); hipFree(h->stage_state); h->stage_state = nullptr; h->stage_state_cap = 0; }
+        HIPCHK(hipMalloc(&h->stage_state, sizeof(double) * sl * b));
+        h->stage_state_cap = B;
+    }
+    const size_t n_in = b * (np + 3 * nw + 2 * ng), n_out = b * (2 * nw + 2 * ng + 2);
+    double *dp = h->stage_d, *dx0 = dp + b * np, *dx = dx0 + b * nw, *dlx = dx + b * nw, *dg = dlx + b * nw, *dlg = dg + b * ng, *df = dlg + b * ng, *dk = df + b;
+    int *dit = (int *)(dk + b), *dst = dit + b;
+    double *hp = h->stage_h, *hx0 = hp + b * np, *hx = hx0 + b * nw, *hlx = hx + b * nw, *hg = hlx + b * nw, *hlg = hg + b * ng, *hf = hlg + b * ng, *hk = hf + b;
+    const int *hit = (const int *)(hk + b), *hst = hit + b;
+#define TRY(x) do { if (rc == BMPC_OK && (x) != hipSuccess) rc = BMPC_ERR_HIP; } while (0)
+    hipStream_t hs = nullptr;
+    {
+        DevGuard dg(h->dev);
+        if (!h->own_stream && hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return BMPC_ERR_HIP;
+        hs = h->own_stream;
+    }
+    memcpy(hp, p, b * np * sizeof(double)); memcpy(hx0, x0, b * nw * sizeof(double));
+    if (lam_x0) memcpy(hlx, lam_x0, b * nw * sizeof(double));
+    if (lam_g0) memcpy(hlg, lam_g0, b * ng * sizeof(double));
+    TRY(hipMemcpyAsync(dp, hp, n_in * sizeof(double), hipMemcpyHostToDevice, hs));      // (x and g of the record travel along: the solve overwrites them)
+    if (rc == BMPC_OK) rc = bmpc_state_from_multipliers(h, B, dp, dx0, lam_g0 ? dlg : nullptr, lam_x0 ? dlx : nullptr, 0.0, h->stage_state, hs);
+    if (rc == BMPC_OK) rc = bmpc_solve_batch_warm(h, B, dp, dx0, h->stage_state, 0, dx, dg, dlg, dlx, df, dit, dst, dk, hs);
     TRY(hipMemcpyAsync(hx, dx, n_out * sizeof(double) + b * 2 * sizeof(int), hipMemcpyDeviceToHost, hs));
     TRY(hipStreamSynchronize(hs));
     if (rc == BMPC_OK) {

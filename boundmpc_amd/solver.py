@@ -210,16 +210,51 @@ class BatchedOCPSolver:
             raise ValueError(f"state must be a contiguous float64 GPU tensor of shape ({B}, {self.state_len})")
         return B
 
+    def _check_multipliers(self, B, lam_g0, lam_x0, dev):
+        import torch
+        for t, n, nm in ((lam_g0, self.n_g, "lam_g0"), (lam_x0, self.n_w, "lam_x0")):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.shape == (B, n)):
+                raise ValueError(f"{nm} must be a contiguous float64 GPU tensor of shape ({B}, {n})")
+            if t.device != dev:
+                raise ValueError(f"{nm} lives on {t.device}, p on {dev}")
+
+    def state_from_multipliers(self, p, x0, lam_g0=None, lam_x0=None, mu0=None, out=None, stream=None):
+        """Dual state [B, state_len] of a warm solve (solve_batch(state=...)) from multipliers in CasADi's convention -- lam_g0 [B, 43 N],
+        lam_x0 [B, 44 N], as a solve returns them; None = zeros -- evaluated at x0 on the GPU (include/boundmpc_hip.h bmpc_state_from_multipliers:
+        the map, what is ignored, the barrier level).  mu0 > 0: the barrier level of the state, else the handle's mu_warm.  Asynchronous on `stream`."""
+        import torch
+        self._check_io(p, x0, out)
+        B = p.shape[0]
+        self._check_multipliers(B, lam_g0, lam_x0, p.device)
+        state = out if out is not None else torch.empty((B, self.state_len), dtype=torch.float64, device=p.device)
+        st = stream if stream is not None else torch.cuda.current_stream(p.device)
+        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.bmpc_state_from_multipliers(self._h, B, dp(p), dp(x0), dp(lam_g0), dp(lam_x0), float(mu0 or 0.0), dp(state),
+                                                         ctypes.c_void_p(st.cuda_stream)), "bmpc_state_from_multipliers")
+        self._inflight = (p, x0, lam_g0, lam_x0, state)      # (asynchronous launch: see solve_batch)
+        return state
+
     # ---- batched device solve ----
-    def solve_batch(self, p, x0, out=None, want=("g", "lam_g", "lam_x", "f", "iters", "status", "kkt"), stream=None, state=None, max_iter=0):
+    def solve_batch(self, p, x0, out=None, want=("g", "lam_g", "lam_x", "f", "iters", "status", "kkt"), stream=None, state=None, max_iter=0,
+                    lam_g0=None, lam_x0=None):
         """p [B][n_p], x0 [B][n_w]: CUDA(ROCm) float64 contiguous tensors.  Returns dict of tensors.
         Asynchronous on `stream` (default: torch's current stream).  With `state` (see new_state) the solve is warm-started
-        from it and updates it in place; `max_iter` > 0 caps the Newton steps of this call (real-time iteration)."""
+        from it and updates it in place; `max_iter` > 0 caps the Newton steps of this call (real-time iteration).
+        With multipliers lam_g0 [B][n_g] / lam_x0 [B][n_w] (CasADi's convention; either may be None) the solve is warm-started from the dual state
+        state_from_multipliers makes of them, returned as out["state"]; multipliers and `state` together are refused."""
         import torch
         self._check_io(p, x0, state)
         B = p.shape[0]
         o = out if out is not None else {}
         dev = p.device
+        if lam_g0 is not None or lam_x0 is not None:
+            if state is not None:
+                raise ValueError("pass either multipliers (lam_g0 / lam_x0) or a dual state, not both")
+            st_ = stream if stream is not None else torch.cuda.current_stream(dev)
+            state = self.state_from_multipliers(p, x0, lam_g0, lam_x0, out=o.get("state"), stream=st_)
+            o["state"] = state
 
         def buf(name, shape, dtype):
             if name not in o or o[name] is None:
@@ -249,7 +284,7 @@ class BatchedOCPSolver:
         # The launch is asynchronous: the kernel reads p / x0 / state and writes the outputs on the launch stream after this call has
         # returned.  The handle keeps them alive until its next launch (a caller that passes temporaries or drops the returned dict would
         # otherwise hand their memory back to the allocator while the kernel is still using it).
-        self._inflight = (p, x0, state, o)
+        self._inflight = (p, x0, state, o, lam_g0, lam_x0)
         return o
 
     def capture_step(self, p, x0, state=None, max_iter=0, want=("iters", "status", "kkt")):
@@ -258,18 +293,32 @@ class BatchedOCPSolver:
         return StepGraph(self, p, x0, state, max_iter, want)
 
     # ---- host-buffer solve (numpy in/out) ----
-    def solve_host(self, p, x0):
+    def solve_host(self, p, x0, lam_g0=None, lam_x0=None):
+        """numpy in / out.  With multipliers lam_g0 [B][n_g] / lam_x0 [B][n_w] (either may be None): converted and warm-solved in the same
+        single call (bmpc_solve_batch_host_dual); without: the stateless solve."""
         p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
         x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
         B = p.shape[0]
         if p.shape != (B, self.n_p) or x0.shape != (B, self.n_w):
             raise ValueError(f"shape mismatch: p {p.shape} x0 {x0.shape}")
+        lam = []
+        for a, n, nm in ((lam_g0, self.n_g, "lam_g0"), (lam_x0, self.n_w, "lam_x0")):
+            if a is not None:
+                a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
+                if a.shape != (B, n):
+                    raise ValueError(f"{nm} has shape {a.shape}, expected {(B, n)}")
+            lam.append(a)
         out = dict(x=np.zeros((B, self.n_w)), g=np.zeros((B, self.n_g)), lam_g=np.zeros((B, self.n_g)), lam_x=np.zeros((B, self.n_w)),
                    f=np.zeros(B), iters=np.zeros(B, dtype=np.int32), status=np.zeros(B, dtype=np.int32), kkt=np.zeros(B))
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _lib.check(self._lib.bmpc_solve_batch_host(self._h, B, vp(p), vp(x0), vp(out["x"]), vp(out["g"]), vp(out["lam_g"]),
-                                                   vp(out["lam_x"]), vp(out["f"]), vp(out["iters"]), vp(out["status"]), vp(out["kkt"])),
-                   "bmpc_solve_batch_host")
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+        if lam_g0 is None and lam_x0 is None:
+            _lib.check(self._lib.bmpc_solve_batch_host(self._h, B, vp(p), vp(x0), vp(out["x"]), vp(out["g"]), vp(out["lam_g"]),
+                                                       vp(out["lam_x"]), vp(out["f"]), vp(out["iters"]), vp(out["status"]), vp(out["kkt"])),
+                       "bmpc_solve_batch_host")
+        else:
+            _lib.check(self._lib.bmpc_solve_batch_host_dual(self._h, B, vp(p), vp(x0), vp(lam[0]), vp(lam[1]), vp(out["x"]), vp(out["g"]),
+                                                            vp(out["lam_g"]), vp(out["lam_x"]), vp(out["f"]), vp(out["iters"]), vp(out["status"]),
+                                                            vp(out["kkt"])), "bmpc_solve_batch_host_dual")
         return out
 
 
@@ -346,12 +395,32 @@ class NlpSolverShim:
         for given, mine, nm in ((lbx, self._lbx, "lbx"), (ubx, self._ubx, "ubx"), (lbg, self._lbg, "lbg"), (ubg, self._ubg, "ubg")):
             if given is not None and not np.array_equal(np.asarray(given, dtype=float).ravel(), mine):
                 raise ValueError(f"{nm} differs from the formulation's structural bounds (casadi_ocp_formulation.py:92-153,272-349)")
-        out = self._s.solve_host(np.asarray(p, dtype=float).ravel()[None, :], np.asarray(x0, dtype=float).ravel()[None, :])
+        # multipliers (CasADi broadcasting: a scalar, or a column / flat vector of the right length); None or all zeros (the reference's initial
+        # `self.lam_g0 = 0`) is the stateless call, otherwise a primal-dual warm start (include/boundmpc_hip.h bmpc_state_from_multipliers)
+        lg, lx = self._multiplier(lam_g0, self._s.n_g, "lam_g0"), self._multiplier(lam_x0, self._s.n_w, "lam_x0")
+        p_, x0_ = np.asarray(p, dtype=float).ravel()[None, :], np.asarray(x0, dtype=float).ravel()[None, :]
+        if lg is None and lx is None:
+            out = self._s.solve_host(p_, x0_)
+        else:
+            out = self._s.solve_host(p_, x0_, lam_g0=lg, lam_x0=lx)
         st = int(out["status"][0])
         self._stats = {"iter_count": int(out["iters"][0]), "success": st == 0, "return_status": _STATUS.get(st, f"status_{st}"),
                        "kkt_error": float(out["kkt"][0])}
         col = lambda a: np.asarray(a[0]).reshape(-1, 1)
         return {"x": col(out["x"]), "f": float(out["f"][0]), "g": col(out["g"]), "lam_x": col(out["lam_x"]), "lam_g": col(out["lam_g"])}
+
+    @staticmethod
+    def _multiplier(v, n, name):
+        """[1, n] float64 array of a multiplier argument, or None for None / all zeros."""
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=float)
+        if a.size == 1:
+            a = np.full(n, float(a.ravel()[0]))
+        elif a.ndim > 2 or (a.ndim == 2 and 1 not in a.shape) or a.size != n:
+            raise ValueError(f"{name} has shape {a.shape}: expected a scalar or a vector of length {n}")
+        a = a.ravel()
+        return None if not a.any() else a[None, :]
 
     def stats(self):
         return dict(self._stats)

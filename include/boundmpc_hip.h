@@ -100,6 +100,24 @@ int bmpc_state_len(const bmpc_handle *h);   /* 57 N + 2 */
 int bmpc_solve_batch_warm(bmpc_handle *h, int B, const double *p, const double *x0, double *state, int max_iter, double *x, double *g,
                           double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt, void *hip_stream);
 
+/* Primal-dual warm start from multipliers in CasADi's convention (what a solve returns as lam_g / lam_x; the reference's lam_g0 / lam_x0,
+ * BoundMPC.py:451-452): the dual state of bmpc_solve_batch_warm, computed on the GPU.  Each problem is evaluated at x0 as a solve begins (no start
+ * rollout); then per node k, with pos(v) = max(v, 0) and the internal rows of the state:
+ *   upper / lower row of jerk j (8), q_j and dq_j (7 each)   pos(lam_x[z]) / pos(-lam_x[z]) of that variable z
+ *   phi >= 0                                                  pos(-lam_x[phi])
+ *   phi <= phi_max, dphi <= dphi_max                          pos(lam_g[36]), pos(lam_g[37])
+ *   tube row m (m < 5): the pair c - wd <= 0, -c - wd <= 0    pos(lam (wd + c)), pos(lam (wd - c)) with lam = pos(lam_g[38 + m])
+ * c and wd >= 0 are the centre value and the half width of the squared tube row c^2 - wd^2 <= 0 at x0; the map is the exact inverse of the
+ * solver's own output map wherever |c| <= wd.  IGNORED: the equality multipliers lam_g[0:36] (the solver recomputes them at every iterate) and
+ * lam_x of unbounded variables.  A non-finite entry counts as 0; a converted multiplier is capped at 1e12.
+ * State slot mu = mu0 when mu0 > 0, else options.mu_warm (the warm solve then starts at clamp(mu, mu_warm, mu_init)); a problem whose converted
+ * multipliers are all 0 gets mu = 0: the cold start of the warm path.  Slot iterations = 0.
+ * A solve with a state gets neither the start rollout (bmpc_set_start_rollout) nor the second attempt (bmpc_set_second_attempt).
+ * DEVICE pointers; lam_g0 [B][43 N] and lam_x0 [B][44 N] may be NULL (= zeros); state [B][bmpc_state_len(h)] is written.  Uses the handle's
+ * workspace: ordered against its other launches like bmpc_solve_batch. */
+int bmpc_state_from_multipliers(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g0, const double *lam_x0,
+                                double mu0, double *state, void *hip_stream);
+
 /* The same step captured once into a hipGraph and replayed per tick: buffers are fixed at capture time, the caller refreshes their contents.
  * Launches of one handle (direct or replayed) share its workspace: the library orders them against each other with an event whatever streams the
  * caller uses (exception: a launch on a stream the CALLER is capturing neither waits for nor records that event).  A graph keeps the workspace and
@@ -171,6 +189,10 @@ int bmpc_stream_graph_create(bmpc_handle *h, int B, const double *path, int path
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
                           double *f, int *iters, int *status, double *kkt);
+/* HOST pointers: the same with multipliers (lam_g0 [B][43 N], lam_x0 [B][44 N]; either may be NULL = zeros): staged copies, the conversion of
+ * bmpc_state_from_multipliers (mu0 = 0), the warm solve on that state, one synchronisation -- the single solver(...) call with lam_g0 / lam_x0. */
+int bmpc_solve_batch_host_dual(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g0, const double *lam_x0,
+                               double *x, double *g, double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt);
 
 /* Timing of the solver kernel with HIP events on the launch stream: the {start, stop} pairs of the last `keep` launches are kept (0 = off).
  * bmpc_kernel_ms(h, back, &ms): duration of the launch `back` launches ago (0 = the last; synchronises on its stop event). */
