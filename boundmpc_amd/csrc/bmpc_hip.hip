@@ -15,6 +15,7 @@
 #include "bmpc_wave.inl"
 #include "bmpc_stream.inl"
 #include "bmpc_dual.inl"
+#include "bmpc_kkt.inl"
 
 typedef KArgsT<bmpc::Opts> KArgs;
 #ifndef BMPC_TEAM_NW
@@ -100,6 +101,37 @@ __global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_dual_kernel(DualAr
     }
 }
 
+// KKT certificate of any primal-dual point (bmpc_kkt.inl; include/boundmpc_hip.h bmpc_kkt_batch).  The launch shape of the conversion kernel above: one wave
+// per problem over the handle's resident waves and workspace slabs, striding over the batch (an evaluation and an adjoint sweep per problem: no work queue).
+static_assert(bmpc::KKT_LEN == BMPC_KKT_LEN && bmpc::KKT_E == BMPC_KKT_E && bmpc::KKT_DUAL == BMPC_KKT_DUAL && bmpc::KKT_PRIM_EQ == BMPC_KKT_PRIM_EQ
+              && bmpc::KKT_PRIM_INEQ == BMPC_KKT_PRIM_INEQ && bmpc::KKT_COMPL == BMPC_KKT_COMPL && bmpc::KKT_LAM_EQ_GAP == BMPC_KKT_LAM_EQ_GAP
+              && bmpc::KKT_LAM_INEQ_GAP == BMPC_KKT_LAM_INEQ_GAP && bmpc::KKT_F == BMPC_KKT_F, "record slots of the header and of the wave program");
+struct KktArgs {
+    int N, S, B; double h; bmpc::Opts o;
+    const double *p, *x, *lam_g0, *lam_x0; double *cert, *g, *lam_g, *rj;
+    double *scratch; long long scr_stride;
+};
+template <bool ZLDS>
+__global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_kkt_kernel(KktArgs a) {
+    __shared__ double lds[bmpc::L_SIZE];
+    bmpc::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = bmpc::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride); W.wv = 0;
+    W.deadline = 0; W.it_base = 0;
+#ifdef BMPC_PROFILE
+    if (threadIdx.x < 32) ((long long *)(lds + bmpc::L_PROF))[threadIdx.x] = 0;
+    __syncthreads();
+    W.tprev = clock64();
+#endif
+    const int np = 141 + 91 * a.S, nw = a.N * bmpc::NZ, ng = a.N * bmpc::NG, nj = a.N * bmpc::NU;
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        bmpc::KktIn d;
+        d.p = a.p + (long long)b * np; d.x = a.x + (long long)b * nw; d.cert = a.cert + (long long)b * bmpc::KKT_LEN;
+        d.lam_g0 = a.lam_g0 ? a.lam_g0 + (long long)b * ng : nullptr; d.lam_x0 = a.lam_x0 ? a.lam_x0 + (long long)b * nw : nullptr;
+        d.g = a.g ? a.g + (long long)b * ng : nullptr; d.lam_g = a.lam_g ? a.lam_g + (long long)b * ng : nullptr; d.rj = a.rj ? a.rj + (long long)b * nj : nullptr;
+        bmpc::wave_certify<ZLDS>(W, d);
+        __syncthreads();
+    }
+}
+
 // (members without an initialiser start at zero / NULL: bmpc_create value-initialises the handle)
 struct bmpc_handle {
     int N, S; double h; bmpc_options o;
@@ -129,6 +161,7 @@ struct bmpc_handle {
     double *latency_us;
     double *stage_d, *stage_h; int stage_cap;   // device and pinned host staging of the host-buffer path (bmpc_solve_batch_host)
     double *stage_state; int stage_state_cap;   // device dual state of the host-buffer path with multipliers (bmpc_solve_batch_host_dual)
+    double *kkt_d, *kkt_h; int kkt_cap;         // device and pinned host staging of the host-buffer certificate (bmpc_kkt_batch_host)
 };
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "boundmpc_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return BMPC_ERR_HIP; } } while (0)
@@ -171,6 +204,7 @@ static void handle_release(bmpc_handle *h) {
     if (h->bridge_ev) hipEventDestroy(h->bridge_ev);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     hipFree(h->scratch); hipFree(h->counter); hipFree(h->aux_int); hipFree(h->qkey); hipFree(h->qorder); hipFree(h->prof); hipFree(h->stage_d); if (h->stage_h) hipHostFree(h->stage_h); hipFree(h->stage_state);
+    hipFree(h->kkt_d); if (h->kkt_h) hipHostFree(h->kkt_h);
     delete h;
 }
 
@@ -501,6 +535,76 @@ extern "C" int bmpc_state_from_multipliers(bmpc_handle *h, int B, const double *
     if (B == 0) return BMPC_OK;
     { const int rc_ = ensure_scratch(h, B < h->grid ? B : h->grid); if (rc_ != BMPC_OK) return rc_; }
     return enqueue_dual(h, B, p, x0, lam_g0, lam_x0, mu0, state, (hipStream_t)hip_stream);
+}
+
+// ---- KKT certificate of any primal-dual point (bmpc_kkt.inl) ----
+// enqueues the certificate kernel on `st`, ordered against the handle's other launches like enqueue_dual
+static int enqueue_kkt(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert, double *g,
+                       double *lam_g, double *rj, hipStream_t st) {
+    if (h->closed) return BMPC_ERR_ARG;
+    const int grid = B < h->grid ? B : h->grid;
+    if (grid > h->scr_waves) return BMPC_ERR_ARG;
+    { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
+    const KArgs k = handle_kargs(h, B, 0);
+    KktArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h; a.o = k.o;
+    a.p = p; a.x = x; a.lam_g0 = lam_g0; a.lam_x0 = lam_x0; a.cert = cert; a.g = g; a.lam_g = lam_g; a.rj = rj; a.scratch = h->scratch; a.scr_stride = h->scr_stride;
+    if (h->N <= 11 && h->S <= bmpc::SMAX_ZLDS) hipLaunchKernelGGL(bmpc_kkt_kernel<true>, dim3(grid), dim3(64), 0, st, a);      // iterate in LDS
+    else hipLaunchKernelGGL(bmpc_kkt_kernel<false>, dim3(grid), dim3(64), 0, st, a);                                          // iterate in the workspace
+    HIPCHK(hipGetLastError());
+    return order_after(h, st);
+}
+extern "C" int bmpc_kkt_len(void) { return BMPC_KKT_LEN; }
+extern "C" int bmpc_kkt_batch(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert,
+                              double *g, double *lam_g, double *rj, void *hip_stream) {
+    if (!h || B < 1 || !p || !x || !cert) return BMPC_ERR_ARG;
+    { const int rc_ = ensure_scratch(h, B < h->grid ? B : h->grid); if (rc_ != BMPC_OK) return rc_; }
+    return enqueue_kkt(h, B, p, x, lam_g0, lam_x0, cert, g, lam_g, rj, (hipStream_t)hip_stream);
+}
+// host-buffer certificate: one staging record [p | x | lam_g0 | lam_x0] in, [cert | g | lam_g | rj] out -- one host-to-device copy, the launch, one
+// device-to-host copy and one stream synchronisation, on the handle's own non-blocking stream (as bmpc_solve_batch_host)
+extern "C" int bmpc_kkt_batch_host(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert,
+                                   double *g, double *lam_g, double *rj) {
+    if (!h || B < 1 || !p || !x || !cert) return BMPC_ERR_ARG;
+    if (h->closed) return BMPC_ERR_ARG;
+    const size_t np = 141 + 91 * h->S, nw = (size_t)h->N * 44, ng = (size_t)h->N * 43, nj = (size_t)h->N * 8, b = (size_t)B;
+    const size_t n_in = b * (np + 2 * nw + ng), n_out = b * (BMPC_KKT_LEN + 2 * ng + nj);
+    if (B > h->kkt_cap) {
+        DevGuard dg(h->dev);
+        wait_for_handle(h);
+        if (h->kkt_d) { hipFree(h->kkt_d); h->kkt_d = nullptr; }
+        if (h->kkt_h) { hipHostFree(h->kkt_h); h->kkt_h = nullptr; }
+        h->kkt_cap = 0;
+        if (hipMalloc(&h->kkt_d, (n_in + n_out) * sizeof(double)) != hipSuccess || hipHostMalloc(&h->kkt_h, (n_in + n_out) * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+            hipFree(h->kkt_d); if (h->kkt_h) hipHostFree(h->kkt_h); h->kkt_d = nullptr; h->kkt_h = nullptr;
+            return BMPC_ERR_HIP;
+        }
+        h->kkt_cap = B;
+    }
+    double *dp = h->kkt_d, *dx = dp + b * np, *dlg0 = dx + b * nw, *dlx0 = dlg0 + b * ng, *dc = dlx0 + b * nw, *dg = dc + b * BMPC_KKT_LEN, *dlg = dg + b * ng, *drj = dlg + b * ng;
+    double *hp = h->kkt_h, *hx = hp + b * np, *hlg0 = hx + b * nw, *hlx0 = hlg0 + b * ng, *hc = hlx0 + b * nw, *hg = hc + b * BMPC_KKT_LEN, *hlg = hg + b * ng, *hrj = hlg + b * ng;
+    int rc = BMPC_OK;
+#define TRY(x) do { if (rc == BMPC_OK && (x) != hipSuccess) rc = BMPC_ERR_HIP; } while (0)
+    hipStream_t hs = nullptr;
+    {
+        DevGuard dg(h->dev);
+        if (!h->own_stream && hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return BMPC_ERR_HIP;
+        hs = h->own_stream;
+    }
+    memcpy(hp, p, b * np * sizeof(double)); memcpy(hx, x, b * nw * sizeof(double));
+    if (lam_g0) memcpy(hlg0, lam_g0, b * ng * sizeof(double)); else memset(hlg0, 0, b * ng * sizeof(double));
+    if (lam_x0) memcpy(hlx0, lam_x0, b * nw * sizeof(double)); else memset(hlx0, 0, b * nw * sizeof(double));
+    TRY(hipMemcpyAsync(dp, hp, n_in * sizeof(double), hipMemcpyHostToDevice, hs));
+    if (rc == BMPC_OK) rc = bmpc_kkt_batch(h, B, dp, dx, lam_g0 ? dlg0 : nullptr, lam_x0 ? dlx0 : nullptr, dc, dg, dlg, drj, hs);
+    TRY(hipMemcpyAsync(hc, dc, n_out * sizeof(double), hipMemcpyDeviceToHost, hs));
+    TRY(hipStreamSynchronize(hs));
+    if (rc == BMPC_OK) {
+        memcpy(cert, hc, b * BMPC_KKT_LEN * sizeof(double));
+        if (g) memcpy(g, hg, b * ng * sizeof(double));
+        if (lam_g) memcpy(lam_g, hlg, b * ng * sizeof(double));
+        if (rj) memcpy(rj, hrj, b * nj * sizeof(double));
+    }
+#undef TRY
+    return rc;
 }
 
 // ---- hipGraph-captured step: {queue reset, solver kernel, restoration kernel} of one (warm-started) solve, instantiated once, replayed per tick ----

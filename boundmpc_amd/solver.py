@@ -11,6 +11,9 @@ import numpy as np
 from . import _lib
 
 NZ, NG = 44, 43
+# slots of the KKT certificate record (include/boundmpc_hip.h BMPC_KKT_*), in order
+KKT_E, KKT_DUAL, KKT_PRIM_EQ, KKT_PRIM_INEQ, KKT_COMPL, KKT_LAM_EQ_GAP, KKT_LAM_INEQ_GAP, KKT_F = range(8)
+KKT_FIELDS = ("E", "dual", "prim_eq", "prim_ineq", "compl", "lam_eq_gap", "lam_ineq_gap", "f")
 
 
 class BatchedOCPSolver:
@@ -236,6 +239,74 @@ class BatchedOCPSolver:
         self._inflight = (p, x0, lam_g0, lam_x0, state)      # (asynchronous launch: see solve_batch)
         return state
 
+    # ---- KKT certificate of any primal-dual point (bmpc_kkt_batch) ----
+    _CERT_WANT = ("g", "lam_g", "rj")
+
+    def certify(self, p, x, lam_g=None, lam_x=None, want=(), out=None, stream=None):
+        """The solver's error measure for points it need not have produced: p [B][n_p], x [B][n_w] and multipliers in CasADi's convention
+        lam_g [B][n_g] / lam_x [B][n_w] (None or 0: none), all float64 contiguous GPU tensors.  Returns a dict with the fields KKT_FIELDS as [B]
+        tensors (views of the record "cert" [B][8]) -- E is what a solve compares with tol -- plus the arrays named in `want`: "g" [B][n_g],
+        "lam_g" [B][n_g] (the consistent multipliers: equality rows recomputed, inequality rows re-exported), "rj" [B][8 N].  The point is taken
+        as given (no start rollout, no second attempt); the record, the gap slots and the non-finite rules: include/boundmpc_hip.h bmpc_kkt_batch.
+        Asynchronous on `stream`; ordered against the handle's solves."""
+        import torch
+        lam_g = None if (lam_g is None or (isinstance(lam_g, (int, float)) and lam_g == 0)) else lam_g
+        lam_x = None if (lam_x is None or (isinstance(lam_x, (int, float)) and lam_x == 0)) else lam_x
+        B = self._check_io(p, x, None)
+        self._check_multipliers(B, lam_g, lam_x, p.device)
+        bad = [k for k in want if k not in self._CERT_WANT]
+        if bad:
+            raise ValueError(f"want {bad}: a certificate offers {self._CERT_WANT}")
+        o = out if out is not None else {}
+        dev = p.device
+        shapes = dict(cert=(B, len(KKT_FIELDS)), g=(B, self.n_g), lam_g=(B, self.n_g), rj=(B, 8 * self.N))
+        ptr = {}
+        for k in ("cert",) + tuple(want):
+            t = o.get(k)
+            if t is None:
+                t = o[k] = torch.empty(shapes[k], dtype=torch.float64, device=dev)
+            elif not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shapes[k] and t.device == dev):
+                raise ValueError(f"out[{k!r}] must be a contiguous float64 GPU tensor of shape {shapes[k]} on {dev}")
+            ptr[k] = t
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.bmpc_kkt_batch(self._h, B, dp(p), dp(x), dp(lam_g), dp(lam_x), dp(ptr["cert"]), dp(ptr.get("g")), dp(ptr.get("lam_g")),
+                                            dp(ptr.get("rj")), ctypes.c_void_p(st.cuda_stream)), "bmpc_kkt_batch")
+        self._inflight_cert = (p, x, lam_g, lam_x, o)      # (asynchronous launch: see solve_batch)
+        for i, k in enumerate(KKT_FIELDS):
+            o[k] = ptr["cert"][:, i]
+        return o
+
+    def certify_host(self, p, x, lam_g=None, lam_x=None, want=()):
+        """certify with numpy in / out (bmpc_kkt_batch_host: staged copies, one synchronisation)."""
+        p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        B = p.shape[0]
+        if p.shape != (B, self.n_p) or x.shape != (B, self.n_w):
+            raise ValueError(f"shape mismatch: p {p.shape} x {x.shape}")
+        lam = []
+        for a, n, nm in ((lam_g, self.n_g, "lam_g"), (lam_x, self.n_w, "lam_x")):
+            if a is not None and not (np.isscalar(a) and a == 0):
+                a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
+                if a.shape != (B, n):
+                    raise ValueError(f"{nm} has shape {a.shape}, expected {(B, n)}")
+            else:
+                a = None
+            lam.append(a)
+        bad = [k for k in want if k not in self._CERT_WANT]
+        if bad:
+            raise ValueError(f"want {bad}: a certificate offers {self._CERT_WANT}")
+        shapes = dict(g=(B, self.n_g), lam_g=(B, self.n_g), rj=(B, 8 * self.N))
+        o = {"cert": np.zeros((B, len(KKT_FIELDS)))}
+        for k in want:
+            o[k] = np.zeros(shapes[k])
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+        _lib.check(self._lib.bmpc_kkt_batch_host(self._h, B, vp(p), vp(x), vp(lam[0]), vp(lam[1]), vp(o["cert"]), vp(o.get("g")), vp(o.get("lam_g")),
+                                                 vp(o.get("rj"))), "bmpc_kkt_batch_host")
+        for i, k in enumerate(KKT_FIELDS):
+            o[k] = o["cert"][:, i]
+        return o
+
     # ---- batched device solve ----
     def solve_batch(self, p, x0, out=None, want=("g", "lam_g", "lam_x", "f", "iters", "status", "kkt"), stream=None, state=None, max_iter=0,
                     lam_g0=None, lam_x0=None):
@@ -407,7 +478,22 @@ class NlpSolverShim:
         self._stats = {"iter_count": int(out["iters"][0]), "success": st == 0, "return_status": _STATUS.get(st, f"status_{st}"),
                        "kkt_error": float(out["kkt"][0])}
         col = lambda a: np.asarray(a[0]).reshape(-1, 1)
-        return {"x": col(out["x"]), "f": float(out["f"][0]), "g": col(out["g"]), "lam_x": col(out["lam_x"]), "lam_g": col(out["lam_g"])}
+        sol = {"x": col(out["x"]), "f": float(out["f"][0]), "g": col(out["g"]), "lam_x": col(out["lam_x"]), "lam_g": col(out["lam_g"])}
+        self._last = (p_.copy(), sol)
+        return sol
+
+    def certificate(self, sol=None):
+        """KKT certificate (BatchedOCPSolver.certify_host: dict of the fields KKT_FIELDS, floats) of a CasADi-style result -- a dict with 'x' and,
+        where known, 'lam_g' / 'lam_x' (columns, flat vectors or a scalar, like the multiplier arguments of a call) -- for the parameter vector of the
+        LAST call.  Default: the last solution.  Any solver's answer to the same problem can be scored: Ipopt's, a candidate warm start."""
+        if getattr(self, "_last", None) is None:
+            raise RuntimeError("certificate() needs a previous solver(...) call: it certifies a point for that call's p")
+        p_, last = self._last
+        sol = last if sol is None else sol
+        x = np.asarray(sol["x"], dtype=float).ravel()[None, :]
+        lg, lx = self._multiplier(sol.get("lam_g"), self._s.n_g, "lam_g"), self._multiplier(sol.get("lam_x"), self._s.n_w, "lam_x")
+        c = self._s.certify_host(p_, x, lam_g=lg, lam_x=lx)
+        return {k: float(c[k][0]) for k in KKT_FIELDS}
 
     @staticmethod
     def _multiplier(v, n, name):

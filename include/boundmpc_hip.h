@@ -118,6 +118,42 @@ int bmpc_solve_batch_warm(bmpc_handle *h, int B, const double *p, const double *
 int bmpc_state_from_multipliers(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g0, const double *lam_x0,
                                 double mu0, double *state, void *hip_stream);
 
+/* KKT certificate of ANY primal-dual point: the solver's error measure for a point (x, lam_g, lam_x) in CasADi's convention that the solver need
+ * not have produced -- Ipopt's answer, an SLSQP run, a shifted plan, a candidate warm start, the rows a graph replay just returned.  `kkt` of a
+ * solve is measured on the solve's own slacks at its last barrier level; a point carries no slacks, so here the slack of an internal inequality
+ * row h_i <= 0 is max(-h_i, 0).  Per problem: the evaluation at x (the point is taken AS GIVEN: neither the start rollout nor the second attempt
+ * applies, nothing is projected); lam_g0[36:43] / lam_x0 mapped onto the 57 N internal multipliers nu by the map of bmpc_state_from_multipliers
+ * (pos(), tube pair lam (wd +- c), cap 1e12, a non-finite entry counts as 0); the adjoint sweep of a solver iteration, which RECOMPUTES the
+ * equality multipliers LAM [N][36] that zero the state part of the Lagrangian gradient and leaves its jerk part RJ [N][8].  The equality
+ * multipliers the caller passes are compared with them (slot 5), never trusted.  Record cert[b][BMPC_KKT_LEN] (doubles):
+ *   BMPC_KKT_E             max(dual / sd, max(prim_eq, prim_ineq), compl / scl), sd = max(100, (sum |LAM| + sum nu) / (93 N)) / 100,
+ *                          scl = max(100, sum nu / (57 N)) / 100: the scaled error a solve compares with options.tol
+ *   BMPC_KKT_DUAL          max |RJ|: stationarity in the jerks, the states eliminated by the adjoint
+ *   BMPC_KKT_PRIM_EQ       max |g[k][0:36]|
+ *   BMPC_KKT_PRIM_INEQ     max_i max(h_i, 0) over the 57 N internal rows (the handle's rows: options.bound_margin included)
+ *   BMPC_KKT_COMPL         max_i nu_i max(-h_i, 0)
+ *   BMPC_KKT_LAM_EQ_GAP    max |lam_g0[k][0:36] - LAM|; 0 when lam_g0 is NULL
+ *   BMPC_KKT_LAM_INEQ_GAP  largest |given - re-exported| over lam_g0[k][36:43] and lam_x0, "re-exported" = nu sent back through the output map of a
+ *                          solve: 0 up to rounding exactly when the signs are right, unbounded variables carry no lam_x and the point is inside
+ *                          its tubes; 0 when both are NULL
+ *   BMPC_KKT_F             the objective at x
+ * OUTSIDE a tube (|c| > wd for a tube row c^2 - wd^2 <= 0) the pair c - wd <= 0, -c - wd <= 0 gets lam (wd + |c|) on the violated row and 0 on the
+ * other: the certificate is that of these split internal rows, and slot 6 shows the multiplier they stand for, lam (wd + |c|) / (2 wd).
+ * NON-FINITE: a non-finite entry of lam_g0 / lam_x0 makes its gap slot (5 or 6) +inf and otherwise counts as 0; a non-finite x or p gives a
+ * non-finite record -- slots 0..4 are NaN as soon as one of f, g, h, LAM, RJ is not finite -- never a fault.
+ * Optional outputs (each may be NULL; they must not overlap the inputs): g [B][43 N]; lam_g [B][43 N], the CONSISTENT multipliers (rows 0:36
+ * recomputed, rows 36:43 re-exported); rj [B][8 N].
+ * DEVICE pointers; lam_g0 [B][43 N] and lam_x0 [B][44 N] may be NULL.  Uses the handle's workspace: ordered against its other launches like
+ * bmpc_solve_batch.  BMPC_ERR_ARG on NULL p / x / cert or B < 1.  bmpc_kkt_batch_host: the same with HOST pointers -- staged copies on a stream
+ * of the handle, one synchronisation. */
+enum { BMPC_KKT_E = 0, BMPC_KKT_DUAL = 1, BMPC_KKT_PRIM_EQ = 2, BMPC_KKT_PRIM_INEQ = 3, BMPC_KKT_COMPL = 4, BMPC_KKT_LAM_EQ_GAP = 5,
+       BMPC_KKT_LAM_INEQ_GAP = 6, BMPC_KKT_F = 7, BMPC_KKT_LEN = 8 };
+int bmpc_kkt_len(void);      /* BMPC_KKT_LEN */
+int bmpc_kkt_batch(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert,
+                   double *g, double *lam_g, double *rj, void *hip_stream);
+int bmpc_kkt_batch_host(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert,
+                        double *g, double *lam_g, double *rj);
+
 /* The same step captured once into a hipGraph and replayed per tick: buffers are fixed at capture time, the caller refreshes their contents.
  * Launches of one handle (direct or replayed) share its workspace: the library orders them against each other with an event whatever streams the
  * caller uses (exception: a launch on a stream the CALLER is capturing neither waits for nor records that event).  A graph keeps the workspace and
