@@ -14,7 +14,8 @@ SYMBOLS = ["bmpc_default_options", "bmpc_default_options_for", "bmpc_error_strin
            "bmpc_graph_launch", "bmpc_graph_destroy", "bmpc_stream_lengths", "bmpc_stream_pack", "bmpc_stream_pack_rt", "bmpc_stream_post",
            "bmpc_stream_graph_create", "bmpc_set_latency_buffer", "bmpc_stream_set_rt_feasibility_tol", "bmpc_stream_tick", "bmpc_set_team_waves", "bmpc_team_info", "bmpc_stream_set_time_budget",
            "bmpc_set_restoration", "bmpc_get_restoration", "bmpc_options_size", "bmpc_build_hash", "bmpc_set_start_rollout", "bmpc_get_start_rollout", "bmpc_set_queue_order", "bmpc_get_queue_order", "bmpc_stream_set_rt_position_row_cap", "bmpc_set_barrier_hold", "bmpc_stream_set_level_rule", "bmpc_set_second_attempt", "bmpc_get_second_attempt",
-           "bmpc_state_from_multipliers", "bmpc_solve_batch_host_dual", "bmpc_kkt_len", "bmpc_kkt_batch", "bmpc_kkt_batch_host"]
+           "bmpc_state_from_multipliers", "bmpc_solve_batch_host_dual", "bmpc_kkt_len", "bmpc_kkt_batch", "bmpc_kkt_batch_host",
+           "bmpc_sens_len", "bmpc_sens_batch", "bmpc_sens_batch_host"]
 
 
 class Options(ctypes.Structure):
@@ -99,6 +100,10 @@ def load():
             lib.bmpc_kkt_len.argtypes = []
             lib.bmpc_kkt_batch.argtypes = [vp, ci] + [vp] * 9
             lib.bmpc_kkt_batch_host.argtypes = [vp, ci] + [vp] * 8
+        if hasattr(lib, "bmpc_sens_batch"):      # parametric sensitivity of the solution
+            lib.bmpc_sens_len.argtypes = []
+            lib.bmpc_sens_batch.argtypes = [vp, ci] + [vp] * 5 + [cd] + [vp] * 5
+            lib.bmpc_sens_batch_host.argtypes = [vp, ci] + [vp] * 5 + [cd] + [vp] * 4
         if hasattr(lib, "bmpc_stream_set_rt_position_row_cap"):
             lib.bmpc_stream_set_rt_position_row_cap.argtypes = [vp, cd]
         lib.bmpc_build_hash.restype = ctypes.c_char_p

@@ -16,6 +16,7 @@
 #include "bmpc_stream.inl"
 #include "bmpc_dual.inl"
 #include "bmpc_kkt.inl"
+#include "bmpc_sens.inl"
 
 typedef KArgsT<bmpc::Opts> KArgs;
 #ifndef BMPC_TEAM_NW
@@ -132,6 +133,37 @@ __global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_kkt_kernel(KktArgs
     }
 }
 
+// Parametric sensitivity of the solution (bmpc_sens.inl; include/boundmpc_hip.h bmpc_sens_batch).  The launch shape of the two kernels above: one wave
+// per problem over the handle's resident waves and workspace slabs, striding over the batch.
+static_assert(bmpc::SENS_LEN == BMPC_SENS_LEN && bmpc::SENS_STATUS == BMPC_SENS_STATUS && bmpc::SENS_DELTA == BMPC_SENS_DELTA && bmpc::SENS_RHS == BMPC_SENS_RHS
+              && bmpc::SENS_DX == BMPC_SENS_DX, "record slots of the header and of the wave program");
+struct SensArgs {
+    int N, S, B; double h; bmpc::Opts o; double mu;
+    const double *p, *x, *lam_g0, *lam_x0, *dp; double *dx, *dlam_eq, *dnu, *rec;
+    double *scratch; long long scr_stride;
+};
+template <bool ZLDS>
+__global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_sens_kernel(SensArgs a) {
+    __shared__ double lds[bmpc::L_SIZE];
+    bmpc::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = bmpc::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride); W.wv = 0;
+    W.deadline = 0; W.it_base = 0;
+#ifdef BMPC_PROFILE
+    if (threadIdx.x < 32) ((long long *)(lds + bmpc::L_PROF))[threadIdx.x] = 0;
+    __syncthreads();
+    W.tprev = clock64();
+#endif
+    const int np = 141 + 91 * a.S, nw = a.N * bmpc::NZ, ng = a.N * bmpc::NG, ne = a.N * bmpc::NE, ni = a.N * bmpc::NI;
+    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
+        bmpc::SensIn d;
+        d.p = a.p + (long long)b * np; d.x = a.x + (long long)b * nw; d.dp = a.dp + (long long)b * np; d.mu = a.mu; d.dx = a.dx + (long long)b * nw;
+        d.lam_g0 = a.lam_g0 ? a.lam_g0 + (long long)b * ng : nullptr; d.lam_x0 = a.lam_x0 ? a.lam_x0 + (long long)b * nw : nullptr;
+        d.dlam_eq = a.dlam_eq ? a.dlam_eq + (long long)b * ne : nullptr; d.dnu = a.dnu ? a.dnu + (long long)b * ni : nullptr;
+        d.rec = a.rec ? a.rec + (long long)b * bmpc::SENS_LEN : nullptr;
+        bmpc::wave_sensitivity<ZLDS>(W, d);
+        __syncthreads();
+    }
+}
+
 // (members without an initialiser start at zero / NULL: bmpc_create value-initialises the handle)
 struct bmpc_handle {
     int N, S; double h; bmpc_options o;
@@ -162,6 +194,7 @@ struct bmpc_handle {
     double *stage_d, *stage_h; int stage_cap;   // device and pinned host staging of the host-buffer path (bmpc_solve_batch_host)
     double *stage_state; int stage_state_cap;   // device dual state of the host-buffer path with multipliers (bmpc_solve_batch_host_dual)
     double *kkt_d, *kkt_h; int kkt_cap;         // device and pinned host staging of the host-buffer certificate (bmpc_kkt_batch_host)
+    double *sens_d, *sens_h; int sens_cap;      // the same of the host-buffer sensitivity (bmpc_sens_batch_host)
 };
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "boundmpc_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return BMPC_ERR_HIP; } } while (0)
@@ -205,6 +238,7 @@ static void handle_release(bmpc_handle *h) {
     if (h->own_stream) hipStreamDestroy(h->own_stream);
     hipFree(h->scratch); hipFree(h->counter); hipFree(h->aux_int); hipFree(h->qkey); hipFree(h->qorder); hipFree(h->prof); hipFree(h->stage_d); if (h->stage_h) hipHostFree(h->stage_h); hipFree(h->stage_state);
     hipFree(h->kkt_d); if (h->kkt_h) hipHostFree(h->kkt_h);
+    hipFree(h->sens_d); if (h->sens_h) hipHostFree(h->sens_h);
     delete h;
 }
 
@@ -602,6 +636,77 @@ extern "C" int bmpc_kkt_batch_host(bmpc_handle *h, int B, const double *p, const
         if (g) memcpy(g, hg, b * ng * sizeof(double));
         if (lam_g) memcpy(lam_g, hlg, b * ng * sizeof(double));
         if (rj) memcpy(rj, hrj, b * nj * sizeof(double));
+    }
+#undef TRY
+    return rc;
+}
+
+// ---- parametric sensitivity of the solution (bmpc_sens.inl) ----
+// enqueues the sensitivity kernel on `st`, ordered against the handle's other launches like enqueue_kkt
+static int enqueue_sens(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, const double *dp, double mu,
+                        double *dx, double *dlam_eq, double *dnu, double *rec, hipStream_t st) {
+    if (h->closed) return BMPC_ERR_ARG;
+    const int grid = B < h->grid ? B : h->grid;
+    if (grid > h->scr_waves) return BMPC_ERR_ARG;
+    { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
+    const KArgs k = handle_kargs(h, B, 0);
+    SensArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h; a.o = k.o; a.mu = mu > 0.0 ? mu : h->o.tol * h->o.mu_min_fac;
+    a.p = p; a.x = x; a.lam_g0 = lam_g0; a.lam_x0 = lam_x0; a.dp = dp; a.dx = dx; a.dlam_eq = dlam_eq; a.dnu = dnu; a.rec = rec;
+    a.scratch = h->scratch; a.scr_stride = h->scr_stride;
+    if (h->N <= 11 && h->S <= bmpc::SMAX_ZLDS) hipLaunchKernelGGL(bmpc_sens_kernel<true>, dim3(grid), dim3(64), 0, st, a);      // iterate in LDS
+    else hipLaunchKernelGGL(bmpc_sens_kernel<false>, dim3(grid), dim3(64), 0, st, a);                                          // iterate in the workspace
+    HIPCHK(hipGetLastError());
+    return order_after(h, st);
+}
+extern "C" int bmpc_sens_len(void) { return BMPC_SENS_LEN; }
+extern "C" int bmpc_sens_batch(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g, const double *lam_x, const double *dp,
+                               double mu, double *dx, double *dlam_eq, double *dnu, double *rec, void *hip_stream) {
+    if (!h || B < 1 || !p || !x || !dp || !dx) return BMPC_ERR_ARG;
+    { const int rc_ = ensure_scratch(h, B < h->grid ? B : h->grid); if (rc_ != BMPC_OK) return rc_; }
+    return enqueue_sens(h, B, p, x, lam_g, lam_x, dp, mu, dx, dlam_eq, dnu, rec, (hipStream_t)hip_stream);
+}
+// host-buffer sensitivity: one staging record [p | x | dp | lam_g | lam_x] in, [dx | dlam_eq | dnu | rec] out -- one host-to-device copy, the launch,
+// one device-to-host copy and one stream synchronisation, on the handle's own non-blocking stream (as bmpc_kkt_batch_host)
+extern "C" int bmpc_sens_batch_host(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g, const double *lam_x, const double *dp,
+                                    double mu, double *dx, double *dlam_eq, double *dnu, double *rec) {
+    if (!h || B < 1 || !p || !x || !dp || !dx) return BMPC_ERR_ARG;
+    if (h->closed) return BMPC_ERR_ARG;
+    const size_t np = 141 + 91 * h->S, nw = (size_t)h->N * 44, ng = (size_t)h->N * 43, ne = (size_t)h->N * 36, ni = (size_t)h->N * 57, b = (size_t)B;
+    const size_t n_in = b * (2 * np + 2 * nw + ng), n_out = b * (nw + ne + ni + BMPC_SENS_LEN);
+    if (B > h->sens_cap) {
+        DevGuard dg(h->dev);
+        wait_for_handle(h);
+        if (h->sens_d) { hipFree(h->sens_d); h->sens_d = nullptr; }
+        if (h->sens_h) { hipHostFree(h->sens_h); h->sens_h = nullptr; }
+        h->sens_cap = 0;
+        if (hipMalloc(&h->sens_d, (n_in + n_out) * sizeof(double)) != hipSuccess || hipHostMalloc(&h->sens_h, (n_in + n_out) * sizeof(double), hipHostMallocDefault) != hipSuccess) {
+            hipFree(h->sens_d); if (h->sens_h) hipHostFree(h->sens_h); h->sens_d = nullptr; h->sens_h = nullptr;
+            return BMPC_ERR_HIP;
+        }
+        h->sens_cap = B;
+    }
+    double *d_p = h->sens_d, *d_x = d_p + b * np, *d_dp = d_x + b * nw, *d_lg = d_dp + b * np, *d_lx = d_lg + b * ng, *d_dx = d_lx + b * nw, *d_dl = d_dx + b * nw, *d_dn = d_dl + b * ne, *d_rc = d_dn + b * ni;
+    double *h_p = h->sens_h, *h_x = h_p + b * np, *h_dp = h_x + b * nw, *h_lg = h_dp + b * np, *h_lx = h_lg + b * ng, *h_dx = h_lx + b * nw, *h_dl = h_dx + b * nw, *h_dn = h_dl + b * ne, *h_rc = h_dn + b * ni;
+    int rc = BMPC_OK;
+#define TRY(x) do { if (rc == BMPC_OK && (x) != hipSuccess) rc = BMPC_ERR_HIP; } while (0)
+    hipStream_t hs = nullptr;
+    {
+        DevGuard dg(h->dev);
+        if (!h->own_stream && hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return BMPC_ERR_HIP;
+        hs = h->own_stream;
+    }
+    memcpy(h_p, p, b * np * sizeof(double)); memcpy(h_x, x, b * nw * sizeof(double)); memcpy(h_dp, dp, b * np * sizeof(double));
+    if (lam_g) memcpy(h_lg, lam_g, b * ng * sizeof(double)); else memset(h_lg, 0, b * ng * sizeof(double));
+    if (lam_x) memcpy(h_lx, lam_x, b * nw * sizeof(double)); else memset(h_lx, 0, b * nw * sizeof(double));
+    TRY(hipMemcpyAsync(d_p, h_p, n_in * sizeof(double), hipMemcpyHostToDevice, hs));
+    if (rc == BMPC_OK) rc = bmpc_sens_batch(h, B, d_p, d_x, lam_g ? d_lg : nullptr, lam_x ? d_lx : nullptr, d_dp, mu, d_dx, dlam_eq ? d_dl : nullptr, dnu ? d_dn : nullptr, d_rc, hs);
+    TRY(hipMemcpyAsync(h_dx, d_dx, n_out * sizeof(double), hipMemcpyDeviceToHost, hs));
+    TRY(hipStreamSynchronize(hs));
+    if (rc == BMPC_OK) {
+        memcpy(dx, h_dx, b * nw * sizeof(double));
+        if (dlam_eq) memcpy(dlam_eq, h_dl, b * ne * sizeof(double));
+        if (dnu) memcpy(dnu, h_dn, b * ni * sizeof(double));
+        if (rec) memcpy(rec, h_rc, b * BMPC_SENS_LEN * sizeof(double));
     }
 #undef TRY
     return rc;

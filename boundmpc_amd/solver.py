@@ -14,6 +14,9 @@ NZ, NG = 44, 43
 # slots of the KKT certificate record (include/boundmpc_hip.h BMPC_KKT_*), in order
 KKT_E, KKT_DUAL, KKT_PRIM_EQ, KKT_PRIM_INEQ, KKT_COMPL, KKT_LAM_EQ_GAP, KKT_LAM_INEQ_GAP, KKT_F = range(8)
 KKT_FIELDS = ("E", "dual", "prim_eq", "prim_ineq", "compl", "lam_eq_gap", "lam_ineq_gap", "f")
+# slots of the sensitivity record (include/boundmpc_hip.h BMPC_SENS_*), in order
+SENS_STATUS, SENS_DELTA, SENS_RHS, SENS_DX = range(4)
+SENS_FIELDS = ("status", "delta", "rhs", "dx_max")
 
 
 class BatchedOCPSolver:
@@ -307,6 +310,78 @@ class BatchedOCPSolver:
             o[k] = o["cert"][:, i]
         return o
 
+    # ---- parametric sensitivity of the solution (bmpc_sens_batch) ----
+    def sensitivity(self, p, x, dp, lam_g=None, lam_x=None, mu=None, stream=None, want_duals=False):
+        """The tangent of the solution along a direction of the parameter vector: p [B][n_p], x [B][n_w], multipliers in CasADi's convention
+        lam_g [B][n_g] / lam_x [B][n_w] (None or 0: zeros) -- usually a solve's outputs -- and dp [B][n_p] or [B][D][n_p] (D directions per problem:
+        the point is tiled to B D rows and the results come back as [B][D][...]); float64 contiguous GPU tensors.  mu: the barrier level of the
+        system (None: options.tol * options.mu_min_fac, the last level of a solve).  Returns a dict: "dx" [B](, D)[n_w], "rec" [B](, D)[4] (status,
+        delta, max |rhs|, max |dx|: SENS_FIELDS) and, with want_duals, "dlam_eq" [..][36 N] and "dnu" [..][57 N].  The system, the record and the
+        rules for non-finite input: include/boundmpc_hip.h bmpc_sens_batch.  Asynchronous on `stream`; ordered against the handle's solves."""
+        import torch
+        lam_g = None if (lam_g is None or (isinstance(lam_g, (int, float)) and lam_g == 0)) else lam_g
+        lam_x = None if (lam_x is None or (isinstance(lam_x, (int, float)) and lam_x == 0)) else lam_x
+        B = self._check_io(p, x, None)
+        self._check_multipliers(B, lam_g, lam_x, p.device)
+        if not (dp.is_cuda and dp.dtype == torch.float64 and dp.is_contiguous() and dp.device == p.device and dp.dim() in (2, 3) and dp.shape[0] == B
+                and dp.shape[-1] == self.n_p):
+            raise ValueError(f"dp must be a contiguous float64 GPU tensor of shape ({B}, {self.n_p}) or ({B}, D, {self.n_p}) on {p.device}")
+        D = dp.shape[1] if dp.dim() == 3 else None
+        if D is not None:
+            if D < 1:
+                raise ValueError("dp has no directions")
+            tile = lambda t: None if t is None else t.repeat_interleave(D, dim=0).contiguous()
+            p, x, lam_g, lam_x, dp = tile(p), tile(x), tile(lam_g), tile(lam_x), dp.reshape(B * D, self.n_p)
+        R = p.shape[0]
+        dev = p.device
+        o = {"dx": torch.empty((R, self.n_w), dtype=torch.float64, device=dev), "rec": torch.empty((R, len(SENS_FIELDS)), dtype=torch.float64, device=dev)}
+        if want_duals:
+            o["dlam_eq"] = torch.empty((R, 36 * self.N), dtype=torch.float64, device=dev)
+            o["dnu"] = torch.empty((R, 57 * self.N), dtype=torch.float64, device=dev)
+        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
+        _lib.check(self._lib.bmpc_sens_batch(self._h, R, ptr(p), ptr(x), ptr(lam_g), ptr(lam_x), ptr(dp), float(mu or 0.0), ptr(o["dx"]), ptr(o.get("dlam_eq")),
+                                             ptr(o.get("dnu")), ptr(o["rec"]), ctypes.c_void_p(st.cuda_stream)), "bmpc_sens_batch")
+        self._inflight_sens = (p, x, lam_g, lam_x, dp, o)      # (asynchronous launch: see solve_batch)
+        if D is not None:
+            o = {k: v.view(B, D, v.shape[-1]) for k, v in o.items()}
+        return o
+
+    def sensitivity_host(self, p, x, dp, lam_g=None, lam_x=None, mu=None, want_duals=False):
+        """sensitivity with numpy in / out (bmpc_sens_batch_host: staged copies, one synchronisation)."""
+        p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
+        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
+        dp = np.ascontiguousarray(dp, dtype=np.float64)
+        dp = dp[None, :] if dp.ndim == 1 else dp
+        B = p.shape[0]
+        if p.shape != (B, self.n_p) or x.shape != (B, self.n_w) or dp.ndim not in (2, 3) or dp.shape[0] != B or dp.shape[-1] != self.n_p:
+            raise ValueError(f"shape mismatch: p {p.shape} x {x.shape} dp {dp.shape}")
+        lam = []
+        for a, n, nm in ((lam_g, self.n_g, "lam_g"), (lam_x, self.n_w, "lam_x")):
+            if a is not None and not (np.isscalar(a) and a == 0):
+                a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
+                if a.shape != (B, n):
+                    raise ValueError(f"{nm} has shape {a.shape}, expected {(B, n)}")
+            else:
+                a = None
+            lam.append(a)
+        D = dp.shape[1] if dp.ndim == 3 else None
+        if D is not None:
+            if D < 1:
+                raise ValueError("dp has no directions")
+            tile = lambda a: None if a is None else np.ascontiguousarray(np.repeat(a, D, axis=0))
+            p, x, lam, dp = tile(p), tile(x), [tile(a) for a in lam], np.ascontiguousarray(dp.reshape(B * D, self.n_p))
+        R = p.shape[0]
+        o = {"dx": np.zeros((R, self.n_w)), "rec": np.zeros((R, len(SENS_FIELDS)))}
+        if want_duals:
+            o["dlam_eq"], o["dnu"] = np.zeros((R, 36 * self.N)), np.zeros((R, 57 * self.N))
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
+        _lib.check(self._lib.bmpc_sens_batch_host(self._h, R, vp(p), vp(x), vp(lam[0]), vp(lam[1]), vp(dp), float(mu or 0.0), vp(o["dx"]), vp(o.get("dlam_eq")),
+                                                  vp(o.get("dnu")), vp(o["rec"])), "bmpc_sens_batch_host")
+        if D is not None:
+            o = {k: v.reshape(B, D, v.shape[-1]) for k, v in o.items()}
+        return o
+
     # ---- batched device solve ----
     def solve_batch(self, p, x0, out=None, want=("g", "lam_g", "lam_x", "f", "iters", "status", "kkt"), stream=None, state=None, max_iter=0,
                     lam_g0=None, lam_x0=None):
@@ -494,6 +569,21 @@ class NlpSolverShim:
         lg, lx = self._multiplier(sol.get("lam_g"), self._s.n_g, "lam_g"), self._multiplier(sol.get("lam_x"), self._s.n_w, "lam_x")
         c = self._s.certify_host(p_, x, lam_g=lg, lam_x=lx)
         return {k: float(c[k][0]) for k in KKT_FIELDS}
+
+    def sensitivity(self, dp, sol=None):
+        """Tangent of the solution along dp (flat [n_p] or [D][n_p]) for the parameter vector of the LAST call, at a CasADi-style result `sol`
+        (default: the last solution), like certificate().  Returns {'dx': [n_w] or [D][n_w], 'rec': ...} (BatchedOCPSolver.sensitivity_host)."""
+        if getattr(self, "_last", None) is None:
+            raise RuntimeError("sensitivity() needs a previous solver(...) call: it differentiates that call's solution with respect to its p")
+        p_, last = self._last
+        sol = last if sol is None else sol
+        x = np.asarray(sol["x"], dtype=float).ravel()[None, :]
+        lg, lx = self._multiplier(sol.get("lam_g"), self._s.n_g, "lam_g"), self._multiplier(sol.get("lam_x"), self._s.n_w, "lam_x")
+        dp = np.asarray(dp, dtype=float)
+        one = dp.ndim == 1 or (dp.ndim == 2 and dp.shape[1] == 1)
+        d3 = dp.reshape(1, 1, -1) if one else dp.reshape(1, dp.shape[0], -1)
+        o = self._s.sensitivity_host(p_, x, d3, lam_g=lg, lam_x=lx)
+        return {k: (v[0, 0] if one else v[0]) for k, v in o.items()}
 
     @staticmethod
     def _multiplier(v, n, name):

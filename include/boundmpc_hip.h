@@ -154,6 +154,44 @@ int bmpc_kkt_batch(bmpc_handle *h, int B, const double *p, const double *x, cons
 int bmpc_kkt_batch_host(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert,
                         double *g, double *lam_g, double *rj);
 
+/* Parametric sensitivity of the solution: how (x, multipliers) move when the parameter vector moves along dp -- the tangent an nlpsol Function
+ * offers with respect to p, for advanced-step corrections between ticks, linear feedback around a plan, derivatives of a closed loop.  Per problem
+ * take a primal-dual point (x, lam_g, lam_x) in CasADi's convention (a solve's outputs, Ipopt's answer, ...), p, a direction dp [n_p] and a
+ * barrier level mu > 0.  Internal quantities: nu [57 N], lam_g[36:43] / lam_x mapped by the map of bmpc_state_from_multipliers (pos(), tube pair
+ * lam (wd +- c), cap 1e12, non-finite -> 0), exactly as bmpc_kkt_batch does; LAM [36 N], the equality multipliers RECOMPUTED by the adjoint sweep
+ * (lam_g[0:36] is never trusted); the slack of internal row i, s_i = max(-h_i(x, p), mu / max(nu_i, mu)) -- a point carries no slacks; this is
+ * -h_i on a converged interior-point answer and stays positive on an active or slightly violated row --; Sigma_i = nu_i / s_i.
+ * The tangent (dx, dLAM, dnu) solves the linearised perturbed barrier KKT system at that point, d/dt along p + t dp, with the Hessian choice of
+ * the handle (options.exact_hessian):
+ *     H dx + Jg^T dLAM + Jh^T dnu = - d/dt grad_x L(x, LAM, nu; p + t dp)
+ *     Jg dx                       = - d/dt g_eq(x; p + t dp)                       (36 N equalities)
+ *     dnu_i                       =   Sigma_i (Jh dx + d/dt h(x; p + t dp))_i      (57 N internal rows, slack eliminated)
+ * At a converged solution with mu its last barrier level (options.tol * options.mu_min_fac) this is the derivative of the solver's own solution
+ * map.  One Riccati factorisation at (x, nu, p) with the inertia rule of a solver iteration, one forward sweep.  The d/dt terms are central
+ * differences of the kernel's own residual evaluation at p +- eps dp with x, nu, s held fixed, eps = 1e-6 max(1, |p|_inf) / |dp|_inf: they carry
+ * the rounding of a difference (measured 1e-10 .. 6e-7 of max |dx|: DESIGN.md 4g).  dp = 0 takes the step 0 and gives dx = 0 exactly; the step is
+ * capped at 1e300.  NO TANGENT exists along the segment switches: the entries phi_switch of p (offset 53 + 9 S, S + 1 of them) select the path
+ * segment by comparison, a piecewise-constant condition without a derivative (as in CasADi); a dp with non-zero entries there is differenced
+ * across a jump or not at all, and the result is meaningless.  Leave those entries of dp at zero.
+ * Record rec[b][BMPC_SENS_LEN] (doubles):
+ *   BMPC_SENS_STATUS  0: factorised with delta = 0.  1: regularised -- the tangent is that of H + delta I.  3: no factorisation, or a non-finite
+ *                     entry of x, p or dp (or a non-finite right-hand side): dx (and dlam_eq, dnu) are NaN then; never a fault
+ *   BMPC_SENS_DELTA   the delta of status 1, else 0
+ *   BMPC_SENS_RHS     max |right-hand side|: the largest of |d/dt h|, |d/dt g_eq| and the jerk part of |d/dt grad_x L| with the states eliminated
+ *   BMPC_SENS_DX      max |dx|
+ * Buffers: dp [B][n_p]; dx [B][44 N] (required); dlam_eq [B][36 N], dnu [B][57 N] (internal rows, the order of the dual state) and rec may be
+ * NULL.  dlam_eq costs a second pair of evaluations: the adjoint's multipliers differenced along the whole tangent (x, nu, p); it satisfies the
+ * stationarity rows with the exact Hessian and delta = 0.  mu <= 0: options.tol * options.mu_min_fac.  lam_g [B][43 N] / lam_x [B][44 N] may be
+ * NULL (= zeros).  DEVICE pointers; outputs must not overlap inputs.  Uses the handle's workspace: ordered against its other launches like
+ * bmpc_solve_batch.  BMPC_ERR_ARG on NULL p / x / dp / dx or B < 1.  bmpc_sens_batch_host: the same with HOST pointers -- staged copies on a
+ * stream of the handle, one synchronisation. */
+enum { BMPC_SENS_STATUS = 0, BMPC_SENS_DELTA = 1, BMPC_SENS_RHS = 2, BMPC_SENS_DX = 3, BMPC_SENS_LEN = 4 };
+int bmpc_sens_len(void);      /* BMPC_SENS_LEN */
+int bmpc_sens_batch(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g, const double *lam_x, const double *dp, double mu,
+                    double *dx, double *dlam_eq, double *dnu, double *rec, void *hip_stream);
+int bmpc_sens_batch_host(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g, const double *lam_x, const double *dp,
+                         double mu, double *dx, double *dlam_eq, double *dnu, double *rec);
+
 /* The same step captured once into a hipGraph and replayed per tick: buffers are fixed at capture time, the caller refreshes their contents.
  * Launches of one handle (direct or replayed) share its workspace: the library orders them against each other with an event whatever streams the
  * caller uses (exception: a launch on a stream the CALLER is capturing neither waits for nor records that event).  A graph keeps the workspace and
