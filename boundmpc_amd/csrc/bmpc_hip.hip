@@ -4,6 +4,7 @@
 // set + per-wave global scratch slab (see bmpc_wave.inl for the algorithm and the lane maps).
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -531,10 +532,22 @@ static int enqueue_solve(bmpc_handle *h, int B, const double *p, const double *x
     return BMPC_OK;
 }
 
+// The second attempt of a stateless solve (wave_solve_retry) reads x0 again after the first attempt has written x: with retry_cap > 0 an output
+// that overlaps the start would hand the second attempt the failed iterate.  (With the cap at 0 in-place solves are fine: x0 is read in full first.)
+static bool second_attempt_rereads_x0(const bmpc_handle *h, int B, const double *x0, const double *x) {
+    if (h->retry_cap <= 0) return false;
+    const size_t n = (size_t)B * h->N * bmpc::NZ * sizeof(double);
+    const uintptr_t a = (uintptr_t)x, b = (uintptr_t)x0;
+    const bool overlap = a < b + n && b < a + n;
+    if (overlap) fprintf(stderr, "boundmpc_hip: x overlaps x0 while the second attempt is on (bmpc_set_second_attempt): it reads x0 again after x is written\n");
+    return overlap;
+}
+
 extern "C" int bmpc_solve_batch(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
                                 double *f, int *iters, int *status, double *kkt, void *hip_stream) {
     if (!h || B < 0 || (B > 0 && (!p || !x0 || !x))) return BMPC_ERR_ARG;
     if (B == 0) return BMPC_OK;
+    if (second_attempt_rereads_x0(h, B, x0, x)) return BMPC_ERR_ARG;
     { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
     return enqueue_solve(h, B, p, x0, nullptr, 0, x, g, lam_g, lam_x, f, iters, status, kkt, (hipStream_t)hip_stream, h->timing != 0);
 }
@@ -739,6 +752,7 @@ static int capture_graph(bmpc_handle *h, bmpc_graph **out, ENQUEUE enqueue) {
 extern "C" int bmpc_graph_create(bmpc_handle *h, int B, const double *p, const double *x0, double *state, int max_iter, double *x, double *g,
                                  double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt, bmpc_graph **out) {
     if (!h || !out || B < 1 || max_iter < 0 || !p || !x0 || !x) return BMPC_ERR_ARG;
+    if (!state && second_attempt_rereads_x0(h, B, x0, x)) return BMPC_ERR_ARG;
     { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
     return capture_graph(h, out, [&](hipStream_t cs) { return enqueue_solve(h, B, p, x0, state, max_iter, x, g, lam_g, lam_x, f, iters, status, kkt, cs, false, true); });
 }

@@ -21,7 +21,7 @@ BMPC_SOLVE_KERNEL(KArgs a) {
         if ((unsigned)b >= (unsigned)a.B) break;             // every wave of every workgroup reaches this exit: the queue is finite
         BMPC_PROBLEM(pr, a, b);
         const long long t0_ = a.latency_us ? (long long)wall_clock64() : 0;
-        BMPC_NAMESPACE::wave_solve<true>(W, pr);      // no second attempt of a status-2 solve here, unlike the one-wave kernel's wave_solve_retry
+        BMPC_NAMESPACE::wave_solve_retry<true>(W, pr);      // with the second attempt of a status-2 stateless solve, like the one-wave kernel (one more trip of a loop; nothing when retry_cap == 0)
         __syncthreads();
         if (a.rcount && threadIdx.x == 0 && *pr.status == 4) atomicAdd(a.rcount, 1);      // jammed: the (one-wave) restoration kernel continues it (bmpc_resto.hip)
         if (a.latency_us && threadIdx.x == 0) a.latency_us[b] = (double)((long long)wall_clock64() - t0_) * 0.01;   // constant 100 MHz counter

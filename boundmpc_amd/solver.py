@@ -128,7 +128,9 @@ class BatchedOCPSolver:
     def set_second_attempt(self, cap):
         """Iterations of the SECOND ATTEMPT of a stateless solve that ends with status 2: once more from x0 on the barrier start of the short horizons
         (mu 0.1, slacks pushed to 1e-2); iterations add up, a second attempt that hits its cap keeps status 2.  Default 100 for N > 11 (on BASELINE
-        configs[3] 22 of the 26 status-2 problems are feasible and converge this way), 0 = off for shorter horizons (include/boundmpc_hip.h)."""
+        configs[3] 22 of the 26 status-2 problems are feasible and converge this way), 0 = off for shorter horizons (include/boundmpc_hip.h).  Holds on
+        every launch shape (one wave per problem, pairs, teams: set_team_waves) and with every restoration mode.  With cap > 0 the output x of
+        bmpc_solve_batch must not overlap x0 (the second attempt reads x0 again): an overlapping call is refused; solve_batch allocates its own x."""
         _lib.check(self._lib.bmpc_set_second_attempt(self._h, int(cap)), "bmpc_set_second_attempt")
 
     def get_second_attempt(self):

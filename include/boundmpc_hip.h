@@ -86,7 +86,11 @@ int bmpc_num_params(const bmpc_handle *h);  /* 141 + 91 S */
 int bmpc_get_bounds(const bmpc_handle *h, double *lbx, double *ubx, double *lbg, double *ubg);
 
 /* DEVICE pointers; g, lam_g, lam_x, f, iters, status, kkt may be NULL.  hip_stream: hipStream_t to launch on (NULL = default stream).
- * Asynchronous w.r.t. the host. */
+ * Asynchronous w.r.t. the host.
+ * x and x0: with the second attempt off (bmpc_set_second_attempt cap 0, the default for N <= 11) x may be x0 itself -- a problem's x0 is read in
+ * full before its x is written, so an in-place solve gives the out-of-place results bit for bit.  With cap > 0 the second attempt reads x0 AGAIN
+ * after the first attempt has written x: the ranges [x, x + 44 N B) and [x0, x0 + 44 N B) must not overlap, and the call returns BMPC_ERR_ARG
+ * (nothing launched) when they do.  The same holds for bmpc_graph_create without a state.  bmpc_solve_batch_host stages its own copies. */
 int bmpc_solve_batch(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
                      double *f, int *iters, int *status, double *kkt, void *hip_stream);
 
@@ -299,7 +303,9 @@ int bmpc_get_queue_order(const bmpc_handle *h);      /* 0 / 1; -1: no handle */
 /* Second attempt: a stateless solve (no dual state buffer) that ends with status 2 is run once more from x0 on the barrier start of the short horizons
  * (mu_init 0.1, slacks pushed to 1e-2) for at most `cap` iterations; `iters` is the sum of both attempts, a second attempt that runs into its cap keeps
  * status 2.  cap = 0: off.  Default 100 for N > 11, 0 for shorter horizons.  (What Ipopt users do by hand with another mu_init; the reference has no
- * counterpart: BoundMPC.py:465-489 reports the failure.) */
+ * counterpart: BoundMPC.py:465-489 reports the failure.)  The rule holds on every launch shape -- one wave per problem, pairs and teams
+ * (bmpc_set_team_waves) -- and with every restoration mode: status and iters do not depend on the batch size.  With cap > 0 the output x of a
+ * stateless device solve must not overlap its x0 (bmpc_solve_batch). */
 int bmpc_set_second_attempt(bmpc_handle *h, int cap);
 int bmpc_get_second_attempt(const bmpc_handle *h);      /* cap; -1: no handle */
 
