@@ -80,4 +80,16 @@ BMPC_D inline void wave_state_from_multipliers(Wave &W, const DualIn &d) {
     WIDE_END
 }
 
+// B problems back to back in every array (NULL stays NULL): what a service launch gets (bmpc_hip.hip) and what the emulator host is called with
+struct DualBatch {
+    const double *p, *x0, *lam_g, *lam_x; double *state; double mu;
+    BMPC_HD DualIn problem(int N, int S, long long b) const {      // problem b of the batch
+        const long long np = 141 + 91 * S, nw = N * NZ, ng = N * NG;
+        DualIn d; d.p = p + b * np; d.x0 = x0 + b * nw; d.state = state + b * (N * NI + 2); d.mu = mu;
+        d.lam_g = lam_g ? lam_g + b * ng : nullptr; d.lam_x = lam_x ? lam_x + b * nw : nullptr;
+        return d;
+    }
+    template <bool ZLDS> BMPC_D void run(Wave &W, int b) const { wave_state_from_multipliers<ZLDS>(W, problem(W.N, W.S, b)); }
+};
+
 }  // namespace BMPC_NAMESPACE

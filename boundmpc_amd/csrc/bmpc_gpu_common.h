@@ -1,9 +1,11 @@
 // bmpc_gpu_common.h -- what the translation units of libboundmpc_hip.so share: the device math macros the wave program
 // (bmpc_wave.inl) is written in, its lane and phase macros (one set per BMPC_NW: one wave, or a workgroup of cooperating waves), the phase
-// stamps, the per-problem slicing of a batch kernel's arguments, and the kernel argument records.  The kernel entry texts shared between
-// units are bmpc_multi_batch.inl (the batch kernel of the team and pair units) and bmpc_tick_kernel.inl (the fused tick of the one-wave tick
-// and team units).  bmpc_hip.hip holds the one-wave-per-problem batch kernel and the C ABI, bmpc_team.hip the team kernels (NW cooperating
-// waves per problem), bmpc_pair.hip the pair kernel, bmpc_resto.hip the restoration kernels, bmpc_tick.hip the one-wave fused ticks.
+// stamps, the prologue of a one-wave kernel, the per-problem slicing of a batch kernel's arguments, and the kernel argument records.  The
+// kernel entry texts shared between units are bmpc_multi_batch.inl (the batch kernel of the team and pair units) and bmpc_tick_kernel.inl (the
+// fused tick of the one-wave tick and team units).  bmpc_hip.hip holds the one-wave-per-problem batch kernel, the service kernel (one entry
+// over the jobs of bmpc_dual.inl, bmpc_kkt.inl and bmpc_sens.inl, each of which slices its own batch) and the C ABI, bmpc_team.hip the team
+// kernels (NW cooperating waves per problem), bmpc_pair.hip the pair kernel, bmpc_resto.hip the restoration kernels, bmpc_tick.hip the
+// one-wave fused ticks.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -74,6 +76,19 @@
 #define BMPC_PROF(W, id) asm volatile("s_nop 0 ; BMPCMARK " #id ::: "memory");
 #endif
 
+// Prologue of a kernel that runs one wave per workgroup (bmpc_hip.hip: solve and service kernels; bmpc_resto.hip): the wave `W` of this workgroup
+// from the argument head {N, S, h, o, scratch, scr_stride} of `a`, on the LDS array `lds` and on workspace slab blockIdx.x; in a unit that
+// stamps its phases (above) of a -DBMPC_PROFILE build also the zeroed stamp area and the first stamp.  A macro for the reason given below.
+#if defined(BMPC_PROFILE) && BMPC_STAMPS >= 1
+#define BMPC_WAVE_STAMP0(W, lds) if (threadIdx.x < 32) ((long long *)((lds) + BMPC_NAMESPACE::L_PROF))[threadIdx.x] = 0; __syncthreads(); W.tprev = clock64()
+#else
+#define BMPC_WAVE_STAMP0(W, lds) W.tprev = 0
+#endif
+#define BMPC_ONE_WAVE(W, a, lds) \
+    BMPC_NAMESPACE::Wave W; W.N = (a).N; W.S = (a).S; W.h = (a).h; W.o = (a).o; W.L = (lds); \
+    W.G = BMPC_NAMESPACE::make_gptr((a).scratch + (long long)blockIdx.x * (a).scr_stride); W.wv = 0; W.deadline = 0; W.it_base = 0; \
+    BMPC_WAVE_STAMP0(W, lds)
+
 // Problem `pr` = problem b of a batch kernel's arguments `a`: its slices of the inputs and of the outputs the caller passed (NULL stays NULL);
 // np, nw, ng: the lengths of a problem's parameter, variable and constraint vectors (computed once, ahead of the kernel's work loop).
 // A macro, expanded in the kernel body: the same lines as a function that takes `a` (by value or by reference) cost the argument loads their
@@ -100,6 +115,12 @@ struct KArgsT {
     long long budget_ticks;  // fused closed-loop tick only: time budget of a tick in counts of the 100 MHz wall clock, from kernel entry (0 = none)
     int *counter2, *rcount;  // restoration kernel (bmpc_resto.hip): its work queue; number of problems the batch kernel left with status 4 (NULL: phase off)
     const int *order;        // one-wave batch kernel: the work queue hands out order[0], order[1], ... instead of 0, 1, ... (NULL: natural order; bmpc_set_queue_order)
+};
+// kernel arguments of a service launch (bmpc_hip.hip bmpc_service_kernel): the head the wave needs, then the batch record of the job
+template <class OPTS, class JOB>
+struct ServiceArgsT {
+    int N, S, B; double h; OPTS o; double *scratch; long long scr_stride;
+    JOB job;
 };
 // stream arguments of a fused tick
 struct SArgs {

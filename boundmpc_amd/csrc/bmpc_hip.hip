@@ -30,14 +30,8 @@ typedef KArgsT<bmpc::Opts> KArgs;
 template <bool ZLDS>
 __global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_solve_kernel(KArgs a) {
     __shared__ double lds[bmpc::L_SIZE];
-    bmpc::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = bmpc::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride); W.wv = 0;
-    W.deadline = 0; W.it_base = 0;
+    BMPC_ONE_WAVE(W, a, lds);
     BMPC_STRIDES(a);
-#ifdef BMPC_PROFILE
-    if (threadIdx.x < 32) ((long long *)(lds + bmpc::L_PROF))[threadIdx.x] = 0;
-    __syncthreads();
-    W.tprev = clock64();
-#endif
     for (;;) {
         int b = 0;
         if (threadIdx.x == 0) b = atomicAdd(a.counter, 1);
@@ -76,91 +70,22 @@ __global__ void __launch_bounds__(256) queue_order_kernel(int B, const double *k
     if (i < B) order[r] = i;
 }
 
-// Primal-dual warm start (bmpc_dual.inl): the dual state of a warm solve from multipliers in CasADi's convention.  One wave per problem over the
-// handle's resident waves and workspace slabs; every problem costs one evaluation, so the waves stride over the batch (no work queue).
-struct DualArgs {
-    int N, S, B; double h; bmpc::Opts o;
-    const double *p, *x0, *lam_g, *lam_x; double *state; double mu;
-    double *scratch; long long scr_stride;
-};
-template <bool ZLDS>
-__global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_dual_kernel(DualArgs a) {
-    __shared__ double lds[bmpc::L_SIZE];
-    bmpc::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = bmpc::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride); W.wv = 0;
-    W.deadline = 0; W.it_base = 0;
-#ifdef BMPC_PROFILE
-    if (threadIdx.x < 32) ((long long *)(lds + bmpc::L_PROF))[threadIdx.x] = 0;
-    __syncthreads();
-    W.tprev = clock64();
-#endif
-    const int np = 141 + 91 * a.S, nw = a.N * bmpc::NZ, ng = a.N * bmpc::NG, sl = a.N * bmpc::NI + 2;
-    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-        bmpc::DualIn d;
-        d.p = a.p + (long long)b * np; d.x0 = a.x0 + (long long)b * nw; d.state = a.state + (long long)b * sl; d.mu = a.mu;
-        d.lam_g = a.lam_g ? a.lam_g + (long long)b * ng : nullptr; d.lam_x = a.lam_x ? a.lam_x + (long long)b * nw : nullptr;
-        bmpc::wave_state_from_multipliers<ZLDS>(W, d);
-        __syncthreads();
-    }
-}
-
-// KKT certificate of any primal-dual point (bmpc_kkt.inl; include/boundmpc_hip.h bmpc_kkt_batch).  The launch shape of the conversion kernel above: one wave
-// per problem over the handle's resident waves and workspace slabs, striding over the batch (an evaluation and an adjoint sweep per problem: no work queue).
+// Service kernel: the jobs that cost a problem a few evaluations, not a solve -- the dual state of a warm solve from multipliers (bmpc_dual.inl,
+// DualBatch), the KKT certificate of any primal-dual point (bmpc_kkt.inl, KktBatch), the parametric sensitivity of the solution (bmpc_sens.inl,
+// SensBatch).  One wave per problem over the handle's resident waves and workspace slabs, striding over the batch (no work queue); a job is the
+// batch record of its file, which slices out problem b and runs the wave program on it.
 static_assert(bmpc::KKT_LEN == BMPC_KKT_LEN && bmpc::KKT_E == BMPC_KKT_E && bmpc::KKT_DUAL == BMPC_KKT_DUAL && bmpc::KKT_PRIM_EQ == BMPC_KKT_PRIM_EQ
               && bmpc::KKT_PRIM_INEQ == BMPC_KKT_PRIM_INEQ && bmpc::KKT_COMPL == BMPC_KKT_COMPL && bmpc::KKT_LAM_EQ_GAP == BMPC_KKT_LAM_EQ_GAP
               && bmpc::KKT_LAM_INEQ_GAP == BMPC_KKT_LAM_INEQ_GAP && bmpc::KKT_F == BMPC_KKT_F, "record slots of the header and of the wave program");
-struct KktArgs {
-    int N, S, B; double h; bmpc::Opts o;
-    const double *p, *x, *lam_g0, *lam_x0; double *cert, *g, *lam_g, *rj;
-    double *scratch; long long scr_stride;
-};
-template <bool ZLDS>
-__global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_kkt_kernel(KktArgs a) {
-    __shared__ double lds[bmpc::L_SIZE];
-    bmpc::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = bmpc::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride); W.wv = 0;
-    W.deadline = 0; W.it_base = 0;
-#ifdef BMPC_PROFILE
-    if (threadIdx.x < 32) ((long long *)(lds + bmpc::L_PROF))[threadIdx.x] = 0;
-    __syncthreads();
-    W.tprev = clock64();
-#endif
-    const int np = 141 + 91 * a.S, nw = a.N * bmpc::NZ, ng = a.N * bmpc::NG, nj = a.N * bmpc::NU;
-    for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-        bmpc::KktIn d;
-        d.p = a.p + (long long)b * np; d.x = a.x + (long long)b * nw; d.cert = a.cert + (long long)b * bmpc::KKT_LEN;
-        d.lam_g0 = a.lam_g0 ? a.lam_g0 + (long long)b * ng : nullptr; d.lam_x0 = a.lam_x0 ? a.lam_x0 + (long long)b * nw : nullptr;
-        d.g = a.g ? a.g + (long long)b * ng : nullptr; d.lam_g = a.lam_g ? a.lam_g + (long long)b * ng : nullptr; d.rj = a.rj ? a.rj + (long long)b * nj : nullptr;
-        bmpc::wave_certify<ZLDS>(W, d);
-        __syncthreads();
-    }
-}
-
-// Parametric sensitivity of the solution (bmpc_sens.inl; include/boundmpc_hip.h bmpc_sens_batch).  The launch shape of the two kernels above: one wave
-// per problem over the handle's resident waves and workspace slabs, striding over the batch.
 static_assert(bmpc::SENS_LEN == BMPC_SENS_LEN && bmpc::SENS_STATUS == BMPC_SENS_STATUS && bmpc::SENS_DELTA == BMPC_SENS_DELTA && bmpc::SENS_RHS == BMPC_SENS_RHS
               && bmpc::SENS_DX == BMPC_SENS_DX, "record slots of the header and of the wave program");
-struct SensArgs {
-    int N, S, B; double h; bmpc::Opts o; double mu;
-    const double *p, *x, *lam_g0, *lam_x0, *dp; double *dx, *dlam_eq, *dnu, *rec;
-    double *scratch; long long scr_stride;
-};
-template <bool ZLDS>
-__global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_sens_kernel(SensArgs a) {
+static_assert(bmpc::NZ == 44 && bmpc::NG == 43 && bmpc::NE == 36 && bmpc::NI == 57 && bmpc::NU == 8, "the array lengths include/boundmpc_hip.h documents (44 N, 43 N, ...)");
+template <bool ZLDS, class JOB>
+__global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_service_kernel(ServiceArgsT<bmpc::Opts, JOB> a) {
     __shared__ double lds[bmpc::L_SIZE];
-    bmpc::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = bmpc::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride); W.wv = 0;
-    W.deadline = 0; W.it_base = 0;
-#ifdef BMPC_PROFILE
-    if (threadIdx.x < 32) ((long long *)(lds + bmpc::L_PROF))[threadIdx.x] = 0;
-    __syncthreads();
-    W.tprev = clock64();
-#endif
-    const int np = 141 + 91 * a.S, nw = a.N * bmpc::NZ, ng = a.N * bmpc::NG, ne = a.N * bmpc::NE, ni = a.N * bmpc::NI;
+    BMPC_ONE_WAVE(W, a, lds);
     for (int b = blockIdx.x; b < a.B; b += gridDim.x) {
-        bmpc::SensIn d;
-        d.p = a.p + (long long)b * np; d.x = a.x + (long long)b * nw; d.dp = a.dp + (long long)b * np; d.mu = a.mu; d.dx = a.dx + (long long)b * nw;
-        d.lam_g0 = a.lam_g0 ? a.lam_g0 + (long long)b * ng : nullptr; d.lam_x0 = a.lam_x0 ? a.lam_x0 + (long long)b * nw : nullptr;
-        d.dlam_eq = a.dlam_eq ? a.dlam_eq + (long long)b * ne : nullptr; d.dnu = a.dnu ? a.dnu + (long long)b * ni : nullptr;
-        d.rec = a.rec ? a.rec + (long long)b * bmpc::SENS_LEN : nullptr;
-        bmpc::wave_sensitivity<ZLDS>(W, d);
+        a.job.template run<ZLDS>(W, b);
         __syncthreads();
     }
 }
@@ -177,7 +102,7 @@ struct bmpc_handle {
     double rt_row_cap;       // real-time mode: a position tube row (l^2 - w^2, any stage) above this vetoes the iterate (bmpc_stream_set_rt_position_row_cap); 0 = off
     double rt_viol_tol = 1e-4;      // acceptance threshold of stream_post in real-time mode (flag bit 1); default = the reference's 1e-4
     double rt_budget_us;     // time budget of a fused tick (bmpc_stream_set_time_budget); 0 = none
-    hipStream_t own_stream;  // graph replays requested on the legacy null stream run here, bracketed by events (bmpc_graph_launch)
+    hipStream_t own_stream;  // handle_stream: host-buffer calls run here, and graph replays requested on the legacy null stream, bracketed by events (bmpc_graph_launch)
     int grid; long long scr_stride; double *scratch; int scr_waves; int graphs_alive; int *counter; unsigned long long *prof;
     int team_grid;           // resident TEAMS (workgroups of BMPC_TEAM_NW waves, bmpc_team.hip) of the device; 0: no team kernel for this handle (N > 10 or S > 4)
     int pair_grid;           // resident PAIRS (workgroups of 2 waves at two waves per SIMD, bmpc_pair.hip); 0: no pair kernel for this handle (N > 11 or S > 4)
@@ -192,14 +117,15 @@ struct bmpc_handle {
     int team_mode;           // bmpc_set_team_waves: 0 automatic (teams when the batch fits into the resident teams), 1 never, BMPC_TEAM_NW whenever possible
     int timing; hipEvent_t *ev; int nev; long long n_timed;   // timing = number of launches whose {start, stop} event pairs are kept (ring)
     double *latency_us;
-    double *stage_d, *stage_h; int stage_cap;   // device and pinned host staging of the host-buffer path (bmpc_solve_batch_host)
-    double *stage_state; int stage_state_cap;   // device dual state of the host-buffer path with multipliers (bmpc_solve_batch_host_dual)
-    double *kkt_d, *kkt_h; int kkt_cap;         // device and pinned host staging of the host-buffer certificate (bmpc_kkt_batch_host)
-    double *sens_d, *sens_h; int sens_cap;      // the same of the host-buffer sensitivity (bmpc_sens_batch_host)
+    char *arena_d, *arena_h; size_t arena_d_cap, arena_h_cap;      // staging arena of the host-buffer calls (host_call): device and pinned host buffer, capacities in bytes
 };
 
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "boundmpc_hip: %s failed: %s\n", #x, hipGetErrorString(e_)); return BMPC_ERR_HIP; } } while (0)
 
+#define TRY(x) do { if (rc == BMPC_OK && (x) != hipSuccess) rc = BMPC_ERR_HIP; } while (0)      // a step of a sequence that runs to its end: skipped once one has failed
+
+// the instantiation of the one-wave kernels for this handle: iterate in LDS (true) or in the workspace (long horizons, 5 or 6 path segments)
+static bool handle_zlds(const bmpc_handle *h) { return h->N <= 11 && h->S <= bmpc::SMAX_ZLDS; }
 // makes the handle's device current for the scope (allocation, free and synchronisation act on the CURRENT device)
 struct DevGuard {
     int prev; bool changed;
@@ -237,9 +163,7 @@ static void handle_release(bmpc_handle *h) {
     if (h->order_ev) hipEventDestroy(h->order_ev);
     if (h->bridge_ev) hipEventDestroy(h->bridge_ev);
     if (h->own_stream) hipStreamDestroy(h->own_stream);
-    hipFree(h->scratch); hipFree(h->counter); hipFree(h->aux_int); hipFree(h->qkey); hipFree(h->qorder); hipFree(h->prof); hipFree(h->stage_d); if (h->stage_h) hipHostFree(h->stage_h); hipFree(h->stage_state);
-    hipFree(h->kkt_d); if (h->kkt_h) hipHostFree(h->kkt_h);
-    hipFree(h->sens_d); if (h->sens_h) hipHostFree(h->sens_h);
+    hipFree(h->scratch); hipFree(h->counter); hipFree(h->aux_int); hipFree(h->qkey); hipFree(h->qorder); hipFree(h->prof); hipFree(h->arena_d); if (h->arena_h) hipHostFree(h->arena_h);
     delete h;
 }
 
@@ -273,7 +197,7 @@ extern "C" int bmpc_create(int N, int S, double dt, const bmpc_options *opts, bm
     int dev = 0, per_cu = 0; hipDeviceProp_t prop;
     bool ok = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess;
     h->dev = dev;
-    if (ok) ok = ((N <= 11 && S <= bmpc::SMAX_ZLDS) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bmpc_solve_kernel<true>, 64, 0)
+    if (ok) ok = (handle_zlds(h) ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bmpc_solve_kernel<true>, 64, 0)
                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bmpc_solve_kernel<false>, 64, 0)) == hipSuccess;
     if (ok) {
         if (per_cu < 1) per_cu = 1;
@@ -471,12 +395,17 @@ static hipError_t reset_queue(bmpc_handle *h, hipStream_t st) {
     hipLaunchKernelGGL(queue_reset_kernel, dim3(1), dim3(64), 0, st, h->counter);
     return hipGetLastError();
 }
+// the wave program's options from the handle's settings (max_iter > 0: the cap of this launch)
+static bmpc::Opts handle_opts(const bmpc_handle *h, int max_iter) {
+    bmpc::Opts o{};
+    o.tol = h->o.tol; o.max_iter = max_iter > 0 ? max_iter : h->o.max_iter; o.mu_init = h->o.mu_init; o.mu_min_fac = h->o.mu_min_fac;
+    o.slack_push = h->o.slack_push; o.exact_hessian = h->o.exact_hessian; o.verbose = 0; o.mu_warm = h->o.mu_warm; o.stall_window = h->o.stall_window; o.bound_margin = h->o.bound_margin;
+    o.restoration = h->resto_on; o.resto_short = h->resto_short; o.resto_cap = h->resto_cap; o.start_rollout = h->start_rollout; o.hold_mu = h->hold_mu; o.retry_cap = h->retry_cap;
+    return o;
+}
 // kernel arguments from the handle's settings; the caller adds its buffers and what its launch shape changes
 static KArgs handle_kargs(const bmpc_handle *h, int B, int max_iter) {
-    KArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h;
-    a.o.tol = h->o.tol; a.o.max_iter = max_iter > 0 ? max_iter : h->o.max_iter; a.o.mu_init = h->o.mu_init; a.o.mu_min_fac = h->o.mu_min_fac;
-    a.o.slack_push = h->o.slack_push; a.o.exact_hessian = h->o.exact_hessian; a.o.verbose = 0; a.o.mu_warm = h->o.mu_warm; a.o.stall_window = h->o.stall_window; a.o.bound_margin = h->o.bound_margin;
-    a.o.restoration = h->resto_on; a.o.resto_short = h->resto_short; a.o.resto_cap = h->resto_cap; a.o.start_rollout = h->start_rollout; a.o.hold_mu = h->hold_mu; a.o.retry_cap = h->retry_cap;
+    KArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h; a.o = handle_opts(h, max_iter);
     a.latency_us = h->latency_us; a.scratch = h->scratch; a.scr_stride = h->scr_stride; a.counter = h->counter; a.prof = h->prof;
     return a;
 }
@@ -499,7 +428,7 @@ static int enqueue_solve(bmpc_handle *h, int B, const double *p, const double *x
     }
     const int rgrid = resto ? resto_grid(h, B) : 0;
     if (rgrid > h->scr_waves) return BMPC_ERR_ARG;
-    const bool zlds = h->N <= 11 && h->S <= bmpc::SMAX_ZLDS;
+    const bool zlds = handle_zlds(h);
     hipEvent_t *pair = nullptr;
     if (timed) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
     if (h->queue_order && !state && solve_waves(h, B) == 1 && B > h->grid && B <= h->q_cap && B <= BMPC_QUEUE_ORDER_MAX) {
@@ -562,167 +491,52 @@ extern "C" int bmpc_solve_batch_warm(bmpc_handle *h, int B, const double *p, con
     return enqueue_solve(h, B, p, x0, state, max_iter, x, g, lam_g, lam_x, f, iters, status, kkt, (hipStream_t)hip_stream, h->timing != 0);
 }
 
-// primal-dual warm start: enqueues the conversion kernel (bmpc_dual.inl) on `st`, ordered against the handle's other launches like enqueue_solve
-static int enqueue_dual(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g, const double *lam_x, double mu0, double *state, hipStream_t st) {
+// ---- service launches: dual state from multipliers (bmpc_dual.inl), KKT certificate (bmpc_kkt.inl), parametric sensitivity (bmpc_sens.inl) ----
+typedef bmpc::DualBatch DualBatch; typedef bmpc::KktBatch KktBatch; typedef bmpc::SensBatch SensBatch;
+// a service kernel runs one wave per problem on the handle's resident waves, whatever kernel solves a batch of this size
+static int service_grid(const bmpc_handle *h, int B) { return B < h->grid ? B : h->grid; }
+// enqueues the service kernel of `job` on `st`, ordered against the handle's other launches like enqueue_solve; callers reserve the workspace first
+template <class JOB>
+static int enqueue_service(bmpc_handle *h, int B, hipStream_t st, const JOB &job) {
     if (h->closed) return BMPC_ERR_ARG;
-    const int grid = B < h->grid ? B : h->grid;
+    const int grid = service_grid(h, B);
     if (grid > h->scr_waves) return BMPC_ERR_ARG;
     { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
-    const KArgs k = handle_kargs(h, B, 0);
-    DualArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h; a.o = k.o;
-    a.p = p; a.x0 = x0; a.lam_g = lam_g; a.lam_x = lam_x; a.state = state; a.mu = mu0; a.scratch = h->scratch; a.scr_stride = h->scr_stride;
-    if (h->N <= 11 && h->S <= bmpc::SMAX_ZLDS) hipLaunchKernelGGL(bmpc_dual_kernel<true>, dim3(grid), dim3(64), 0, st, a);      // iterate in LDS
-    else hipLaunchKernelGGL(bmpc_dual_kernel<false>, dim3(grid), dim3(64), 0, st, a);                                          // iterate in the workspace
+    const ServiceArgsT<bmpc::Opts, JOB> a{h->N, h->S, B, h->h, handle_opts(h, 0), h->scratch, h->scr_stride, job};
+    if (handle_zlds(h)) hipLaunchKernelGGL((bmpc_service_kernel<true, JOB>), dim3(grid), dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((bmpc_service_kernel<false, JOB>), dim3(grid), dim3(64), 0, st, a);
     HIPCHK(hipGetLastError());
     return order_after(h, st);
+}
+template <class JOB>
+static int launch_service(bmpc_handle *h, int B, void *hip_stream, const JOB &job) {
+    { const int rc_ = ensure_scratch(h, service_grid(h, B)); if (rc_ != BMPC_OK) return rc_; }
+    return enqueue_service(h, B, (hipStream_t)hip_stream, job);
 }
 extern "C" int bmpc_state_from_multipliers(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g0, const double *lam_x0,
                                            double mu0, double *state, void *hip_stream) {
     if (!h || B < 0 || (B > 0 && (!p || !x0 || !state))) return BMPC_ERR_ARG;
     if (B == 0) return BMPC_OK;
-    { const int rc_ = ensure_scratch(h, B < h->grid ? B : h->grid); if (rc_ != BMPC_OK) return rc_; }
-    return enqueue_dual(h, B, p, x0, lam_g0, lam_x0, mu0, state, (hipStream_t)hip_stream);
-}
-
-// ---- KKT certificate of any primal-dual point (bmpc_kkt.inl) ----
-// enqueues the certificate kernel on `st`, ordered against the handle's other launches like enqueue_dual
-static int enqueue_kkt(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert, double *g,
-                       double *lam_g, double *rj, hipStream_t st) {
-    if (h->closed) return BMPC_ERR_ARG;
-    const int grid = B < h->grid ? B : h->grid;
-    if (grid > h->scr_waves) return BMPC_ERR_ARG;
-    { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
-    const KArgs k = handle_kargs(h, B, 0);
-    KktArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h; a.o = k.o;
-    a.p = p; a.x = x; a.lam_g0 = lam_g0; a.lam_x0 = lam_x0; a.cert = cert; a.g = g; a.lam_g = lam_g; a.rj = rj; a.scratch = h->scratch; a.scr_stride = h->scr_stride;
-    if (h->N <= 11 && h->S <= bmpc::SMAX_ZLDS) hipLaunchKernelGGL(bmpc_kkt_kernel<true>, dim3(grid), dim3(64), 0, st, a);      // iterate in LDS
-    else hipLaunchKernelGGL(bmpc_kkt_kernel<false>, dim3(grid), dim3(64), 0, st, a);                                          // iterate in the workspace
-    HIPCHK(hipGetLastError());
-    return order_after(h, st);
+    return launch_service(h, B, hip_stream, DualBatch{p, x0, lam_g0, lam_x0, state, mu0});
 }
 extern "C" int bmpc_kkt_len(void) { return BMPC_KKT_LEN; }
 extern "C" int bmpc_kkt_batch(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert,
                               double *g, double *lam_g, double *rj, void *hip_stream) {
     if (!h || B < 1 || !p || !x || !cert) return BMPC_ERR_ARG;
-    { const int rc_ = ensure_scratch(h, B < h->grid ? B : h->grid); if (rc_ != BMPC_OK) return rc_; }
-    return enqueue_kkt(h, B, p, x, lam_g0, lam_x0, cert, g, lam_g, rj, (hipStream_t)hip_stream);
-}
-// host-buffer certificate: one staging record [p | x | lam_g0 | lam_x0] in, [cert | g | lam_g | rj] out -- one host-to-device copy, the launch, one
-// device-to-host copy and one stream synchronisation, on the handle's own non-blocking stream (as bmpc_solve_batch_host)
-extern "C" int bmpc_kkt_batch_host(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert,
-                                   double *g, double *lam_g, double *rj) {
-    if (!h || B < 1 || !p || !x || !cert) return BMPC_ERR_ARG;
-    if (h->closed) return BMPC_ERR_ARG;
-    const size_t np = 141 + 91 * h->S, nw = (size_t)h->N * 44, ng = (size_t)h->N * 43, nj = (size_t)h->N * 8, b = (size_t)B;
-    const size_t n_in = b * (np + 2 * nw + ng), n_out = b * (BMPC_KKT_LEN + 2 * ng + nj);
-    if (B > h->kkt_cap) {
-        DevGuard dg(h->dev);
-        wait_for_handle(h);
-        if (h->kkt_d) { hipFree(h->kkt_d); h->kkt_d = nullptr; }
-        if (h->kkt_h) { hipHostFree(h->kkt_h); h->kkt_h = nullptr; }
-        h->kkt_cap = 0;
-        if (hipMalloc(&h->kkt_d, (n_in + n_out) * sizeof(double)) != hipSuccess || hipHostMalloc(&h->kkt_h, (n_in + n_out) * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-            hipFree(h->kkt_d); if (h->kkt_h) hipHostFree(h->kkt_h); h->kkt_d = nullptr; h->kkt_h = nullptr;
-            return BMPC_ERR_HIP;
-        }
-        h->kkt_cap = B;
-    }
-    double *dp = h->kkt_d, *dx = dp + b * np, *dlg0 = dx + b * nw, *dlx0 = dlg0 + b * ng, *dc = dlx0 + b * nw, *dg = dc + b * BMPC_KKT_LEN, *dlg = dg + b * ng, *drj = dlg + b * ng;
-    double *hp = h->kkt_h, *hx = hp + b * np, *hlg0 = hx + b * nw, *hlx0 = hlg0 + b * ng, *hc = hlx0 + b * nw, *hg = hc + b * BMPC_KKT_LEN, *hlg = hg + b * ng, *hrj = hlg + b * ng;
-    int rc = BMPC_OK;
-#define TRY(x) do { if (rc == BMPC_OK && (x) != hipSuccess) rc = BMPC_ERR_HIP; } while (0)
-    hipStream_t hs = nullptr;
-    {
-        DevGuard dg(h->dev);
-        if (!h->own_stream && hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return BMPC_ERR_HIP;
-        hs = h->own_stream;
-    }
-    memcpy(hp, p, b * np * sizeof(double)); memcpy(hx, x, b * nw * sizeof(double));
-    if (lam_g0) memcpy(hlg0, lam_g0, b * ng * sizeof(double)); else memset(hlg0, 0, b * ng * sizeof(double));
-    if (lam_x0) memcpy(hlx0, lam_x0, b * nw * sizeof(double)); else memset(hlx0, 0, b * nw * sizeof(double));
-    TRY(hipMemcpyAsync(dp, hp, n_in * sizeof(double), hipMemcpyHostToDevice, hs));
-    if (rc == BMPC_OK) rc = bmpc_kkt_batch(h, B, dp, dx, lam_g0 ? dlg0 : nullptr, lam_x0 ? dlx0 : nullptr, dc, dg, dlg, drj, hs);
-    TRY(hipMemcpyAsync(hc, dc, n_out * sizeof(double), hipMemcpyDeviceToHost, hs));
-    TRY(hipStreamSynchronize(hs));
-    if (rc == BMPC_OK) {
-        memcpy(cert, hc, b * BMPC_KKT_LEN * sizeof(double));
-        if (g) memcpy(g, hg, b * ng * sizeof(double));
-        if (lam_g) memcpy(lam_g, hlg, b * ng * sizeof(double));
-        if (rj) memcpy(rj, hrj, b * nj * sizeof(double));
-    }
-#undef TRY
-    return rc;
-}
-
-// ---- parametric sensitivity of the solution (bmpc_sens.inl) ----
-// enqueues the sensitivity kernel on `st`, ordered against the handle's other launches like enqueue_kkt
-static int enqueue_sens(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, const double *dp, double mu,
-                        double *dx, double *dlam_eq, double *dnu, double *rec, hipStream_t st) {
-    if (h->closed) return BMPC_ERR_ARG;
-    const int grid = B < h->grid ? B : h->grid;
-    if (grid > h->scr_waves) return BMPC_ERR_ARG;
-    { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
-    const KArgs k = handle_kargs(h, B, 0);
-    SensArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h; a.o = k.o; a.mu = mu > 0.0 ? mu : h->o.tol * h->o.mu_min_fac;
-    a.p = p; a.x = x; a.lam_g0 = lam_g0; a.lam_x0 = lam_x0; a.dp = dp; a.dx = dx; a.dlam_eq = dlam_eq; a.dnu = dnu; a.rec = rec;
-    a.scratch = h->scratch; a.scr_stride = h->scr_stride;
-    if (h->N <= 11 && h->S <= bmpc::SMAX_ZLDS) hipLaunchKernelGGL(bmpc_sens_kernel<true>, dim3(grid), dim3(64), 0, st, a);      // iterate in LDS
-    else hipLaunchKernelGGL(bmpc_sens_kernel<false>, dim3(grid), dim3(64), 0, st, a);                                          // iterate in the workspace
-    HIPCHK(hipGetLastError());
-    return order_after(h, st);
+    return launch_service(h, B, hip_stream, KktBatch{p, x, lam_g0, lam_x0, cert, g, lam_g, rj});
 }
 extern "C" int bmpc_sens_len(void) { return BMPC_SENS_LEN; }
 extern "C" int bmpc_sens_batch(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g, const double *lam_x, const double *dp,
                                double mu, double *dx, double *dlam_eq, double *dnu, double *rec, void *hip_stream) {
     if (!h || B < 1 || !p || !x || !dp || !dx) return BMPC_ERR_ARG;
-    { const int rc_ = ensure_scratch(h, B < h->grid ? B : h->grid); if (rc_ != BMPC_OK) return rc_; }
-    return enqueue_sens(h, B, p, x, lam_g, lam_x, dp, mu, dx, dlam_eq, dnu, rec, (hipStream_t)hip_stream);
+    return launch_service(h, B, hip_stream, SensBatch{p, x, lam_g, lam_x, dp, mu > 0.0 ? mu : h->o.tol * h->o.mu_min_fac, dx, dlam_eq, dnu, rec});
 }
-// host-buffer sensitivity: one staging record [p | x | dp | lam_g | lam_x] in, [dx | dlam_eq | dnu | rec] out -- one host-to-device copy, the launch,
-// one device-to-host copy and one stream synchronisation, on the handle's own non-blocking stream (as bmpc_kkt_batch_host)
-extern "C" int bmpc_sens_batch_host(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g, const double *lam_x, const double *dp,
-                                    double mu, double *dx, double *dlam_eq, double *dnu, double *rec) {
-    if (!h || B < 1 || !p || !x || !dp || !dx) return BMPC_ERR_ARG;
-    if (h->closed) return BMPC_ERR_ARG;
-    const size_t np = 141 + 91 * h->S, nw = (size_t)h->N * 44, ng = (size_t)h->N * 43, ne = (size_t)h->N * 36, ni = (size_t)h->N * 57, b = (size_t)B;
-    const size_t n_in = b * (2 * np + 2 * nw + ng), n_out = b * (nw + ne + ni + BMPC_SENS_LEN);
-    if (B > h->sens_cap) {
-        DevGuard dg(h->dev);
-        wait_for_handle(h);
-        if (h->sens_d) { hipFree(h->sens_d); h->sens_d = nullptr; }
-        if (h->sens_h) { hipHostFree(h->sens_h); h->sens_h = nullptr; }
-        h->sens_cap = 0;
-        if (hipMalloc(&h->sens_d, (n_in + n_out) * sizeof(double)) != hipSuccess || hipHostMalloc(&h->sens_h, (n_in + n_out) * sizeof(double), hipHostMallocDefault) != hipSuccess) {
-            hipFree(h->sens_d); if (h->sens_h) hipHostFree(h->sens_h); h->sens_d = nullptr; h->sens_h = nullptr;
-            return BMPC_ERR_HIP;
-        }
-        h->sens_cap = B;
-    }
-    double *d_p = h->sens_d, *d_x = d_p + b * np, *d_dp = d_x + b * nw, *d_lg = d_dp + b * np, *d_lx = d_lg + b * ng, *d_dx = d_lx + b * nw, *d_dl = d_dx + b * nw, *d_dn = d_dl + b * ne, *d_rc = d_dn + b * ni;
-    double *h_p = h->sens_h, *h_x = h_p + b * np, *h_dp = h_x + b * nw, *h_lg = h_dp + b * np, *h_lx = h_lg + b * ng, *h_dx = h_lx + b * nw, *h_dl = h_dx + b * nw, *h_dn = h_dl + b * ne, *h_rc = h_dn + b * ni;
-    int rc = BMPC_OK;
-#define TRY(x) do { if (rc == BMPC_OK && (x) != hipSuccess) rc = BMPC_ERR_HIP; } while (0)
-    hipStream_t hs = nullptr;
-    {
-        DevGuard dg(h->dev);
-        if (!h->own_stream && hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return BMPC_ERR_HIP;
-        hs = h->own_stream;
-    }
-    memcpy(h_p, p, b * np * sizeof(double)); memcpy(h_x, x, b * nw * sizeof(double)); memcpy(h_dp, dp, b * np * sizeof(double));
-    if (lam_g) memcpy(h_lg, lam_g, b * ng * sizeof(double)); else memset(h_lg, 0, b * ng * sizeof(double));
-    if (lam_x) memcpy(h_lx, lam_x, b * nw * sizeof(double)); else memset(h_lx, 0, b * nw * sizeof(double));
-    TRY(hipMemcpyAsync(d_p, h_p, n_in * sizeof(double), hipMemcpyHostToDevice, hs));
-    if (rc == BMPC_OK) rc = bmpc_sens_batch(h, B, d_p, d_x, lam_g ? d_lg : nullptr, lam_x ? d_lx : nullptr, d_dp, mu, d_dx, dlam_eq ? d_dl : nullptr, dnu ? d_dn : nullptr, d_rc, hs);
-    TRY(hipMemcpyAsync(h_dx, d_dx, n_out * sizeof(double), hipMemcpyDeviceToHost, hs));
-    TRY(hipStreamSynchronize(hs));
-    if (rc == BMPC_OK) {
-        memcpy(dx, h_dx, b * nw * sizeof(double));
-        if (dlam_eq) memcpy(dlam_eq, h_dl, b * ne * sizeof(double));
-        if (dnu) memcpy(dnu, h_dn, b * ni * sizeof(double));
-        if (rec) memcpy(rec, h_rc, b * BMPC_SENS_LEN * sizeof(double));
-    }
-#undef TRY
-    return rc;
+
+// the handle's own non-blocking stream (created on first use): host-buffer calls and graph replays requested on the legacy null stream run there
+static int handle_stream(bmpc_handle *h, hipStream_t *out) {
+    if (!h->own_stream) { DevGuard dg(h->dev); HIPCHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking)); }
+    *out = h->own_stream;
+    return BMPC_OK;
 }
 
 // ---- hipGraph-captured step: {queue reset, solver kernel, restoration kernel} of one (warm-started) solve, instantiated once, replayed per tick ----
@@ -766,10 +580,9 @@ extern "C" int bmpc_graph_launch(bmpc_graph *gr, void *hip_stream) {
     const bool bridged = st == nullptr;
     if (bridged) {
         DevGuard dg(h->dev);
-        if (!h->own_stream) HIPCHK(hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking));
+        { const int rc_ = handle_stream(h, &st); if (rc_ != BMPC_OK) return rc_; }
         HIPCHK(hipEventRecord(h->bridge_ev, nullptr));
-        HIPCHK(hipStreamWaitEvent(h->own_stream, h->bridge_ev, 0));
-        st = h->own_stream;
+        HIPCHK(hipStreamWaitEvent(st, h->bridge_ev, 0));
     }
     { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
     hipEvent_t *pair = nullptr;
@@ -792,114 +605,127 @@ extern "C" int bmpc_graph_destroy(bmpc_graph *gr) {
     return BMPC_OK;
 }
 
-// host-buffer path: device and pinned host staging buffers are owned by the handle and grow on demand (no hipMalloc per call: the
-// single-problem solver(...) call of the drop-in shim runs every tick).  One staging record holds everything that crosses PCIe for a
-// call, inputs first: [p | x0 | x | lam_x | g | lam_g | f | kkt] doubles, then [iters | status] ints -- so a call is ONE host-to-device
-// copy of the inputs, the launch, ONE device-to-host copy of the outputs and one stream synchronisation (until round 3: two blocking
-// copies in, a device synchronisation and eight blocking copies out, ~190 us around a 1.1 ms single-problem launch).
-static int host_stage_reserve(bmpc_handle *h, int B) {
-    if (B <= h->stage_cap) return BMPC_OK;
-    const size_t np = 141 + 91 * h->S, nw = (size_t)h->N * 44, ng = (size_t)h->N * 43;
-    const size_t bytes = ((size_t)B * (np + 3 * nw + 2 * ng + 2)) * sizeof(double) + (size_t)B * 2 * sizeof(int);
-    if (h->stage_d) { hipFree(h->stage_d); h->stage_d = nullptr; }
-    if (h->stage_h) { hipHostFree(h->stage_h); h->stage_h = nullptr; }
-    h->stage_cap = 0;
-    if (hipMalloc(&h->stage_d, bytes) != hipSuccess || hipHostMalloc(&h->stage_h, bytes, hipHostMallocDefault) != hipSuccess) {
-        hipFree(h->stage_d); if (h->stage_h) hipHostFree(h->stage_h); h->stage_d = nullptr; h->stage_h = nullptr;
-        return BMPC_ERR_HIP;
+// ---- host-buffer calls ----
+// Device and pinned host staging are owned by the handle and grow on demand (no hipMalloc per call: the single-problem solver(...) call of the
+// drop-in shim runs every tick).  ONE arena serves every kind of call: a call synchronises its stream before it returns, on error paths too, so
+// nothing of an earlier call is in flight when the next one fills or grows it.  The device buffer holds the call's record and, behind it,
+// `tail_bytes` that never cross PCIe (the dual state of bmpc_solve_batch_host_dual); the pinned buffer holds the record.
+static int arena_reserve(bmpc_handle *h, size_t rec_bytes, size_t tail_bytes) {
+    if (rec_bytes + tail_bytes <= h->arena_d_cap && rec_bytes <= h->arena_h_cap) return BMPC_OK;
+    DevGuard dg(h->dev);
+    wait_for_handle(h);
+    if (rec_bytes + tail_bytes > h->arena_d_cap) {
+        hipFree(h->arena_d); h->arena_d = nullptr; h->arena_d_cap = 0;
+        if (hipMalloc(&h->arena_d, rec_bytes + tail_bytes) != hipSuccess) { h->arena_d = nullptr; return BMPC_ERR_HIP; }
+        h->arena_d_cap = rec_bytes + tail_bytes;
     }
-    h->stage_cap = B;
+    if (rec_bytes > h->arena_h_cap) {
+        if (h->arena_h) hipHostFree(h->arena_h);
+        h->arena_h = nullptr; h->arena_h_cap = 0;
+        if (hipHostMalloc(&h->arena_h, rec_bytes, hipHostMallocDefault) != hipSuccess) { h->arena_h = nullptr; return BMPC_ERR_HIP; }
+        h->arena_h_cap = rec_bytes;
+    }
     return BMPC_OK;
+}
+// One field of a host call's staging record: B problems back to back, `bytes` each.  host: the caller's array (NULL: an optional one it left out).
+// FIELD_IN is copied into the record (zeros when left out), FIELD_OUT copied back; an input staged in the slot an output lands in names both
+// arrays (bmpc_solve_batch_host_dual).  The fields lie in the record in list order, inputs first: everything up to the last input is ONE
+// host-to-device copy, everything from the first output on ONE device-to-host copy.
+enum { FIELD_IN = 1, FIELD_OUT = 2 };
+struct Field { int io; const void *in; void *out; size_t bytes; };
+static Field field_in(const void *host, size_t bytes) { return Field{FIELD_IN, host, nullptr, bytes}; }
+static Field field_out(void *host, size_t bytes) { return Field{FIELD_OUT, nullptr, host, bytes}; }
+// A host-buffer call: the record staged in, launch(dev, tail, stream) -- dev[i]: field i on the device, tail: `tail_bytes` behind the record --
+// and the outputs staged back: one copy each way, one stream synchronisation, on the handle's own non-blocking stream (round 5; it was the
+// legacy null stream, on which the call serialised against every blocking stream of a torch process).
+template <int NF, class LAUNCH>
+static int host_call(bmpc_handle *h, int B, const Field (&f)[NF], size_t tail_bytes, LAUNCH launch) {
+    if (h->closed) return BMPC_ERR_ARG;
+    size_t off[NF + 1], in_end = 0, out_begin = 0; bool have_out = false;
+    off[0] = 0;
+    for (int i = 0; i < NF; i++) {
+        off[i + 1] = off[i] + (size_t)B * f[i].bytes;
+        if (f[i].io & FIELD_IN) in_end = off[i + 1];
+        if ((f[i].io & FIELD_OUT) && !have_out) { out_begin = off[i]; have_out = true; }
+    }
+    int rc = arena_reserve(h, off[NF], tail_bytes);
+    if (rc != BMPC_OK) return rc;
+    hipStream_t hs = nullptr;
+    rc = handle_stream(h, &hs);
+    if (rc != BMPC_OK) return rc;
+    char *d = h->arena_d, *s = h->arena_h;
+    void *dev[NF];
+    for (int i = 0; i < NF; i++) {
+        dev[i] = d + off[i];
+        if (!(f[i].io & FIELD_IN)) continue;
+        if (f[i].in) memcpy(s + off[i], f[i].in, off[i + 1] - off[i]); else memset(s + off[i], 0, off[i + 1] - off[i]);
+    }
+    TRY(hipMemcpyAsync(d, s, in_end, hipMemcpyHostToDevice, hs));
+    if (rc == BMPC_OK) rc = launch(dev, d + off[NF], hs);
+    TRY(hipMemcpyAsync(s + out_begin, d + out_begin, off[NF] - out_begin, hipMemcpyDeviceToHost, hs));
+    if (hipStreamSynchronize(hs) != hipSuccess && rc == BMPC_OK) rc = BMPC_ERR_HIP;      // after a failed step too: the next call reuses the arena
+    if (rc != BMPC_OK) return rc;
+    for (int i = 0; i < NF; i++) if ((f[i].io & FIELD_OUT) && f[i].out) memcpy(f[i].out, s + off[i], off[i + 1] - off[i]);
+    return BMPC_OK;
+}
+#define DEV(i) ((double *)dev[i])
+#define DEV_IF(ptr, i) ((ptr) ? DEV(i) : nullptr)
+
+// The record of a solve: [p | x0 | x | lam_x | g | lam_g | f | kkt] doubles, then [iters | status] ints (until round 3: two blocking copies in, a
+// device synchronisation and eight blocking copies out, ~190 us around a 1.1 ms single-problem launch).  dual: the call with multipliers --
+// lam_x0 / lam_g0 are staged where the outputs lam_x / lam_g will be written (the conversion reads them before the solve behind it overwrites
+// them, in stream order), so the inputs are still ONE host-to-device copy (x and g of the record travel along: the solve overwrites them); the
+// dual state between conversion and solve is the tail of the device arena.
+static int solve_host(bmpc_handle *h, int B, bool dual, const double *p, const double *x0, const double *lam_g0, const double *lam_x0, double *x,
+                      double *g, double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt) {
+    if (!h || B < 0 || (B > 0 && (!p || !x0 || !x))) return BMPC_ERR_ARG;
+    if (B == 0) return BMPC_OK;
+    const size_t np = (141 + 91 * h->S) * sizeof(double), nw = h->N * bmpc::NZ * sizeof(double), ng = h->N * bmpc::NG * sizeof(double);
+    const int staged = dual ? FIELD_IN | FIELD_OUT : FIELD_OUT;
+    enum { P, X0, X, LAM_X, G, LAM_G, F, KKT, ITERS, STATUS };
+    const Field fl[] = {field_in(p, np), field_in(x0, nw), field_out(x, nw), Field{staged, lam_x0, lam_x, nw}, field_out(g, ng), Field{staged, lam_g0, lam_g, ng},
+                        field_out(f, sizeof(double)), field_out(kkt, sizeof(double)), field_out(iters, sizeof(int)), field_out(status, sizeof(int))};
+    return host_call(h, B, fl, dual ? (size_t)B * (h->N * bmpc::NI + 2) * sizeof(double) : 0, [&](void *const *dev, char *tail, hipStream_t hs) {
+        if (!dual) return bmpc_solve_batch(h, B, DEV(P), DEV(X0), DEV(X), DEV(G), DEV(LAM_G), DEV(LAM_X), DEV(F), (int *)dev[ITERS], (int *)dev[STATUS], DEV(KKT), hs);
+        const int rc = bmpc_state_from_multipliers(h, B, DEV(P), DEV(X0), DEV_IF(lam_g0, LAM_G), DEV_IF(lam_x0, LAM_X), 0.0, (double *)tail, hs);
+        if (rc != BMPC_OK) return rc;
+        return bmpc_solve_batch_warm(h, B, DEV(P), DEV(X0), (double *)tail, 0, DEV(X), DEV(G), DEV(LAM_G), DEV(LAM_X), DEV(F), (int *)dev[ITERS], (int *)dev[STATUS], DEV(KKT), hs);
+    });
 }
 extern "C" int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
                                      double *f, int *iters, int *status, double *kkt) {
-    if (!h || B < 0 || (B > 0 && (!p || !x0 || !x))) return BMPC_ERR_ARG;
-    if (B == 0) return BMPC_OK;
-    int rc = host_stage_reserve(h, B);
-    if (rc != BMPC_OK) return rc;
-    const size_t np = 141 + 91 * h->S, nw = (size_t)h->N * 44, ng = (size_t)h->N * 43, b = (size_t)B;
-    const size_t n_in = b * (np + nw), n_out = b * (2 * nw + 2 * ng + 2);
-    double *dp = h->stage_d, *dx0 = dp + b * np, *dx = dx0 + b * nw, *dlx = dx + b * nw, *dg = dlx + b * nw, *dlg = dg + b * ng, *df = dlg + b * ng, *dk = df + b;
-    int *dit = (int *)(dk + b), *dst = dit + b;
-    double *hp = h->stage_h, *hx0 = hp + b * np, *hx = hx0 + b * nw, *hlx = hx + b * nw, *hg = hlx + b * nw, *hlg = hg + b * ng, *hf = hlg + b * ng, *hk = hf + b;
-    const int *hit = (const int *)(hk + b), *hst = hit + b;
-#define TRY(x) do { if (rc == BMPC_OK && (x) != hipSuccess) rc = BMPC_ERR_HIP; } while (0)
-    // on a non-blocking stream of the handle (round 5; it was the legacy null stream, on which the call serialised against every blocking stream
-    // of a torch process): the staged copies and the launch touch only the handle's own buffers
-    hipStream_t hs = nullptr;
-    {
-        DevGuard dg(h->dev);
-        if (!h->own_stream && hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return BMPC_ERR_HIP;
-        hs = h->own_stream;
-    }
-    memcpy(hp, p, b * np * sizeof(double)); memcpy(hx0, x0, b * nw * sizeof(double));
-    TRY(hipMemcpyAsync(dp, hp, n_in * sizeof(double), hipMemcpyHostToDevice, hs));
-    if (rc == BMPC_OK) rc = bmpc_solve_batch(h, B, dp, dx0, dx, dg, dlg, dlx, df, dit, dst, dk, hs);
-    TRY(hipMemcpyAsync(hx, dx, n_out * sizeof(double) + b * 2 * sizeof(int), hipMemcpyDeviceToHost, hs));
-    TRY(hipStreamSynchronize(hs));
-    if (rc == BMPC_OK) {
-        memcpy(x, hx, b * nw * sizeof(double));
-        if (g) memcpy(g, hg, b * ng * sizeof(double));
-        if (lam_g) memcpy(lam_g, hlg, b * ng * sizeof(double));
-        if (lam_x) memcpy(lam_x, hlx, b * nw * sizeof(double));
-        if (f) memcpy(f, hf, b * sizeof(double));
-        if (kkt) memcpy(kkt, hk, b * sizeof(double));
-        if (iters) memcpy(iters, hit, b * sizeof(int));
-        if (status) memcpy(status, hst, b * sizeof(int));
-    }
-#undef TRY
-    return rc;
+    return solve_host(h, B, false, p, x0, nullptr, nullptr, x, g, lam_g, lam_x, f, iters, status, kkt);
 }
-
-// host-buffer path with multipliers: the staging record of bmpc_solve_batch_host, with lam_x0 / lam_g0 staged where the outputs lam_x / lam_g will be
-// written (the conversion reads them before the solve behind it overwrites them, in stream order), so the inputs are still ONE host-to-device copy
 extern "C" int bmpc_solve_batch_host_dual(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g0, const double *lam_x0,
                                           double *x, double *g, double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt) {
-    if (!h || B < 0 || (B > 0 && (!p || !x0 || !x))) return BMPC_ERR_ARG;
-    if (B == 0) return BMPC_OK;
-    if (h->closed) return BMPC_ERR_ARG;
-    int rc = host_stage_reserve(h, B);
-    if (rc != BMPC_OK) return rc;
-    const size_t np = 141 + 91 * h->S, nw = (size_t)h->N * 44, ng = (size_t)h->N * 43, b = (size_t)B, sl = (size_t)h->N * bmpc::NI + 2;
-    if (B > h->stage_state_cap) {
-        DevGuard dg(h->dev);
-        if (h->stage_state) { wait_for_handle(h); hipFree(h->stage_state); h->stage_state = nullptr; h->stage_state_cap = 0; }
-        HIPCHK(hipMalloc(&h->stage_state, sizeof(double) * sl * b));
-        h->stage_state_cap = B;
-    }
-    const size_t n_in = b * (np + 3 * nw + 2 * ng), n_out = b * (2 * nw + 2 * ng + 2);
-    double *dp = h->stage_d, *dx0 = dp + b * np, *dx = dx0 + b * nw, *dlx = dx + b * nw, *dg = dlx + b * nw, *dlg = dg + b * ng, *df = dlg + b * ng, *dk = df + b;
-    int *dit = (int *)(dk + b), *dst = dit + b;
-    double *hp = h->stage_h, *hx0 = hp + b * np, *hx = hx0 + b * nw, *hlx = hx + b * nw, *hg = hlx + b * nw, *hlg = hg + b * ng, *hf = hlg + b * ng, *hk = hf + b;
-    const int *hit = (const int *)(hk + b), *hst = hit + b;
-#define TRY(x) do { if (rc == BMPC_OK && (x) != hipSuccess) rc = BMPC_ERR_HIP; } while (0)
-    hipStream_t hs = nullptr;
-    {
-        DevGuard dg(h->dev);
-        if (!h->own_stream && hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking) != hipSuccess) return BMPC_ERR_HIP;
-        hs = h->own_stream;
-    }
-    memcpy(hp, p, b * np * sizeof(double)); memcpy(hx0, x0, b * nw * sizeof(double));
-    if (lam_x0) memcpy(hlx, lam_x0, b * nw * sizeof(double));
-    if (lam_g0) memcpy(hlg, lam_g0, b * ng * sizeof(double));
-    TRY(hipMemcpyAsync(dp, hp, n_in * sizeof(double), hipMemcpyHostToDevice, hs));      // (x and g of the record travel along: the solve overwrites them)
-    if (rc == BMPC_OK) rc = bmpc_state_from_multipliers(h, B, dp, dx0, lam_g0 ? dlg : nullptr, lam_x0 ? dlx : nullptr, 0.0, h->stage_state, hs);
-    if (rc == BMPC_OK) rc = bmpc_solve_batch_warm(h, B, dp, dx0, h->stage_state, 0, dx, dg, dlg, dlx, df, dit, dst, dk, hs);
-    TRY(hipMemcpyAsync(hx, dx, n_out * sizeof(double) + b * 2 * sizeof(int), hipMemcpyDeviceToHost, hs));
-    TRY(hipStreamSynchronize(hs));
-    if (rc == BMPC_OK) {
-        memcpy(x, hx, b * nw * sizeof(double));
-        if (g) memcpy(g, hg, b * ng * sizeof(double));
-        if (lam_g) memcpy(lam_g, hlg, b * ng * sizeof(double));
-        if (lam_x) memcpy(lam_x, hlx, b * nw * sizeof(double));
-        if (f) memcpy(f, hf, b * sizeof(double));
-        if (kkt) memcpy(kkt, hk, b * sizeof(double));
-        if (iters) memcpy(iters, hit, b * sizeof(int));
-        if (status) memcpy(status, hst, b * sizeof(int));
-    }
-#undef TRY
-    return rc;
+    return solve_host(h, B, true, p, x0, lam_g0, lam_x0, x, g, lam_g, lam_x, f, iters, status, kkt);
 }
+// the record of a certificate: [p | x | lam_g0 | lam_x0] in, [cert | g | lam_g | rj] out
+extern "C" int bmpc_kkt_batch_host(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert,
+                                   double *g, double *lam_g, double *rj) {
+    if (!h || B < 1 || !p || !x || !cert) return BMPC_ERR_ARG;
+    const size_t np = (141 + 91 * h->S) * sizeof(double), nw = h->N * bmpc::NZ * sizeof(double), ng = h->N * bmpc::NG * sizeof(double);
+    enum { P, X, LAM_G0, LAM_X0, CERT, G, LAM_G, RJ };
+    const Field fl[] = {field_in(p, np), field_in(x, nw), field_in(lam_g0, ng), field_in(lam_x0, nw),
+                        field_out(cert, BMPC_KKT_LEN * sizeof(double)), field_out(g, ng), field_out(lam_g, ng), field_out(rj, h->N * bmpc::NU * sizeof(double))};
+    return host_call(h, B, fl, 0, [&](void *const *dev, char *, hipStream_t hs) {
+        return bmpc_kkt_batch(h, B, DEV(P), DEV(X), DEV_IF(lam_g0, LAM_G0), DEV_IF(lam_x0, LAM_X0), DEV(CERT), DEV(G), DEV(LAM_G), DEV(RJ), hs);
+    });
+}
+// the record of a sensitivity: [p | x | dp | lam_g | lam_x] in, [dx | dlam_eq | dnu | rec] out
+extern "C" int bmpc_sens_batch_host(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g, const double *lam_x, const double *dp,
+                                    double mu, double *dx, double *dlam_eq, double *dnu, double *rec) {
+    if (!h || B < 1 || !p || !x || !dp || !dx) return BMPC_ERR_ARG;
+    const size_t np = (141 + 91 * h->S) * sizeof(double), nw = h->N * bmpc::NZ * sizeof(double), ng = h->N * bmpc::NG * sizeof(double);
+    enum { P, X, DP, LAM_G, LAM_X, DX, DLAM_EQ, DNU, REC };
+    const Field fl[] = {field_in(p, np), field_in(x, nw), field_in(dp, np), field_in(lam_g, ng), field_in(lam_x, nw), field_out(dx, nw),
+                        field_out(dlam_eq, h->N * bmpc::NE * sizeof(double)), field_out(dnu, h->N * bmpc::NI * sizeof(double)), field_out(rec, BMPC_SENS_LEN * sizeof(double))};
+    return host_call(h, B, fl, 0, [&](void *const *dev, char *, hipStream_t hs) {
+        return bmpc_sens_batch(h, B, DEV(P), DEV(X), DEV_IF(lam_g, LAM_G), DEV_IF(lam_x, LAM_X), DEV(DP), mu, DEV(DX), DEV_IF(dlam_eq, DLAM_EQ), DEV_IF(dnu, DNU), DEV(REC), hs);
+    });
+}
+#undef DEV
+#undef DEV_IF
 
 extern "C" int bmpc_set_latency_buffer(bmpc_handle *h, double *latency_us) { if (!h) return BMPC_ERR_ARG; h->latency_us = latency_us; return BMPC_OK; }
 extern "C" int bmpc_set_timing(bmpc_handle *h, int keep) {
@@ -950,7 +776,7 @@ static int enqueue_tick(bmpc_handle *h, int B, const double *path, int path_entr
     const bool resto = h->resto_on != 0 && a.budget_ticks == 0;
     a.o.restoration = resto ? h->resto_on : 0;      // (the handle's MODE, not a flag: 2 = after a numerical breakdown only, as every other launch shape runs it)
     if (use_team(h, B)) HIPCHK(bmpc_team_launch_tick(BMPC_TEAM_NW, resto, &a, &s, B, st));
-    else HIPCHK(bmpc_tick_launch(h->N <= 11 && h->S <= bmpc::SMAX_ZLDS, resto, &a, &s, B, st));      // (long horizons, 5 or 6 path segments: iterate in the workspace)
+    else HIPCHK(bmpc_tick_launch(handle_zlds(h), resto, &a, &s, B, st));      // (long horizons, 5 or 6 path segments: iterate in the workspace)
     if (timed) { HIPCHK(hipEventRecord(pair[1], st)); h->n_timed++; }
     if (!capturing) return order_after(h, st);
     return BMPC_OK;

@@ -140,4 +140,17 @@ BMPC_D inline void wave_certify(Wave &W, const KktIn &d) {
     WIDE_END
 }
 
+// B problems back to back in every array (NULL stays NULL): what a service launch gets (bmpc_hip.hip) and what the emulator host is called with
+struct KktBatch {
+    const double *p, *x, *lam_g0, *lam_x0; double *cert, *g, *lam_g, *rj;
+    BMPC_HD KktIn problem(int N, int S, long long b) const {      // problem b of the batch
+        const long long np = 141 + 91 * S, nw = N * NZ, ng = N * NG, nj = N * NU;
+        KktIn d; d.p = p + b * np; d.x = x + b * nw; d.cert = cert + b * KKT_LEN;
+        d.lam_g0 = lam_g0 ? lam_g0 + b * ng : nullptr; d.lam_x0 = lam_x0 ? lam_x0 + b * nw : nullptr;
+        d.g = g ? g + b * ng : nullptr; d.lam_g = lam_g ? lam_g + b * ng : nullptr; d.rj = rj ? rj + b * nj : nullptr;
+        return d;
+    }
+    template <bool ZLDS> BMPC_D void run(Wave &W, int b) const { wave_certify<ZLDS>(W, problem(W.N, W.S, b)); }
+};
+
 }  // namespace BMPC_NAMESPACE

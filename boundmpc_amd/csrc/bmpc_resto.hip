@@ -28,8 +28,7 @@ __global__ void __launch_bounds__(64, 1) bmpc_resto_kernel(KArgs a) {
     // handful of waves behind the batch (configs[3]: 218 -> 1xx ms with mode 1; profiles/r06_h_configs3_failures.txt).
     const bool fresh = a.rcount == nullptr;
     if (!fresh && *(volatile int *)a.rcount == 0) return;      // nothing jammed in this batch (wave-uniform: one word)
-    bmpc::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = bmpc::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride); W.wv = 0;
-    W.deadline = 0; W.tprev = 0; W.it_base = 0;
+    BMPC_ONE_WAVE(W, a, lds);
     BMPC_STRIDES(a);
     for (;;) {
         int b = 0, st = 0;

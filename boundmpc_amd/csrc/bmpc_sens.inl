@@ -253,4 +253,17 @@ BMPC_D inline void wave_sensitivity(Wave &W, const SensIn &d) {
     WIDE_END
 }
 
+// B problems back to back in every array (NULL stays NULL): what a service launch gets (bmpc_hip.hip) and what the emulator host is called with
+struct SensBatch {
+    const double *p, *x, *lam_g0, *lam_x0, *dp; double mu; double *dx, *dlam_eq, *dnu, *rec;
+    BMPC_HD SensIn problem(int N, int S, long long b) const {      // problem b of the batch
+        const long long np = 141 + 91 * S, nw = N * NZ, ng = N * NG, ne = N * NE, ni = N * NI;
+        SensIn d; d.p = p + b * np; d.x = x + b * nw; d.dp = dp + b * np; d.mu = mu; d.dx = dx + b * nw;
+        d.lam_g0 = lam_g0 ? lam_g0 + b * ng : nullptr; d.lam_x0 = lam_x0 ? lam_x0 + b * nw : nullptr;
+        d.dlam_eq = dlam_eq ? dlam_eq + b * ne : nullptr; d.dnu = dnu ? dnu + b * ni : nullptr; d.rec = rec ? rec + b * SENS_LEN : nullptr;
+        return d;
+    }
+    template <bool ZLDS> BMPC_D void run(Wave &W, int b) const { wave_sensitivity<ZLDS>(W, problem(W.N, W.S, b)); }
+};
+
 }  // namespace BMPC_NAMESPACE

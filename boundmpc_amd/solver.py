@@ -19,6 +19,33 @@ SENS_STATUS, SENS_DELTA, SENS_RHS, SENS_DX = range(4)
 SENS_FIELDS = ("status", "delta", "rhs", "dx_max")
 
 
+def _ptr(a):
+    """The address of a torch tensor or a numpy array for a ctypes call; None stays None (an optional argument left out)."""
+    if a is None:
+        return None
+    return ctypes.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _multiplier_or_none(v):
+    """None or a scalar 0 (the reference's initial `lam_g0 = 0`) means: no multipliers of that kind."""
+    return None if v is None or (np.isscalar(v) and v == 0) else v
+
+
+def _check_want(want, offered, what):
+    bad = [k for k in want if k not in offered]
+    if bad:
+        raise ValueError(f"want {bad}: a {what} offers {offered}")
+
+
+def _host_rows(*named):
+    """(name, array, row length) ... -> B and the arrays as contiguous float64 [B][row length]; one ValueError names every shape."""
+    arrs = [np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64) for _, a, _ in named]
+    B = arrs[0].shape[0]
+    if any(a.shape != (B, n) for a, (_, _, n) in zip(arrs, named)):
+        raise ValueError("shape mismatch: " + " ".join(f"{nm} {a.shape}" for a, (nm, _, _) in zip(arrs, named)))
+    return [B] + arrs
+
+
 class BatchedOCPSolver:
     def __init__(self, N, S, dt, tol=1e-8, max_iter=500, mu_init=None, slack_push=None, exact_hessian=True, mu_warm=1e-2, stall_window=None, bound_margin=0.0,
                  restoration=None, resto_short=None, resto_cap=None, start_rollout=None, mu_min_fac=None, fixed_barrier=None, level_c=0.02):
@@ -97,8 +124,7 @@ class BatchedOCPSolver:
     # ---- structural constants (casadi_ocp_formulation.py:384-391) ----
     def bounds(self):
         lbx, ubx, lbg, ubg = np.zeros(self.n_w), np.zeros(self.n_w), np.zeros(self.n_g), np.zeros(self.n_g)
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-        _lib.check(self._lib.bmpc_get_bounds(self._h, vp(lbx), vp(ubx), vp(lbg), vp(ubg)), "bmpc_get_bounds")
+        _lib.check(self._lib.bmpc_get_bounds(self._h, _ptr(lbx), _ptr(ubx), _ptr(lbg), _ptr(ubg)), "bmpc_get_bounds")
         return lbx, ubx, lbg, ubg
 
     def launch_info(self):
@@ -228,6 +254,18 @@ class BatchedOCPSolver:
             if t.device != dev:
                 raise ValueError(f"{nm} lives on {t.device}, p on {dev}")
 
+    def _host_multipliers(self, B, lam_g, lam_x, names):
+        """The numpy multiplier pair of a host call as contiguous float64 [B][n_g] / [B][n_w], or None where there is none."""
+        out = []
+        for a, n, nm in ((lam_g, self.n_g, names[0]), (lam_x, self.n_w, names[1])):
+            a = _multiplier_or_none(a)
+            if a is not None:
+                a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
+                if a.shape != (B, n):
+                    raise ValueError(f"{nm} has shape {a.shape}, expected {(B, n)}")
+            out.append(a)
+        return out
+
     def state_from_multipliers(self, p, x0, lam_g0=None, lam_x0=None, mu0=None, out=None, stream=None):
         """Dual state [B, state_len] of a warm solve (solve_batch(state=...)) from multipliers in CasADi's convention -- lam_g0 [B, 43 N],
         lam_x0 [B, 44 N], as a solve returns them; None = zeros -- evaluated at x0 on the GPU (include/boundmpc_hip.h bmpc_state_from_multipliers:
@@ -238,8 +276,7 @@ class BatchedOCPSolver:
         self._check_multipliers(B, lam_g0, lam_x0, p.device)
         state = out if out is not None else torch.empty((B, self.state_len), dtype=torch.float64, device=p.device)
         st = stream if stream is not None else torch.cuda.current_stream(p.device)
-        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(self._lib.bmpc_state_from_multipliers(self._h, B, dp(p), dp(x0), dp(lam_g0), dp(lam_x0), float(mu0 or 0.0), dp(state),
+        _lib.check(self._lib.bmpc_state_from_multipliers(self._h, B, _ptr(p), _ptr(x0), _ptr(lam_g0), _ptr(lam_x0), float(mu0 or 0.0), _ptr(state),
                                                          ctypes.c_void_p(st.cuda_stream)), "bmpc_state_from_multipliers")
         self._inflight = (p, x0, lam_g0, lam_x0, state)      # (asynchronous launch: see solve_batch)
         return state
@@ -255,13 +292,10 @@ class BatchedOCPSolver:
         as given (no start rollout, no second attempt); the record, the gap slots and the non-finite rules: include/boundmpc_hip.h bmpc_kkt_batch.
         Asynchronous on `stream`; ordered against the handle's solves."""
         import torch
-        lam_g = None if (lam_g is None or (isinstance(lam_g, (int, float)) and lam_g == 0)) else lam_g
-        lam_x = None if (lam_x is None or (isinstance(lam_x, (int, float)) and lam_x == 0)) else lam_x
+        lam_g, lam_x = _multiplier_or_none(lam_g), _multiplier_or_none(lam_x)
         B = self._check_io(p, x, None)
         self._check_multipliers(B, lam_g, lam_x, p.device)
-        bad = [k for k in want if k not in self._CERT_WANT]
-        if bad:
-            raise ValueError(f"want {bad}: a certificate offers {self._CERT_WANT}")
+        _check_want(want, self._CERT_WANT, "certificate")
         o = out if out is not None else {}
         dev = p.device
         shapes = dict(cert=(B, len(KKT_FIELDS)), g=(B, self.n_g), lam_g=(B, self.n_g), rj=(B, 8 * self.N))
@@ -274,9 +308,8 @@ class BatchedOCPSolver:
                 raise ValueError(f"out[{k!r}] must be a contiguous float64 GPU tensor of shape {shapes[k]} on {dev}")
             ptr[k] = t
         st = stream if stream is not None else torch.cuda.current_stream(dev)
-        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(self._lib.bmpc_kkt_batch(self._h, B, dp(p), dp(x), dp(lam_g), dp(lam_x), dp(ptr["cert"]), dp(ptr.get("g")), dp(ptr.get("lam_g")),
-                                            dp(ptr.get("rj")), ctypes.c_void_p(st.cuda_stream)), "bmpc_kkt_batch")
+        _lib.check(self._lib.bmpc_kkt_batch(self._h, B, _ptr(p), _ptr(x), _ptr(lam_g), _ptr(lam_x), _ptr(ptr["cert"]), _ptr(ptr.get("g")), _ptr(ptr.get("lam_g")),
+                                            _ptr(ptr.get("rj")), ctypes.c_void_p(st.cuda_stream)), "bmpc_kkt_batch")
         self._inflight_cert = (p, x, lam_g, lam_x, o)      # (asynchronous launch: see solve_batch)
         for i, k in enumerate(KKT_FIELDS):
             o[k] = ptr["cert"][:, i]
@@ -284,30 +317,15 @@ class BatchedOCPSolver:
 
     def certify_host(self, p, x, lam_g=None, lam_x=None, want=()):
         """certify with numpy in / out (bmpc_kkt_batch_host: staged copies, one synchronisation)."""
-        p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
-        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
-        B = p.shape[0]
-        if p.shape != (B, self.n_p) or x.shape != (B, self.n_w):
-            raise ValueError(f"shape mismatch: p {p.shape} x {x.shape}")
-        lam = []
-        for a, n, nm in ((lam_g, self.n_g, "lam_g"), (lam_x, self.n_w, "lam_x")):
-            if a is not None and not (np.isscalar(a) and a == 0):
-                a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
-                if a.shape != (B, n):
-                    raise ValueError(f"{nm} has shape {a.shape}, expected {(B, n)}")
-            else:
-                a = None
-            lam.append(a)
-        bad = [k for k in want if k not in self._CERT_WANT]
-        if bad:
-            raise ValueError(f"want {bad}: a certificate offers {self._CERT_WANT}")
+        B, p, x = _host_rows(("p", p, self.n_p), ("x", x, self.n_w))
+        lam = self._host_multipliers(B, lam_g, lam_x, ("lam_g", "lam_x"))
+        _check_want(want, self._CERT_WANT, "certificate")
         shapes = dict(g=(B, self.n_g), lam_g=(B, self.n_g), rj=(B, 8 * self.N))
         o = {"cert": np.zeros((B, len(KKT_FIELDS)))}
         for k in want:
             o[k] = np.zeros(shapes[k])
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
-        _lib.check(self._lib.bmpc_kkt_batch_host(self._h, B, vp(p), vp(x), vp(lam[0]), vp(lam[1]), vp(o["cert"]), vp(o.get("g")), vp(o.get("lam_g")),
-                                                 vp(o.get("rj"))), "bmpc_kkt_batch_host")
+        _lib.check(self._lib.bmpc_kkt_batch_host(self._h, B, _ptr(p), _ptr(x), _ptr(lam[0]), _ptr(lam[1]), _ptr(o["cert"]), _ptr(o.get("g")), _ptr(o.get("lam_g")),
+                                                 _ptr(o.get("rj"))), "bmpc_kkt_batch_host")
         for i, k in enumerate(KKT_FIELDS):
             o[k] = o["cert"][:, i]
         return o
@@ -321,8 +339,7 @@ class BatchedOCPSolver:
         delta, max |rhs|, max |dx|: SENS_FIELDS) and, with want_duals, "dlam_eq" [..][36 N] and "dnu" [..][57 N].  The system, the record and the
         rules for non-finite input: include/boundmpc_hip.h bmpc_sens_batch.  Asynchronous on `stream`; ordered against the handle's solves."""
         import torch
-        lam_g = None if (lam_g is None or (isinstance(lam_g, (int, float)) and lam_g == 0)) else lam_g
-        lam_x = None if (lam_x is None or (isinstance(lam_x, (int, float)) and lam_x == 0)) else lam_x
+        lam_g, lam_x = _multiplier_or_none(lam_g), _multiplier_or_none(lam_x)
         B = self._check_io(p, x, None)
         self._check_multipliers(B, lam_g, lam_x, p.device)
         if not (dp.is_cuda and dp.dtype == torch.float64 and dp.is_contiguous() and dp.device == p.device and dp.dim() in (2, 3) and dp.shape[0] == B
@@ -341,9 +358,8 @@ class BatchedOCPSolver:
             o["dlam_eq"] = torch.empty((R, 36 * self.N), dtype=torch.float64, device=dev)
             o["dnu"] = torch.empty((R, 57 * self.N), dtype=torch.float64, device=dev)
         st = stream if stream is not None else torch.cuda.current_stream(dev)
-        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        _lib.check(self._lib.bmpc_sens_batch(self._h, R, ptr(p), ptr(x), ptr(lam_g), ptr(lam_x), ptr(dp), float(mu or 0.0), ptr(o["dx"]), ptr(o.get("dlam_eq")),
-                                             ptr(o.get("dnu")), ptr(o["rec"]), ctypes.c_void_p(st.cuda_stream)), "bmpc_sens_batch")
+        _lib.check(self._lib.bmpc_sens_batch(self._h, R, _ptr(p), _ptr(x), _ptr(lam_g), _ptr(lam_x), _ptr(dp), float(mu or 0.0), _ptr(o["dx"]), _ptr(o.get("dlam_eq")),
+                                             _ptr(o.get("dnu")), _ptr(o["rec"]), ctypes.c_void_p(st.cuda_stream)), "bmpc_sens_batch")
         self._inflight_sens = (p, x, lam_g, lam_x, dp, o)      # (asynchronous launch: see solve_batch)
         if D is not None:
             o = {k: v.view(B, D, v.shape[-1]) for k, v in o.items()}
@@ -351,22 +367,12 @@ class BatchedOCPSolver:
 
     def sensitivity_host(self, p, x, dp, lam_g=None, lam_x=None, mu=None, want_duals=False):
         """sensitivity with numpy in / out (bmpc_sens_batch_host: staged copies, one synchronisation)."""
-        p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
-        x = np.ascontiguousarray(np.atleast_2d(x), dtype=np.float64)
         dp = np.ascontiguousarray(dp, dtype=np.float64)
         dp = dp[None, :] if dp.ndim == 1 else dp
-        B = p.shape[0]
-        if p.shape != (B, self.n_p) or x.shape != (B, self.n_w) or dp.ndim not in (2, 3) or dp.shape[0] != B or dp.shape[-1] != self.n_p:
+        B, p, x = _host_rows(("p", p, self.n_p), ("x", x, self.n_w))
+        if dp.ndim not in (2, 3) or dp.shape[0] != B or dp.shape[-1] != self.n_p:
             raise ValueError(f"shape mismatch: p {p.shape} x {x.shape} dp {dp.shape}")
-        lam = []
-        for a, n, nm in ((lam_g, self.n_g, "lam_g"), (lam_x, self.n_w, "lam_x")):
-            if a is not None and not (np.isscalar(a) and a == 0):
-                a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
-                if a.shape != (B, n):
-                    raise ValueError(f"{nm} has shape {a.shape}, expected {(B, n)}")
-            else:
-                a = None
-            lam.append(a)
+        lam = self._host_multipliers(B, lam_g, lam_x, ("lam_g", "lam_x"))
         D = dp.shape[1] if dp.ndim == 3 else None
         if D is not None:
             if D < 1:
@@ -377,9 +383,8 @@ class BatchedOCPSolver:
         o = {"dx": np.zeros((R, self.n_w)), "rec": np.zeros((R, len(SENS_FIELDS)))}
         if want_duals:
             o["dlam_eq"], o["dnu"] = np.zeros((R, 36 * self.N)), np.zeros((R, 57 * self.N))
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
-        _lib.check(self._lib.bmpc_sens_batch_host(self._h, R, vp(p), vp(x), vp(lam[0]), vp(lam[1]), vp(dp), float(mu or 0.0), vp(o["dx"]), vp(o.get("dlam_eq")),
-                                                  vp(o.get("dnu")), vp(o["rec"])), "bmpc_sens_batch_host")
+        _lib.check(self._lib.bmpc_sens_batch_host(self._h, R, _ptr(p), _ptr(x), _ptr(lam[0]), _ptr(lam[1]), _ptr(dp), float(mu or 0.0), _ptr(o["dx"]), _ptr(o.get("dlam_eq")),
+                                                  _ptr(o.get("dnu")), _ptr(o["rec"])), "bmpc_sens_batch_host")
         if D is not None:
             o = {k: v.reshape(B, D, v.shape[-1]) for k, v in o.items()}
         return o
@@ -418,16 +423,15 @@ class BatchedOCPSolver:
         if "status" in want: ptr["status"] = buf("status", (B,), torch.int32)
         if "kkt" in want: ptr["kkt"] = buf("kkt", (B,), torch.float64)
         st = stream if stream is not None else torch.cuda.current_stream(dev)
-        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
         if state is None and not max_iter:
-            _lib.check(self._lib.bmpc_solve_batch(self._h, B, dp(p), dp(x0), dp(x), dp(ptr["g"]), dp(ptr["lam_g"]), dp(ptr["lam_x"]),
-                                                  dp(ptr["f"]), dp(ptr["iters"]), dp(ptr["status"]), dp(ptr["kkt"]),
+            _lib.check(self._lib.bmpc_solve_batch(self._h, B, _ptr(p), _ptr(x0), _ptr(x), _ptr(ptr["g"]), _ptr(ptr["lam_g"]), _ptr(ptr["lam_x"]),
+                                                  _ptr(ptr["f"]), _ptr(ptr["iters"]), _ptr(ptr["status"]), _ptr(ptr["kkt"]),
                                                   ctypes.c_void_p(st.cuda_stream)), "bmpc_solve_batch")
         else:
             if state is None:
                 raise ValueError("max_iter per call needs a state buffer (new_state)")
-            _lib.check(self._lib.bmpc_solve_batch_warm(self._h, B, dp(p), dp(x0), dp(state), int(max_iter), dp(x), dp(ptr["g"]), dp(ptr["lam_g"]),
-                                                       dp(ptr["lam_x"]), dp(ptr["f"]), dp(ptr["iters"]), dp(ptr["status"]), dp(ptr["kkt"]),
+            _lib.check(self._lib.bmpc_solve_batch_warm(self._h, B, _ptr(p), _ptr(x0), _ptr(state), int(max_iter), _ptr(x), _ptr(ptr["g"]), _ptr(ptr["lam_g"]),
+                                                       _ptr(ptr["lam_x"]), _ptr(ptr["f"]), _ptr(ptr["iters"]), _ptr(ptr["status"]), _ptr(ptr["kkt"]),
                                                        ctypes.c_void_p(st.cuda_stream)), "bmpc_solve_batch_warm")
         # The launch is asynchronous: the kernel reads p / x0 / state and writes the outputs on the launch stream after this call has
         # returned.  The handle keeps them alive until its next launch (a caller that passes temporaries or drops the returned dict would
@@ -444,29 +448,18 @@ class BatchedOCPSolver:
     def solve_host(self, p, x0, lam_g0=None, lam_x0=None):
         """numpy in / out.  With multipliers lam_g0 [B][n_g] / lam_x0 [B][n_w] (either may be None): converted and warm-solved in the same
         single call (bmpc_solve_batch_host_dual); without: the stateless solve."""
-        p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
-        x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
-        B = p.shape[0]
-        if p.shape != (B, self.n_p) or x0.shape != (B, self.n_w):
-            raise ValueError(f"shape mismatch: p {p.shape} x0 {x0.shape}")
-        lam = []
-        for a, n, nm in ((lam_g0, self.n_g, "lam_g0"), (lam_x0, self.n_w, "lam_x0")):
-            if a is not None:
-                a = np.ascontiguousarray(np.atleast_2d(a), dtype=np.float64)
-                if a.shape != (B, n):
-                    raise ValueError(f"{nm} has shape {a.shape}, expected {(B, n)}")
-            lam.append(a)
+        B, p, x0 = _host_rows(("p", p, self.n_p), ("x0", x0, self.n_w))
+        lam = self._host_multipliers(B, lam_g0, lam_x0, ("lam_g0", "lam_x0"))
         out = dict(x=np.zeros((B, self.n_w)), g=np.zeros((B, self.n_g)), lam_g=np.zeros((B, self.n_g)), lam_x=np.zeros((B, self.n_w)),
                    f=np.zeros(B), iters=np.zeros(B, dtype=np.int32), status=np.zeros(B, dtype=np.int32), kkt=np.zeros(B))
-        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
-        if lam_g0 is None and lam_x0 is None:
-            _lib.check(self._lib.bmpc_solve_batch_host(self._h, B, vp(p), vp(x0), vp(out["x"]), vp(out["g"]), vp(out["lam_g"]),
-                                                       vp(out["lam_x"]), vp(out["f"]), vp(out["iters"]), vp(out["status"]), vp(out["kkt"])),
+        if lam[0] is None and lam[1] is None:
+            _lib.check(self._lib.bmpc_solve_batch_host(self._h, B, _ptr(p), _ptr(x0), _ptr(out["x"]), _ptr(out["g"]), _ptr(out["lam_g"]),
+                                                       _ptr(out["lam_x"]), _ptr(out["f"]), _ptr(out["iters"]), _ptr(out["status"]), _ptr(out["kkt"])),
                        "bmpc_solve_batch_host")
         else:
-            _lib.check(self._lib.bmpc_solve_batch_host_dual(self._h, B, vp(p), vp(x0), vp(lam[0]), vp(lam[1]), vp(out["x"]), vp(out["g"]),
-                                                            vp(out["lam_g"]), vp(out["lam_x"]), vp(out["f"]), vp(out["iters"]), vp(out["status"]),
-                                                            vp(out["kkt"])), "bmpc_solve_batch_host_dual")
+            _lib.check(self._lib.bmpc_solve_batch_host_dual(self._h, B, _ptr(p), _ptr(x0), _ptr(lam[0]), _ptr(lam[1]), _ptr(out["x"]), _ptr(out["g"]),
+                                                            _ptr(out["lam_g"]), _ptr(out["lam_x"]), _ptr(out["f"]), _ptr(out["iters"]), _ptr(out["status"]),
+                                                            _ptr(out["kkt"])), "bmpc_solve_batch_host_dual")
         return out
 
 
@@ -485,10 +478,9 @@ class StepGraph:
         self.out = {"x": torch.empty((B, solver.n_w), dtype=torch.float64, device=dev)}
         for k in want:
             self.out[k] = torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev)
-        dp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None
-        g = lambda k: dp(self.out.get(k))
+        g = lambda k: _ptr(self.out.get(k))
         self._g = ctypes.c_void_p()
-        _lib.check(solver._lib.bmpc_graph_create(solver._h, B, dp(p), dp(x0), dp(state), int(max_iter), dp(self.out["x"]), g("g"), g("lam_g"),
+        _lib.check(solver._lib.bmpc_graph_create(solver._h, B, _ptr(p), _ptr(x0), _ptr(state), int(max_iter), _ptr(self.out["x"]), g("g"), g("lam_g"),
                                                  g("lam_x"), g("f"), g("iters"), g("status"), g("kkt"), ctypes.byref(self._g)), "bmpc_graph_create")
         solver._children.add(self)
 

@@ -1,5 +1,5 @@
 // TEST-ONLY: CPU build of the primal-dual warm-start conversion (boundmpc_amd/csrc/bmpc_dual.inl) over the lane emulator of the wave
-// program (the same text the GPU kernel bmpc_dual_kernel runs; phases as loops over the 64 lanes in a caller-chosen order).  Used by
+// program (the same text the GPU kernel bmpc_service_kernel<ZLDS, DualBatch> runs, its slicing of the batch included; phases as loops over the 64 lanes in a caller-chosen order).  Used by
 // tests/test_dual_warm_start.py; never built, loaded or fallen back to by the product.
 #include <cstdio>
 #include <cstring>
@@ -19,15 +19,13 @@ extern "C" int bmpc_emu_state_from_multipliers(int N, int S, double h, const bmp
                                                const double *lam_g, const double *lam_x, double mu0, double *state, int lane_order, int poison) {
     if (S > bmpc::SMAX || S < 2 || N < 1 || N > bmpc::NMAX) return 1;
     const bmpc::Scr sc = bmpc::make_scr(N);
-    const int np = 141 + 91 * S, nw = N * bmpc::NZ, ng = N * bmpc::NG, sl = N * bmpc::NI + 2;
+    const bmpc::DualBatch a{p, x0, lam_g, lam_x, state, mu0};
     std::vector<double> lds(bmpc::L_SIZE, 0.0), scr(sc.size, 0.0);
     for (int b = 0; b < B; b++) {
         if (poison) { std::fill(lds.begin(), lds.end(), std::nan("")); std::fill(scr.begin(), scr.end(), std::nan("")); }
         bmpc::Wave W; W.N = N; W.S = S; W.h = h; W.o = *opts; W.L = lds.data(); W.G = bmpc::make_gptr(scr.data()); W.wv = 0; W.it_base = 0;
         for (int i = 0; i < 64; i++) W.order[i] = lane_order == 0 ? i : (lane_order == 1 ? 63 - i : (i * 37 + 11) % 64);
-        bmpc::DualIn d;
-        d.p = p + (size_t)b * np; d.x0 = x0 + (size_t)b * nw; d.state = state + (size_t)b * sl; d.mu = mu0;
-        d.lam_g = lam_g ? lam_g + (size_t)b * ng : nullptr; d.lam_x = lam_x ? lam_x + (size_t)b * nw : nullptr;
+        const bmpc::DualIn d = a.problem(N, S, b);
         if (N <= 11 && S <= bmpc::SMAX_ZLDS) bmpc::wave_state_from_multipliers<true>(W, d); else bmpc::wave_state_from_multipliers<false>(W, d);
     }
     return 0;

@@ -1,5 +1,5 @@
 // TEST-ONLY: CPU build of the KKT certificate (boundmpc_amd/csrc/bmpc_kkt.inl) over the lane emulator of the wave program (the same text the
-// GPU kernel bmpc_kkt_kernel runs; phases as loops over the 64 lanes in a caller-chosen order).  Used by tests/test_kkt_certificate.py; never
+// GPU kernel bmpc_service_kernel<ZLDS, KktBatch> runs, its slicing of the batch included; phases as loops over the 64 lanes in a caller-chosen order).  Used by tests/test_kkt_certificate.py; never
 // built, loaded or fallen back to by the product.
 #include <cstdio>
 #include <cstring>
@@ -22,16 +22,13 @@ extern "C" int bmpc_emu_kkt(int N, int S, double h, const bmpc::Opts *opts, int 
                             const double *lam_x0, double *cert, double *g, double *lam_g, double *rj, int lane_order, int poison) {
     if (S > bmpc::SMAX || S < 2 || N < 1 || N > bmpc::NMAX) return 1;
     const bmpc::Scr sc = bmpc::make_scr(N);
-    const int np = 141 + 91 * S, nw = N * bmpc::NZ, ng = N * bmpc::NG, nj = N * bmpc::NU;
+    const bmpc::KktBatch a{p, x, lam_g0, lam_x0, cert, g, lam_g, rj};
     std::vector<double> lds(bmpc::L_SIZE, 0.0), scr(sc.size, 0.0);
     for (int b = 0; b < B; b++) {
         if (poison) { std::fill(lds.begin(), lds.end(), std::nan("")); std::fill(scr.begin(), scr.end(), std::nan("")); }
         bmpc::Wave W; W.N = N; W.S = S; W.h = h; W.o = *opts; W.L = lds.data(); W.G = bmpc::make_gptr(scr.data()); W.wv = 0; W.it_base = 0;
         for (int i = 0; i < 64; i++) W.order[i] = lane_order == 0 ? i : (lane_order == 1 ? 63 - i : (i * 37 + 11) % 64);
-        bmpc::KktIn d;
-        d.p = p + (size_t)b * np; d.x = x + (size_t)b * nw; d.cert = cert + (size_t)b * bmpc::KKT_LEN;
-        d.lam_g0 = lam_g0 ? lam_g0 + (size_t)b * ng : nullptr; d.lam_x0 = lam_x0 ? lam_x0 + (size_t)b * nw : nullptr;
-        d.g = g ? g + (size_t)b * ng : nullptr; d.lam_g = lam_g ? lam_g + (size_t)b * ng : nullptr; d.rj = rj ? rj + (size_t)b * nj : nullptr;
+        const bmpc::KktIn d = a.problem(N, S, b);
         if (N <= 11 && S <= bmpc::SMAX_ZLDS) bmpc::wave_certify<true>(W, d); else bmpc::wave_certify<false>(W, d);
     }
     return 0;

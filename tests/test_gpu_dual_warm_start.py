@@ -1,4 +1,4 @@
-"""Primal-dual warm start on the MI355X: the conversion kernel (bmpc_dual_kernel, boundmpc_amd/csrc/bmpc_dual.inl) against the numpy checker
+"""Primal-dual warm start on the MI355X: the conversion kernel (bmpc_service_kernel over DualBatch, boundmpc_amd/csrc/bmpc_dual.inl) against the numpy checker
 of tests/test_dual_warm_start.py, warm solves from multipliers against the oracle on every launch shape, the drop-in closed loop with the
 reference's lam_g0 / lam_x0 hand-over restored, the unchanged default path, hostile input and cross-stream ordering.  `pytest -m gpu`."""
 import os

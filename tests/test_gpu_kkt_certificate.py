@@ -1,4 +1,4 @@
-"""KKT certificate of any primal-dual point on the MI355X (bmpc_kkt_kernel, boundmpc_amd/csrc/bmpc_kkt.inl): the record against the numpy checker of
+"""KKT certificate of any primal-dual point on the MI355X (bmpc_service_kernel over KktBatch, boundmpc_amd/csrc/bmpc_kkt.inl): the record against the numpy checker of
 tests/test_kkt_certificate.py (same inputs, same tolerances) through the device entry point, the host entry point and the shim; determinism;
 interleaving with solves on other streams; the GPU solve's own outputs of configs[1] at full size; stale rows.  `pytest -m gpu`."""
 import os

@@ -1,4 +1,4 @@
-"""Parametric solution sensitivities on the MI355X (bmpc_sens_kernel, boundmpc_amd/csrc/bmpc_sens.inl): dx against the numpy checker of
+"""Parametric solution sensitivities on the MI355X (bmpc_service_kernel over SensBatch, boundmpc_amd/csrc/bmpc_sens.inl): dx against the numpy checker of
 tests/test_sensitivity.py (its checked set, read from tests/golden/sensitivity_checked_set.npz; the same bound: 100 x the checker's own floor),
 the three equations at full size, differenced real solves, and the contract cases through the device entry point, the host entry point and the
 shim: zero direction, linearity, NULL multipliers, non-finite input, regularisation, argument errors, determinism, [B, D, n_p], interleaving
@@ -67,7 +67,7 @@ def test_gpu_full_size_tangent_satisfies_the_three_equations(rows, solvers):
 
 @pytest.mark.parametrize("N,S", [(4, 5), (12, 4)])
 def test_gpu_instantiation_without_the_lds_iterate_satisfies_the_equations(rows, N, S):
-    """bmpc_sens_kernel<false> (S > 4 or N > 11: iterate and direction in the workspace slab) on the hardware: the three equations at S = 5, the
+    """bmpc_service_kernel<false, SensBatch> (S > 4 or N > 11: iterate and direction in the workspace slab) on the hardware: the three equations at S = 5, the
     equality rows and the row equation at N = 12 (as the emulator test), device and host entry points bit-equal"""
     from boundmpc_amd import BatchedOCPSolver
     fl = floor_of(rows)
