@@ -1,0 +1,70 @@
+// bmpc_args.h -- the kernel argument records and what every kernel entry does with them: the wave of a workgroup from the argument head, and
+// problem b of a batch as the wave program's Problem.  Nothing of HIP in here: bmpc_gpu_common.h includes it for the kernels, and the CPU
+// emulators of the kernel text (tests/emu) include it to run these very lines.  The macros name BMPC_NAMESPACE::Wave / Problem / make_gptr of the
+// wave program (bmpc_wave.inl) and are expanded behind it.
+#pragma once
+
+// The wave `W` of a workgroup from the argument head {N, S, h, o} of `a`, on the LDS array `lds` and the workspace slab `slab`; wave: its index in
+// the workgroup (0 in a one-wave kernel).  A macro for the reason given at BMPC_PROBLEM.
+#define BMPC_WAVE_INIT(W, a, lds, slab, wave) \
+    BMPC_NAMESPACE::Wave W; W.N = (a).N; W.S = (a).S; W.h = (a).h; W.o = (a).o; W.L = (lds); \
+    W.G = BMPC_NAMESPACE::make_gptr(slab); W.wv = (wave); W.deadline = 0; W.it_base = 0
+
+// Problem `pr` = problem b of a batch kernel's arguments `a`: its slices of the inputs and of the outputs the caller passed (NULL stays NULL);
+// np, nw, ng: the lengths of a problem's parameter, variable and constraint vectors (computed once, ahead of the kernel's work loop).
+// A macro, expanded in the kernel body: the same lines as a function that takes `a` (by value or by reference) cost the argument loads their
+// no-clobber property, and the register allocation of the whole kernel moves.
+#define BMPC_STRIDES(a) const int np = 141 + 91 * (a).S, nw = (a).N * BMPC_NAMESPACE::NZ, ng = (a).N * BMPC_NAMESPACE::NG
+#define BMPC_PROBLEM(pr, a, b) \
+    BMPC_NAMESPACE::Problem pr; \
+    pr.p = (a).p + (long long)(b) * np; pr.x0 = (a).x0 + (long long)(b) * nw; \
+    pr.x = (a).x ? (a).x + (long long)(b) * nw : nullptr; pr.g = (a).g ? (a).g + (long long)(b) * ng : nullptr; \
+    pr.lam_g = (a).lam_g ? (a).lam_g + (long long)(b) * ng : nullptr; pr.lam_x = (a).lam_x ? (a).lam_x + (long long)(b) * nw : nullptr; \
+    pr.f = (a).f ? (a).f + (b) : nullptr; pr.kkt = (a).kkt ? (a).kkt + (b) : nullptr; \
+    pr.iters = (a).iters ? (a).iters + (b) : nullptr; pr.status = (a).status ? (a).status + (b) : nullptr; \
+    pr.state = (a).state ? (a).state + (long long)(b) * ((a).N * BMPC_NAMESPACE::NI + 2) : nullptr; \
+    pr.resto_from = -1
+// The restoration kernel's slicing (bmpc_resto.hip; its own, not BMPC_PROBLEM: x, iters and status are always there, and the shared lines with
+// these overrides compile to another kernel).  fresh: an ordinary solve from x0; else the continuation of what a batch kernel left with status 4 --
+// from the iterate it left in x (read before x is rewritten), counting on from its iterations.  BMPC_RESTO_X0_RETRY: the x0_retry argument of
+// wave_solve_retry that goes with it (a continuation's second attempt is a fresh solve from the caller's x0).
+#define BMPC_RESTO_PROBLEM(pr, a, b, fresh) \
+    BMPC_NAMESPACE::Problem pr; \
+    pr.p = (a).p + (long long)(b) * np; pr.x0 = ((fresh) ? (a).x0 : (a).x) + (long long)(b) * nw; \
+    pr.x = (a).x + (long long)(b) * nw; pr.g = (a).g ? (a).g + (long long)(b) * ng : nullptr; \
+    pr.lam_g = (a).lam_g ? (a).lam_g + (long long)(b) * ng : nullptr; pr.lam_x = (a).lam_x ? (a).lam_x + (long long)(b) * nw : nullptr; \
+    pr.f = (a).f ? (a).f + (b) : nullptr; pr.kkt = (a).kkt ? (a).kkt + (b) : nullptr; \
+    pr.iters = (a).iters + (b); pr.status = (a).status + (b); \
+    pr.state = (a).state ? (a).state + (long long)(b) * ((a).N * BMPC_NAMESPACE::NI + 2) : nullptr; \
+    pr.resto_from = (fresh) ? -1 : (a).iters[(b)]
+#define BMPC_RESTO_X0_RETRY(a, b, fresh) ((fresh) ? nullptr : (a).x0 + (long long)(b) * nw)
+// The fused tick's slicing (bmpc_tick_kernel.inl): p, x0 and the dual state are the ones the tick packed, x, g and status are always given, the
+// multiplier outputs are not.
+#define BMPC_TICK_PROBLEM(pr, a, b, p_, x0_, dual_) \
+    BMPC_NAMESPACE::Problem pr; \
+    pr.p = (p_); pr.x0 = (x0_); pr.x = (a).x + (long long)(b) * nw; pr.g = (a).g + (long long)(b) * ng; pr.lam_g = nullptr; pr.lam_x = nullptr; \
+    pr.f = nullptr; pr.kkt = (a).kkt ? (a).kkt + (b) : nullptr; pr.iters = (a).iters ? (a).iters + (b) : nullptr; pr.status = (a).status + (b); \
+    pr.state = (dual_); pr.resto_from = -1
+
+// kernel arguments of a solve; OPTS = the Opts type of the wave program's namespace (same layout in every instantiation)
+template <class OPTS>
+struct KArgsT {
+    int N, S, B; double h; OPTS o;
+    const double *p, *x0; double *x, *g, *lam_g, *lam_x, *f, *kkt; int *iters, *status;
+    double *state;           // optional [B][57 N + 2] dual state of a receding-horizon stream (bmpc_solve_batch_warm)
+    double *latency_us;      // optional [B]: in-kernel duration of each solve (bmpc_set_latency_buffer)
+    double *scratch; long long scr_stride; int *counter; unsigned long long *prof;
+    long long budget_ticks;  // fused closed-loop tick only: time budget of a tick in counts of the 100 MHz wall clock, from kernel entry (0 = none)
+    int *counter2, *rcount;  // restoration kernel (bmpc_resto.hip): its work queue; number of problems the batch kernel left with status 4 (NULL: phase off)
+    const int *order;        // one-wave batch kernel: the work queue hands out order[0], order[1], ... instead of 0, 1, ... (NULL: natural order; bmpc_set_queue_order)
+};
+// kernel arguments of a service launch (bmpc_hip.hip bmpc_service_kernel): the head the wave needs, then the batch record of the job
+template <class OPTS, class JOB>
+struct ServiceArgsT {
+    int N, S, B; double h; OPTS o; double *scratch; long long scr_stride;
+    JOB job;
+};
+// stream arguments of a fused tick
+struct SArgs {
+    const double *path; int path_stride; double *ss, *rb, *traj; int flags; double rt_tol; double rt_row_cap; double lvl_c, lvl_lo, lvl_hi;
+};

@@ -1,6 +1,6 @@
 // bmpc_gpu_common.h -- what the translation units of libboundmpc_hip.so share: the device math macros the wave program
 // (bmpc_wave.inl) is written in, its lane and phase macros (one set per BMPC_NW: one wave, or a workgroup of cooperating waves), the phase
-// stamps, the prologue of a one-wave kernel, the per-problem slicing of a batch kernel's arguments, and the kernel argument records.  The
+// stamps and the prologue of a one-wave kernel; bmpc_args.h holds the kernel argument records and the per-problem slicing of a batch.  The
 // kernel entry texts shared between units are bmpc_multi_batch.inl (the batch kernel of the team and pair units) and bmpc_tick_kernel.inl (the
 // fused tick of the one-wave tick and team units).  bmpc_hip.hip holds the one-wave-per-problem batch kernel, the service kernel (one entry
 // over the jobs of bmpc_dual.inl, bmpc_kkt.inl and bmpc_sens.inl, each of which slices its own batch) and the C ABI, bmpc_team.hip the team
@@ -8,6 +8,8 @@
 // one-wave fused ticks.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "bmpc_args.h"      // the kernel argument records, the wave initialiser and the per-problem slicers (host-clean: the CPU emulators run them too)
 
 #define BMPC_HD __host__ __device__ __forceinline__
 #define BMPC_D __device__ __forceinline__
@@ -77,55 +79,16 @@
 #endif
 
 // Prologue of a kernel that runs one wave per workgroup (bmpc_hip.hip: solve and service kernels; bmpc_resto.hip): the wave `W` of this workgroup
-// from the argument head {N, S, h, o, scratch, scr_stride} of `a`, on the LDS array `lds` and on workspace slab blockIdx.x; in a unit that
-// stamps its phases (above) of a -DBMPC_PROFILE build also the zeroed stamp area and the first stamp.  A macro for the reason given below.
+// from the argument head {N, S, h, o, scratch, scr_stride} of `a` (BMPC_WAVE_INIT of bmpc_args.h), on the LDS array `lds` and on workspace slab
+// blockIdx.x; in a unit that stamps its phases (above) of a -DBMPC_PROFILE build also the zeroed stamp area and the first stamp.
 #if defined(BMPC_PROFILE) && BMPC_STAMPS >= 1
 #define BMPC_WAVE_STAMP0(W, lds) if (threadIdx.x < 32) ((long long *)((lds) + BMPC_NAMESPACE::L_PROF))[threadIdx.x] = 0; __syncthreads(); W.tprev = clock64()
 #else
 #define BMPC_WAVE_STAMP0(W, lds) W.tprev = 0
 #endif
 #define BMPC_ONE_WAVE(W, a, lds) \
-    BMPC_NAMESPACE::Wave W; W.N = (a).N; W.S = (a).S; W.h = (a).h; W.o = (a).o; W.L = (lds); \
-    W.G = BMPC_NAMESPACE::make_gptr((a).scratch + (long long)blockIdx.x * (a).scr_stride); W.wv = 0; W.deadline = 0; W.it_base = 0; \
+    BMPC_WAVE_INIT(W, a, lds, (a).scratch + (long long)blockIdx.x * (a).scr_stride, 0); \
     BMPC_WAVE_STAMP0(W, lds)
-
-// Problem `pr` = problem b of a batch kernel's arguments `a`: its slices of the inputs and of the outputs the caller passed (NULL stays NULL);
-// np, nw, ng: the lengths of a problem's parameter, variable and constraint vectors (computed once, ahead of the kernel's work loop).
-// A macro, expanded in the kernel body: the same lines as a function that takes `a` (by value or by reference) cost the argument loads their
-// no-clobber property, and the register allocation of the whole kernel moves.
-#define BMPC_STRIDES(a) const int np = 141 + 91 * (a).S, nw = (a).N * BMPC_NAMESPACE::NZ, ng = (a).N * BMPC_NAMESPACE::NG
-#define BMPC_PROBLEM(pr, a, b) \
-    BMPC_NAMESPACE::Problem pr; \
-    pr.p = (a).p + (long long)(b) * np; pr.x0 = (a).x0 + (long long)(b) * nw; \
-    pr.x = (a).x ? (a).x + (long long)(b) * nw : nullptr; pr.g = (a).g ? (a).g + (long long)(b) * ng : nullptr; \
-    pr.lam_g = (a).lam_g ? (a).lam_g + (long long)(b) * ng : nullptr; pr.lam_x = (a).lam_x ? (a).lam_x + (long long)(b) * nw : nullptr; \
-    pr.f = (a).f ? (a).f + (b) : nullptr; pr.kkt = (a).kkt ? (a).kkt + (b) : nullptr; \
-    pr.iters = (a).iters ? (a).iters + (b) : nullptr; pr.status = (a).status ? (a).status + (b) : nullptr; \
-    pr.state = (a).state ? (a).state + (long long)(b) * ((a).N * BMPC_NAMESPACE::NI + 2) : nullptr; \
-    pr.resto_from = -1
-
-// kernel arguments of a solve; OPTS = the Opts type of the wave program's namespace (same layout in every instantiation)
-template <class OPTS>
-struct KArgsT {
-    int N, S, B; double h; OPTS o;
-    const double *p, *x0; double *x, *g, *lam_g, *lam_x, *f, *kkt; int *iters, *status;
-    double *state;           // optional [B][57 N + 2] dual state of a receding-horizon stream (bmpc_solve_batch_warm)
-    double *latency_us;      // optional [B]: in-kernel duration of each solve (bmpc_set_latency_buffer)
-    double *scratch; long long scr_stride; int *counter; unsigned long long *prof;
-    long long budget_ticks;  // fused closed-loop tick only: time budget of a tick in counts of the 100 MHz wall clock, from kernel entry (0 = none)
-    int *counter2, *rcount;  // restoration kernel (bmpc_resto.hip): its work queue; number of problems the batch kernel left with status 4 (NULL: phase off)
-    const int *order;        // one-wave batch kernel: the work queue hands out order[0], order[1], ... instead of 0, 1, ... (NULL: natural order; bmpc_set_queue_order)
-};
-// kernel arguments of a service launch (bmpc_hip.hip bmpc_service_kernel): the head the wave needs, then the batch record of the job
-template <class OPTS, class JOB>
-struct ServiceArgsT {
-    int N, S, B; double h; OPTS o; double *scratch; long long scr_stride;
-    JOB job;
-};
-// stream arguments of a fused tick
-struct SArgs {
-    const double *path; int path_stride; double *ss, *rb, *traj; int flags; double rt_tol; double rt_row_cap; double lvl_c, lvl_lo, lvl_hi;
-};
 
 // ---- restoration kernel (bmpc_resto.hip): continues the problems a batch kernel left with the internal status 4 ----
 hipError_t bmpc_resto_launch(bool zlds, const void *kargs, int grid, hipStream_t st);

@@ -3,14 +3,10 @@
 // Included after the wave program; the unit defines KArgs and BMPC_SOLVE_KERNEL, the kernel's declarator (launch bounds and name).
 BMPC_SOLVE_KERNEL(KArgs a) {
     __shared__ double lds[BMPC_NAMESPACE::L_SIZE];
-    BMPC_NAMESPACE::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = BMPC_NAMESPACE::make_gptr(a.scratch + (long long)blockIdx.x * a.scr_stride);
-    W.wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    W.deadline = 0; W.it_base = 0;
+    BMPC_WAVE_INIT(W, a, lds, a.scratch + (long long)blockIdx.x * a.scr_stride, __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)));
     BMPC_STRIDES(a);
 #ifdef BMPC_PROFILE
-    if (threadIdx.x < 32) ((long long *)(lds + BMPC_NAMESPACE::L_PROF))[threadIdx.x] = 0;
-    __syncthreads();
-    W.tprev = clock64();
+    BMPC_WAVE_STAMP0(W, lds);
 #endif
     for (;;) {
         // one lane takes the next problem off the queue for the workgroup

@@ -37,18 +37,9 @@ __global__ void __launch_bounds__(64, 1) bmpc_resto_kernel(KArgs a) {
         if ((unsigned)b >= (unsigned)a.B) break;             // every wave reaches this exit: the queue is finite
         if (!fresh && st != 4) continue;
         if (fresh && a.order) b = __builtin_amdgcn_readfirstlane(a.order[b]);      // longest-expected-first order (queue_order_kernel)
-        // (its own slicing, not BMPC_PROBLEM: x, iters and status are always there, and a continuation starts from x; the shared lines with
-        // these overrides compile to another kernel)
-        bmpc::Problem pr;
-        pr.p = a.p + (long long)b * np; pr.x0 = (fresh ? a.x0 : a.x) + (long long)b * nw;      // continuation: the iterate the batch kernel left (read before x is rewritten)
-        pr.x = a.x + (long long)b * nw; pr.g = a.g ? a.g + (long long)b * ng : nullptr;
-        pr.lam_g = a.lam_g ? a.lam_g + (long long)b * ng : nullptr; pr.lam_x = a.lam_x ? a.lam_x + (long long)b * nw : nullptr;
-        pr.f = a.f ? a.f + b : nullptr; pr.kkt = a.kkt ? a.kkt + b : nullptr;
-        pr.iters = a.iters + b; pr.status = a.status + b;
-        pr.state = a.state ? a.state + (long long)b * (a.N * bmpc::NI + 2) : nullptr;
-        pr.resto_from = fresh ? -1 : a.iters[b];
+        BMPC_RESTO_PROBLEM(pr, a, b, fresh);      // (its own slicing: a continuation starts from the iterate the batch kernel left in x)
         const long long t0_ = a.latency_us ? (long long)wall_clock64() : 0;
-        bmpc::wave_solve_retry<ZLDS, false, true>(W, pr, fresh ? nullptr : a.x0 + (long long)b * nw);      // (a continuation's second attempt is a fresh solve from the caller's x0)
+        bmpc::wave_solve_retry<ZLDS, false, true>(W, pr, BMPC_RESTO_X0_RETRY(a, b, fresh));
         __syncthreads();
         if (a.latency_us && threadIdx.x == 0) a.latency_us[b] = (fresh ? 0.0 : a.latency_us[b]) + (double)((long long)wall_clock64() - t0_) * 0.01;   // continuation: on top of the batch kernel's share
     }

@@ -36,14 +36,10 @@ __global__ void __launch_bounds__(64 * BMPC_NW, 1) bmpc_team_tick_kernel(KArgs a
     }
     if (BMPC_NW == 1 || wv == 0) bmpcs::stream_pack(a.N, a.S, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, threadIdx.x, 64, s.lvl_c, s.lvl_lo, s.lvl_hi);
     __syncthreads();
-    BMPC_NAMESPACE::Wave W; W.N = a.N; W.S = a.S; W.h = a.h; W.o = a.o; W.L = lds; W.G = BMPC_NAMESPACE::make_gptr(a.scratch + (long long)b * a.scr_stride); W.wv = wv;
-    // (the tick's own slicing: p and x0 are the packed ones, x, g and status are always given, the multiplier outputs are not)
-    BMPC_NAMESPACE::Problem pr;
-    pr.p = p; pr.x0 = x0; pr.x = a.x + (long long)b * nw; pr.g = a.g + (long long)b * ng; pr.lam_g = nullptr; pr.lam_x = nullptr;
-    pr.f = nullptr; pr.kkt = a.kkt ? a.kkt + b : nullptr; pr.iters = a.iters ? a.iters + b : nullptr; pr.status = a.status + b; pr.state = dual;
+    BMPC_WAVE_INIT(W, a, lds, a.scratch + (long long)b * a.scr_stride, wv);
+    BMPC_TICK_PROBLEM(pr, a, b, p, x0, dual);
     const long long t0_ = a.latency_us ? (long long)wall_clock64() : 0;
-    W.deadline = a.budget_ticks ? tk0_ + a.budget_ticks : 0; W.it_base = 0;
-    pr.resto_from = -1;
+    W.deadline = a.budget_ticks ? tk0_ + a.budget_ticks : 0;
     BMPC_NAMESPACE::wave_solve<ZLDS, true, RESTO>(W, pr);
     __syncthreads();
     if (a.latency_us && threadIdx.x == 0) a.latency_us[b] = (double)((long long)wall_clock64() - t0_) * 0.01;

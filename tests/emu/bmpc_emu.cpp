@@ -1,25 +1,92 @@
-// TEST-ONLY lane emulator of the wave program (boundmpc_amd/csrc/bmpc_wave.inl).
+// TEST-ONLY lane emulator of the wave program (boundmpc_amd/csrc/bmpc_wave.inl), one wave per problem (BMPC_NW = 1, the default) or a team of
+// BMPC_NW cooperating waves (-DBMPC_NW=4, -DBMPC_NW=2; with -DBMPC_WSG the pair of csrc/bmpc_pair.hip).
 //
-// Compiles the SAME kernel text with g++ and executes each phase as a loop over the 64 lanes
-// in a caller-chosen order.  It exists so the kernel's indexing, phase structure and numerics
-// can be unit-tested in a container without a GPU (pytest -m "not gpu"), and so that
-// intra-phase cross-lane dependences show up as order-dependent results.  It is NOT part of
-// the product: boundmpc_amd never builds, loads or falls back to it.
-#include <cmath>
+// Compiles the SAME kernel text with g++ and executes each phase as a loop over the 64 lanes in a caller-chosen order, a wide phase of a team
+// as a loop over its waves in a caller-chosen order (bmpc_emu_host.h), and runs per problem the lines the kernel entries run: the argument
+// record, the wave initialiser and the slicers of csrc/bmpc_args.h.  It exists so the kernel's indexing, phase structure and numerics can be
+// unit-tested in a container without a GPU (pytest -m "not gpu"), and so that intra-phase cross-lane (and cross-wave) dependences show up as
+// order-dependent results.  It is NOT part of the product: boundmpc_amd never builds, loads or falls back to it.
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
-#include <vector>
 #ifdef _OPENMP
 #include <omp.h>
 #endif
 
+#ifndef BMPC_NW
+#define BMPC_NW 1
+#endif
+#if BMPC_NW > 1
+#define BMPC_NAMESPACE bmpct
+#endif
 #include "bmpc_emu_host.h"
-#define LANES_BEGIN for (int li_ = 0; li_ < 64; ++li_) { const int lane = W.order[li_]; (void)lane;
-#define LANES_END }
-#define LIDX lane
+namespace ns = BMPC_NAMESPACE;
+typedef KArgsT<ns::Opts> KArgs;
 
-#include "../../boundmpc_amd/csrc/bmpc_wave.inl"
+#if BMPC_NW > 1
+#define EMU_SOLVE bmpc_emu_team_solve
+extern "C" int bmpc_emu_team_waves() { return BMPC_NW; }
+extern "C" int bmpc_emu_team_lds_doubles() { return ns::L_SIZE; }
+#else
+#define EMU_SOLVE bmpc_emu_solve
+#endif
+// A batch of B problems, each on a workgroup of its own.  BMPC_EMU_POISON=1: LDS and workspace hold NaN before every problem (emu_wave).
+// One wave: what the one-wave batch kernel and the restoration kernel behind it compute (bmpc_hip.hip bmpc_solve_kernel, bmpc_resto.hip).
+// One wave with BMPC_EMU_INKERNEL=1: the solve of a fused tick (bmpc_tick_kernel.inl), with the restoration phase inside and only the outputs
+// a tick has -- x, g, kkt, iters, status; x, g and status must be given.
+// Teams: the multi-wave batch kernel's call (bmpc_multi_batch.inl) on the text with the restoration phase inside, as the fused team tick runs
+// it; the team BATCH kernel hands jammed problems to the one-wave restoration kernel, which no emulator build runs behind a team.
+extern "C" int EMU_SOLVE(int N, int S, double h, const ns::Opts *opts, int B, const double *p, const double *x0, double *state, double *x, double *g,
+                         double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt, int lane_order, int wave_order, int nthreads) {
+    if (!ns::emu_shape_ok(N, S)) return 1;
+    KArgs a = ns::emu_args(N, S, B, h, *opts);
+    a.p = p; a.x0 = x0; a.state = state; a.x = x; a.g = g; a.lam_g = lam_g; a.lam_x = lam_x; a.f = f; a.iters = iters; a.status = status; a.kkt = kkt;
+    const ns::Scr sc = ns::make_scr(N);
+    const bool zl = ns::emu_zlds(N, S);
+    BMPC_STRIDES(a);
+#ifdef _OPENMP
+    if (nthreads > 0) omp_set_num_threads(nthreads);
+#endif
+    const bool poison = getenv("BMPC_EMU_POISON") != nullptr;
+#if BMPC_NW == 1
+    const bool inkernel = getenv("BMPC_EMU_INKERNEL") != nullptr;
+    // The batch kernel leaves a jammed problem (internal status 4) with its iterate in x, and the restoration kernel continues it from there: for
+    // both, x, iters and status are always there -- private ones here, copied to the caller's (where given) behind the hand-over.
+    std::vector<double> xb((size_t)B * nw); std::vector<int> itb(B, 0), stb(B, 0);
+    if (!inkernel) { a.x = xb.data(); a.iters = itb.data(); a.status = stb.data(); }
+#endif
+#pragma omp parallel
+    {
+        std::vector<double> lds(ns::L_SIZE, 0.0), scr(sc.size, 0.0);
+#pragma omp for schedule(dynamic, 1)
+        for (int b = 0; b < B; b++) {
+            ns::Wave W = ns::emu_wave(a, lds, scr, lane_order, wave_order, poison);
+#if BMPC_NW > 1
+            BMPC_PROBLEM(pr, a, b);
+            if (zl) ns::wave_solve_retry<true, false, true>(W, pr); else ns::wave_solve_retry<false, false, true>(W, pr);
+#else
+            if (inkernel) {
+                BMPC_TICK_PROBLEM(pr, a, b, p + (size_t)b * np, x0 + (size_t)b * nw, state ? state + (size_t)b * (N * ns::NI + 2) : nullptr);
+                if (zl) ns::wave_solve<true, false, true>(W, pr); else ns::wave_solve<false, false, true>(W, pr);
+                continue;
+            }
+            BMPC_PROBLEM(pr, a, b);
+            if (zl) ns::wave_solve_retry<true>(W, pr); else ns::wave_solve_retry<false>(W, pr);
+            if (stb[b] == 4) {
+                BMPC_RESTO_PROBLEM(rp, a, b, false);
+                const std::vector<double> x0b(rp.x0, rp.x0 + nw); rp.x0 = x0b.data();      // (a copy: the lanes of a phase run one after the other here, and x is rewritten while x0 is still read)
+                if (zl) ns::wave_solve_retry<true, false, true>(W, rp, BMPC_RESTO_X0_RETRY(a, b, false)); else ns::wave_solve_retry<false, false, true>(W, rp, BMPC_RESTO_X0_RETRY(a, b, false));
+            }
+            if (x) memcpy(x + (size_t)b * nw, pr.x, sizeof(double) * nw);
+            if (iters) iters[b] = itb[b];
+            if (status) status[b] = stb[b];
+#endif
+        }
+    }
+    return 0;
+}
+
+#if BMPC_NW == 1
 #define BMPCS_SYNC()
 #include "../../boundmpc_amd/csrc/bmpc_stream.inl"
 
@@ -43,64 +110,16 @@ extern "C" void bmpc_emu_fk_motion(const double *q, const double *dq, const doub
     for (int c = 0; c < 3; c++) out[18 + c] = M.jk[c];
 }
 
-extern "C" int bmpc_emu_solve(int N, int S, double h, const bmpc::Opts *opts, int B, const double *p, const double *x0, double *state, double *x, double *g,
-                              double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt, int lane_order, int nthreads) {
-    if (S > bmpc::SMAX || S < 2 || N < 1 || N > bmpc::NMAX) return 1;
-    const bmpc::Scr sc = bmpc::make_scr(N);
-    const int np = 141 + 91 * S, nw = N * bmpc::NZ, ng = N * bmpc::NG;
-#ifdef _OPENMP
-    if (nthreads > 0) omp_set_num_threads(nthreads);
-#endif
-    const bool poison = getenv("BMPC_EMU_POISON") != nullptr;
-    const bool inkernel = getenv("BMPC_EMU_INKERNEL") != nullptr;
-#pragma omp parallel
-    {
-        std::vector<double> lds(bmpc::L_SIZE, 0.0), scr(sc.size, 0.0);
-#pragma omp for schedule(dynamic, 1)
-        for (int b = 0; b < B; b++) {
-            // BMPC_EMU_POISON=1: LDS and workspace are filled with NaN before every problem -- a read of something this solve has not
-            // written (what a reused slab or LDS holds on the GPU) then shows up in the outputs
-            if (poison) { std::fill(lds.begin(), lds.end(), std::nan("")); std::fill(scr.begin(), scr.end(), std::nan("")); }
-            bmpc::Wave W; W.N = N; W.S = S; W.h = h; W.o = *opts; W.L = lds.data(); W.G = bmpc::make_gptr(scr.data()); W.it_base = 0;
-            for (int i = 0; i < 64; i++) W.order[i] = lane_order == 0 ? i : (lane_order == 1 ? 63 - i : (i * 37 + 11) % 64);
-            bmpc::Problem pr;
-            pr.p = p + (size_t)b * np; pr.x0 = x0 + (size_t)b * nw;
-            pr.x = x ? x + (size_t)b * nw : nullptr; pr.g = g ? g + (size_t)b * ng : nullptr;
-            pr.lam_g = lam_g ? lam_g + (size_t)b * ng : nullptr; pr.lam_x = lam_x ? lam_x + (size_t)b * nw : nullptr;
-            pr.f = f ? f + b : nullptr; pr.kkt = kkt ? kkt + b : nullptr; pr.iters = iters ? iters + b : nullptr; pr.status = status ? status + b : nullptr;
-            pr.state = state ? state + (size_t)b * (N * bmpc::NI + 2) : nullptr;
-            pr.resto_from = -1;
-            const bool zl = N <= 11 && S <= bmpc::SMAX_ZLDS;
-            if (inkernel) {      // the restoration phase inside the kernel (what the fused closed-loop ticks run)
-                if (zl) bmpc::wave_solve<true, false, true>(W, pr); else bmpc::wave_solve<false, false, true>(W, pr);
-            } else {             // the batch kernels: main phase only; a jammed problem (internal status 4) is continued by the restoration kernel from its iterate
-                std::vector<double> xb(nw); int it_ = 0, st_ = 0;
-                bmpc::Problem q = pr; q.x = xb.data(); q.iters = &it_; q.status = &st_;
-                if (zl) bmpc::wave_solve_retry<true>(W, q); else bmpc::wave_solve_retry<false>(W, q);      // (the batch kernels' call: with the second attempt of a status-2 solve)
-                if (st_ == 4) {
-                    std::vector<double> x0b(xb);
-                    q.x0 = x0b.data(); q.resto_from = it_;
-                    if (zl) bmpc::wave_solve_retry<true, false, true>(W, q, pr.x0); else bmpc::wave_solve_retry<false, false, true>(W, q, pr.x0);      // (the restoration kernel's call)
-                }
-                if (pr.x) memcpy(pr.x, xb.data(), sizeof(double) * nw);
-                if (pr.iters) *pr.iters = it_;
-                if (pr.status) *pr.status = st_;
-            }
-        }
-    }
-    return 0;
-}
 // debug: one Newton direction at (x, t, nu, mu); dumps the scratch slab
 extern "C" int bmpc_emu_newton(int N, int S, double h, const bmpc::Opts *opts, const double *p, const double *x, const double *t, const double *nu,
                                double mu, double delta, double *scratch_out, double *lds_out) {
     using namespace bmpc;
     const Scr sc = make_scr(N); const POff po = make_poff_lds(S, L_ZL);
     std::vector<double> lds(L_SIZE, 0.0), scr(sc.size, 0.0);
-    Wave W; W.N = N; W.S = S; W.h = h; W.o = *opts; W.L = lds.data(); W.G = bmpc::make_gptr(scr.data()); W.it_base = 0;
-    for (int i = 0; i < 64; i++) W.order[i] = i;
+    Wave W = emu_wave(emu_args(N, S, 1, h, *opts), lds, scr, 0);
     for (int i = 0; i < po.size; i++) W.L[L_PAR + lds_index_of_p(S, i, L_ZL)] = p[i];
     wave_init_tables(W, po);
-    const bool zl = N <= 11 && S <= bmpc::SMAX_ZLDS; W.Zc = zl ? W.L + L_ZL : (W.G + sc.Z).ptr(); W.Zt = zl ? W.L + L_PB : (W.G + sc.ZT).ptr(); W.Dz = zl ? W.L + L_PB + 512 : (W.G + sc.DZ).ptr();
+    const bool zl = emu_zlds(N, S); W.Zc = zl ? W.L + L_ZL : (W.G + sc.Z).ptr(); W.Zt = zl ? W.L + L_PB : (W.G + sc.ZT).ptr(); W.Dz = zl ? W.L + L_PB + 512 : (W.G + sc.DZ).ptr();
     for (int i = 0; i < N * NZ; i++) W.Zc[i] = x[i];
     for (int i = 0; i < N * NI; i++) { W.G[sc.T + i] = t[i]; W.G[sc.NUm + i] = nu[i]; }
     wave_eval(W, po, sc, W.Zc, sc.G, sc.HIN, false);
@@ -124,3 +143,4 @@ extern "C" void bmpc_emu_scr_offsets(int N, int *out) {
 extern "C" void bmpc_emu_sincos(int n, const double *x, double *s, double *c) { for (int i = 0; i < n; i++) bmpc::bmpc_sincos(x[i], s + i, c + i); }
 extern "C" int bmpc_emu_lds_doubles() { return bmpc::L_SIZE; }
 extern "C" int bmpc_emu_scratch_doubles(int N) { return bmpc::make_scr(N).size; }
+#endif

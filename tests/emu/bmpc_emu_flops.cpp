@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
+#include <algorithm>
 #include <vector>
 namespace fc {
 static unsigned long long g_flops = 0, g_special = 0, g_phase[32], g_mark = 0;
@@ -38,9 +39,7 @@ static inline bool operator!=(Real a, Real b) { return a.v != b.v; }
 }
 using fc::Real;
 using namespace fc;
-#define BMPC_EMU 1
-#define BMPC_HD
-#define BMPC_D
+#define BMPC_EMU_OWN_MATH      // (bmpc_emu_host.h: the math macros below count what they execute)
 #define BMPC_SINCOS(x, s, c) (fc::cs(), fc::cs(), *(s) = Real(std::sin((x).v)), *(c) = Real(std::cos((x).v)))
 #define BMPC_EXP(x) (fc::cs(), Real(std::exp(Real(x).v)))
 #define BMPC_LOG(x) (fc::cs(), Real(std::log(Real(x).v)))
@@ -55,30 +54,26 @@ using namespace fc;
 #define BMPC_POW15(x) ((x) * BMPC_SQRT(x))
 #define BMPC_RINT(x) Real(__builtin_rint(Real(x).v))
 #define BMPC_POW(x, y) (fc::cs(), Real(std::pow(Real(x).v, Real(y).v)))
-#define LANES_BEGIN for (int li_ = 0; li_ < 64; ++li_) { const int lane = W.order[li_]; (void)lane;
-#define LANES_END }
-#define LIDX lane
 #define BMPC_PROF(W, id) { fc::g_phase[id] += fc::g_flops - fc::g_mark; fc::g_mark = fc::g_flops; }
 #define double Real
-#include "../../boundmpc_amd/csrc/bmpc_wave.inl"
+#include "bmpc_emu_host.h"      // (the emulator host, the entry records and the wave program, all on the counting number type)
 #undef double
 
 // out[0] = total iterations, out[1] = converged solves, out[2] = flops, out[3] = divisions/roots/transcendentals among them, out[4..35] = flops per phase slot
 extern "C" int bmpc_emu_count_flops(int N, int S, double h, const bmpc::Opts *opts, int B, const double *p, const double *x0, unsigned long long *out) {
-    if (S > bmpc::SMAX || S < 2 || N < 1 || N > bmpc::NMAX) return 1;
-    const bmpc::Scr sc = bmpc::make_scr(N);
-    const int np = 141 + 91 * S, nw = N * bmpc::NZ;
+    if (!bmpc::emu_shape_ok(N, S)) return 1;
     fc::g_flops = fc::g_special = fc::g_mark = 0; for (int i = 0; i < 32; i++) fc::g_phase[i] = 0;
-    std::vector<Real> lds(bmpc::L_SIZE, Real(0.0)), scr(sc.size, Real(0.0)), x(nw);
+    KArgsT<bmpc::Opts> a = bmpc::emu_args(N, S, B, Real(h), *opts);
+    BMPC_STRIDES(a);
+    std::vector<Real> lds(bmpc::L_SIZE, Real(0.0)), scr(bmpc::make_scr(N).size, Real(0.0)), x((size_t)B * nw);
+    std::vector<int> it(B, 0), st(B, 0);
+    a.p = (const Real *)p; a.x0 = (const Real *)x0; a.x = x.data(); a.iters = it.data(); a.status = st.data();
     unsigned long long its = 0, okc = 0;
     for (int b = 0; b < B; b++) {
-        bmpc::Wave W; W.N = N; W.S = S; W.h = Real(h); W.o = *opts; W.L = lds.data(); W.G = bmpc::make_gptr(scr.data()); W.it_base = 0;
-        for (int i = 0; i < 64; i++) W.order[i] = i;
-        bmpc::Problem pr; int it = 0, st = 0;
-        pr.p = (const Real *)p + (size_t)b * np; pr.x0 = (const Real *)x0 + (size_t)b * nw;
-        pr.x = x.data(); pr.g = nullptr; pr.lam_g = nullptr; pr.lam_x = nullptr; pr.f = nullptr; pr.kkt = nullptr; pr.iters = &it; pr.status = &st; pr.state = nullptr; pr.resto_from = -1;
-        if (N <= 11 && S <= bmpc::SMAX_ZLDS) bmpc::wave_solve_retry<true>(W, pr); else bmpc::wave_solve_retry<false>(W, pr);
-        its += (unsigned long long)it; okc += st == 0;
+        bmpc::Wave W = bmpc::emu_wave(a, lds, scr, 0);
+        BMPC_PROBLEM(pr, a, b);
+        if (bmpc::emu_zlds(N, S)) bmpc::wave_solve_retry<true>(W, pr); else bmpc::wave_solve_retry<false>(W, pr);
+        its += (unsigned long long)it[b]; okc += st[b] == 0;
     }
     out[0] = its; out[1] = okc; out[2] = fc::g_flops; out[3] = fc::g_special;
     for (int i = 0; i < 32; i++) out[4 + i] = fc::g_phase[i];

@@ -15,6 +15,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
+#include <algorithm>
 #include <unordered_set>
 #include <vector>
 namespace fc {
@@ -79,9 +80,7 @@ static inline Real bi(const Real &a, const Real &b, double v, int cost) { return
 }
 using fc::Real;
 using namespace fc;
-#define BMPC_EMU 1
-#define BMPC_HD
-#define BMPC_D
+#define BMPC_EMU_OWN_MATH      // (bmpc_emu_host.h: the math macros below build the data-flow graph)
 #define BMPC_SINCOS(x, s, c) (*(s) = fc::un(Real(x), std::sin(Real(x).v), 1), *(c) = fc::un(Real(x), std::cos(Real(x).v), 1))
 #define BMPC_EXP(x) fc::un(Real(x), std::exp(Real(x).v), 1)
 #define BMPC_LOG(x) fc::un(Real(x), std::log(Real(x).v), 1)
@@ -96,9 +95,7 @@ using namespace fc;
 #define BMPC_POW15(x) ((x) * BMPC_SQRT(x))
 #define BMPC_RINT(x) fc::un(Real(x), __builtin_rint(Real(x).v), 0)
 #define BMPC_POW(x, y) fc::bi(Real(x), Real(y), std::pow(Real(x).v, Real(y).v), 1)
-#define LANES_BEGIN for (int li_ = 0; li_ < 64; ++li_) { const int lane = W.order[li_]; (void)lane;
-#define LANES_END } fc::g_written.clear();
-#define LIDX lane
+#define BMPC_EMU_PHASE_END fc::g_written.clear();      // (bmpc_emu_host.h LANES_END: "written in this phase" starts anew)
 // the stamp `id` closes the phase whose operations were executed since the previous stamp: they were created with g_slot = a placeholder and are
 // re-stamped here (the nodes since the last stamp form a contiguous tail of the arena)
 static size_t g_tail = 1;
@@ -107,7 +104,7 @@ static size_t g_tail = 1;
 struct PlainOpts { double tol; int max_iter; double mu_init; double mu_min_fac; double slack_push; int exact_hessian; int verbose; double mu_warm; int stall_window;
                    double bound_margin; int restoration; int resto_short; int resto_cap; int start_rollout; int hold_mu; int retry_cap; };
 #define double Real
-#include "../../boundmpc_amd/csrc/bmpc_wave.inl"
+#include "bmpc_emu_host.h"      // (the emulator host, the entry records and the wave program, all on the graph-building number type)
 #undef double
 
 // out[0] = iterations, out[1] = converged, out[2] = executed flops, out[3] = useful flops, out[4] = stores, out[5] = duplicate stores, out[6] = dummy stores,
@@ -116,11 +113,10 @@ extern "C" int bmpc_emu_count_useful(int N, int S, double h, const PlainOpts *po
     bmpc::Opts oo; oo.tol = Real(po_->tol); oo.max_iter = po_->max_iter; oo.mu_init = Real(po_->mu_init); oo.mu_min_fac = Real(po_->mu_min_fac); oo.slack_push = Real(po_->slack_push);
     oo.exact_hessian = po_->exact_hessian; oo.verbose = 0; oo.mu_warm = Real(po_->mu_warm); oo.stall_window = po_->stall_window; oo.bound_margin = Real(po_->bound_margin);
     oo.restoration = po_->restoration; oo.resto_short = po_->resto_short; oo.resto_cap = po_->resto_cap; oo.start_rollout = po_->start_rollout; oo.hold_mu = po_->hold_mu; oo.retry_cap = po_->retry_cap;
-    const bmpc::Opts *opts = &oo;
-    if (S > bmpc::SMAX || S < 2 || N < 1 || N > bmpc::NMAX) return 1;
-    const bmpc::Scr sc = bmpc::make_scr(N);
-    const int np = 141 + 91 * S, nw = N * bmpc::NZ, ng = N * bmpc::NG;
-    std::vector<Real> lds(bmpc::L_SIZE, Real(0.0)), scr(sc.size, Real(0.0)), x(nw), pp(np), xx(nw), g(ng), lg(ng);
+    if (!bmpc::emu_shape_ok(N, S)) return 1;
+    KArgsT<bmpc::Opts> a = bmpc::emu_args(N, S, 1, Real(h), oo);
+    BMPC_STRIDES(a);
+    std::vector<Real> lds(bmpc::L_SIZE, Real(0.0)), scr(bmpc::make_scr(N).size, Real(0.0)), x(nw), pp(np), xx(nw), g(ng);
     for (int i = 0; i < np; i++) pp[i] = Real(p[i]);
     for (int i = 0; i < nw; i++) xx[i] = Real(x0[i]);
     fc::g_nodes.assign(1, fc::Node{0, 0, 0, 31, 1, 0}); g_tail = 1; fc::g_written.clear(); fc::g_dup_stores = fc::g_dummy_stores = fc::g_stores = 0;
@@ -128,12 +124,11 @@ extern "C" int bmpc_emu_count_useful(int N, int S, double h, const PlainOpts *po
     auto reg = [](std::vector<Real> &v) { fc::g_mem_lo[fc::g_nmem] = (const char *)v.data(); fc::g_mem_hi[fc::g_nmem] = (const char *)(v.data() + v.size()); fc::g_nmem++; };
     reg(lds); reg(scr); reg(x); reg(g);
     fc::g_dummy = (const void *)(lds.data() + bmpc::L_DUMMY);
-    bmpc::Wave W; W.N = N; W.S = S; W.h = Real(h); W.o = *opts; W.L = lds.data(); W.G = bmpc::make_gptr(scr.data()); W.it_base = 0;
-    for (int i = 0; i < 64; i++) W.order[i] = i;
-    bmpc::Problem pr; int it = 0, st = 0;
-    pr.p = pp.data(); pr.x0 = xx.data();
-    pr.x = x.data(); pr.g = g.data(); pr.lam_g = nullptr; pr.lam_x = nullptr; pr.f = nullptr; pr.kkt = nullptr; pr.iters = &it; pr.status = &st; pr.state = nullptr; pr.resto_from = -1;
-    if (N <= 11 && S <= bmpc::SMAX_ZLDS) bmpc::wave_solve_retry<true>(W, pr); else bmpc::wave_solve_retry<false>(W, pr);
+    int it = 0, st = 0;
+    a.p = pp.data(); a.x0 = xx.data(); a.x = x.data(); a.g = g.data(); a.iters = &it; a.status = &st;
+    bmpc::Wave W = bmpc::emu_wave(a, lds, scr, 0);
+    BMPC_PROBLEM(pr, a, 0);
+    if (bmpc::emu_zlds(N, S)) bmpc::wave_solve_retry<true>(W, pr); else bmpc::wave_solve_retry<false>(W, pr);
     for (int i = 0; i < 72; i++) out[i] = 0;
     out[0] = (unsigned long long)it; out[1] = st == 0; out[4] = fc::g_stores; out[5] = fc::g_dup_stores; out[6] = fc::g_dummy_stores;
     for (size_t n = 1; n < fc::g_nodes.size(); n++) {

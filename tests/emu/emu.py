@@ -1,15 +1,16 @@
-"""TEST-ONLY: ctypes binding of the CPU lane emulator of the wave program (tests/emu/bmpc_emu.cpp).
+"""TEST-ONLY: ctypes bindings of the CPU lane emulators of the wave program (tests/emu/*.cpp) and the one place that builds them.
 Not part of the product; see the header of bmpc_emu.cpp."""
 import ctypes
+import functools
 import os
 import subprocess
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_LIB = os.path.join(_HERE, "libbmpc_emu.so")
-_SRC = [os.path.join(_HERE, "bmpc_emu.cpp"), os.path.join(_HERE, "..", "..", "boundmpc_amd", "csrc", "bmpc_wave.inl"),
-        os.path.join(_HERE, "..", "..", "boundmpc_amd", "csrc", "bmpc_stream.inl"), os.path.join(_HERE, "bmpc_emu_host.h")]
+_CSRC = os.path.join(_HERE, "..", "..", "boundmpc_amd", "csrc")
+# what every emulator is built from beside its own source: the host header, the kernels' entry records and slicers, the wave program
+_COMMON = [os.path.join(_HERE, "bmpc_emu_host.h"), os.path.join(_CSRC, "bmpc_args.h"), os.path.join(_CSRC, "bmpc_wave.inl")]
 
 
 class Opts(ctypes.Structure):
@@ -19,22 +20,29 @@ class Opts(ctypes.Structure):
                 ("bound_margin", ctypes.c_double), ("restoration", ctypes.c_int), ("resto_short", ctypes.c_int), ("resto_cap", ctypes.c_int), ("start_rollout", ctypes.c_int), ("hold_mu", ctypes.c_int), ("retry_cap", ctypes.c_int)]
 
 
-def build(force=False):
-    if force or not os.path.exists(_LIB) or any(os.path.getmtime(_LIB) < os.path.getmtime(s) for s in _SRC):
-        subprocess.check_call(["g++", "-O2", "-fopenmp", "-fPIC", "-shared", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-enum-compare",
-                               "-o", _LIB, _SRC[0]])
-    return _LIB
-
-
-_lib = None
+@functools.lru_cache(maxsize=None)
+def _build(lib_name, source, flags=(), deps=()):
+    """tests/emu/<lib_name>, loaded: compiled from tests/emu/<source> with `flags` when it is missing or older than the source, the common files
+    or one of `deps` (files of csrc).  Cached: the staleness test runs once per process and library."""
+    path, src = os.path.join(_HERE, lib_name), os.path.join(_HERE, source)
+    if not os.path.exists(path) or any(os.path.getmtime(path) < os.path.getmtime(s) for s in [src] + _COMMON + [os.path.join(_CSRC, d) for d in deps]):
+        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-enum-compare", *flags, "-o", path, src])
+    return ctypes.CDLL(path)
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        build()
-        _lib = ctypes.CDLL(_LIB)
-    return _lib
+    """the one-wave emulator: solves, the stream functions and the debug entries"""
+    return _build("libbmpc_emu.so", "bmpc_emu.cpp", ("-fopenmp", "-DBMPC_NW=1"), ("bmpc_stream.inl",))
+
+
+def build():
+    """puts the one-wave library in place (for callers that start worker processes next); returns nothing"""
+    lib()
+
+
+def service_lib(kind):
+    """kind = "dual" / "kkt" / "sens": the service job of csrc/bmpc_<kind>.inl over the one-wave emulator (tests/emu/bmpc_emu_<kind>.cpp)"""
+    return _build(f"libbmpc_emu_{kind}.so", f"bmpc_emu_{kind}.cpp", (), ("bmpc_dual.inl", f"bmpc_{kind}.inl"))
 
 
 def default_opts(**kw):
@@ -48,53 +56,45 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
 
-def solve(p, x0, N, S, h, opts=None, lane_order=0, nthreads=0, state=None):
+def opts_for(N, opts=None):
+    """`opts`, or the defaults of a handle for this horizon (long horizons: higher barrier start, restoration on breakdown only, second attempt)"""
+    if opts is not None:
+        return opts
+    return default_opts(mu_init=3.0, slack_push=0.1, stall_window=20, restoration=2, retry_cap=100) if N > 11 else default_opts()
+
+
+def _solve(entry, p, x0, N, S, h, opts, lane_order, wave_order, nthreads, state):
     p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
     x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
     B = p.shape[0]
     out = dict(x=np.zeros((B, N * 44)), g=np.zeros((B, N * 43)), lam_g=np.zeros((B, N * 43)), lam_x=np.zeros((B, N * 44)),
                f=np.zeros(B), iters=np.zeros(B, dtype=np.int32), status=np.zeros(B, dtype=np.int32), kkt=np.zeros(B))
-    o = opts if opts is not None else (default_opts(mu_init=3.0, slack_push=0.1, stall_window=20, restoration=2, retry_cap=100) if N > 11 else default_opts())
-    rc = lib().bmpc_emu_solve(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), ctypes.byref(o), ctypes.c_int(B), _p(p), _p(x0), _p(state) if state is not None else None,
-                              _p(out["x"]), _p(out["g"]), _p(out["lam_g"]), _p(out["lam_x"]), _p(out["f"]), _p(out["iters"]),
-                              _p(out["status"]), _p(out["kkt"]), ctypes.c_int(lane_order), ctypes.c_int(nthreads))
+    rc = entry(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), ctypes.byref(opts_for(N, opts)), ctypes.c_int(B), _p(p), _p(x0), _p(state),
+               _p(out["x"]), _p(out["g"]), _p(out["lam_g"]), _p(out["lam_x"]), _p(out["f"]), _p(out["iters"]), _p(out["status"]), _p(out["kkt"]),
+               ctypes.c_int(lane_order), ctypes.c_int(wave_order), ctypes.c_int(nthreads))
     assert rc == 0
     return out
 
 
-# ---- team variant of the wave program (tests/emu/bmpc_emu_team.cpp: NW cooperating waves per problem) ----
-_TLIBS = {}
+def solve(p, x0, N, S, h, opts=None, lane_order=0, nthreads=0, state=None):
+    """The one-wave program on the CPU, lanes in `lane_order` (0 forward, 1 reverse, 2 scrambled).  With BMPC_EMU_INKERNEL set it runs the
+    solve of a fused tick, which yields only x, g, kkt, iters and status: lam_g, lam_x and f stay zero and are no results."""
+    return _solve(lib().bmpc_emu_solve, p, x0, N, S, h, opts, lane_order, 0, nthreads, state)
 
 
+# ---- team variant of the wave program (tests/emu/bmpc_emu.cpp with BMPC_NW cooperating waves per problem) ----
 def team_lib(nw=4):
     """nw = 4 / 2: teams (workspace rows in LDS); nw = "pair": the two-wave team with the workspace in the global slab (BMPC_WSG, csrc/bmpc_pair.hip)"""
-    if nw not in _TLIBS:
-        pair = nw == "pair"
-        path = os.path.join(_HERE, "libbmpc_emu_pair.so" if pair else f"libbmpc_emu_team{nw}.so")
-        src = [os.path.join(_HERE, "bmpc_emu_team.cpp"), _SRC[1], _SRC[3]]
-        if not os.path.exists(path) or any(os.path.getmtime(path) < os.path.getmtime(s) for s in src):
-            subprocess.check_call(["g++", "-O2", "-fopenmp", "-fPIC", "-shared", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-enum-compare"]
-                                  + (["-DBMPC_NW=2", "-DBMPC_WSG"] if pair else [f"-DBMPC_NW={nw}"]) + ["-o", path, src[0]])
-        _TLIBS[nw] = ctypes.CDLL(path)
-        assert _TLIBS[nw].bmpc_emu_team_waves() == (2 if pair else nw)
-    return _TLIBS[nw]
+    pair = nw == "pair"
+    L = _build("libbmpc_emu_pair.so" if pair else f"libbmpc_emu_team{nw}.so", "bmpc_emu.cpp", ("-fopenmp",) + (("-DBMPC_NW=2", "-DBMPC_WSG") if pair else (f"-DBMPC_NW={nw}",)))
+    assert L.bmpc_emu_team_waves() == (2 if pair else nw)
+    return L
 
 
 def solve_team(p, x0, N, S, h, nw=4, opts=None, lane_order=0, wave_order=0, nthreads=0, state=None):
     """The team program (nw waves per problem) on the CPU: wide phases run wave after wave in `wave_order` (0 forward, 1 reverse,
     2 scrambled), lanes in `lane_order`."""
-    p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
-    x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
-    B = p.shape[0]
-    out = dict(x=np.zeros((B, N * 44)), g=np.zeros((B, N * 43)), lam_g=np.zeros((B, N * 43)), lam_x=np.zeros((B, N * 44)),
-               f=np.zeros(B), iters=np.zeros(B, dtype=np.int32), status=np.zeros(B, dtype=np.int32), kkt=np.zeros(B))
-    o = opts if opts is not None else (default_opts(mu_init=3.0, slack_push=0.1, stall_window=20, restoration=2, retry_cap=100) if N > 11 else default_opts())
-    rc = team_lib(nw).bmpc_emu_team_solve(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), ctypes.byref(o), ctypes.c_int(B), _p(p), _p(x0),
-                                          _p(state) if state is not None else None, _p(out["x"]), _p(out["g"]), _p(out["lam_g"]), _p(out["lam_x"]),
-                                          _p(out["f"]), _p(out["iters"]), _p(out["status"]), _p(out["kkt"]), ctypes.c_int(lane_order),
-                                          ctypes.c_int(wave_order), ctypes.c_int(nthreads))
-    assert rc == 0
-    return out
+    return _solve(team_lib(nw).bmpc_emu_team_solve, p, x0, N, S, h, opts, lane_order, wave_order, nthreads, state)
 
 
 # ---- CPU build of the stream functions (boundmpc_amd/csrc/bmpc_stream.inl) ----
@@ -139,25 +139,14 @@ def fk_motion(q, dq, ddq, u):
 
 
 # ---- flop-counting build of the same kernel text (tests/emu/bmpc_emu_flops.cpp) ----
-_FLIB = os.path.join(_HERE, "libbmpc_emu_flops.so")
-_fl = None
-
-
 def count_flops(p, x0, N, S, h, opts=None):
     """fp64 operations the kernel text executes (summed over the lanes of every phase) while solving the batch: dict with iterations,
     converged, flops, special, flops_per_iteration, per_phase (slot id of tests/gpu_profile_phases.py -> flops)."""
-    global _fl
-    src = os.path.join(_HERE, "bmpc_emu_flops.cpp")
-    if not os.path.exists(_FLIB) or any(os.path.getmtime(_FLIB) < os.path.getmtime(s) for s in (src, _SRC[1])):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-enum-compare", "-Wno-format", "-o", _FLIB, src])
-        _fl = None
-    if _fl is None:
-        _fl = ctypes.CDLL(_FLIB)
+    _fl = _build("libbmpc_emu_flops.so", "bmpc_emu_flops.cpp", ("-Wno-format",))
     p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
     x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
-    o = opts if opts is not None else (default_opts(mu_init=3.0, slack_push=0.1, stall_window=20, restoration=2, retry_cap=100) if N > 11 else default_opts())
     out = np.zeros(36, dtype=np.uint64)
-    rc = _fl.bmpc_emu_count_flops(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), ctypes.byref(o), ctypes.c_int(p.shape[0]), _p(p), _p(x0), _p(out))
+    rc = _fl.bmpc_emu_count_flops(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), ctypes.byref(opts_for(N, opts)), ctypes.c_int(p.shape[0]), _p(p), _p(x0), _p(out))
     assert rc == 0
     its = int(out[0])
     return dict(iterations=its, converged=int(out[1]), flops=int(out[2]), special=int(out[3]), flops_per_iteration=float(out[2]) / max(its, 1),
@@ -165,25 +154,14 @@ def count_flops(p, x0, N, S, h, opts=None):
 
 
 # ---- mask-aware flop count of the same kernel text (tests/emu/bmpc_emu_useful.cpp): executed vs useful operations by data flow ----
-_ULIB = os.path.join(_HERE, "libbmpc_emu_useful.so")
-_ul = None
-
-
 def count_useful(p, x0, N, S, h, opts=None):
     """ONE problem: fp64 operations the kernel text executes and, of those, the ones whose result reaches a store (not the dummy word, not a
     clamped duplicate within the phase) or a decision.  dict: iterations, executed, useful, stores, duplicate_stores, dummy_stores,
     per_phase {slot: (executed, useful)}."""
-    global _ul
-    src = os.path.join(_HERE, "bmpc_emu_useful.cpp")
-    if not os.path.exists(_ULIB) or any(os.path.getmtime(_ULIB) < os.path.getmtime(s) for s in (src, _SRC[1])):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-enum-compare", "-Wno-format", "-o", _ULIB, src])
-        _ul = None
-    if _ul is None:
-        _ul = ctypes.CDLL(_ULIB)
+    _ul = _build("libbmpc_emu_useful.so", "bmpc_emu_useful.cpp", ("-Wno-format",))
     p = np.ascontiguousarray(np.asarray(p, dtype=np.float64).ravel()); x0 = np.ascontiguousarray(np.asarray(x0, dtype=np.float64).ravel())
-    o = opts if opts is not None else (default_opts(mu_init=3.0, slack_push=0.1, stall_window=20, restoration=2, retry_cap=100) if N > 11 else default_opts())
     out = np.zeros(72, dtype=np.uint64)
-    rc = _ul.bmpc_emu_count_useful(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), ctypes.byref(o), _p(p), _p(x0), _p(out))
+    rc = _ul.bmpc_emu_count_useful(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), ctypes.byref(opts_for(N, opts)), _p(p), _p(x0), _p(out))
     assert rc == 0
     return dict(iterations=int(out[0]), converged=int(out[1]), executed=int(out[2]), useful=int(out[3]), stores=int(out[4]), duplicate_stores=int(out[5]),
                 dummy_stores=int(out[6]), per_phase={s_: (int(out[8 + 2 * s_]), int(out[9 + 2 * s_])) for s_ in range(32) if out[8 + 2 * s_]})

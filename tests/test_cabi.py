@@ -163,7 +163,7 @@ def test_library_carries_the_hash_of_its_sources(tmp_path, monkeypatch):
     # every translation unit and every header the kernels include is part of the hash
     names = {os.path.basename(p) for p in build.SOURCES}
     assert {"bmpc_hip.hip", "bmpc_team.hip", "bmpc_resto.hip", "bmpc_tick.hip", "bmpc_wave.inl", "bmpc_stream.inl", "bmpc_gpu_common.h", "boundmpc_hip.h",
-            "bmpc_pair.hip", "bmpc_multi_batch.inl", "bmpc_tick_kernel.inl"} <= names
+            "bmpc_pair.hip", "bmpc_multi_batch.inl", "bmpc_tick_kernel.inl", "bmpc_args.h"} <= names
     # a library from other sources is refused at load time
     monkeypatch.setattr(build, "source_hash", lambda: "0" * 16)
     monkeypatch.setattr(_lib, "_lib", None)

@@ -4,7 +4,6 @@ conversion (boundmpc_amd/csrc/bmpc_dual.inl) on the CPU lane emulator, the host 
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -151,15 +150,9 @@ def test_oracle_warm_resolve_from_the_checker_state(cold):
 
 
 # ---- the kernel text on the CPU lane emulator (tests/emu/bmpc_emu_dual.cpp) ----
-_EMU = os.path.join(ROOT, "tests", "emu", "libbmpc_emu_dual.so")
-_EMU_SRC = [os.path.join(ROOT, "tests", "emu", "bmpc_emu_dual.cpp"), os.path.join(ROOT, "boundmpc_amd", "csrc", "bmpc_wave.inl"),
-            os.path.join(ROOT, "boundmpc_amd", "csrc", "bmpc_dual.inl"), os.path.join(ROOT, "tests", "emu", "bmpc_emu_host.h")]
-
-
 def _emu():
-    if not os.path.exists(_EMU) or any(os.path.getmtime(_EMU) < os.path.getmtime(s) for s in _EMU_SRC):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-enum-compare", "-o", _EMU, _EMU_SRC[0]])
-    return ctypes.CDLL(_EMU)
+    from tests.emu import emu
+    return emu.service_lib("dual")
 
 
 def emu_state(p, x0, lam_g, lam_x, N, S, mu0=0.0, lane_order=0, poison=True):

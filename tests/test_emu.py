@@ -245,7 +245,7 @@ def test_flop_counting_build_of_the_kernel_text_runs_the_same_iterations():
     assert 1.0e6 < c["flops_per_iteration"] < 2.5e6
 
 
-# ---- team variant of the wave program (NW cooperating waves per problem; tests/emu/bmpc_emu_team.cpp) ----
+# ---- team variant of the wave program (NW cooperating waves per problem; tests/emu/bmpc_emu.cpp with -DBMPC_NW) ----
 @pytest.mark.parametrize("nw", [4, 2, "pair"])
 def test_team_program_matches_oracle_and_is_order_invariant(nw):
     """The team text (wide passes over 64 NW lanes, helper wave of the Riccati sweep, workspace rows in LDS; "pair": two waves with the workspace

@@ -59,7 +59,7 @@ def test_one_wave_emulator_against_the_oracle(name, mode, cap):
 @pytest.mark.parametrize("mode", [0, 2])
 @pytest.mark.parametrize("nw", [4, "pair"])
 def test_team_and_pair_emulators_make_the_second_attempt(nw, mode):
-    """Set B through the multi-wave text with retry_cap = 100: tests/emu/bmpc_emu_team.cpp calls wave_solve_retry like the pair / team batch kernel
+    """Set B through the multi-wave text with retry_cap = 100: the team build of tests/emu/bmpc_emu.cpp calls wave_solve_retry like the pair / team batch kernel
     (bmpc_multi_batch.inl).  Without the second attempt 11 of the 12 rows end as status 2; with it the oracle's statuses and iterations (within 2)."""
     P, X, N, S, dt = eps.problem_set("B")
     ref, ref0 = eps.oracle("B", mode, 100), eps.oracle("B", mode, 0)

@@ -12,7 +12,6 @@ tolerance relative to the VALUE of a residual would be unattainable for any two 
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -131,15 +130,9 @@ def lagrangian_gradient(p, x, lam_eq, nu, N, S, h=0.1):
 
 
 # ---- the kernel text on the CPU lane emulator (tests/emu/bmpc_emu_kkt.cpp) ----
-_EMU = os.path.join(ROOT, "tests", "emu", "libbmpc_emu_kkt.so")
-_EMU_SRC = [os.path.join(ROOT, "tests", "emu", "bmpc_emu_kkt.cpp")] + [os.path.join(ROOT, "boundmpc_amd", "csrc", n) for n in ("bmpc_wave.inl", "bmpc_dual.inl", "bmpc_kkt.inl")] \
-    + [os.path.join(ROOT, "tests", "emu", "bmpc_emu_host.h")]
-
-
 def _emu():
-    if not os.path.exists(_EMU) or any(os.path.getmtime(_EMU) < os.path.getmtime(s) for s in _EMU_SRC):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-enum-compare", "-o", _EMU, _EMU_SRC[0]])
-    return ctypes.CDLL(_EMU)
+    from tests.emu import emu
+    return emu.service_lib("kkt")
 
 
 def emu_cert(p, x, lam_g, lam_x, N, S, lane_order=0, poison=True, want=True):

@@ -20,7 +20,6 @@ recomputed here on every run and written to profiles/sensitivity.txt by tests/gp
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -164,15 +163,9 @@ class Checker:
 
 
 # ---- the kernel text on the CPU lane emulator (tests/emu/bmpc_emu_sens.cpp) ----
-_EMU = os.path.join(ROOT, "tests", "emu", "libbmpc_emu_sens.so")
-_EMU_SRC = [os.path.join(ROOT, "tests", "emu", "bmpc_emu_sens.cpp")] + [os.path.join(ROOT, "boundmpc_amd", "csrc", n) for n in ("bmpc_wave.inl", "bmpc_dual.inl", "bmpc_sens.inl")] \
-    + [os.path.join(ROOT, "tests", "emu", "bmpc_emu_host.h")]
-
-
 def _emu():
-    if not os.path.exists(_EMU) or any(os.path.getmtime(_EMU) < os.path.getmtime(s) for s in _EMU_SRC):
-        subprocess.check_call(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-Wno-unknown-pragmas", "-Wno-enum-compare", "-o", _EMU, _EMU_SRC[0]])
-    return ctypes.CDLL(_EMU)
+    from tests.emu import emu
+    return emu.service_lib("sens")
 
 
 def emu_sens(p, x, dp, lam_g, lam_x, N, S=S_, mu=MU, lane_order=0, poison=True, want=True, opts=None):
