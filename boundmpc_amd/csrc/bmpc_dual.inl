@@ -1,7 +1,7 @@
 // bmpc_dual.inl -- primal-dual warm start: the dual state of a warm solve ([nu (N x 57) | mu | iterations], bmpc_solve_batch_warm) from
 // multipliers in CasADi's convention (lam_g [N][43], lam_x [N][44]: what a solve returns, what Ipopt's warm_start_init_point reads).
 //
-// The map is the inverse of the output pass of wave_solve (bmpc_wave.inl, "outputs in the reference's conventions"), per node k, with
+// The map is the inverse of the output map of wave_solve (bmpc_wave.inl out_g_entry, out_lam_x_entry), per node k, with
 // pos(v) = max(v, 0):
 //   IJU + j, IJL + j (j < 8)       pos(lam_x[j]), pos(-lam_x[j])             (and the same for IQU / IQL with the q entries, IDQU / IDQL with dq)
 //   IPHI0                          pos(-lam_x[ZPHI])                          (phi has the lower bound 0 only)
@@ -11,8 +11,8 @@
 // leaves, the same words the output pass reads: the two rows sum to 2 wd lam and differ by 2 c lam, so the map is the exact inverse of the
 // forward map wherever |c| <= wd.  Not read: the equality rows lam_g[0:36] (the adjoint sweep recomputes the equality multipliers at every
 // iterate) and lam_x of the unbounded variables.  A non-finite entry counts as 0; a converted multiplier is capped at DUAL_NU_CAP.
-// The row pass reuses the row table of wave_init_tables (sign and source variable of the box rows) and the output pass's wave-uniform trip
-// counts on clamped indices (build.py lint_isa).
+// dual_row below is the map, once: it reuses the row table of wave_init_tables (sign and source variable of the box rows); the output map is
+// out_g_entry / out_lam_x_entry of bmpc_wave.inl.  The row passes use the output pass's wave-uniform trip counts on clamped indices (build.py lint_isa).
 #pragma once
 
 namespace BMPC_NAMESPACE {
@@ -29,45 +29,46 @@ struct DualIn {
     double mu;                                 // > 0: the barrier level of the state; else the handle's mu_warm
 };
 
-BMPC_D inline double dual_finite(double v) { return BMPC_FABS(v) <= 1.7976931348623157e308 ? v : 0.0; }      // (NaN and +-inf -> 0)
+BMPC_D inline double dual_finite(double v) { return bmpc_finite(v) ? v : 0.0; }      // (NaN and +-inf -> 0)
 BMPC_D inline double dual_cap(double v) { return v > 0.0 ? (v < DUAL_NU_CAP ? v : DUAL_NU_CAP) : 0.0; }      // pos() with the cap; NaN -> 0
 
-// One problem: evaluation at x0 exactly as a solve begins (parameter vector into LDS, x0 into the iterate, tables, wave_eval; no start
-// rollout), then the row pass above.  State slot mu: d.mu when positive, else o.mu_warm; 0 (the cold start of the warm path) when every
-// converted multiplier is 0.  Slot iterations: 0.
+// The map above for one internal row: the capped nu of row id (< 57 N: the caller clamps) from lam_g / lam_x (NULL = zeros), the row table in
+// LDS (wave_init_tables) and the reference records the evaluation at the point left.  Every load is unconditional, on a clamped index.
+// Callers: the row passes of wave_state_from_multipliers, wave_certify (bmpc_kkt.inl) and wave_sensitivity (bmpc_sens.inl).
+BMPC_D inline double dual_row(const double *L, const LPtr WL, const Scr &sc, const double *lam_g, const double *lam_x, int id) {
+    const bool hx = lam_x != nullptr, hg = lam_g != nullptr;
+    const int k = id / NI, r = id - k * NI;
+    const int rb = r <= IPHI0 ? r : IPHI0;                                                  // box row of the table (clamped)
+    const int ig = r < ITUBE ? (r > IPHIMAX ? 37 : 36) : 38 + ((r - ITUBE) >> 1);          // lam_g entry of a non-box row
+    const int m = r < ITUBE ? 0 : (r - ITUBE) >> 1;
+    const double sgn = L[L_ROWT + rb], src = L[L_ROWT + 2 * NI + rb];
+    const double vx = hx ? dual_finite(lam_x[k * NZ + (int)src]) : 0.0;
+    const double vg = hg ? dual_finite(lam_g[k * NG + ig]) : 0.0;
+    const LPtr rr = WL + sc.REF + k * RREC;
+    const double c = rr[RC + m], wd = rr[RWD + m];
+    double v;
+    if (r <= IPHI0) v = sgn * vx;
+    else if (r < ITUBE) v = vg;
+    else { const double lam = vg > 0.0 ? vg : 0.0; v = ((r - ITUBE) & 1) ? lam * (wd - c) : lam * (wd + c); }
+    return dual_cap(v);
+}
+
+// One problem: evaluation at x0 exactly as a solve begins (wave_load_point, wave_eval; no start rollout), then the row pass.  State slot mu:
+// d.mu when positive, else o.mu_warm; 0 (the cold start of the warm path) when every converted multiplier is 0.  Slot iterations: 0.
 template <bool ZLDS>
 BMPC_D inline void wave_state_from_multipliers(Wave &W, const DualIn &d) {
     const int N = W.N, S = W.S;
-    double *L = W.L; const GPtr G = W.G; const LPtr WL = BMPC_WL(W);
+    double *L = W.L; const LPtr WL = BMPC_WL(W);
     const POff po = make_poff_lds(S, L_ZL);
     const Scr sc = make_scr(N);
-    const int np = po.size, nw = N * NZ, ni = N * NI;
-    if (ZLDS) { W.Zc = L + L_ZL; W.Zt = L + L_PB; W.Dz = L + L_PB + 512; } else { W.Zc = (G + sc.Z).ptr(); W.Zt = (G + sc.ZT).ptr(); W.Dz = (G + sc.DZ).ptr(); }
-    WIDE_BEGIN
-        for (int id = wl; id < np; id += WS) L[L_PAR + (ZLDS ? id : lds_index_of_p(S, id, L_ZL))] = d.p[id];
-        for (int id = wl; id < nw; id += WS) W.Zc[id] = d.x0[id];
-    WIDE_END
-    wave_init_tables(W, po);
+    const int ni = N * NI;
+    wave_load_point<ZLDS>(W, po, sc, d.p, d.x0);
     wave_eval(W, po, sc, W.Zc, sc.G, sc.HIN, false);
-    const bool hx = d.lam_x != nullptr, hg = d.lam_g != nullptr;
     WIDE_BEGIN
         double nmax = 0.0;
         for (int t_ = 0; t_ < (ni + WS - 1) / WS; t_++) {
             const int id0 = wl + WS * t_, id = id0 < ni ? id0 : ni - 1;
-            const int k = id / NI, r = id - k * NI;
-            const int rb = r <= IPHI0 ? r : IPHI0;                                                  // box row of the table (clamped)
-            const int ig = r < ITUBE ? (r > IPHIMAX ? 37 : 36) : 38 + ((r - ITUBE) >> 1);          // lam_g entry of a non-box row
-            const int m = r < ITUBE ? 0 : (r - ITUBE) >> 1;
-            const double sgn = L[L_ROWT + rb], src = L[L_ROWT + 2 * NI + rb];
-            const double vx = hx ? dual_finite(d.lam_x[k * NZ + (int)src]) : 0.0;
-            const double vg = hg ? dual_finite(d.lam_g[k * NG + ig]) : 0.0;
-            const LPtr rr = WL + sc.REF + k * RREC;
-            const double c = rr[RC + m], wd = rr[RWD + m];
-            double v;
-            if (r <= IPHI0) v = sgn * vx;
-            else if (r < ITUBE) v = vg;
-            else { const double lam = vg > 0.0 ? vg : 0.0; v = ((r - ITUBE) & 1) ? lam * (wd - c) : lam * (wd + c); }
-            const double nu = dual_cap(v);
+            const double nu = dual_row(L, WL, sc, d.lam_g, d.lam_x, id);
             d.state[id] = nu;
             nmax = nu > nmax ? nu : nmax;
         }

@@ -1,13 +1,12 @@
 // bmpc_kkt.inl -- KKT certificate of ANY primal-dual point (x, lam_g, lam_x) in CasADi's convention: the solver's own error measure for a point it
 // did not produce (Ipopt's answer, a shifted plan, a candidate warm start, the rows a graph replay just returned).  include/boundmpc_hip.h
 // bmpc_kkt_batch has the record; this is the wave program behind it, built from the pieces of a solver iteration:
-//   1. parameter vector into LDS, x into the iterate, tables, wave_eval -- the point is taken as given: no start rollout, no projection;
-//   2. lam_g / lam_x onto the 57 N internal multipliers nu by the map of bmpc_dual.inl (restated below: pos(), tube pair lam (wd +- c), the cap
-//      DUAL_NU_CAP, a non-finite entry counts as 0), into sc.NUm;
+//   1. wave_load_point as a solve begins, wave_eval -- the point is taken as given: no start rollout, no projection;
+//   2. lam_g / lam_x onto the 57 N internal multipliers nu by the map of bmpc_dual.inl (dual_row; its file comment states the map), into sc.NUm;
 //   3. wave_adjoint(..., use_hat = false, mu = 0), as at the top of every solver iteration: the equality multipliers LAM [N][36] that zero the
 //      state part of the Lagrangian gradient, and the jerk part RJ [N][8] that remains;
-//   4. two wide passes with the deterministic WRED_* reductions: the residuals, then the outputs in the reference's convention (the output map of
-//      wave_solve) with the gaps between the caller's multipliers and the consistent ones.
+//   4. two wide passes with the deterministic WRED_* reductions: the residuals, then the outputs in the reference's convention (out_g_entry /
+//      out_lam_x_entry of bmpc_wave.inl, the output map of wave_solve) with the gaps between the caller's multipliers and the consistent ones.
 // The error E is that of wave_solve (its "KKT error (Ipopt-style scaling)") with the slack of a row replaced by max(-h_i, 0): a point carries no
 // slacks.  The passes use the output pass's wave-uniform trip counts on clamped indices (build.py lint_isa).  A maximum drops NaN (v > m is
 // false), so non-finite values are counted on their own: one non-finite f, g, h, LAM or RJ makes the five error slots NaN.
@@ -24,9 +23,8 @@ struct KktIn {
     double *g, *lam_g, *rj;                    // optional outputs [43 N], [43 N], [8 N]; must not overlap the inputs
 };
 
-BMPC_D inline bool kkt_finite(double v) { return BMPC_FABS(v) <= 1.7976931348623157e308; }      // (false for NaN and +-inf)
 // |given - consistent| of one multiplier entry; +inf when the given entry (or the difference) is not finite
-BMPC_D inline double kkt_gap(double given, double own) { const double d = BMPC_FABS(given - own); return kkt_finite(d) ? d : __builtin_inf(); }
+BMPC_D inline double kkt_gap(double given, double own) { const double d = BMPC_FABS(given - own); return bmpc_finite(d) ? d : __builtin_inf(); }
 
 template <bool ZLDS>
 BMPC_D inline void wave_certify(Wave &W, const KktIn &d) {
@@ -34,39 +32,16 @@ BMPC_D inline void wave_certify(Wave &W, const KktIn &d) {
     double *L = W.L; const GPtr G = W.G; const LPtr WL = BMPC_WL(W);
     const POff po = make_poff_lds(S, L_ZL);
     const Scr sc = make_scr(N);
-    const int np = po.size, nw = N * NZ, ni = N * NI, ne = N * NE, nrj = N * NU, ngt = N * NG;
-#ifdef BMPC_EMU
-    LaneRegs LRs[WS];      // (emulator: one register set per lane)
-#else
-    LaneRegs LRs[1];
-#endif
-    if (ZLDS) { W.Zc = L + L_ZL; W.Zt = L + L_PB; W.Dz = L + L_PB + 512; } else { W.Zc = (G + sc.Z).ptr(); W.Zt = (G + sc.ZT).ptr(); W.Dz = (G + sc.DZ).ptr(); }
-    WIDE_BEGIN
-        for (int id = wl; id < np; id += WS) L[L_PAR + (ZLDS ? id : lds_index_of_p(S, id, L_ZL))] = d.p[id];
-        for (int id = wl; id < nw; id += WS) W.Zc[id] = d.x[id];
-    WIDE_END
-    wave_init_tables(W, po);
-    const double *PAR = L + L_PAR;
+    const int nw = N * NZ, ni = N * NI, ne = N * NE, nrj = N * NU, ngt = N * NG;
+    BMPC_LANE_REGS(LRs);
+    wave_load_point<ZLDS>(W, po, sc, d.p, d.x);
     const double fval = wave_eval(W, po, sc, W.Zc, sc.G, sc.HIN, false);
     const bool hx = d.lam_x0 != nullptr, hg = d.lam_g0 != nullptr;
-    // ---- multipliers of the internal rows (the row pass of bmpc_dual.inl, restated; into the workspace instead of a dual state) ----
+    // ---- multipliers of the internal rows (dual_row of bmpc_dual.inl; into the workspace instead of a dual state) ----
     WIDE_BEGIN
         for (int t_ = 0; t_ < (ni + WS - 1) / WS; t_++) {
             const int id0 = wl + WS * t_, id = id0 < ni ? id0 : ni - 1;
-            const int k = id / NI, r = id - k * NI;
-            const int rb = r <= IPHI0 ? r : IPHI0;                                                  // box row of the table (clamped)
-            const int ig = r < ITUBE ? (r > IPHIMAX ? 37 : 36) : 38 + ((r - ITUBE) >> 1);          // lam_g entry of a non-box row
-            const int m = r < ITUBE ? 0 : (r - ITUBE) >> 1;
-            const double sgn = L[L_ROWT + rb], src = L[L_ROWT + 2 * NI + rb];
-            const double vx = hx ? dual_finite(d.lam_x0[k * NZ + (int)src]) : 0.0;
-            const double vg = hg ? dual_finite(d.lam_g0[k * NG + ig]) : 0.0;
-            const LPtr rr = WL + sc.REF + k * RREC;
-            const double c = rr[RC + m], wd = rr[RWD + m];
-            double v;
-            if (r <= IPHI0) v = sgn * vx;
-            else if (r < ITUBE) v = vg;
-            else { const double lam = vg > 0.0 ? vg : 0.0; v = ((r - ITUBE) & 1) ? lam * (wd - c) : lam * (wd + c); }
-            WL[sc.NUm + id] = dual_cap(v);
+            WL[sc.NUm + id] = dual_row(L, WL, sc, d.lam_g0, d.lam_x0, id);
         }
     WIDE_END
     TEAM_SYNC();
@@ -78,17 +53,17 @@ BMPC_D inline void wave_certify(Wave &W, const KktIn &d) {
             const int id0 = wl + WS * t_, id = id0 < ni ? id0 : ni - 1; const bool ok_ = id0 < ni;
             const double hv = WL[sc.HIN + id], nu = WL[sc.NUm + id];
             const double viol = hv > 0.0 ? hv : 0.0, slack = hv < 0.0 ? -hv : 0.0, c = nu * slack;
-            pi = viol > pi ? viol : pi; cm = c > cm ? c : cm; sn += ok_ ? nu : 0.0; bad = kkt_finite(hv) ? bad : 1.0;
+            pi = viol > pi ? viol : pi; cm = c > cm ? c : cm; sn += ok_ ? nu : 0.0; bad = bmpc_finite(hv) ? bad : 1.0;
         }
         for (int t_ = 0; t_ < (ne + WS - 1) / WS; t_++) {
             const int id0 = wl + WS * t_, id = id0 < ne ? id0 : ne - 1; const bool ok_ = id0 < ne;
             const double gv = WL[sc.G + id], lv = WL[sc.LAM + id], v = BMPC_FABS(gv);
-            pe = v > pe ? v : pe; sl += ok_ ? BMPC_FABS(lv) : 0.0; bad = (kkt_finite(gv) && kkt_finite(lv)) ? bad : 1.0;
+            pe = v > pe ? v : pe; sl += ok_ ? BMPC_FABS(lv) : 0.0; bad = (bmpc_finite(gv) && bmpc_finite(lv)) ? bad : 1.0;
         }
         for (int t_ = 0; t_ < (nrj + WS - 1) / WS; t_++) {
             const int id0 = wl + WS * t_, id = id0 < nrj ? id0 : nrj - 1;
             const double rv = WL[sc.RJ + id], v = BMPC_FABS(rv);
-            ed = v > ed ? v : ed; bad = kkt_finite(rv) ? bad : 1.0;
+            ed = v > ed ? v : ed; bad = bmpc_finite(rv) ? bad : 1.0;
             if (d.rj) d.rj[id] = rv;
         }
         WRED_PUT_MAX(L_REDW, 0, ed); WRED_PUT_MAX(L_REDW, 1, pe); WRED_PUT_MAX(L_REDW, 2, pi); WRED_PUT_MAX(L_REDW, 3, cm);
@@ -96,31 +71,24 @@ BMPC_D inline void wave_certify(Wave &W, const KktIn &d) {
     WIDE_END
     const double ed = WRED_GET_MAX(L_REDW, 0), pe = WRED_GET_MAX(L_REDW, 1), pi = WRED_GET_MAX(L_REDW, 2), cm = WRED_GET_MAX(L_REDW, 3),
                  sl = WRED_GET_SUM(L_REDW, 4), sn = WRED_GET_SUM(L_REDW, 5);
-    const bool bad = WRED_GET_MAX(L_KKPW, 0) > 0.0 || !kkt_finite(fval);
+    const bool bad = WRED_GET_MAX(L_KKPW, 0) > 0.0 || !bmpc_finite(fval);
     TEAM_SYNC();      // (every partial has been read before the next pass rewrites the area)
-    // ---- the consistent multipliers in the reference's convention (the output map of wave_solve) and the gaps to the caller's ----
+    // ---- the consistent multipliers in the reference's convention (out_g_entry, out_lam_x_entry) and the gaps to the caller's ----
     WIDE_BEGIN
         double ge = 0, gi = 0;
         for (int t_ = 0; t_ < (ngt + WS - 1) / WS; t_++) {
             const int id0 = wl + WS * t_, id = id0 < ngt ? id0 : ngt - 1;
-            const int k = id / NG, i = id - k * NG;
-            const double *Zn = W.Zc + k * NZ; const LPtr rr = WL + sc.REF + k * RREC, nu = WL + sc.NUm + k * NI;
-            double gv, lv;
-            if (i < NE) { gv = WL[sc.G + k * NE + i]; lv = WL[sc.LAM + k * NE + i]; }
-            else if (i == 36) { gv = Zn[ZPHI] - PAR[po.phimax]; lv = nu[IPHIMAX]; }
-            else if (i == 37) { gv = Zn[ZDPHI] - PAR[po.dphimax]; lv = nu[IDPHIMAX]; }
-            else { const int m = i - 38; const double c = rr[RC + m], wd = rr[RWD + m]; gv = c * c - wd * wd; lv = wd > 0 ? (nu[ITUBE + 2 * m] + nu[ITUBE + 2 * m + 1]) / (2 * wd) : 0.0; }
+            double gv, lv; out_g_entry(W, po, sc, id, gv, lv);
             const double gap = hg ? kkt_gap(d.lam_g0[id], lv) : 0.0;
-            const double gap_e = i < NE ? gap : 0.0, gap_i = i < NE ? 0.0 : gap;
+            const bool eq = id % NG < NE;
+            const double gap_e = eq ? gap : 0.0, gap_i = eq ? 0.0 : gap;
             ge = gap_e > ge ? gap_e : ge; gi = gap_i > gi ? gap_i : gi;
             if (d.g) d.g[id] = gv;
             if (d.lam_g) d.lam_g[id] = lv;
         }
         for (int t_ = 0; t_ < (nw + WS - 1) / WS; t_++) {
             const int id0 = wl + WS * t_, id = id0 < nw ? id0 : nw - 1;
-            const int k = id / NZ, z = id - k * NZ; const LPtr nu = WL + sc.NUm + k * NI; double v = 0;
-            if (z < 8) v = nu[IJU + z] - nu[IJL + z]; else if (z < ZDQ) v = nu[IQU + z - ZQ] - nu[IQL + z - ZQ];
-            else if (z < ZDDQ) v = nu[IDQU + z - ZDQ] - nu[IDQL + z - ZDQ]; else if (z == ZPHI) v = -nu[IPHI0];
+            const double v = out_lam_x_entry(W, sc, id);
             const double gap = hx ? kkt_gap(d.lam_x0[id], v) : 0.0;
             gi = gap > gi ? gap : gi;
         }

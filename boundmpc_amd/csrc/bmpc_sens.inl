@@ -1,7 +1,6 @@
 // bmpc_sens.inl -- parametric sensitivity of the solution: the tangent (dx, dLAM, dnu) along a direction dp of the parameter vector, at ANY
 // primal-dual point (x, lam_g, lam_x) in CasADi's convention and a barrier level mu.  include/boundmpc_hip.h bmpc_sens_batch has the definition
-// (the linearised perturbed barrier KKT system) and the record; this is the wave program behind it, built from the phases of a solver iteration
-// (wave_solve itself is untouched):
+// (the linearised perturbed barrier KKT system) and the record; this is the wave program behind it, built from the phases of a solver iteration:
 //   1. the evaluation at (x, p) and the multipliers nu of the 57 N internal rows by the map of bmpc_dual.inl, as bmpc_kkt.inl does it; the slack
 //      of a row s = max(-h, mu / max(nu, mu)) and the barrier ratio Sigma = nu / s, which goes where a solver iteration keeps nu / t (sc.SG);
 //   2. the right-hand side by DIFFERENCING THE RESIDUAL: wave_eval + wave_adjoint at p + eps dp and at p - eps dp with x and nu held fixed.  The
@@ -35,8 +34,6 @@ struct SensIn {
     double *dlam_eq, *dnu, *rec;                    // optional outputs [36 N], [57 N], [SENS_LEN]
 };
 
-BMPC_D inline bool sens_finite(double v) { return BMPC_FABS(v) <= 1.7976931348623157e308; }      // (false for NaN and +-inf)
-
 // the parameter vector p + t dp into LDS, and the tables that depend on it
 template <bool ZLDS>
 BMPC_D inline void sens_load_p(Wave &W, const POff &po, const SensIn &d, double t) {
@@ -58,12 +55,8 @@ BMPC_D inline void wave_sensitivity(Wave &W, const SensIn &d) {
     const POff po = make_poff_lds(S, L_ZL);
     const Scr sc = make_scr(N);
     const int np = po.size, nw = N * NZ, ni = N * NI, ne = N * NE, nrj = N * NU;
-#ifdef BMPC_EMU
-    LaneRegs LRs[WS];      // (emulator: one register set per lane)
-#else
-    LaneRegs LRs[1];
-#endif
-    if (ZLDS) { W.Zc = L + L_ZL; W.Zt = L + L_PB; W.Dz = L + L_PB + 512; } else { W.Zc = (G + sc.Z).ptr(); W.Zt = (G + sc.ZT).ptr(); W.Dz = (G + sc.DZ).ptr(); }
+    BMPC_LANE_REGS(LRs);
+    wave_iterate_ptrs<ZLDS>(W, sc);
     double *DX = (G + sc.DZ).ptr();      // the tangent dx, kept in the slab (the LDS direction area is the block area of the next sweep)
     const double nan_ = __builtin_nan("");
     const bool duals = d.dlam_eq != nullptr || d.dnu != nullptr;
@@ -73,12 +66,12 @@ BMPC_D inline void wave_sensitivity(Wave &W, const SensIn &d) {
         for (int t_ = 0; t_ < (np + WS - 1) / WS; t_++) {
             const int id0 = wl + WS * t_, id = id0 < np ? id0 : np - 1;
             const double a = BMPC_FABS(d.p[id]), b = BMPC_FABS(d.dp[id]);
-            mp = a > mp ? a : mp; md = b > md ? b : md; bad = (sens_finite(a) && sens_finite(b)) ? bad : 1.0;
+            mp = a > mp ? a : mp; md = b > md ? b : md; bad = (bmpc_finite(a) && bmpc_finite(b)) ? bad : 1.0;
         }
         for (int t_ = 0; t_ < (nw + WS - 1) / WS; t_++) {
             const int id0 = wl + WS * t_, id = id0 < nw ? id0 : nw - 1;
             const double a = BMPC_FABS(d.x[id]);
-            mx = a > mx ? a : mx; bad = sens_finite(a) ? bad : 1.0;
+            mx = a > mx ? a : mx; bad = bmpc_finite(a) ? bad : 1.0;
         }
         WRED_PUT_MAX(L_REDW, 0, mp); WRED_PUT_MAX(L_REDW, 1, md); WRED_PUT_MAX(L_REDW, 2, mx); WRED_PUT_MAX(L_REDW, 3, bad);
     WIDE_END
@@ -89,31 +82,18 @@ BMPC_D inline void wave_sensitivity(Wave &W, const SensIn &d) {
     const double eps = dinf > 0.0 ? BMPC_FMIN(SENS_EPS * BMPC_FMAX(1.0, pinf) / BMPC_FMAX(dinf, SENS_TINY), 1e300) : 0.0, inv2e = dinf > 0.0 ? 0.5 / eps : 0.0;
     double delta = 0.0, rhs = 0.0, dxm = 0.0; bool ok = false;
     if (!bad_in) {      // (wave-uniform)
-        // ---- 1. the point: evaluation, multipliers of the internal rows (the row pass of bmpc_kkt.inl), slacks and barrier ratios ----
+        // ---- 1. the point: evaluation, multipliers of the internal rows (dual_row of bmpc_dual.inl), slacks and barrier ratios ----
         WIDE_BEGIN
             for (int t_ = 0; t_ < (nw + WS - 1) / WS; t_++) { const int id0 = wl + WS * t_, id = id0 < nw ? id0 : nw - 1; W.Zc[id] = d.x[id]; }
         WIDE_END
         sens_load_p<ZLDS>(W, po, d, 0.0);
         wave_eval(W, po, sc, W.Zc, sc.G, sc.HIN, false);
-        const bool hx = d.lam_x0 != nullptr, hg = d.lam_g0 != nullptr;
         const double mu = d.mu;
         WIDE_BEGIN
             for (int t_ = 0; t_ < (ni + WS - 1) / WS; t_++) {
                 const int id0 = wl + WS * t_, id = id0 < ni ? id0 : ni - 1;
-                const int k = id / NI, r = id - k * NI;
-                const int rb = r <= IPHI0 ? r : IPHI0;                                                  // box row of the table (clamped)
-                const int ig = r < ITUBE ? (r > IPHIMAX ? 37 : 36) : 38 + ((r - ITUBE) >> 1);          // lam_g entry of a non-box row
-                const int m = r < ITUBE ? 0 : (r - ITUBE) >> 1;
-                const double sgn = L[L_ROWT + rb], src = L[L_ROWT + 2 * NI + rb];
-                const double vx = hx ? dual_finite(d.lam_x0[k * NZ + (int)src]) : 0.0;
-                const double vg = hg ? dual_finite(d.lam_g0[k * NG + ig]) : 0.0;
-                const LPtr rr = WL + sc.REF + k * RREC;
-                const double c = rr[RC + m], wd = rr[RWD + m], hv = WL[sc.HIN + id];
-                double v;
-                if (r <= IPHI0) v = sgn * vx;
-                else if (r < ITUBE) v = vg;
-                else { const double lam = vg > 0.0 ? vg : 0.0; v = ((r - ITUBE) & 1) ? lam * (wd - c) : lam * (wd + c); }
-                const double nu = dual_cap(v), nm = nu > mu ? nu : mu, s0 = mu / nm, s = -hv > s0 ? -hv : s0;
+                const double hv = WL[sc.HIN + id];
+                const double nu = dual_row(L, WL, sc, d.lam_g0, d.lam_x0, id), nm = nu > mu ? nu : mu, s0 = mu / nm, s = -hv > s0 ? -hv : s0;
                 WL[sc.NUm + id] = nu; WL[sc.SG + id] = nu / s;
             }
         WIDE_END
@@ -135,21 +115,21 @@ BMPC_D inline void wave_sensitivity(Wave &W, const SensIn &d) {
                         const int id0 = wl + WS * t_, id = id0 < ni ? id0 : ni - 1;
                         const double hd_ = (WL[sc.HT + id] - WL[sc.HIN + id]) * inv2e, v = WL[sc.SG + id] * hd_, a = BMPC_FABS(hd_);
                         WL[sc.DT + id] = hd_; WL[sc.DNU + id] = v;
-                        mr = a > mr ? a : mr; bad = (sens_finite(a) && sens_finite(v)) ? bad : 1.0;
+                        mr = a > mr ? a : mr; bad = (bmpc_finite(a) && bmpc_finite(v)) ? bad : 1.0;
                     }
                     for (int t_ = 0; t_ < (ne + WS - 1) / WS; t_++) {
                         const int id0 = wl + WS * t_, id = id0 < ne ? id0 : ne - 1;
                         const double gd_ = (WL[sc.GT + id] - WL[sc.G + id]) * inv2e, a = BMPC_FABS(gd_);
                         const bool ok_ = id0 < ne;      // (in place: a clamped duplicate may read what its owner has written -- it stores to a spare word and counts nowhere)
                         WL[ok_ ? sc.G + id : sc.GVP + 6] = gd_;
-                        mr = (ok_ && a > mr) ? a : mr; bad = (!ok_ || sens_finite(a)) ? bad : 1.0;
+                        mr = (ok_ && a > mr) ? a : mr; bad = (!ok_ || bmpc_finite(a)) ? bad : 1.0;
                     }
                     for (int t_ = 0; t_ < (nrj + WS - 1) / WS; t_++) {
                         const int id0 = wl + WS * t_, id = id0 < nrj ? id0 : nrj - 1;
                         const double rd_ = (WL[sc.DE + id] - WL[sc.E + id]) * inv2e, a = BMPC_FABS(rd_);
                         const bool ok_ = id0 < nrj;
                         WL[ok_ ? sc.DE + id : sc.GVP + 6] = rd_;
-                        mr = (ok_ && a > mr) ? a : mr; bad = (!ok_ || sens_finite(a)) ? bad : 1.0;
+                        mr = (ok_ && a > mr) ? a : mr; bad = (!ok_ || bmpc_finite(a)) ? bad : 1.0;
                     }
                     WRED_PUT_MAX(L_REDW, 0, mr); WRED_PUT_MAX(L_REDW, 1, bad);
                 WIDE_END
@@ -191,7 +171,7 @@ BMPC_D inline void wave_sensitivity(Wave &W, const SensIn &d) {
                         const int id0 = wl + WS * t_, id = id0 < nw ? id0 : nw - 1;
                         const double v = W.Dz[id], a = BMPC_FABS(v);
                         if (ZLDS) DX[id] = v;
-                        m = a > m ? a : m; bad = sens_finite(a) ? bad : 1.0;
+                        m = a > m ? a : m; bad = bmpc_finite(a) ? bad : 1.0;
                     }
                     WRED_PUT_MAX(L_REDW, 0, m); WRED_PUT_MAX(L_REDW, 1, bad);
                 WIDE_END

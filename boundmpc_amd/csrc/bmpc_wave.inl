@@ -681,6 +681,7 @@ BMPC_D inline double ineq_dir(const double *dZ, const double *rr, int i) {
     const double s = rr[RGC + m * 4 + 0] * dZ[vo] + rr[RGC + m * 4 + 1] * dZ[vo + 1] + rr[RGC + m * 4 + 2] * dZ[vo + 2] + rr[RGC + m * 4 + 3] * dZ[ZPHI];
     return (((i - ITUBE) & 1) ? -s : s) - rr[RW1 + m] * dZ[ZPHI];
 }
+BMPC_D inline bool bmpc_finite(double v) { return BMPC_FABS(v) <= 1.7976931348623157e308; }      // (false for NaN and +-inf)
 
 // integrator-chain coefficients CF[f'][f]: row field f' (q,dq,ddq,j of the next node) vs column field f (q,dq,ddq,j,u)
 BMPC_D inline double chain_cf(double h, int fr, int fc) {
@@ -727,6 +728,49 @@ BMPC_D inline void wave_init_tables(Wave &W, const POff &po) {
     W.ca = 2 * L[L_PAR + po.w + 5] / (W.h * W.h); W.cb = 2 * L[L_PAR + po.w + 5] / W.h;
 }
 
+// ---- how every wave program begins: where the iterate lives, and a point (p, x) taken in ----
+// iterate, trial iterate and direction: in LDS (ZLDS) or in the workspace slab
+template <bool ZLDS>
+BMPC_D inline void wave_iterate_ptrs(Wave &W, const Scr &sc) {
+    double *L = W.L; const GPtr G = W.G;
+    if (ZLDS) { W.Zc = L + L_ZL; W.Zt = L + L_PB; W.Dz = L + L_PB + 512; } else { W.Zc = (G + sc.Z).ptr(); W.Zt = (G + sc.ZT).ptr(); W.Dz = (G + sc.DZ).ptr(); }
+}
+// "a solve begins": coalesced load of the parameter vector into LDS and of x into the iterate, then the tables.  The warm-start conversion
+// (bmpc_dual.inl) and the certificate (bmpc_kkt.inl) start here and wave_solve with twin lines (see there); the sensitivities (bmpc_sens.inl)
+// load p + t dp instead.
+template <bool ZLDS>
+BMPC_D inline void wave_load_point(Wave &W, const POff &po, const Scr &sc, const double *p, const double *x) {
+    double *L = W.L; const int S = W.S, np = po.size, nw = W.N * NZ;
+    wave_iterate_ptrs<ZLDS>(W, sc);
+    WIDE_BEGIN
+        for (int id = wl; id < np; id += WS) L[L_PAR + (ZLDS ? id : lds_index_of_p(S, id, L_ZL))] = p[id];
+        for (int id = wl; id < nw; id += WS) W.Zc[id] = x[id];
+    WIDE_END
+    wave_init_tables(W, po);
+}
+
+// ---- the output map: the internal rows in the reference's conventions (casadi nlpsol), one entry per call ----
+// Read: the iterate W.Zc, the parameter vector, G / LAM and the reference records of the last evaluation, the multipliers nu [N][57] at sc.NUm.
+// Caller: wave_certify (bmpc_kkt.inl); the output pass of wave_solve keeps twin lines (see there).  The multiplier map dual_row (bmpc_dual.inl)
+// is the inverse.
+// entry id of [N][43]: the constraint value gv and its multiplier lv
+BMPC_D inline void out_g_entry(const Wave &W, const POff &po, const Scr &sc, int id, double &gv, double &lv) {
+    const double *PAR = W.L + L_PAR; const LPtr WL = BMPC_WL(W);
+    const int k = id / NG, i = id - k * NG;
+    const double *Zn = W.Zc + k * NZ; const LPtr rr = WL + sc.REF + k * RREC, nu = WL + sc.NUm + k * NI;
+    if (i < NE) { gv = WL[sc.G + k * NE + i]; lv = WL[sc.LAM + k * NE + i]; }
+    else if (i == 36) { gv = Zn[ZPHI] - PAR[po.phimax]; lv = nu[IPHIMAX]; }
+    else if (i == 37) { gv = Zn[ZDPHI] - PAR[po.dphimax]; lv = nu[IDPHIMAX]; }
+    else { const int m = i - 38; const double c = rr[RC + m], wd = rr[RWD + m]; gv = c * c - wd * wd; lv = wd > 0 ? (nu[ITUBE + 2 * m] + nu[ITUBE + 2 * m + 1]) / (2 * wd) : 0.0; }
+}
+// entry id of [N][44]: the multiplier of the variable's bounds (0 for an unbounded one)
+BMPC_D inline double out_lam_x_entry(const Wave &W, const Scr &sc, int id) {
+    const int k = id / NZ, z = id - k * NZ; const LPtr nu = BMPC_WL(W) + sc.NUm + k * NI; double v = 0;
+    if (z < 8) v = nu[IJU + z] - nu[IJL + z]; else if (z < ZDQ) v = nu[IQU + z - ZQ] - nu[IQL + z - ZQ];
+    else if (z < ZDDQ) v = nu[IDQU + z - ZDQ] - nu[IDQL + z - ZDQ]; else if (z == ZPHI) v = -nu[IPHI0];
+    return v;
+}
+
 #ifndef BMPC_RU
 #define BMPC_RU 9   // N=10: all 570 rows of a pass in one trip per lane (6: two trips; 10 starts to spill); +2 % (profiles/r02_n_rows_in_flight_ab.txt)
 #endif
@@ -735,6 +779,12 @@ static_assert(64 * BMPC_RU >= 10 * 57, "one batch must cover the 570 multiplier 
 constexpr int RU = BMPC_RU;   // rows of a lane-strided pass kept in flight per lane (loads of a batch are issued before their first use)
 constexpr int RUW = cdiv_(RU, NW);   // the same for the wide passes of a team: NW x 64 lanes share the rows
 struct LaneRegs { double mc[16]; double pf[24]; double ghd; };   // ghd: the lane's share of (QP gradient) . dZ, accumulated by the forward sweep   // pf: software prefetch of the next stage's inputs (global -> registers -> LDS)   // a lane's 4x4 state block of M, kept in registers between the M and the Schur phases
+// the register sets a wave program hands to its sweeps: the lane's own on the GPU, one per lane of the team in the emulator
+#ifdef BMPC_EMU
+#define BMPC_LANE_REGS(name) LaneRegs name[WS]
+#else
+#define BMPC_LANE_REGS(name) LaneRegs name[1]
+#endif
 
 // ----------------------------------------------------------------------------------------
 // wave-uniform deterministic reductions through LDS (RED has 6 x 64 slots)
@@ -2683,14 +2733,10 @@ BMPC_D inline void wave_solve(Wave &W, const Problem &pr) {
     Scr sc = make_scr(N);
     const Opts &o = W.o;
     const int np = po.size, nw = N * NZ, ni = N * NI, ne = N * NE;
-#ifdef BMPC_EMU
-    LaneRegs LRs[WS];      // (emulator: one register set per lane of the team)
-#else
-    LaneRegs LRs[1];
-#endif
-    // ---- coalesced load of the parameter vector into LDS and of x0 into the iterate ----
+    BMPC_LANE_REGS(LRs);
     constexpr bool zlds = ZLDS;
     const bool longh = !ZLDS && N > 11;      // long-horizon rules of the algorithm (oracle/bmpc_oracle.c): the instantiation without the LDS iterate also serves S > 4 at short horizons
+    // (the lines of wave_load_point, its twin, kept here: calling it changes this function's compiled code -- profiles/point_maps_refactor.txt)
     if (ZLDS) { W.Zc = L + L_ZL; W.Zt = L + L_PB; W.Dz = L + L_PB + 512; } else { W.Zc = (G + sc.Z).ptr(); W.Zt = (G + sc.ZT).ptr(); W.Dz = (G + sc.DZ).ptr(); }
     WIDE_BEGIN
         for (int id = wl; id < np; id += WS) L[L_PAR + (ZLDS ? id : lds_index_of_p(S, id, L_ZL))] = pr.p[id];
@@ -3200,6 +3246,7 @@ _Pragma("unroll") \
         if (pr.x) for (int t_ = 0; t_ < (nw + WS - 1) / WS; t_++) { const int id0 = wl + WS * t_, id = id0 < nw ? id0 : nw - 1; pr.x[id] = W.Zc[id]; }
         for (int t_ = 0; t_ < (N * NG + WS - 1) / WS; t_++) {
             const int id0 = wl + WS * t_, id = id0 < N * NG ? id0 : N * NG - 1;
+            // (twin of out_g_entry, and below of out_lam_x_entry, kept as text: the calls change this function's compiled code -- profiles/point_maps_refactor.txt)
             const int k = id / NG, i = id - k * NG;
             const double *Zn = W.Zc + k * NZ; const LPtr rr = WL + sc.REF + k * RREC, nu = WL + sc.NUm + k * NI;
             double gv, lv;

@@ -10,55 +10,22 @@ import pytest
 
 from oracle import c_oracle
 from oracle.nlp import internal_ineq
+from tests.multiplier_map import NG, NI, NU_CAP, NZ, nu_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
-NZ, NG, NI = 44, 43, 57
-NU_CAP = 1e12      # DUAL_NU_CAP of bmpc_dual.inl
-
-
-# ---- the map (include/boundmpc_hip.h bmpc_state_from_multipliers) in numpy ----
-def _fin(a):
-    a = np.array(a, dtype=float)
-    a[~np.isfinite(a)] = 0.0
-    return a
-
-
-def _cap(v):
-    with np.errstate(invalid="ignore"):
-        return np.where(v > 0, np.minimum(v, NU_CAP), 0.0)      # (NaN -> 0)
-
-
-def tube_centres(p, x, N, S):
-    """c [N][5], wd [N][5] of the squared tube rows at x, from the oracle's internal rows h[47 + 2m] = c - wd, h[48 + 2m] = -c - wd."""
-    H = internal_ineq(np.asarray(x, dtype=float), np.asarray(p, dtype=float), N, S).reshape(N, NI)
-    up, lo = H[:, 47::2], H[:, 48::2]
-    return (up - lo) / 2, -(up + lo) / 2
 
 
 def checker(p, x0, lam_g, lam_x, N, S, mu0=0.0, mu_warm=1e-2):
-    """state [B][57 N + 2] (and the per-row scale of the tube rows' rounding, lam (|c| + wd)) of the map, evaluated at x0."""
+    """state [B][57 N + 2] (and the per-row scale of the tube rows' rounding, lam (|c| + wd)) of the map (tests/multiplier_map.nu_of),
+    evaluated at x0."""
     p, x0 = np.atleast_2d(p), np.atleast_2d(x0)
     B = p.shape[0]
-    lg = np.zeros((B, N * NG)) if lam_g is None else _fin(np.atleast_2d(lam_g))
-    lx = np.zeros((B, N * NZ)) if lam_x is None else _fin(np.atleast_2d(lam_x))
+    lg, lx = (None if a is None else np.atleast_2d(a) for a in (lam_g, lam_x))
     state, scale = np.zeros((B, N * NI + 2)), np.zeros((B, N * NI))
     for b in range(B):
-        g, z = lg[b].reshape(N, NG), lx[b].reshape(N, NZ)
-        nu, sc = np.zeros((N, NI)), np.zeros((N, NI))
-        for lo, zs in ((0, slice(0, 8)), (16, slice(8, 15)), (30, slice(15, 22))):
-            n = zs.stop - zs.start
-            nu[:, lo:lo + n] = z[:, zs]
-            nu[:, lo + n:lo + 2 * n] = -z[:, zs]
-        nu[:, 44] = -z[:, 41]
-        nu[:, 45], nu[:, 46] = g[:, 36], g[:, 37]
-        c, wd = tube_centres(p[b], x0[b], N, S)
-        lam = np.maximum(g[:, 38:43], 0.0)
-        with np.errstate(invalid="ignore", over="ignore"):
-            nu[:, 47::2], nu[:, 48::2] = lam * (wd + c), lam * (wd - c)
-            sc[:, 47::2] = sc[:, 48::2] = lam * (np.abs(c) + wd)
-        nu = _cap(nu)
-        state[b, :N * NI], scale[b] = nu.ravel(), np.nan_to_num(sc.ravel())
+        nu, sc = nu_of(p[b], x0[b], None if lg is None else lg[b], None if lx is None else lx[b], N, S)[:2]
+        state[b, :N * NI], scale[b] = nu.ravel(), sc.ravel()
         state[b, N * NI] = (mu0 if mu0 > 0 else mu_warm) if nu.max() > 0 else 0.0
     return state, scale
 

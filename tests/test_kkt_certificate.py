@@ -1,5 +1,5 @@
 """KKT certificate of any primal-dual point (include/boundmpc_hip.h bmpc_kkt_batch), without a GPU: an independent numpy checker of the record
-(oracle/nlp.py values, the multiplier map restated, the C oracle's adjoint, and -- independently of that adjoint -- a complex-step gradient of the
+(oracle/nlp.py values, the multiplier map of tests/multiplier_map.py, the C oracle's adjoint, and -- independently of that adjoint -- a complex-step gradient of the
 Lagrangian), the kernel text (boundmpc_amd/csrc/bmpc_kkt.inl) on the CPU lane emulator against it, the ordering "solution below cold start", the
 gap rules and the C ABI.
 
@@ -17,58 +17,16 @@ import numpy as np
 import pytest
 
 from oracle import c_oracle, nlp
+from tests.multiplier_map import export_of, nu_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
 NZ, NG, NE, NI, NU = 44, 43, 36, 57, 8
-NU_CAP = 1e12      # DUAL_NU_CAP of bmpc_dual.inl
 FIELDS = ("E", "dual", "prim_eq", "prim_ineq", "compl", "lam_eq_gap", "lam_ineq_gap", "f")
 PROFILE = os.path.join(ROOT, "profiles", "kkt_certificate.txt")
 
 
 # ---- the record in numpy -------------------------------------------------------------------------------------------------------------------
-def _fin(a):
-    a = np.array(a, dtype=float)
-    a[~np.isfinite(a)] = 0.0
-    return a
-
-
-def nu_of(p, x, lam_g, lam_x, N, S):
-    """nu [N][57] of the internal rows from multipliers in CasADi's convention (the map of bmpc_state_from_multipliers), the rounding scale
-    lam (|c| + wd) of its tube rows, and c, wd [N][5] of the squared tube rows at x."""
-    g = np.zeros((N, NG)) if lam_g is None else _fin(lam_g).reshape(N, NG)
-    z = np.zeros((N, NZ)) if lam_x is None else _fin(lam_x).reshape(N, NZ)
-    H = nlp.internal_ineq(np.asarray(x, dtype=float), np.asarray(p, dtype=float), N, S).reshape(N, NI)
-    up, lo = H[:, 47::2], H[:, 48::2]
-    c, wd = (up - lo) / 2, -(up + lo) / 2
-    nu, sc = np.zeros((N, NI)), np.zeros((N, NI))
-    for r0, zs in ((0, slice(0, 8)), (16, slice(8, 15)), (30, slice(15, 22))):
-        n = zs.stop - zs.start
-        nu[:, r0:r0 + n], nu[:, r0 + n:r0 + 2 * n] = z[:, zs], -z[:, zs]
-    nu[:, 44] = -z[:, 41]
-    nu[:, 45], nu[:, 46] = g[:, 36], g[:, 37]
-    lam = np.maximum(g[:, 38:43], 0.0)
-    with np.errstate(invalid="ignore", over="ignore"):
-        nu[:, 47::2], nu[:, 48::2] = lam * (wd + c), lam * (wd - c)
-        sc[:, 47::2] = sc[:, 48::2] = lam * (np.abs(c) + wd)
-        nu = np.where(nu > 0, np.minimum(nu, NU_CAP), 0.0)
-    return nu, np.nan_to_num(sc), c, wd, H
-
-
-def export_of(nu, wd):
-    """lam_g[36:43] [N][7] and lam_x [N][44] of internal multipliers nu: the output map of a solve."""
-    N = nu.shape[0]
-    lg, lx = np.zeros((N, 7)), np.zeros((N, NZ))
-    lg[:, 0], lg[:, 1] = nu[:, 45], nu[:, 46]
-    with np.errstate(invalid="ignore", divide="ignore"):
-        lg[:, 2:] = np.where(wd > 0, (nu[:, 47::2] + nu[:, 48::2]) / (2 * wd), 0.0)
-    lx[:, 0:8] = nu[:, 0:8] - nu[:, 8:16]
-    lx[:, 8:15] = nu[:, 16:23] - nu[:, 23:30]
-    lx[:, 15:22] = nu[:, 30:37] - nu[:, 37:44]
-    lx[:, 41] = -nu[:, 44]
-    return lg, lx
-
-
 def _gap(given, own):
     with np.errstate(invalid="ignore", over="ignore"):
         d = np.abs(np.asarray(given, dtype=float) - own)

@@ -3,7 +3,7 @@ tangent, the kernel text (boundmpc_amd/csrc/bmpc_sens.inl) on the CPU lane emula
 solves, the contract cases and the C ABI.
 
 THE CHECKER (dense, numpy.linalg; nothing of the code under test).  Jg and Jh by complex step through oracle/nlp.py; nu by the multiplier map
-restated in test_kkt_certificate.nu_of; LAM from the state columns of the stationarity equation (Jg restricted to the state columns is square
+of tests/multiplier_map.nu_of; LAM from the state columns of the stationarity equation (Jg restricted to the state columns is square
 and regular); s and Sigma by the definition.  The system
     H dx + Jg^T dLAM + Jh^T dnu = -r,   Jg dx = -g',   dnu = Sigma (Jh dx + h')
 is solved in the null space of Jg: dx = xp + Z y with Jg xp = -g', Z = [I; -Jg_S^-1 Jg_J] (jerk columns J, state columns S), and
@@ -25,7 +25,8 @@ import numpy as np
 import pytest
 
 from oracle import c_oracle, nlp
-from tests.test_kkt_certificate import lagrangian_gradient, nu_of
+from tests.multiplier_map import nu_of
+from tests.test_kkt_certificate import lagrangian_gradient
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NZ, NG, NE, NI, NU = 44, 43, 36, 57, 8
