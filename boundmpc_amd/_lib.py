@@ -8,21 +8,42 @@ import os
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BOUNDMPC_HIP_LIB") or os.path.join(HERE, "csrc", "libboundmpc_hip.so")   # override: A/B builds of the same source
 
-SYMBOLS = ["bmpc_default_options", "bmpc_default_options_for", "bmpc_error_string", "bmpc_create", "bmpc_destroy", "bmpc_num_vars", "bmpc_num_cons",
-           "bmpc_num_params", "bmpc_get_bounds", "bmpc_solve_batch", "bmpc_solve_batch_host", "bmpc_set_timing",
-           "bmpc_last_kernel_ms", "bmpc_kernel_ms", "bmpc_launch_info", "bmpc_state_len", "bmpc_solve_batch_warm", "bmpc_graph_create",
-           "bmpc_graph_launch", "bmpc_graph_destroy", "bmpc_stream_lengths", "bmpc_stream_pack", "bmpc_stream_pack_rt", "bmpc_stream_post",
-           "bmpc_stream_graph_create", "bmpc_set_latency_buffer", "bmpc_stream_set_rt_feasibility_tol", "bmpc_stream_tick", "bmpc_set_team_waves", "bmpc_team_info", "bmpc_stream_set_time_budget",
-           "bmpc_set_restoration", "bmpc_get_restoration", "bmpc_options_size", "bmpc_build_hash", "bmpc_set_start_rollout", "bmpc_get_start_rollout", "bmpc_set_queue_order", "bmpc_get_queue_order", "bmpc_stream_set_rt_position_row_cap", "bmpc_set_barrier_hold", "bmpc_stream_set_level_rule", "bmpc_set_second_attempt", "bmpc_get_second_attempt",
-           "bmpc_state_from_multipliers", "bmpc_solve_batch_host_dual", "bmpc_kkt_len", "bmpc_kkt_batch", "bmpc_kkt_batch_host",
-           "bmpc_sens_len", "bmpc_sens_batch", "bmpc_sens_batch_host"]
-
 
 class Options(ctypes.Structure):
     _fields_ = [("tol", ctypes.c_double), ("max_iter", ctypes.c_int), ("mu_init", ctypes.c_double),
                 ("mu_min_fac", ctypes.c_double), ("slack_push", ctypes.c_double),
                 ("exact_hessian", ctypes.c_int), ("verbose", ctypes.c_int), ("mu_warm", ctypes.c_double), ("stall_window", ctypes.c_int),
                 ("bound_margin", ctypes.c_double)]
+
+
+_vp, _ci, _cd, _P = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.POINTER
+_SOLVE_OUT = [_vp] * 8          # x, g, lam_g, lam_x, f, iters, status, kkt
+_TICK = [_vp, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci]      # handle, B, path, entries, ... traj, flags
+# the C ABI of include/boundmpc_hip.h: name -> (restype, argtypes)
+SIGNATURES = {
+    "bmpc_default_options": (_ci, [_P(Options)]), "bmpc_default_options_for": (_ci, [_ci, _P(Options)]), "bmpc_options_size": (_ci, []),
+    "bmpc_error_string": (ctypes.c_char_p, [_ci]), "bmpc_build_hash": (ctypes.c_char_p, []),
+    "bmpc_create": (_ci, [_ci, _ci, _cd, _P(Options), _P(_vp)]), "bmpc_destroy": (_ci, [_vp]),
+    "bmpc_num_vars": (_ci, [_vp]), "bmpc_num_cons": (_ci, [_vp]), "bmpc_num_params": (_ci, [_vp]), "bmpc_state_len": (_ci, [_vp]),
+    "bmpc_get_bounds": (_ci, [_vp] * 5), "bmpc_launch_info": (_ci, [_vp, _P(_ci), _P(_ci), _P(ctypes.c_longlong)]),
+    "bmpc_solve_batch": (_ci, [_vp, _ci, _vp, _vp] + _SOLVE_OUT + [_vp]), "bmpc_solve_batch_host": (_ci, [_vp, _ci, _vp, _vp] + _SOLVE_OUT),
+    "bmpc_solve_batch_warm": (_ci, [_vp, _ci, _vp, _vp, _vp, _ci] + _SOLVE_OUT + [_vp]),
+    "bmpc_solve_batch_host_dual": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp] + _SOLVE_OUT),
+    "bmpc_state_from_multipliers": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _cd, _vp, _vp]),
+    "bmpc_graph_create": (_ci, [_vp, _ci, _vp, _vp, _vp, _ci] + _SOLVE_OUT + [_P(_vp)]), "bmpc_graph_launch": (_ci, [_vp, _vp]), "bmpc_graph_destroy": (_ci, [_vp]),
+    "bmpc_kkt_len": (_ci, []), "bmpc_kkt_batch": (_ci, [_vp, _ci] + [_vp] * 9), "bmpc_kkt_batch_host": (_ci, [_vp, _ci] + [_vp] * 8),
+    "bmpc_sens_len": (_ci, []), "bmpc_sens_batch": (_ci, [_vp, _ci] + [_vp] * 5 + [_cd] + [_vp] * 5), "bmpc_sens_batch_host": (_ci, [_vp, _ci] + [_vp] * 5 + [_cd] + [_vp] * 4),
+    "bmpc_stream_lengths": (_ci, [_vp] + [_P(_ci)] * 4), "bmpc_stream_pack": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 6), "bmpc_stream_pack_rt": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 7),
+    "bmpc_stream_post": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 6 + [_ci, _vp]), "bmpc_stream_tick": (_ci, _TICK + [_vp]), "bmpc_stream_graph_create": (_ci, _TICK + [_P(_vp)]),
+    "bmpc_stream_set_rt_feasibility_tol": (_ci, [_vp, _cd]), "bmpc_stream_set_rt_position_row_cap": (_ci, [_vp, _cd]), "bmpc_stream_set_time_budget": (_ci, [_vp, _cd]),
+    "bmpc_stream_set_level_rule": (_ci, [_vp, _cd, _cd, _cd]), "bmpc_set_barrier_hold": (_ci, [_vp, _ci]),
+    "bmpc_set_latency_buffer": (_ci, [_vp, _vp]), "bmpc_set_timing": (_ci, [_vp, _ci]), "bmpc_last_kernel_ms": (_ci, [_vp, _P(ctypes.c_float)]), "bmpc_kernel_ms": (_ci, [_vp, _ci, _P(ctypes.c_float)]),
+    "bmpc_set_team_waves": (_ci, [_vp, _ci]), "bmpc_team_info": (_ci, [_vp, _ci, _P(_ci), _P(_ci), _P(_ci)]),
+    "bmpc_set_restoration": (_ci, [_vp, _ci, _ci, _ci]), "bmpc_get_restoration": (_ci, [_vp, _P(_ci), _P(_ci), _P(_ci)]),
+    "bmpc_set_start_rollout": (_ci, [_vp, _ci]), "bmpc_get_start_rollout": (_ci, [_vp]), "bmpc_set_queue_order": (_ci, [_vp, _ci]), "bmpc_get_queue_order": (_ci, [_vp]),
+    "bmpc_set_second_attempt": (_ci, [_vp, _ci]), "bmpc_get_second_attempt": (_ci, [_vp]),
+}
+SYMBOLS = list(SIGNATURES)
 
 
 class BoundMPCHipError(RuntimeError):
@@ -44,72 +65,17 @@ def load():
             f"HIP extension {LIB_PATH} is missing - build it with `python -m boundmpc_amd.build` "
             "(hipcc --offload-arch=gfx950).  There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
-    vp, ci, cd = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
-    lib.bmpc_default_options.argtypes = [ctypes.POINTER(Options)]
-    lib.bmpc_default_options_for.argtypes = [ctypes.c_int, ctypes.POINTER(Options)]
-    lib.bmpc_error_string.restype = ctypes.c_char_p
-    lib.bmpc_error_string.argtypes = [ci]
-    lib.bmpc_create.argtypes = [ci, ci, cd, ctypes.POINTER(Options), ctypes.POINTER(vp)]
-    lib.bmpc_destroy.argtypes = [vp]
-    for n in ("bmpc_num_vars", "bmpc_num_cons", "bmpc_num_params"):
-        getattr(lib, n).argtypes = [vp]
-    lib.bmpc_get_bounds.argtypes = [vp, vp, vp, vp, vp]
-    lib.bmpc_solve_batch.argtypes = [vp, ci] + [vp] * 11
-    lib.bmpc_solve_batch_host.argtypes = [vp, ci] + [vp] * 10
-    lib.bmpc_state_len.argtypes = [vp]
-    lib.bmpc_solve_batch_warm.argtypes = [vp, ci, vp, vp, vp, ci] + [vp] * 9
-    lib.bmpc_graph_create.argtypes = [vp, ci, vp, vp, vp, ci] + [vp] * 8 + [ctypes.POINTER(vp)]
-    lib.bmpc_graph_launch.argtypes = [vp, vp]
-    lib.bmpc_graph_destroy.argtypes = [vp]
-    lib.bmpc_stream_lengths.argtypes = [vp] + [ctypes.POINTER(ci)] * 4
-    lib.bmpc_stream_pack.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp, vp]
-    lib.bmpc_stream_pack_rt.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
-    lib.bmpc_stream_post.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp]
-    lib.bmpc_stream_set_rt_feasibility_tol.argtypes = [vp, cd]
-    lib.bmpc_stream_tick.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, vp]
-    lib.bmpc_stream_graph_create.argtypes = [vp, ci, vp, ci, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, ci, ctypes.POINTER(vp)]
-    lib.bmpc_set_latency_buffer.argtypes = [vp, vp]
-    lib.bmpc_stream_set_time_budget.argtypes = [vp, cd]
-    lib.bmpc_set_team_waves.argtypes = [vp, ci]
-    lib.bmpc_team_info.argtypes = [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
-    lib.bmpc_set_timing.argtypes = [vp, ci]
-    lib.bmpc_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
-    lib.bmpc_kernel_ms.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_float)]
-    lib.bmpc_launch_info.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ctypes.c_longlong)]
-    if os.environ.get("BOUNDMPC_HIP_LIB") and not hasattr(lib, "bmpc_set_restoration"):
-        pass      # diagnostic A/B run against a build of an older revision (tests/gpu_ab.py): no restoration entry points; the in-tree library is always checked
-    else:
-        lib.bmpc_set_restoration.argtypes = [vp, ci, ci, ci]
-        lib.bmpc_get_restoration.argtypes = [vp, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(ci)]
-        if hasattr(lib, "bmpc_set_start_rollout"):      # (absent from A/B builds of older revisions)
-            lib.bmpc_set_start_rollout.argtypes = [vp, ci]
-            lib.bmpc_get_start_rollout.argtypes = [vp]
-        if hasattr(lib, "bmpc_set_queue_order"):
-            lib.bmpc_set_queue_order.argtypes = [vp, ci]
-            lib.bmpc_get_queue_order.argtypes = [vp]
-        if hasattr(lib, "bmpc_set_barrier_hold"):
-            lib.bmpc_set_barrier_hold.argtypes = [vp, ci]
-            lib.bmpc_stream_set_level_rule.argtypes = [vp, cd, cd, cd]
-        if hasattr(lib, "bmpc_set_second_attempt"):
-            lib.bmpc_set_second_attempt.argtypes = [vp, ci]
-            lib.bmpc_get_second_attempt.argtypes = [vp]
-        if hasattr(lib, "bmpc_state_from_multipliers"):      # primal-dual warm start
-            lib.bmpc_state_from_multipliers.argtypes = [vp, ci, vp, vp, vp, vp, cd, vp, vp]
-            lib.bmpc_solve_batch_host_dual.argtypes = [vp, ci] + [vp] * 12
-        if hasattr(lib, "bmpc_kkt_batch"):      # KKT certificate of any primal-dual point
-            lib.bmpc_kkt_len.argtypes = []
-            lib.bmpc_kkt_batch.argtypes = [vp, ci] + [vp] * 9
-            lib.bmpc_kkt_batch_host.argtypes = [vp, ci] + [vp] * 8
-        if hasattr(lib, "bmpc_sens_batch"):      # parametric sensitivity of the solution
-            lib.bmpc_sens_len.argtypes = []
-            lib.bmpc_sens_batch.argtypes = [vp, ci] + [vp] * 5 + [cd] + [vp] * 5
-            lib.bmpc_sens_batch_host.argtypes = [vp, ci] + [vp] * 5 + [cd] + [vp] * 4
-        if hasattr(lib, "bmpc_stream_set_rt_position_row_cap"):
-            lib.bmpc_stream_set_rt_position_row_cap.argtypes = [vp, cd]
-        lib.bmpc_build_hash.restype = ctypes.c_char_p
+    in_tree = not os.environ.get("BOUNDMPC_HIP_LIB")      # (a library given by hand -- the A/B build of an older revision, tests/gpu_ab.py -- may lack entry points and is not tied to the tree)
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if hasattr(lib, name):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
+        elif in_tree:
+            raise BoundMPCHipError(f"{LIB_PATH} does not export {name} (stale build?): rebuild with `python -m boundmpc_amd.build`")
+    if hasattr(lib, "bmpc_build_hash"):
         from . import build as _build
         want, have = _build.source_hash(), lib.bmpc_build_hash().decode()
-        if not os.environ.get("BOUNDMPC_HIP_LIB") and want != have:
+        if in_tree and want != have:
             raise BoundMPCHipError(f"{LIB_PATH} was built from other sources or flags (library {have}, tree {want}): rebuild with `python -m boundmpc_amd.build`")
         if lib.bmpc_options_size() != ctypes.sizeof(Options):
             raise BoundMPCHipError(f"{LIB_PATH}: bmpc_options is {lib.bmpc_options_size()} bytes, this binding expects {ctypes.sizeof(Options)} (stale build?)")

@@ -4,6 +4,20 @@
 // wave program (bmpc_wave.inl) and are expanded behind it.
 #pragma once
 
+// The horizon rule, once: horizons up to BMPC_SHORT_NMAX keep the iterate in LDS (with S <= SMAX_ZLDS) and run the first option set below,
+// longer ones the second -- a cold start far from the solution wants a more central first barrier level and roomier slacks (the values of the
+// barrier restart; 3-15 % fewer iterations than 0.3 / 1e-2 at N = 16..40), stalls are met by barrier restarts, so they are looked
+// for earlier, the restoration phase follows a numerical breakdown only, and a solve that ends with status 2 gets a second attempt.
+// bmpc_opts_for fills a WHOLE option record (OPTS = the Opts of a wave program's namespace) with the defaults of a handle of horizon N.
+enum { BMPC_SHORT_NMAX = 11 };
+template <class OPTS>
+inline void bmpc_opts_for(int N, OPTS &o) {
+    const bool lng = N > BMPC_SHORT_NMAX;
+    o.tol = 1e-8; o.max_iter = 500; o.mu_init = lng ? 3.0 : 0.1; o.mu_min_fac = 0.1; o.slack_push = lng ? 0.1 : 1e-2; o.exact_hessian = 1; o.verbose = 0;
+    o.mu_warm = 1e-2; o.stall_window = lng ? 20 : 40; o.bound_margin = 0.0;
+    o.restoration = lng ? 2 : 1; o.resto_short = 6; o.resto_cap = 40; o.start_rollout = 1; o.hold_mu = 0; o.retry_cap = lng ? 100 : 0;
+}
+
 // The wave `W` of a workgroup from the argument head {N, S, h, o} of `a`, on the LDS array `lds` and the workspace slab `slab`; wave: its index in
 // the workgroup (0 in a one-wave kernel).  A macro for the reason given at BMPC_PROBLEM.
 #define BMPC_WAVE_INIT(W, a, lds, slab, wave) \

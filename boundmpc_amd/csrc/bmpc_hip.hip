@@ -4,9 +4,11 @@
 // set + per-wave global scratch slab (see bmpc_wave.inl for the algorithm and the lane maps).
 #include <hip/hip_runtime.h>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 
 #include "../../include/boundmpc_hip.h"
@@ -92,7 +94,9 @@ __global__ void __launch_bounds__(64, BMPC_WAVES_PER_EU) bmpc_service_kernel(Ser
 
 // (members without an initialiser start at zero / NULL: bmpc_create value-initialises the handle)
 struct bmpc_handle {
-    int N, S; double h; bmpc_options o;
+    int N, S; double h;
+    bmpc::Opts o;            // everything the wave program reads: the public options (bmpc_create) and what the setters add (bmpc_set_restoration, _start_rollout,
+                             // _barrier_hold, _second_attempt); defaults of horizon N: bmpc_opts_for (bmpc_args.h)
     int dev;                 // device the handle was created on: workspace, work queue, events and streams of the handle live there
     int refs = 1; bool closed;   // one reference for the creator, one per captured graph (their kernels carry the workspace addresses);
                              // bmpc_destroy closes the handle, the memory goes when the last reference does
@@ -105,14 +109,10 @@ struct bmpc_handle {
     hipStream_t own_stream;  // handle_stream: host-buffer calls run here, and graph replays requested on the legacy null stream, bracketed by events (bmpc_graph_launch)
     int grid; long long scr_stride; double *scratch; int scr_waves; int graphs_alive; int *counter; unsigned long long *prof;
     int team_grid;           // resident TEAMS (workgroups of BMPC_TEAM_NW waves, bmpc_team.hip) of the device; 0: no team kernel for this handle (N > 10 or S > 4)
-    int pair_grid;           // resident PAIRS (workgroups of 2 waves at two waves per SIMD, bmpc_pair.hip); 0: no pair kernel for this handle (N > 11 or S > 4)
+    int pair_grid;           // resident PAIRS (workgroups of 2 waves at two waves per SIMD, bmpc_pair.hip); 0: no pair kernel for this handle (long horizon or S > 4)
     int *aux_int; int aux_cap;      // [2][aux_cap] status / iters of a batch whose caller passed NULL (the restoration kernel reads them)
-    int hold_mu;            // bmpc_set_barrier_hold: 1 = a solve holds the barrier level it starts on
-    int retry_cap;          // bmpc_set_second_attempt: iterations of the second attempt of a stateless solve that ends with status 2 (0 = none; default 100 for N > 11)
     double level_c, level_lo, level_hi;      // bmpc_stream_set_level_rule: stream_pack sets the level of a stream's next tick (level_hi <= 0: off)
-    int start_rollout = 1;  // 1 (default): a stateless solve whose x0 is far off its own dynamics starts from the rollout of x0's jerks (bmpc_set_start_rollout)
-    int resto_on, resto_short = 6, resto_cap = 40;      // restoration phase (bmpc_set_restoration): mode 0 off / 1 full (default N <= 11) / 2 after a numerical breakdown only (default N > 11); jam = resto_short consecutive short steps; iterations per phase
-    int queue_order;         // bmpc_set_queue_order: 1 = a batch beyond the resident waves is solved in the order of decreasing f(x0) (default for N > 11), 0 = natural order
+    int queue_order;         // bmpc_set_queue_order: 1 = a batch beyond the resident waves is solved in the order of decreasing f(x0) (default for long horizons), 0 = natural order
     double *qkey; int *qorder; int q_cap;      // [q_cap] keys and order of the last such batch
     int team_mode;           // bmpc_set_team_waves: 0 automatic (teams when the batch fits into the resident teams), 1 never, BMPC_TEAM_NW whenever possible
     int timing; hipEvent_t *ev; int nev; long long n_timed;   // timing = number of launches whose {start, stop} event pairs are kept (ring)
@@ -125,7 +125,7 @@ struct bmpc_handle {
 #define TRY(x) do { if (rc == BMPC_OK && (x) != hipSuccess) rc = BMPC_ERR_HIP; } while (0)      // a step of a sequence that runs to its end: skipped once one has failed
 
 // the instantiation of the one-wave kernels for this handle: iterate in LDS (true) or in the workspace (long horizons, 5 or 6 path segments)
-static bool handle_zlds(const bmpc_handle *h) { return h->N <= 11 && h->S <= bmpc::SMAX_ZLDS; }
+static bool handle_zlds(const bmpc_handle *h) { return h->N <= BMPC_SHORT_NMAX && h->S <= bmpc::SMAX_ZLDS; }
 // makes the handle's device current for the scope (allocation, free and synchronisation act on the CURRENT device)
 struct DevGuard {
     int prev; bool changed;
@@ -167,18 +167,20 @@ static void handle_release(bmpc_handle *h) {
     delete h;
 }
 
-extern "C" int bmpc_default_options(bmpc_options *o) {
+// The frozen public struct is the leading part of the wave program's option record; copy_public is the one place that converts between the two.
+#define SAME_PLACE(f) (offsetof(bmpc_options, f) == offsetof(bmpc::Opts, f))
+static_assert(SAME_PLACE(tol) && SAME_PLACE(max_iter) && SAME_PLACE(mu_init) && SAME_PLACE(mu_min_fac) && SAME_PLACE(slack_push) && SAME_PLACE(exact_hessian)
+              && SAME_PLACE(verbose) && SAME_PLACE(mu_warm) && SAME_PLACE(stall_window) && SAME_PLACE(bound_margin)
+              && sizeof(bmpc_options) == offsetof(bmpc::Opts, restoration), "bmpc_options is the leading part of bmpc::Opts");
+#undef SAME_PLACE
+static void copy_public(void *dst, const void *src) { memcpy(dst, src, sizeof(bmpc_options)); }
+extern "C" int bmpc_default_options_for(int N, bmpc_options *o) {
     if (!o) return BMPC_ERR_ARG;
-    o->tol = 1e-8; o->max_iter = 500; o->mu_init = 0.1; o->mu_min_fac = 0.1; o->slack_push = 1e-2; o->exact_hessian = 1; o->verbose = 0; o->mu_warm = 1e-2; o->stall_window = 40; o->bound_margin = 0.0;
+    bmpc::Opts d; bmpc_opts_for(N, d);
+    copy_public(o, &d);
     return BMPC_OK;
 }
-extern "C" int bmpc_default_options_for(int N, bmpc_options *o) {
-    const int rc = bmpc_default_options(o);
-    if (rc == BMPC_OK && N > 11) { o->mu_init = 3.0; o->slack_push = 0.1; o->stall_window = 20; }   // long horizons: a cold start far from the solution wants a more central first
-                                                                               // barrier level and roomier slacks (the values of the barrier restart; 3-15 % fewer iterations than 0.3 / 1e-2 at N = 16..40,
-                                                                               // DESIGN.md 2); stalls are met by barrier restarts (bmpc_wave.inl), so they are looked for earlier
-    return rc;
-}
+extern "C" int bmpc_default_options(bmpc_options *o) { return bmpc_default_options_for(BMPC_SHORT_NMAX, o); }
 extern "C" const char *bmpc_error_string(int c) {
     switch (c) { case BMPC_OK: return "ok"; case BMPC_ERR_ARG: return "invalid argument"; case BMPC_ERR_HIP: return "HIP runtime error";
                  case BMPC_ERR_NOGPU: return "no HIP device available"; default: return "unknown error"; }
@@ -191,9 +193,8 @@ extern "C" int bmpc_create(int N, int S, double dt, const bmpc_options *opts, bm
     bmpc_handle *h = new (std::nothrow) bmpc_handle();
     if (!h) return BMPC_ERR_ARG;
     h->N = N; h->S = S; h->h = dt;
-    h->retry_cap = N > 11 ? 100 : 0; h->queue_order = N > 11 ? 1 : 0;
-    h->resto_on = N <= 11 ? 1 : 2;      // restoration phase: full for short horizons, after a numerical breakdown only for long ones (bmpc_set_restoration)
-    if (opts) h->o = *opts; else bmpc_default_options_for(N, &h->o);
+    bmpc_opts_for(N, h->o); h->queue_order = N > BMPC_SHORT_NMAX ? 1 : 0;
+    if (opts) copy_public(&h->o, opts);      // (what the public struct does not carry keeps the default of the horizon)
     int dev = 0, per_cu = 0; hipDeviceProp_t prop;
     bool ok = hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess;
     h->dev = dev;
@@ -262,19 +263,28 @@ extern "C" int bmpc_get_bounds(const bmpc_handle *h, double *lbx, double *ubx, d
     return BMPC_OK;
 }
 
-// workspace for `waves` resident waves; growing frees the old slabs, which no launch may still be using: the handle's last launch is
-// waited for first, and captured graphs (which carry the old address) forbid growth -- size the first solve / capture for the largest batch
-static int ensure_scratch(bmpc_handle *h, int waves) {
-    if (waves <= h->scr_waves) return BMPC_OK;
+// Grows handle-owned device buffers that share one capacity (`cap`, committed last: a failed step leaves capacity 0, and the next call starts
+// over from whatever is allocated).  Growing frees the old buffers, which no launch may still be using: the handle's last launch is waited for
+// first, and captured graphs (which carry the old addresses) forbid growth with `refusal` -- size the first solve / capture for the largest batch.
+struct DevBuf { void **ptr; size_t bytes; };
+template <int NB>
+static int grow_buffers(bmpc_handle *h, int *cap, int want, const DevBuf (&bufs)[NB], const char *refusal) {
+    if (want <= *cap) return BMPC_OK;
     DevGuard dg(h->dev);
-    if (h->graphs_alive > 0 && h->scratch) {
-        fprintf(stderr, "boundmpc_hip: a larger batch needs a larger workspace, but %d captured graph(s) hold the current one\n", h->graphs_alive);
-        return BMPC_ERR_ARG;
+    if (*bufs[0].ptr) {
+        if (h->graphs_alive > 0) { fprintf(stderr, refusal, h->graphs_alive); return BMPC_ERR_ARG; }
+        wait_for_handle(h);
     }
-    if (h->scratch) { wait_for_handle(h); HIPCHK(hipFree(h->scratch)); h->scratch = nullptr; h->scr_waves = 0; }
-    HIPCHK(hipMalloc(&h->scratch, sizeof(double) * (size_t)h->scr_stride * waves));
-    h->scr_waves = waves;
+    *cap = 0;
+    for (const DevBuf &b : bufs) if (*b.ptr) { void *old = *b.ptr; *b.ptr = nullptr; HIPCHK(hipFree(old)); }
+    for (const DevBuf &b : bufs) HIPCHK(hipMalloc(b.ptr, b.bytes));
+    *cap = want;
     return BMPC_OK;
+}
+// workspace for `waves` resident waves
+static int ensure_scratch(bmpc_handle *h, int waves) {
+    return grow_buffers(h, &h->scr_waves, waves, {{(void **)&h->scratch, sizeof(double) * (size_t)h->scr_stride * waves}},
+                        "boundmpc_hip: a larger batch needs a larger workspace, but %d captured graph(s) hold the current one\n");
 }
 
 // event pair of the next timed launch (ring of h->timing pairs, created on first use)
@@ -302,68 +312,54 @@ static bool use_team(const bmpc_handle *h, int B) { return solve_waves(h, B) == 
 static int launch_grid(const bmpc_handle *h, int B) { const int w = solve_waves(h, B), g = w == BMPC_TEAM_NW ? h->team_grid : (w == 2 ? h->pair_grid : h->grid); return B < g ? B : g; }
 // the restoration kernel (bmpc_resto.hip) runs one wave per problem whatever kernel solved the batch
 static int resto_grid(const bmpc_handle *h, int B) { return B < h->grid ? B : h->grid; }
-// what a batch of B needs besides the caller's buffers: workspace slabs for the resident waves of both kernels, and -- the hand-over to the
-// restoration kernel goes through status[] and iters[] -- handle-owned stand-ins for a caller that passes NULL there.  Never inside a capture.
+// a stateless batch of B that is handed out longest-expected-first (bmpc_set_queue_order): one wave per problem, several rounds of the resident waves
+static bool queue_ordered(const bmpc_handle *h, int B) { return h->queue_order && B <= BMPC_QUEUE_ORDER_MAX && solve_waves(h, B) == 1 && B > h->grid; }
+// what a batch of B needs besides the caller's buffers: workspace slabs for the resident waves of both kernels, -- the hand-over to the
+// restoration kernel goes through status[] and iters[] -- handle-owned stand-ins for a caller that passes NULL there, and the keys and
+// order of a queue-ordered batch.  Never inside a capture.
 static int reserve_for_batch(bmpc_handle *h, int B) {
-    const int lg = launch_grid(h, B), rg = h->resto_on ? resto_grid(h, B) : 0;
-    const int rc = ensure_scratch(h, lg > rg ? lg : rg);
-    if (rc != BMPC_OK) return rc;
-    if (B > h->aux_cap) {
-        DevGuard dg(h->dev);
-        if (h->graphs_alive > 0 && h->aux_int) { fprintf(stderr, "boundmpc_hip: a larger batch needs larger status buffers, but captured graphs hold the current ones\n"); return BMPC_ERR_ARG; }
-        if (h->aux_int) { wait_for_handle(h); HIPCHK(hipFree(h->aux_int)); h->aux_int = nullptr; h->aux_cap = 0; }
-        HIPCHK(hipMalloc(&h->aux_int, sizeof(int) * 2 * (size_t)B));
-        h->aux_cap = B;
-    }
-    if (h->queue_order && B > h->q_cap && B <= BMPC_QUEUE_ORDER_MAX && solve_waves(h, B) == 1 && B > h->grid) {
-        DevGuard dg(h->dev);
-        if (h->graphs_alive > 0 && h->qkey) { fprintf(stderr, "boundmpc_hip: a larger batch needs larger queue-order buffers, but captured graphs hold the current ones\n"); return BMPC_ERR_ARG; }
-        if (h->qkey) { wait_for_handle(h); hipFree(h->qkey); hipFree(h->qorder); h->qkey = nullptr; h->qorder = nullptr; h->q_cap = 0; }
-        HIPCHK(hipMalloc(&h->qkey, sizeof(double) * (size_t)B)); HIPCHK(hipMalloc(&h->qorder, sizeof(int) * (size_t)B));
-        h->q_cap = B;
-    }
+    const int lg = launch_grid(h, B), rg = h->o.restoration ? resto_grid(h, B) : 0;
+    int rc = ensure_scratch(h, lg > rg ? lg : rg);
+    if (rc == BMPC_OK) rc = grow_buffers(h, &h->aux_cap, B, {{(void **)&h->aux_int, sizeof(int) * 2 * (size_t)B}},
+                                         "boundmpc_hip: a larger batch needs larger status buffers, but captured graphs hold the current ones\n");
+    if (rc == BMPC_OK && queue_ordered(h, B)) rc = grow_buffers(h, &h->q_cap, B, {{(void **)&h->qkey, sizeof(double) * (size_t)B}, {(void **)&h->qorder, sizeof(int) * (size_t)B}},
+                                                                "boundmpc_hip: a larger batch needs larger queue-order buffers, but captured graphs hold the current ones\n");
+    return rc;
+}
+// a 0 / 1 setting of the handle (field: where it lives; not looked at without a handle)
+static int set_switch(bmpc_handle *h, int *field, int v) {
+    if (!h || v < 0 || v > 1) return BMPC_ERR_ARG;
+    *field = v;
     return BMPC_OK;
 }
-extern "C" int bmpc_set_queue_order(bmpc_handle *h, int mode) {
-    if (!h || mode < 0 || mode > 1) return BMPC_ERR_ARG;
-    h->queue_order = mode;
-    return BMPC_OK;
-}
+extern "C" int bmpc_set_queue_order(bmpc_handle *h, int mode) { return set_switch(h, h ? &h->queue_order : nullptr, mode); }
 extern "C" int bmpc_get_queue_order(const bmpc_handle *h) { return h ? h->queue_order : -1; }
 extern "C" int bmpc_set_restoration(bmpc_handle *h, int enabled, int short_steps, int cap) {
     if (!h || short_steps > 1000 || cap > 100000 || cap == 0 || enabled > 2) return BMPC_ERR_ARG;      // (every argument is checked before any is applied)
-    if (enabled >= 0) h->resto_on = enabled;
-    if (short_steps >= 0) h->resto_short = short_steps;
-    if (cap >= 1) h->resto_cap = cap;
+    if (enabled >= 0) h->o.restoration = enabled;
+    if (short_steps >= 0) h->o.resto_short = short_steps;
+    if (cap >= 1) h->o.resto_cap = cap;
     return BMPC_OK;
 }
 extern "C" int bmpc_get_restoration(const bmpc_handle *h, int *enabled, int *short_steps, int *cap) {
     if (!h) return BMPC_ERR_ARG;
-    if (enabled) *enabled = h->resto_on; if (short_steps) *short_steps = h->resto_short; if (cap) *cap = h->resto_cap;
+    if (enabled) *enabled = h->o.restoration; if (short_steps) *short_steps = h->o.resto_short; if (cap) *cap = h->o.resto_cap;
     return BMPC_OK;
 }
-extern "C" int bmpc_set_start_rollout(bmpc_handle *h, int enabled) {
-    if (!h || enabled < 0 || enabled > 1) return BMPC_ERR_ARG;
-    h->start_rollout = enabled;
-    return BMPC_OK;
-}
-extern "C" int bmpc_set_barrier_hold(bmpc_handle *h, int enabled) {
-    if (!h || enabled < 0 || enabled > 1) return BMPC_ERR_ARG;
-    h->hold_mu = enabled;
-    return BMPC_OK;
-}
+extern "C" int bmpc_set_start_rollout(bmpc_handle *h, int enabled) { return set_switch(h, h ? &h->o.start_rollout : nullptr, enabled); }
+extern "C" int bmpc_set_barrier_hold(bmpc_handle *h, int enabled) { return set_switch(h, h ? &h->o.hold_mu : nullptr, enabled); }
 extern "C" int bmpc_set_second_attempt(bmpc_handle *h, int cap) {
     if (!h || cap < 0 || cap > 100000) return BMPC_ERR_ARG;
-    h->retry_cap = cap;
+    h->o.retry_cap = cap;
     return BMPC_OK;
 }
-extern "C" int bmpc_get_second_attempt(const bmpc_handle *h) { return h ? h->retry_cap : -1; }
+extern "C" int bmpc_get_second_attempt(const bmpc_handle *h) { return h ? h->o.retry_cap : -1; }
 extern "C" int bmpc_stream_set_level_rule(bmpc_handle *h, double c, double lo, double hi) {
     if (!h || !(c >= 0.0) || !(lo >= 0.0) || !(hi >= 0.0) || (hi > 0.0 && !(lo > 0.0 && lo <= hi))) return BMPC_ERR_ARG;
     h->level_c = c; h->level_lo = lo; h->level_hi = hi;
     return BMPC_OK;
 }
-extern "C" int bmpc_get_start_rollout(const bmpc_handle *h) { return h ? h->start_rollout : -1; }
+extern "C" int bmpc_get_start_rollout(const bmpc_handle *h) { return h ? h->o.start_rollout : -1; }
 extern "C" int bmpc_options_size(void) { return (int)sizeof(bmpc_options); }
 #ifndef BMPC_BUILD_HASH_STR
 #define BMPC_BUILD_HASH_STR "0000000000000000"
@@ -397,30 +393,32 @@ static hipError_t reset_queue(bmpc_handle *h, hipStream_t st) {
 }
 // the wave program's options from the handle's settings (max_iter > 0: the cap of this launch)
 static bmpc::Opts handle_opts(const bmpc_handle *h, int max_iter) {
-    bmpc::Opts o{};
-    o.tol = h->o.tol; o.max_iter = max_iter > 0 ? max_iter : h->o.max_iter; o.mu_init = h->o.mu_init; o.mu_min_fac = h->o.mu_min_fac;
-    o.slack_push = h->o.slack_push; o.exact_hessian = h->o.exact_hessian; o.verbose = 0; o.mu_warm = h->o.mu_warm; o.stall_window = h->o.stall_window; o.bound_margin = h->o.bound_margin;
-    o.restoration = h->resto_on; o.resto_short = h->resto_short; o.resto_cap = h->resto_cap; o.start_rollout = h->start_rollout; o.hold_mu = h->hold_mu; o.retry_cap = h->retry_cap;
+    bmpc::Opts o = h->o;
+    if (max_iter > 0) o.max_iter = max_iter;
+    o.verbose = 0;
     return o;
 }
-// kernel arguments from the handle's settings; the caller adds its buffers and what its launch shape changes
-static KArgs handle_kargs(const bmpc_handle *h, int B, int max_iter) {
-    KArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h; a.o = handle_opts(h, max_iter);
+// What a solve of B problems reads and writes, in the order of the C ABI (state: NULL = stateless; max_iter: 0 = the handle's; the outputs
+// behind x are optional), and what a closed-loop tick adds to it.  The entry points fill them once; everything below passes them on.
+struct SolveIO { const double *p, *x0; double *state; int max_iter; double *x, *g, *lam_g, *lam_x, *f; int *iters, *status; double *kkt; };
+struct StreamIO { const double *path; int path_entries; double *sstate, *robot, *traj; int flags; };
+// kernel arguments from the handle's settings and a solve record; the caller adds what its launch shape changes
+static KArgs handle_kargs(const bmpc_handle *h, int B, const SolveIO &s) {
+    KArgs a{}; a.N = h->N; a.S = h->S; a.B = B; a.h = h->h; a.o = handle_opts(h, s.max_iter);
     a.latency_us = h->latency_us; a.scratch = h->scratch; a.scr_stride = h->scr_stride; a.counter = h->counter; a.prof = h->prof;
+    a.p = s.p; a.x0 = s.x0; a.x = s.x; a.g = s.g; a.lam_g = s.lam_g; a.lam_x = s.lam_x; a.f = s.f; a.kkt = s.kkt; a.iters = s.iters; a.status = s.status; a.state = s.state;
     return a;
 }
-// fills the kernel arguments and enqueues {reset of the work-queue counter, solver kernel} on `st`
-static int enqueue_solve(bmpc_handle *h, int B, const double *p, const double *x0, double *state, int max_iter, double *x, double *g, double *lam_g,
-                         double *lam_x, double *f, int *iters, int *status, double *kkt, hipStream_t st, bool timed, bool capturing = false) {
+// enqueues {reset of the work-queue counter, solver kernel} on `st`
+static int enqueue_solve(bmpc_handle *h, int B, const SolveIO &s, hipStream_t st, bool timed, bool capturing = false) {
     if (h->closed) return BMPC_ERR_ARG;
     if (!capturing) { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
-    KArgs a = handle_kargs(h, B, max_iter);
-    if (state) a.o.retry_cap = 0;
-    a.p = p; a.x0 = x0; a.x = x; a.g = g; a.lam_g = lam_g; a.lam_x = lam_x; a.f = f; a.kkt = kkt; a.iters = iters; a.status = status; a.state = state;
+    KArgs a = handle_kargs(h, B, s);
+    if (s.state) a.o.retry_cap = 0;
     const int grid = launch_grid(h, B);
     if (grid > h->scr_waves) return BMPC_ERR_ARG;      // callers reserve the workspace first (never inside a stream capture)
     // restoration phase: the batch kernels hand a jammed problem over through status[] / iters[] (handle-owned when the caller wants neither)
-    const bool resto = h->resto_on != 0;
+    const bool resto = h->o.restoration != 0;
     a.counter2 = h->counter + 1; a.rcount = resto ? h->counter + 2 : nullptr;
     if (resto && (!a.status || !a.iters)) {
         if (B > h->aux_cap) return BMPC_ERR_ARG;
@@ -431,7 +429,7 @@ static int enqueue_solve(bmpc_handle *h, int B, const double *p, const double *x
     const bool zlds = handle_zlds(h);
     hipEvent_t *pair = nullptr;
     if (timed) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
-    if (h->queue_order && !state && solve_waves(h, B) == 1 && B > h->grid && B <= h->q_cap && B <= BMPC_QUEUE_ORDER_MAX) {
+    if (queue_ordered(h, B) && !s.state && B <= h->q_cap) {
         // Longest-expected-first: an evaluation pass (the same kernel with max_iter = 0: f at x0, nothing else written), the ranking, then the solve
         // hands the problems out in that order.  Inside the timed region: it is part of what the batch costs.  A result does not depend on which
         // wave solves it or when (bitwise invariance under permutation of the batch is a test), so the outputs are those of the natural order.
@@ -448,7 +446,7 @@ static int enqueue_solve(bmpc_handle *h, int B, const double *p, const double *x
     HIPCHK(reset_queue(h, st));
     // long horizons with the FULL restoration phase (mode 1 is not their default): the whole batch runs in the instantiation that holds the phase, so the
     // continuations of the few problems that need it sit in the work queue instead of following the batch on a handful of waves (same results)
-    const bool whole_in_resto = h->resto_on == 1 && !zlds && solve_waves(h, B) == 1;
+    const bool whole_in_resto = h->o.restoration == 1 && !zlds && solve_waves(h, B) == 1;
     if (whole_in_resto) { KArgs f = a; f.rcount = nullptr; HIPCHK(bmpc_resto_launch(zlds, &f, grid, st)); }
     else if (use_team(h, B)) HIPCHK(bmpc_team_launch_solve(BMPC_TEAM_NW, &a, grid, st));      // a workgroup of waves per problem (bmpc_team.hip)
     else if (solve_waves(h, B) == 2) HIPCHK(bmpc_pair_launch_solve(&a, grid, st));           // two waves per problem at two waves per SIMD (bmpc_pair.hip)
@@ -464,7 +462,7 @@ static int enqueue_solve(bmpc_handle *h, int B, const double *p, const double *x
 // The second attempt of a stateless solve (wave_solve_retry) reads x0 again after the first attempt has written x: with retry_cap > 0 an output
 // that overlaps the start would hand the second attempt the failed iterate.  (With the cap at 0 in-place solves are fine: x0 is read in full first.)
 static bool second_attempt_rereads_x0(const bmpc_handle *h, int B, const double *x0, const double *x) {
-    if (h->retry_cap <= 0) return false;
+    if (h->o.retry_cap <= 0) return false;
     const size_t n = (size_t)B * h->N * bmpc::NZ * sizeof(double);
     const uintptr_t a = (uintptr_t)x, b = (uintptr_t)x0;
     const bool overlap = a < b + n && b < a + n;
@@ -472,46 +470,42 @@ static bool second_attempt_rereads_x0(const bmpc_handle *h, int B, const double 
     return overlap;
 }
 
+// a direct solve on the caller's stream: stateless (bmpc_solve_batch) or warm-started from / updating io.state (bmpc_solve_batch_warm)
+static int launch_solve(bmpc_handle *h, int B, bool warm, const SolveIO &io, void *hip_stream) {
+    if (!h || B < 0 || io.max_iter < 0 || (B > 0 && (!io.p || !io.x0 || !io.x || (warm && !io.state)))) return BMPC_ERR_ARG;
+    if (B == 0) return BMPC_OK;
+    if (!warm && second_attempt_rereads_x0(h, B, io.x0, io.x)) return BMPC_ERR_ARG;
+    { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
+    return enqueue_solve(h, B, io, (hipStream_t)hip_stream, h->timing != 0);
+}
 extern "C" int bmpc_solve_batch(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
                                 double *f, int *iters, int *status, double *kkt, void *hip_stream) {
-    if (!h || B < 0 || (B > 0 && (!p || !x0 || !x))) return BMPC_ERR_ARG;
-    if (B == 0) return BMPC_OK;
-    if (second_attempt_rereads_x0(h, B, x0, x)) return BMPC_ERR_ARG;
-    { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
-    return enqueue_solve(h, B, p, x0, nullptr, 0, x, g, lam_g, lam_x, f, iters, status, kkt, (hipStream_t)hip_stream, h->timing != 0);
+    return launch_solve(h, B, false, SolveIO{p, x0, nullptr, 0, x, g, lam_g, lam_x, f, iters, status, kkt}, hip_stream);
 }
 
 extern "C" int bmpc_state_len(const bmpc_handle *h) { return h ? h->N * bmpc::NI + 2 : -1; }
 
 extern "C" int bmpc_solve_batch_warm(bmpc_handle *h, int B, const double *p, const double *x0, double *state, int max_iter, double *x, double *g,
                                      double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt, void *hip_stream) {
-    if (!h || B < 0 || max_iter < 0 || (B > 0 && (!p || !x0 || !x || !state))) return BMPC_ERR_ARG;
-    if (B == 0) return BMPC_OK;
-    { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
-    return enqueue_solve(h, B, p, x0, state, max_iter, x, g, lam_g, lam_x, f, iters, status, kkt, (hipStream_t)hip_stream, h->timing != 0);
+    return launch_solve(h, B, true, SolveIO{p, x0, state, max_iter, x, g, lam_g, lam_x, f, iters, status, kkt}, hip_stream);
 }
 
 // ---- service launches: dual state from multipliers (bmpc_dual.inl), KKT certificate (bmpc_kkt.inl), parametric sensitivity (bmpc_sens.inl) ----
 typedef bmpc::DualBatch DualBatch; typedef bmpc::KktBatch KktBatch; typedef bmpc::SensBatch SensBatch;
 // a service kernel runs one wave per problem on the handle's resident waves, whatever kernel solves a batch of this size
 static int service_grid(const bmpc_handle *h, int B) { return B < h->grid ? B : h->grid; }
-// enqueues the service kernel of `job` on `st`, ordered against the handle's other launches like enqueue_solve; callers reserve the workspace first
+// reserves the workspace and enqueues the service kernel of `job` on the caller's stream, ordered against the handle's other launches like enqueue_solve
 template <class JOB>
-static int enqueue_service(bmpc_handle *h, int B, hipStream_t st, const JOB &job) {
+static int launch_service(bmpc_handle *h, int B, void *hip_stream, const JOB &job) {
+    const int grid = service_grid(h, B); hipStream_t st = (hipStream_t)hip_stream;
+    { const int rc_ = ensure_scratch(h, grid); if (rc_ != BMPC_OK) return rc_; }
     if (h->closed) return BMPC_ERR_ARG;
-    const int grid = service_grid(h, B);
-    if (grid > h->scr_waves) return BMPC_ERR_ARG;
     { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
     const ServiceArgsT<bmpc::Opts, JOB> a{h->N, h->S, B, h->h, handle_opts(h, 0), h->scratch, h->scr_stride, job};
     if (handle_zlds(h)) hipLaunchKernelGGL((bmpc_service_kernel<true, JOB>), dim3(grid), dim3(64), 0, st, a);
     else hipLaunchKernelGGL((bmpc_service_kernel<false, JOB>), dim3(grid), dim3(64), 0, st, a);
     HIPCHK(hipGetLastError());
     return order_after(h, st);
-}
-template <class JOB>
-static int launch_service(bmpc_handle *h, int B, void *hip_stream, const JOB &job) {
-    { const int rc_ = ensure_scratch(h, service_grid(h, B)); if (rc_ != BMPC_OK) return rc_; }
-    return enqueue_service(h, B, (hipStream_t)hip_stream, job);
 }
 extern "C" int bmpc_state_from_multipliers(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g0, const double *lam_x0,
                                            double mu0, double *state, void *hip_stream) {
@@ -568,7 +562,8 @@ extern "C" int bmpc_graph_create(bmpc_handle *h, int B, const double *p, const d
     if (!h || !out || B < 1 || max_iter < 0 || !p || !x0 || !x) return BMPC_ERR_ARG;
     if (!state && second_attempt_rereads_x0(h, B, x0, x)) return BMPC_ERR_ARG;
     { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
-    return capture_graph(h, out, [&](hipStream_t cs) { return enqueue_solve(h, B, p, x0, state, max_iter, x, g, lam_g, lam_x, f, iters, status, kkt, cs, false, true); });
+    const SolveIO io{p, x0, state, max_iter, x, g, lam_g, lam_x, f, iters, status, kkt};
+    return capture_graph(h, out, [&](hipStream_t cs) { return enqueue_solve(h, B, io, cs, false, true); });
 }
 extern "C" int bmpc_graph_launch(bmpc_graph *gr, void *hip_stream) {
     if (!gr || !gr->h || gr->h->closed) return BMPC_ERR_ARG;
@@ -676,29 +671,27 @@ static int host_call(bmpc_handle *h, int B, const Field (&f)[NF], size_t tail_by
 // lam_x0 / lam_g0 are staged where the outputs lam_x / lam_g will be written (the conversion reads them before the solve behind it overwrites
 // them, in stream order), so the inputs are still ONE host-to-device copy (x and g of the record travel along: the solve overwrites them); the
 // dual state between conversion and solve is the tail of the device arena.
-static int solve_host(bmpc_handle *h, int B, bool dual, const double *p, const double *x0, const double *lam_g0, const double *lam_x0, double *x,
-                      double *g, double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt) {
-    if (!h || B < 0 || (B > 0 && (!p || !x0 || !x))) return BMPC_ERR_ARG;
+static int solve_host(bmpc_handle *h, int B, const double *lam_g0, const double *lam_x0, bool dual, const SolveIO &io) {
+    if (!h || B < 0 || (B > 0 && (!io.p || !io.x0 || !io.x))) return BMPC_ERR_ARG;
     if (B == 0) return BMPC_OK;
     const size_t np = (141 + 91 * h->S) * sizeof(double), nw = h->N * bmpc::NZ * sizeof(double), ng = h->N * bmpc::NG * sizeof(double);
     const int staged = dual ? FIELD_IN | FIELD_OUT : FIELD_OUT;
     enum { P, X0, X, LAM_X, G, LAM_G, F, KKT, ITERS, STATUS };
-    const Field fl[] = {field_in(p, np), field_in(x0, nw), field_out(x, nw), Field{staged, lam_x0, lam_x, nw}, field_out(g, ng), Field{staged, lam_g0, lam_g, ng},
-                        field_out(f, sizeof(double)), field_out(kkt, sizeof(double)), field_out(iters, sizeof(int)), field_out(status, sizeof(int))};
+    const Field fl[] = {field_in(io.p, np), field_in(io.x0, nw), field_out(io.x, nw), Field{staged, lam_x0, io.lam_x, nw}, field_out(io.g, ng), Field{staged, lam_g0, io.lam_g, ng},
+                        field_out(io.f, sizeof(double)), field_out(io.kkt, sizeof(double)), field_out(io.iters, sizeof(int)), field_out(io.status, sizeof(int))};
     return host_call(h, B, fl, dual ? (size_t)B * (h->N * bmpc::NI + 2) * sizeof(double) : 0, [&](void *const *dev, char *tail, hipStream_t hs) {
-        if (!dual) return bmpc_solve_batch(h, B, DEV(P), DEV(X0), DEV(X), DEV(G), DEV(LAM_G), DEV(LAM_X), DEV(F), (int *)dev[ITERS], (int *)dev[STATUS], DEV(KKT), hs);
-        const int rc = bmpc_state_from_multipliers(h, B, DEV(P), DEV(X0), DEV_IF(lam_g0, LAM_G), DEV_IF(lam_x0, LAM_X), 0.0, (double *)tail, hs);
-        if (rc != BMPC_OK) return rc;
-        return bmpc_solve_batch_warm(h, B, DEV(P), DEV(X0), (double *)tail, 0, DEV(X), DEV(G), DEV(LAM_G), DEV(LAM_X), DEV(F), (int *)dev[ITERS], (int *)dev[STATUS], DEV(KKT), hs);
+        const SolveIO d{DEV(P), DEV(X0), dual ? (double *)tail : nullptr, 0, DEV(X), DEV(G), DEV(LAM_G), DEV(LAM_X), DEV(F), (int *)dev[ITERS], (int *)dev[STATUS], DEV(KKT)};
+        const int rc = dual ? bmpc_state_from_multipliers(h, B, d.p, d.x0, DEV_IF(lam_g0, LAM_G), DEV_IF(lam_x0, LAM_X), 0.0, d.state, hs) : BMPC_OK;
+        return rc != BMPC_OK ? rc : launch_solve(h, B, dual, d, hs);
     });
 }
 extern "C" int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
                                      double *f, int *iters, int *status, double *kkt) {
-    return solve_host(h, B, false, p, x0, nullptr, nullptr, x, g, lam_g, lam_x, f, iters, status, kkt);
+    return solve_host(h, B, nullptr, nullptr, false, SolveIO{p, x0, nullptr, 0, x, g, lam_g, lam_x, f, iters, status, kkt});
 }
 extern "C" int bmpc_solve_batch_host_dual(bmpc_handle *h, int B, const double *p, const double *x0, const double *lam_g0, const double *lam_x0,
                                           double *x, double *g, double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt) {
-    return solve_host(h, B, true, p, x0, lam_g0, lam_x0, x, g, lam_g, lam_x, f, iters, status, kkt);
+    return solve_host(h, B, lam_g0, lam_x0, true, SolveIO{p, x0, nullptr, 0, x, g, lam_g, lam_x, f, iters, status, kkt});
 }
 // the record of a certificate: [p | x | lam_g0 | lam_x0] in, [cert | g | lam_g | rj] out
 extern "C" int bmpc_kkt_batch_host(bmpc_handle *h, int B, const double *p, const double *x, const double *lam_g0, const double *lam_x0, double *cert,
@@ -758,23 +751,31 @@ __global__ void __launch_bounds__(64) bmpc_stream_post_kernel(int N, int S, int 
                        x + (long long)b * 44 * N, g + (long long)b * 43 * N, status[b], traj + (long long)b * bmpcs::tr_len(N), flags, rt_tol, sh, threadIdx.x, 64, rt_row_cap);
 }
 // (the fused one-launch tick kernels of one wave per stream live in bmpc_tick.hip, those of the teams in bmpc_team.hip)
+// The argument test of the four stream entry points (max_iter: 0 where the entry point has none; need: the arrays it cannot do without, looked
+// at for B > 0 only).  False: BMPC_ERR_ARG.
+static bool stream_args_ok(const bmpc_handle *h, int B, int max_iter, int path_entries, std::initializer_list<const void *> need) {
+    if (!h || B < 0 || max_iter < 0 || path_entries < h->S + 1 || h->N > bmpcs::STREAM_NMAX) return false;      // (STREAM_NMAX: the solver's own limit)
+    if (B > 0) for (const void *q : need) if (!q) return false;
+    return true;
+}
+static bool tick_args_ok(const bmpc_handle *h, int B, const SolveIO &s, const StreamIO &t) {
+    return stream_args_ok(h, B, s.max_iter, t.path_entries, {t.path, t.sstate, t.robot, s.p, s.x0, s.x, s.g, s.status, t.traj});
+}
 // enqueues the fused tick on `st` (direct launch or inside a capture)
-static int enqueue_tick(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0, double *dual_state,
-                        int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags, hipStream_t st, bool capturing) {
+static int enqueue_tick(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, hipStream_t st, bool capturing) {
     if (h->closed) return BMPC_ERR_ARG;
     if (!capturing) { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
-    KArgs a = handle_kargs(h, B, max_iter);
+    KArgs a = handle_kargs(h, B, io);
     a.o.retry_cap = 0; a.budget_ticks = (long long)(h->rt_budget_us * 100.0);
-    a.p = p; a.x0 = x0; a.x = x; a.g = g; a.kkt = kkt; a.iters = iters; a.status = status; a.state = dual_state;
     if (B > h->scr_waves) return BMPC_ERR_ARG;
-    SArgs s; s.path = path; s.path_stride = path_entries * bmpcs::PT_LEN; s.ss = sstate; s.rb = robot; s.traj = traj; s.flags = flags; s.rt_tol = h->rt_viol_tol; s.rt_row_cap = h->rt_row_cap; s.lvl_c = h->level_c; s.lvl_lo = h->level_lo; s.lvl_hi = h->level_hi;
+    SArgs s; s.path = t.path; s.path_stride = t.path_entries * bmpcs::PT_LEN; s.ss = t.sstate; s.rb = t.robot; s.traj = t.traj; s.flags = t.flags; s.rt_tol = h->rt_viol_tol; s.rt_row_cap = h->rt_row_cap; s.lvl_c = h->level_c; s.lvl_lo = h->level_lo; s.lvl_hi = h->level_hi;
     const bool timed = !capturing && h->timing != 0;
     hipEvent_t *pair = nullptr;
     if (timed) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
     // The post-processing of a fused tick needs the final solution, so here the restoration phase runs INSIDE the kernel (instantiations with
     // RESTO); a time-budgeted real-time tick never gets as far as a jam (six short steps) and runs the lean instantiation with the phase off.
-    const bool resto = h->resto_on != 0 && a.budget_ticks == 0;
-    a.o.restoration = resto ? h->resto_on : 0;      // (the handle's MODE, not a flag: 2 = after a numerical breakdown only, as every other launch shape runs it)
+    const bool resto = h->o.restoration != 0 && a.budget_ticks == 0;
+    if (!resto) a.o.restoration = 0;      // (else the handle's MODE, not a flag: 2 = after a numerical breakdown only, as every other launch shape runs it)
     if (use_team(h, B)) HIPCHK(bmpc_team_launch_tick(BMPC_TEAM_NW, resto, &a, &s, B, st));
     else HIPCHK(bmpc_tick_launch(handle_zlds(h), resto, &a, &s, B, st));      // (long horizons, 5 or 6 path segments: iterate in the workspace)
     if (timed) { HIPCHK(hipEventRecord(pair[1], st)); h->n_timed++; }
@@ -783,23 +784,24 @@ static int enqueue_tick(bmpc_handle *h, int B, const double *path, int path_entr
 }
 static bool tick_fusable(const bmpc_handle *h, int B) { return B <= (use_team(h, B) ? h->team_grid : h->grid); }      // stream b = workgroup b: every stream needs a resident workgroup
 // enqueues one closed-loop tick on `st`: fused into one launch when every stream has a resident workgroup, else {pack, solve, post}
-static int enqueue_stream_tick(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0, double *dual_state,
-                               int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags, hipStream_t st, bool capturing) {
-    if (tick_fusable(h, B)) return enqueue_tick(h, B, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, st, capturing);
+static int enqueue_stream_tick(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, hipStream_t st, bool capturing) {
+    if (tick_fusable(h, B)) return enqueue_tick(h, B, io, t, st, capturing);
     // real-time mode: the warm start continues from the iterate of the previous tick on every launch shape (fused or not)
-    int rc = bmpc_stream_pack_rt(h, B, path, path_entries, sstate, robot, p, x0, dual_state, (flags & 2) ? x : nullptr, st);
-    if (rc == BMPC_OK) rc = enqueue_solve(h, B, p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt, st, !capturing && h->timing != 0, capturing);
-    if (rc == BMPC_OK) rc = bmpc_stream_post(h, B, path, path_entries, sstate, robot, x, g, status, traj, flags, st);
+    int rc = bmpc_stream_pack_rt(h, B, t.path, t.path_entries, t.sstate, t.robot, (double *)io.p, (double *)io.x0, io.state, (t.flags & 2) ? io.x : nullptr, st);
+    if (rc == BMPC_OK) rc = enqueue_solve(h, B, io, st, !capturing && h->timing != 0, capturing);
+    if (rc == BMPC_OK) rc = bmpc_stream_post(h, B, t.path, t.path_entries, t.sstate, t.robot, io.x, io.g, io.status, t.traj, t.flags, st);
     return rc;
 }
+// (a tick has no lam_g, lam_x and f: those slots of its solve record stay NULL)
 extern "C" int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
                                 double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
                                 void *hip_stream) {
-    if (!h || B < 0 || max_iter < 0 || path_entries < h->S + 1 || (B > 0 && (!path || !sstate || !robot || !p || !x0 || !x || !g || !status || !traj))) return BMPC_ERR_ARG;
-    if (h->N > bmpcs::STREAM_NMAX) return BMPC_ERR_ARG;      // (the solver's own limit)
+    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
+    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
+    if (!tick_args_ok(h, B, io, t)) return BMPC_ERR_ARG;
     if (B == 0) return BMPC_OK;
     { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
-    return enqueue_stream_tick(h, B, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, (hipStream_t)hip_stream, false);
+    return enqueue_stream_tick(h, B, io, t, (hipStream_t)hip_stream, false);
 }
 
 extern "C" int bmpc_stream_set_rt_feasibility_tol(bmpc_handle *h, double tol) {
@@ -828,8 +830,7 @@ extern "C" int bmpc_stream_pack(bmpc_handle *h, int B, const double *path, int p
 }
 extern "C" int bmpc_stream_pack_rt(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, const double *robot, double *p, double *x0,
                                    double *dual_state, const double *xlast, void *hip_stream) {
-    if (!h || B < 0 || path_entries < h->S + 1 || (B > 0 && (!path || !sstate || !robot || !p || !x0))) return BMPC_ERR_ARG;
-    if (h->N > bmpcs::STREAM_NMAX) return BMPC_ERR_ARG;      // (the solver's own limit)
+    if (!stream_args_ok(h, B, 0, path_entries, {path, sstate, robot, p, x0})) return BMPC_ERR_ARG;
     if (B == 0) return BMPC_OK;
     if (h->closed) return BMPC_ERR_ARG;
     hipLaunchKernelGGL(bmpc_stream_pack_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, path, path_entries * bmpcs::PT_LEN,
@@ -839,8 +840,7 @@ extern "C" int bmpc_stream_pack_rt(bmpc_handle *h, int B, const double *path, in
 }
 extern "C" int bmpc_stream_post(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, double *robot, const double *x, const double *g,
                                 const int *status, double *traj, int flags, void *hip_stream) {
-    if (!h || B < 0 || path_entries < h->S + 1 || (B > 0 && (!path || !sstate || !robot || !x || !g || !status || !traj))) return BMPC_ERR_ARG;
-    if (h->N > bmpcs::STREAM_NMAX) return BMPC_ERR_ARG;      // (the solver's own limit)
+    if (!stream_args_ok(h, B, 0, path_entries, {path, sstate, robot, x, g, status, traj})) return BMPC_ERR_ARG;
     if (B == 0) return BMPC_OK;
     hipLaunchKernelGGL(bmpc_stream_post_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, h->h, path,
                        path_entries * bmpcs::PT_LEN, sstate, robot, x, g, status, traj, flags, h->rt_viol_tol, h->rt_row_cap);
@@ -851,10 +851,11 @@ extern "C" int bmpc_stream_post(bmpc_handle *h, int B, const double *path, int p
 extern "C" int bmpc_stream_graph_create(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
                                         double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj,
                                         int flags, bmpc_graph **out) {
-    if (!h || !out || B < 1 || max_iter < 0 || path_entries < h->S + 1 || !path || !sstate || !robot || !p || !x0 || !x || !g || !status || !traj) return BMPC_ERR_ARG;
-    if (h->N > bmpcs::STREAM_NMAX) return BMPC_ERR_ARG;      // (the solver's own limit)
+    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
+    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
+    if (!out || B < 1 || !tick_args_ok(h, B, io, t)) return BMPC_ERR_ARG;
     { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
-    return capture_graph(h, out, [&](hipStream_t cs) { return enqueue_stream_tick(h, B, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, cs, true); });
+    return capture_graph(h, out, [&](hipStream_t cs) { return enqueue_stream_tick(h, B, io, t, cs, true); });
 }
 
 #ifdef BMPC_PROFILE

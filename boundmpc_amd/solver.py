@@ -17,6 +17,9 @@ KKT_FIELDS = ("E", "dual", "prim_eq", "prim_ineq", "compl", "lam_eq_gap", "lam_i
 # slots of the sensitivity record (include/boundmpc_hip.h BMPC_SENS_*), in order
 SENS_STATUS, SENS_DELTA, SENS_RHS, SENS_DX = range(4)
 SENS_FIELDS = ("status", "delta", "rhs", "dx_max")
+# the outputs of a solve in the order of the C ABI: name -> (row length as an attribute of the solver, None: one number per problem; dtype)
+SOLVE_OUTPUTS = {"x": ("n_w", "float64"), "g": ("n_g", "float64"), "lam_g": ("n_g", "float64"), "lam_x": ("n_w", "float64"), "f": (None, "float64"),
+                 "iters": (None, "int32"), "status": (None, "int32"), "kkt": (None, "float64")}
 
 
 def _ptr(a):
@@ -24,6 +27,12 @@ def _ptr(a):
     if a is None:
         return None
     return ctypes.c_void_p(a.data_ptr()) if hasattr(a, "data_ptr") else a.ctypes.data_as(ctypes.c_void_p)
+
+
+def _stream_ptr(stream, device):
+    """`stream`, or torch's current stream on `device`, as the stream argument of a ctypes call"""
+    import torch
+    return ctypes.c_void_p((stream if stream is not None else torch.cuda.current_stream(device)).cuda_stream)
 
 
 def _multiplier_or_none(v):
@@ -35,6 +44,40 @@ def _check_want(want, offered, what):
     bad = [k for k in want if k not in offered]
     if bad:
         raise ValueError(f"want {bad}: a {what} offers {offered}")
+
+
+def _new(shape, dtype="float64", device=None):
+    """An output array: a torch tensor on `device`, or (None) a zeroed numpy array."""
+    if device is None:
+        return np.zeros(shape, dtype=dtype)
+    import torch
+    return torch.empty(shape, dtype=getattr(torch, dtype), device=device)
+
+
+def _directions(dp, B, point):
+    """dp [B][n_p] or [B][D][n_p] (torch or numpy) -> D (None: one direction), the arrays of `point` with every row repeated D times (None stays
+    None) and dp as [B D][n_p]."""
+    if dp.ndim == 2:
+        return None, point, dp
+    D = dp.shape[1]
+    if D < 1:
+        raise ValueError("dp has no directions")
+    tile = lambda a: None if a is None else (a.repeat_interleave(D, dim=0).contiguous() if hasattr(a, "repeat_interleave") else np.ascontiguousarray(np.repeat(a, D, axis=0)))
+    return D, [tile(a) for a in point], dp.reshape(B * D, dp.shape[-1])
+
+
+def _take_start_rollout_off(solver):
+    """For a user of the caller's handle whose starts are the reference's own: start rollout off while it lives.  Returns the setting as found, for
+    _give_start_rollout_back in its close() (None: an A/B library from before the option has no such entry point)."""
+    was = solver.get_start_rollout() if hasattr(solver._lib, "bmpc_get_start_rollout") else None
+    if was is not None:
+        solver.set_start_rollout(False)
+    return was
+
+
+def _give_start_rollout_back(solver, was):
+    if was is not None and getattr(solver, "_h", None):
+        solver.set_start_rollout(was)
 
 
 def _host_rows(*named):
@@ -87,10 +130,9 @@ class BatchedOCPSolver:
             _lib.check(self._lib.bmpc_stream_set_level_rule(self._h, *[float(v) for v in self._level_rule]), "bmpc_stream_set_level_rule")
         # restoration phase (include/boundmpc_hip.h bmpc_set_restoration): None keeps the handle's default (on for N <= 11; 6 short steps; 40 iterations)
         if not (restoration is None and resto_short is None and resto_cap is None):
-            _lib.check(self._lib.bmpc_set_restoration(self._h, -1 if restoration is None else int(restoration), -1 if resto_short is None else int(resto_short),
-                                                      -1 if resto_cap is None else int(resto_cap)), "bmpc_set_restoration")
+            self.set_restoration(restoration, resto_short, resto_cap)
         if start_rollout is not None:      # rollout of a cold start that is not a trajectory (bmpc_set_start_rollout; default on)
-            _lib.check(self._lib.bmpc_set_start_rollout(self._h, int(bool(start_rollout))), "bmpc_set_start_rollout")
+            self.set_start_rollout(start_rollout)
         self.N, self.S, self.dt = int(N), int(S), float(dt)
         self.n_w, self.n_g, self.n_p = N * NZ, N * NG, 141 + 91 * S
         self.state_len = int(self._lib.bmpc_state_len(self._h))
@@ -266,6 +308,17 @@ class BatchedOCPSolver:
             out.append(a)
         return out
 
+    def _solve_shape(self, B, name):
+        n = SOLVE_OUTPUTS[name][0]
+        return (B, getattr(self, n)) if n else (B,)
+
+    def _cert_shapes(self, B):
+        return dict(cert=(B, len(KKT_FIELDS)), g=(B, self.n_g), lam_g=(B, self.n_g), rj=(B, 8 * self.N))
+
+    def _sens_outputs(self, R, want_duals, device=None):
+        shapes = dict(dx=(R, self.n_w), rec=(R, len(SENS_FIELDS)), dlam_eq=(R, 36 * self.N), dnu=(R, 57 * self.N))
+        return {k: _new(shapes[k], device=device) for k in (("dx", "rec", "dlam_eq", "dnu") if want_duals else ("dx", "rec"))}
+
     def state_from_multipliers(self, p, x0, lam_g0=None, lam_x0=None, mu0=None, out=None, stream=None):
         """Dual state [B, state_len] of a warm solve (solve_batch(state=...)) from multipliers in CasADi's convention -- lam_g0 [B, 43 N],
         lam_x0 [B, 44 N], as a solve returns them; None = zeros -- evaluated at x0 on the GPU (include/boundmpc_hip.h bmpc_state_from_multipliers:
@@ -275,9 +328,8 @@ class BatchedOCPSolver:
         B = p.shape[0]
         self._check_multipliers(B, lam_g0, lam_x0, p.device)
         state = out if out is not None else torch.empty((B, self.state_len), dtype=torch.float64, device=p.device)
-        st = stream if stream is not None else torch.cuda.current_stream(p.device)
         _lib.check(self._lib.bmpc_state_from_multipliers(self._h, B, _ptr(p), _ptr(x0), _ptr(lam_g0), _ptr(lam_x0), float(mu0 or 0.0), _ptr(state),
-                                                         ctypes.c_void_p(st.cuda_stream)), "bmpc_state_from_multipliers")
+                                                         _stream_ptr(stream, p.device)), "bmpc_state_from_multipliers")
         self._inflight = (p, x0, lam_g0, lam_x0, state)      # (asynchronous launch: see solve_batch)
         return state
 
@@ -298,18 +350,17 @@ class BatchedOCPSolver:
         _check_want(want, self._CERT_WANT, "certificate")
         o = out if out is not None else {}
         dev = p.device
-        shapes = dict(cert=(B, len(KKT_FIELDS)), g=(B, self.n_g), lam_g=(B, self.n_g), rj=(B, 8 * self.N))
+        shapes = self._cert_shapes(B)
         ptr = {}
         for k in ("cert",) + tuple(want):
             t = o.get(k)
             if t is None:
-                t = o[k] = torch.empty(shapes[k], dtype=torch.float64, device=dev)
+                t = o[k] = _new(shapes[k], device=dev)
             elif not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shapes[k] and t.device == dev):
                 raise ValueError(f"out[{k!r}] must be a contiguous float64 GPU tensor of shape {shapes[k]} on {dev}")
             ptr[k] = t
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
         _lib.check(self._lib.bmpc_kkt_batch(self._h, B, _ptr(p), _ptr(x), _ptr(lam_g), _ptr(lam_x), _ptr(ptr["cert"]), _ptr(ptr.get("g")), _ptr(ptr.get("lam_g")),
-                                            _ptr(ptr.get("rj")), ctypes.c_void_p(st.cuda_stream)), "bmpc_kkt_batch")
+                                            _ptr(ptr.get("rj")), _stream_ptr(stream, dev)), "bmpc_kkt_batch")
         self._inflight_cert = (p, x, lam_g, lam_x, o)      # (asynchronous launch: see solve_batch)
         for i, k in enumerate(KKT_FIELDS):
             o[k] = ptr["cert"][:, i]
@@ -320,10 +371,8 @@ class BatchedOCPSolver:
         B, p, x = _host_rows(("p", p, self.n_p), ("x", x, self.n_w))
         lam = self._host_multipliers(B, lam_g, lam_x, ("lam_g", "lam_x"))
         _check_want(want, self._CERT_WANT, "certificate")
-        shapes = dict(g=(B, self.n_g), lam_g=(B, self.n_g), rj=(B, 8 * self.N))
-        o = {"cert": np.zeros((B, len(KKT_FIELDS)))}
-        for k in want:
-            o[k] = np.zeros(shapes[k])
+        shapes = self._cert_shapes(B)
+        o = {k: _new(shapes[k]) for k in ("cert",) + tuple(want)}
         _lib.check(self._lib.bmpc_kkt_batch_host(self._h, B, _ptr(p), _ptr(x), _ptr(lam[0]), _ptr(lam[1]), _ptr(o["cert"]), _ptr(o.get("g")), _ptr(o.get("lam_g")),
                                                  _ptr(o.get("rj"))), "bmpc_kkt_batch_host")
         for i, k in enumerate(KKT_FIELDS):
@@ -345,24 +394,15 @@ class BatchedOCPSolver:
         if not (dp.is_cuda and dp.dtype == torch.float64 and dp.is_contiguous() and dp.device == p.device and dp.dim() in (2, 3) and dp.shape[0] == B
                 and dp.shape[-1] == self.n_p):
             raise ValueError(f"dp must be a contiguous float64 GPU tensor of shape ({B}, {self.n_p}) or ({B}, D, {self.n_p}) on {p.device}")
-        D = dp.shape[1] if dp.dim() == 3 else None
-        if D is not None:
-            if D < 1:
-                raise ValueError("dp has no directions")
-            tile = lambda t: None if t is None else t.repeat_interleave(D, dim=0).contiguous()
-            p, x, lam_g, lam_x, dp = tile(p), tile(x), tile(lam_g), tile(lam_x), dp.reshape(B * D, self.n_p)
+        D, (p, x, lam_g, lam_x), dp = _directions(dp, B, (p, x, lam_g, lam_x))
         R = p.shape[0]
         dev = p.device
-        o = {"dx": torch.empty((R, self.n_w), dtype=torch.float64, device=dev), "rec": torch.empty((R, len(SENS_FIELDS)), dtype=torch.float64, device=dev)}
-        if want_duals:
-            o["dlam_eq"] = torch.empty((R, 36 * self.N), dtype=torch.float64, device=dev)
-            o["dnu"] = torch.empty((R, 57 * self.N), dtype=torch.float64, device=dev)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        o = self._sens_outputs(R, want_duals, dev)
         _lib.check(self._lib.bmpc_sens_batch(self._h, R, _ptr(p), _ptr(x), _ptr(lam_g), _ptr(lam_x), _ptr(dp), float(mu or 0.0), _ptr(o["dx"]), _ptr(o.get("dlam_eq")),
-                                             _ptr(o.get("dnu")), _ptr(o["rec"]), ctypes.c_void_p(st.cuda_stream)), "bmpc_sens_batch")
+                                             _ptr(o.get("dnu")), _ptr(o["rec"]), _stream_ptr(stream, dev)), "bmpc_sens_batch")
         self._inflight_sens = (p, x, lam_g, lam_x, dp, o)      # (asynchronous launch: see solve_batch)
         if D is not None:
-            o = {k: v.view(B, D, v.shape[-1]) for k, v in o.items()}
+            o = {k: v.reshape(B, D, v.shape[-1]) for k, v in o.items()}
         return o
 
     def sensitivity_host(self, p, x, dp, lam_g=None, lam_x=None, mu=None, want_duals=False):
@@ -373,16 +413,9 @@ class BatchedOCPSolver:
         if dp.ndim not in (2, 3) or dp.shape[0] != B or dp.shape[-1] != self.n_p:
             raise ValueError(f"shape mismatch: p {p.shape} x {x.shape} dp {dp.shape}")
         lam = self._host_multipliers(B, lam_g, lam_x, ("lam_g", "lam_x"))
-        D = dp.shape[1] if dp.ndim == 3 else None
-        if D is not None:
-            if D < 1:
-                raise ValueError("dp has no directions")
-            tile = lambda a: None if a is None else np.ascontiguousarray(np.repeat(a, D, axis=0))
-            p, x, lam, dp = tile(p), tile(x), [tile(a) for a in lam], np.ascontiguousarray(dp.reshape(B * D, self.n_p))
+        D, (p, x, *lam), dp = _directions(dp, B, (p, x, *lam))
         R = p.shape[0]
-        o = {"dx": np.zeros((R, self.n_w)), "rec": np.zeros((R, len(SENS_FIELDS)))}
-        if want_duals:
-            o["dlam_eq"], o["dnu"] = np.zeros((R, 36 * self.N)), np.zeros((R, 57 * self.N))
+        o = self._sens_outputs(R, want_duals)
         _lib.check(self._lib.bmpc_sens_batch_host(self._h, R, _ptr(p), _ptr(x), _ptr(lam[0]), _ptr(lam[1]), _ptr(dp), float(mu or 0.0), _ptr(o["dx"]), _ptr(o.get("dlam_eq")),
                                                   _ptr(o.get("dnu")), _ptr(o["rec"])), "bmpc_sens_batch_host")
         if D is not None:
@@ -397,7 +430,6 @@ class BatchedOCPSolver:
         from it and updates it in place; `max_iter` > 0 caps the Newton steps of this call (real-time iteration).
         With multipliers lam_g0 [B][n_g] / lam_x0 [B][n_w] (CasADi's convention; either may be None) the solve is warm-started from the dual state
         state_from_multipliers makes of them, returned as out["state"]; multipliers and `state` together are refused."""
-        import torch
         self._check_io(p, x0, state)
         B = p.shape[0]
         o = out if out is not None else {}
@@ -405,34 +437,20 @@ class BatchedOCPSolver:
         if lam_g0 is not None or lam_x0 is not None:
             if state is not None:
                 raise ValueError("pass either multipliers (lam_g0 / lam_x0) or a dual state, not both")
-            st_ = stream if stream is not None else torch.cuda.current_stream(dev)
-            state = self.state_from_multipliers(p, x0, lam_g0, lam_x0, out=o.get("state"), stream=st_)
-            o["state"] = state
+            state = o["state"] = self.state_from_multipliers(p, x0, lam_g0, lam_x0, out=o.get("state"), stream=stream)
 
-        def buf(name, shape, dtype):
-            if name not in o or o[name] is None:
-                o[name] = torch.empty(shape, dtype=dtype, device=dev)
-            return o[name]
-        x = buf("x", (B, self.n_w), torch.float64)
-        ptr = {k: None for k in ("g", "lam_g", "lam_x", "f", "iters", "status", "kkt")}
-        if "g" in want: ptr["g"] = buf("g", (B, self.n_g), torch.float64)
-        if "lam_g" in want: ptr["lam_g"] = buf("lam_g", (B, self.n_g), torch.float64)
-        if "lam_x" in want: ptr["lam_x"] = buf("lam_x", (B, self.n_w), torch.float64)
-        if "f" in want: ptr["f"] = buf("f", (B,), torch.float64)
-        if "iters" in want: ptr["iters"] = buf("iters", (B,), torch.int32)
-        if "status" in want: ptr["status"] = buf("status", (B,), torch.int32)
-        if "kkt" in want: ptr["kkt"] = buf("kkt", (B,), torch.float64)
-        st = stream if stream is not None else torch.cuda.current_stream(dev)
+        given = [k for k in SOLVE_OUTPUTS if k == "x" or k in want]
+        for k in given:
+            if o.get(k) is None:
+                o[k] = _new(self._solve_shape(B, k), SOLVE_OUTPUTS[k][1], dev)
+        outs = [_ptr(o[k]) if k in given else None for k in SOLVE_OUTPUTS]
+        st = _stream_ptr(stream, dev)
         if state is None and not max_iter:
-            _lib.check(self._lib.bmpc_solve_batch(self._h, B, _ptr(p), _ptr(x0), _ptr(x), _ptr(ptr["g"]), _ptr(ptr["lam_g"]), _ptr(ptr["lam_x"]),
-                                                  _ptr(ptr["f"]), _ptr(ptr["iters"]), _ptr(ptr["status"]), _ptr(ptr["kkt"]),
-                                                  ctypes.c_void_p(st.cuda_stream)), "bmpc_solve_batch")
+            _lib.check(self._lib.bmpc_solve_batch(self._h, B, _ptr(p), _ptr(x0), *outs, st), "bmpc_solve_batch")
         else:
             if state is None:
                 raise ValueError("max_iter per call needs a state buffer (new_state)")
-            _lib.check(self._lib.bmpc_solve_batch_warm(self._h, B, _ptr(p), _ptr(x0), _ptr(state), int(max_iter), _ptr(x), _ptr(ptr["g"]), _ptr(ptr["lam_g"]),
-                                                       _ptr(ptr["lam_x"]), _ptr(ptr["f"]), _ptr(ptr["iters"]), _ptr(ptr["status"]), _ptr(ptr["kkt"]),
-                                                       ctypes.c_void_p(st.cuda_stream)), "bmpc_solve_batch_warm")
+            _lib.check(self._lib.bmpc_solve_batch_warm(self._h, B, _ptr(p), _ptr(x0), _ptr(state), int(max_iter), *outs, st), "bmpc_solve_batch_warm")
         # The launch is asynchronous: the kernel reads p / x0 / state and writes the outputs on the launch stream after this call has
         # returned.  The handle keeps them alive until its next launch (a caller that passes temporaries or drops the returned dict would
         # otherwise hand their memory back to the allocator while the kernel is still using it).
@@ -450,16 +468,12 @@ class BatchedOCPSolver:
         single call (bmpc_solve_batch_host_dual); without: the stateless solve."""
         B, p, x0 = _host_rows(("p", p, self.n_p), ("x0", x0, self.n_w))
         lam = self._host_multipliers(B, lam_g0, lam_x0, ("lam_g0", "lam_x0"))
-        out = dict(x=np.zeros((B, self.n_w)), g=np.zeros((B, self.n_g)), lam_g=np.zeros((B, self.n_g)), lam_x=np.zeros((B, self.n_w)),
-                   f=np.zeros(B), iters=np.zeros(B, dtype=np.int32), status=np.zeros(B, dtype=np.int32), kkt=np.zeros(B))
+        out = {k: _new(self._solve_shape(B, k), dt) for k, (_, dt) in SOLVE_OUTPUTS.items()}
+        outs = [_ptr(a) for a in out.values()]
         if lam[0] is None and lam[1] is None:
-            _lib.check(self._lib.bmpc_solve_batch_host(self._h, B, _ptr(p), _ptr(x0), _ptr(out["x"]), _ptr(out["g"]), _ptr(out["lam_g"]),
-                                                       _ptr(out["lam_x"]), _ptr(out["f"]), _ptr(out["iters"]), _ptr(out["status"]), _ptr(out["kkt"])),
-                       "bmpc_solve_batch_host")
+            _lib.check(self._lib.bmpc_solve_batch_host(self._h, B, _ptr(p), _ptr(x0), *outs), "bmpc_solve_batch_host")
         else:
-            _lib.check(self._lib.bmpc_solve_batch_host_dual(self._h, B, _ptr(p), _ptr(x0), _ptr(lam[0]), _ptr(lam[1]), _ptr(out["x"]), _ptr(out["g"]),
-                                                            _ptr(out["lam_g"]), _ptr(out["lam_x"]), _ptr(out["f"]), _ptr(out["iters"]), _ptr(out["status"]),
-                                                            _ptr(out["kkt"])), "bmpc_solve_batch_host_dual")
+            _lib.check(self._lib.bmpc_solve_batch_host_dual(self._h, B, _ptr(p), _ptr(x0), _ptr(lam[0]), _ptr(lam[1]), *outs), "bmpc_solve_batch_host_dual")
         return out
 
 
@@ -467,27 +481,18 @@ class StepGraph:
     """One solver step captured into a hipGraph (bmpc_graph_create / _launch / _destroy)."""
 
     def __init__(self, solver, p, x0, state, max_iter, want):
-        import torch
         B = solver._check_io(p, x0, state)
         if not (p.is_contiguous() and x0.is_contiguous()):
             raise ValueError("capture needs contiguous p and x0 (their addresses are baked into the graph)")
         self._solver, self.p, self.x0, self.state = solver, p, x0, state
-        dev = p.device
-        shapes = dict(g=((B, solver.n_g), torch.float64), lam_g=((B, solver.n_g), torch.float64), lam_x=((B, solver.n_w), torch.float64),
-                      f=((B,), torch.float64), iters=((B,), torch.int32), status=((B,), torch.int32), kkt=((B,), torch.float64))
-        self.out = {"x": torch.empty((B, solver.n_w), dtype=torch.float64, device=dev)}
-        for k in want:
-            self.out[k] = torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev)
-        g = lambda k: _ptr(self.out.get(k))
+        self.out = {k: _new(solver._solve_shape(B, k), SOLVE_OUTPUTS[k][1], p.device) for k in ("x",) + tuple(want)}
         self._g = ctypes.c_void_p()
-        _lib.check(solver._lib.bmpc_graph_create(solver._h, B, _ptr(p), _ptr(x0), _ptr(state), int(max_iter), _ptr(self.out["x"]), g("g"), g("lam_g"),
-                                                 g("lam_x"), g("f"), g("iters"), g("status"), g("kkt"), ctypes.byref(self._g)), "bmpc_graph_create")
+        _lib.check(solver._lib.bmpc_graph_create(solver._h, B, _ptr(p), _ptr(x0), _ptr(state), int(max_iter), *[_ptr(self.out.get(k)) for k in SOLVE_OUTPUTS],
+                                                 ctypes.byref(self._g)), "bmpc_graph_create")
         solver._children.add(self)
 
     def launch(self, stream=None):
-        import torch
-        st = stream if stream is not None else torch.cuda.current_stream(self.p.device)
-        _lib.check(self._solver._lib.bmpc_graph_launch(self._g, ctypes.c_void_p(st.cuda_stream)), "bmpc_graph_launch")
+        _lib.check(self._solver._lib.bmpc_graph_launch(self._g, _stream_ptr(stream, self.p.device)), "bmpc_graph_launch")
         return self.out
 
     def close(self):
@@ -515,16 +520,13 @@ class NlpSolverShim:
         self._s = batched
         # behind the reference's BoundMPC every x0 is the reference's own (its cold start or a shifted plan, BoundMPC.py:316-375): taken as given, like Ipopt does
         # (a setting of the caller's handle, kept while the shim lives: close() puts the previous value back)
-        self._rollout_was = batched.get_start_rollout() if hasattr(batched._lib, "bmpc_get_start_rollout") else None
-        if self._rollout_was is not None:
-            batched.set_start_rollout(False)
+        self._rollout_was = _take_start_rollout_off(batched)
         self._stats = {"iter_count": 0, "success": False, "return_status": "not run"}
         self._lbx, self._ubx, self._lbg, self._ubg = batched.bounds()
 
     def close(self):
         """Gives the batched solver back as it was found (the start-rollout setting); the handle itself stays the caller's."""
-        if getattr(self, "_rollout_was", None) is not None and getattr(self._s, "_h", None):
-            self._s.set_start_rollout(self._rollout_was)
+        _give_start_rollout_back(self._s, getattr(self, "_rollout_was", None))
         self._rollout_was = None
 
     def generate_dependencies(self, *a, **k):   # BoundMPC.py:155-157 -- nothing to generate
@@ -555,29 +557,28 @@ class NlpSolverShim:
         """KKT certificate (BatchedOCPSolver.certify_host: dict of the fields KKT_FIELDS, floats) of a CasADi-style result -- a dict with 'x' and,
         where known, 'lam_g' / 'lam_x' (columns, flat vectors or a scalar, like the multiplier arguments of a call) -- for the parameter vector of the
         LAST call.  Default: the last solution.  Any solver's answer to the same problem can be scored: Ipopt's, a candidate warm start."""
-        if getattr(self, "_last", None) is None:
-            raise RuntimeError("certificate() needs a previous solver(...) call: it certifies a point for that call's p")
-        p_, last = self._last
-        sol = last if sol is None else sol
-        x = np.asarray(sol["x"], dtype=float).ravel()[None, :]
-        lg, lx = self._multiplier(sol.get("lam_g"), self._s.n_g, "lam_g"), self._multiplier(sol.get("lam_x"), self._s.n_w, "lam_x")
+        p_, x, lg, lx = self._point_of_last_call(sol, "certificate() needs a previous solver(...) call: it certifies a point for that call's p")
         c = self._s.certify_host(p_, x, lam_g=lg, lam_x=lx)
         return {k: float(c[k][0]) for k in KKT_FIELDS}
 
     def sensitivity(self, dp, sol=None):
         """Tangent of the solution along dp (flat [n_p] or [D][n_p]) for the parameter vector of the LAST call, at a CasADi-style result `sol`
         (default: the last solution), like certificate().  Returns {'dx': [n_w] or [D][n_w], 'rec': ...} (BatchedOCPSolver.sensitivity_host)."""
-        if getattr(self, "_last", None) is None:
-            raise RuntimeError("sensitivity() needs a previous solver(...) call: it differentiates that call's solution with respect to its p")
-        p_, last = self._last
-        sol = last if sol is None else sol
-        x = np.asarray(sol["x"], dtype=float).ravel()[None, :]
-        lg, lx = self._multiplier(sol.get("lam_g"), self._s.n_g, "lam_g"), self._multiplier(sol.get("lam_x"), self._s.n_w, "lam_x")
+        p_, x, lg, lx = self._point_of_last_call(sol, "sensitivity() needs a previous solver(...) call: it differentiates that call's solution with respect to its p")
         dp = np.asarray(dp, dtype=float)
         one = dp.ndim == 1 or (dp.ndim == 2 and dp.shape[1] == 1)
         d3 = dp.reshape(1, 1, -1) if one else dp.reshape(1, dp.shape[0], -1)
         o = self._s.sensitivity_host(p_, x, d3, lam_g=lg, lam_x=lx)
         return {k: (v[0, 0] if one else v[0]) for k, v in o.items()}
+
+    def _point_of_last_call(self, sol, complaint):
+        """p of the last call and the point `sol` (None: the last solution) as [1][n] rows: p, x, lam_g, lam_x (None: no multipliers of that kind)"""
+        if getattr(self, "_last", None) is None:
+            raise RuntimeError(complaint)
+        p_, last = self._last
+        sol = last if sol is None else sol
+        x = np.asarray(sol["x"], dtype=float).ravel()[None, :]
+        return p_, x, self._multiplier(sol.get("lam_g"), self._s.n_g, "lam_g"), self._multiplier(sol.get("lam_x"), self._s.n_w, "lam_x")
 
     @staticmethod
     def _multiplier(v, n, name):

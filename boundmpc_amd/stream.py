@@ -15,6 +15,7 @@ import numpy as np
 from scipy.spatial.transform import Rotation as R
 
 from . import _lib
+from .solver import _give_start_rollout_back, _ptr, _stream_ptr, _take_start_rollout_off
 
 # csrc/bmpc_stream.inl
 PT = dict(P=0, IW=3, DPN=6, DR=9, RRV=12, PLO=15, PUP=17, RLO=19, RUP=21, BP1=23, BP2=26, BR1=29, BR2=32, CUM=35, EPMIN=36, ERMIN=37,
@@ -193,9 +194,7 @@ class StreamBatch:
         # the warm starts of a stream are the reference's own (stream_pack: its cold start or the shifted plan, BoundMPC.py:316-375): taken as given, also
         # by the stateless ticks (cold duals); on closed loops the rollout of a start that is off its dynamics costs plans (oracle/bmpc_oracle.c solve_one)
         # (a setting of the caller's handle: the previous value comes back in close(); an A/B library from before the option has no such entry point)
-        self._rollout_was = solver.get_start_rollout() if hasattr(solver._lib, "bmpc_get_start_rollout") else None
-        if self._rollout_was is not None:
-            solver.set_start_rollout(False)
+        self._rollout_was = _take_start_rollout_off(solver)
         lens = [ctypes.c_int() for _ in range(4)]
         _lib.check(solver._lib.bmpc_stream_lengths(solver._h, *[ctypes.byref(v) for v in lens]), "bmpc_stream_lengths")
         self.pt_len, self.ss_len, self.rb_len, self.tr_len = (v.value for v in lens)
@@ -238,21 +237,27 @@ class StreamBatch:
         self.robot.copy_(torch.as_tensor(np.ascontiguousarray(rec), dtype=torch.float64))
 
     def _stream(self, stream):
-        import torch
-        return ctypes.c_void_p((stream if stream is not None else torch.cuda.current_stream(self.path.device)).cuda_stream)
+        return _stream_ptr(stream, self.path.device)
+
+    @staticmethod
+    def _flags(simulate, accept_capped):
+        return int(bool(simulate)) | (2 if accept_capped else 0)
+
+    def _tick_args(self, max_iter, warm_dual, simulate, accept_capped):
+        """the arguments bmpc_stream_tick and bmpc_stream_graph_create share: everything between the handle and the stream / the graph"""
+        return (self.B, _ptr(self.path), self.entries, _ptr(self.state), _ptr(self.robot), _ptr(self.p), _ptr(self.x0), _ptr(self.dual) if warm_dual else None,
+                int(max_iter), _ptr(self.x), _ptr(self.g), _ptr(self.iters), _ptr(self.status), _ptr(self.kkt), _ptr(self.traj), self._flags(simulate, accept_capped))
 
     def pack(self, warm_dual=False, stream=None, continue_rejected=False):
         """continue_rejected (real-time mode): the warm start continues from the solver's last iterate when the acceptance rule rejected
         it (bmpc_stream_pack_rt with xlast = x), as the fused tick does; False = restart from the last accepted plan (the reference)."""
-        dp = lambda t: ctypes.c_void_p(t.data_ptr())
-        _lib.check(self.solver._lib.bmpc_stream_pack_rt(self.solver._h, self.B, dp(self.path), self.entries, dp(self.state), dp(self.robot), dp(self.p),
-                                                        dp(self.x0), dp(self.dual) if warm_dual else None, dp(self.x) if continue_rejected else None,
+        _lib.check(self.solver._lib.bmpc_stream_pack_rt(self.solver._h, self.B, _ptr(self.path), self.entries, _ptr(self.state), _ptr(self.robot), _ptr(self.p),
+                                                        _ptr(self.x0), _ptr(self.dual) if warm_dual else None, _ptr(self.x) if continue_rejected else None,
                                                         self._stream(stream)), "bmpc_stream_pack_rt")
 
     def post(self, simulate=True, stream=None, accept_capped=False):
-        dp = lambda t: ctypes.c_void_p(t.data_ptr())
-        _lib.check(self.solver._lib.bmpc_stream_post(self.solver._h, self.B, dp(self.path), self.entries, dp(self.state), dp(self.robot), dp(self.x),
-                                                     dp(self.g), dp(self.status), dp(self.traj), int(bool(simulate)) | (2 if accept_capped else 0),
+        _lib.check(self.solver._lib.bmpc_stream_post(self.solver._h, self.B, _ptr(self.path), self.entries, _ptr(self.state), _ptr(self.robot), _ptr(self.x),
+                                                     _ptr(self.g), _ptr(self.status), _ptr(self.traj), self._flags(simulate, accept_capped),
                                                      self._stream(stream)), "bmpc_stream_post")
 
     def tick(self, max_iter=0, warm_dual=False, simulate=True, stream=None, accept_capped=False, fused=True):
@@ -263,11 +268,8 @@ class StreamBatch:
         if max_iter and not warm_dual:
             raise ValueError("an iteration cap needs the dual state (warm_dual=True): the multipliers must be shifted with the plan")
         if fused:
-            dp = lambda t: ctypes.c_void_p(t.data_ptr())
-            _lib.check(self.solver._lib.bmpc_stream_tick(
-                self.solver._h, self.B, dp(self.path), self.entries, dp(self.state), dp(self.robot), dp(self.p), dp(self.x0),
-                dp(self.dual) if warm_dual else None, int(max_iter), dp(self.x), dp(self.g), dp(self.iters), dp(self.status), dp(self.kkt),
-                dp(self.traj), int(bool(simulate)) | (2 if accept_capped else 0), self._stream(stream)), "bmpc_stream_tick")
+            _lib.check(self.solver._lib.bmpc_stream_tick(self.solver._h, *self._tick_args(max_iter, warm_dual, simulate, accept_capped), self._stream(stream)),
+                       "bmpc_stream_tick")
             return
         self.pack(warm_dual, stream, continue_rejected=accept_capped)      # the same continuation rule as the fused launch
         out = dict(x=self.x, g=self.g, iters=self.iters, status=self.status, kkt=self.kkt)
@@ -306,12 +308,9 @@ class StreamBatch:
         if key not in self._graphs:
             if max_iter and not warm_dual:
                 raise ValueError("an iteration cap needs the dual state (warm_dual=True)")
-            dp = lambda t: ctypes.c_void_p(t.data_ptr())
             g = ctypes.c_void_p()
-            _lib.check(self.solver._lib.bmpc_stream_graph_create(
-                self.solver._h, self.B, dp(self.path), self.entries, dp(self.state), dp(self.robot), dp(self.p), dp(self.x0),
-                dp(self.dual) if warm_dual else None, int(max_iter), dp(self.x), dp(self.g), dp(self.iters), dp(self.status), dp(self.kkt),
-                dp(self.traj), int(bool(simulate)) | (2 if accept_capped else 0), ctypes.byref(g)), "bmpc_stream_graph_create")
+            _lib.check(self.solver._lib.bmpc_stream_graph_create(self.solver._h, *self._tick_args(max_iter, warm_dual, simulate, accept_capped), ctypes.byref(g)),
+                       "bmpc_stream_graph_create")
             self._graphs[key] = g
         # (a replay requested on the legacy null stream is run by the library on a stream of the handle, bracketed by events:
         # bmpc_graph_launch)
@@ -321,9 +320,8 @@ class StreamBatch:
         for g in self._graphs.values():
             self.solver._lib.bmpc_graph_destroy(g)
         self._graphs = {}
-        if getattr(self, "_rollout_was", None) is not None and getattr(self.solver, "_h", None):      # the handle's start-rollout setting as it was found
-            self.solver.set_start_rollout(self._rollout_was)
-            self._rollout_was = None
+        _give_start_rollout_back(self.solver, getattr(self, "_rollout_was", None))      # the handle's start-rollout setting as it was found
+        self._rollout_was = None
 
     def __del__(self):
         try:

@@ -141,6 +141,10 @@ extern "C" void bmpc_emu_scr_offsets(int N, int *out) {
     for (unsigned i = 0; i < sizeof(v) / sizeof(int); i++) out[i] = v[i];
 }
 extern "C" void bmpc_emu_sincos(int n, const double *x, double *s, double *c) { for (int i = 0; i < n; i++) bmpc::bmpc_sincos(x[i], s + i, c + i); }
+// the library's horizon rule (csrc/bmpc_args.h): the option record of a handle of horizon N, its size, the longest short horizon
+extern "C" void bmpc_emu_opts_for(int N, bmpc::Opts *o) { bmpc_opts_for(N, *o); }
+extern "C" int bmpc_emu_opts_size() { return (int)sizeof(bmpc::Opts); }
+extern "C" int bmpc_emu_short_nmax() { return BMPC_SHORT_NMAX; }
 extern "C" int bmpc_emu_lds_doubles() { return bmpc::L_SIZE; }
 extern "C" int bmpc_emu_scratch_doubles(int N) { return bmpc::make_scr(N).size; }
 #endif

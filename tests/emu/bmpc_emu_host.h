@@ -52,7 +52,7 @@
 namespace BMPC_NAMESPACE {
 // the shape test of every entry, and the launch functions' choice of the instantiation with the iterate in LDS
 inline bool emu_shape_ok(int N, int S) { return S <= SMAX && S >= 2 && N >= 1 && N <= NMAX; }
-inline bool emu_zlds(int N, int S) { return N <= 11 && S <= SMAX_ZLDS; }
+inline bool emu_zlds(int N, int S) { return N <= BMPC_SHORT_NMAX && S <= SMAX_ZLDS; }
 // the argument head every kernel argument record starts with
 inline KArgsT<Opts> emu_args(int N, int S, int B, double h, const Opts &o) { KArgsT<Opts> a{}; a.N = N; a.S = S; a.B = B; a.h = h; a.o = o; return a; }
 // The wave of one emulated workgroup from the argument head of `a` (the kernels' initialiser), on `lds` and the workspace `scr`; lanes in

@@ -25,11 +25,11 @@ for (N, tight, B, seed, label) in ((10, False, 64, 0, "configs[1]/[2]: N=10"), (
     o = c_oracle.count_flops(P, X, N, 4, 0.1)
     # mask-aware tally (tests/emu/bmpc_emu_useful.cpp): of the executed operations, those whose result reaches a store (not the dummy word, not a clamped
     # duplicate of the same phase) or a decision; data-flow graph of whole solves of the first problems (N = 30: the first 12 iterations of one solve: memory)
-    us = [emu.count_useful(P[i], X[i], N, 4, 0.1, opts=None if N <= 11 else emu.default_opts(mu_init=3.0, slack_push=0.1, stall_window=20, restoration=2, max_iter=12))
-          for i in range(4 if N <= 11 else 1)]
+    short = N <= emu.lib().bmpc_emu_short_nmax()
+    us = [emu.count_useful(P[i], X[i], N, 4, 0.1, opts=None if short else emu.opts_for(N, max_iter=12, retry_cap=0)) for i in range(4 if short else 1)]
     ue, uu, ui = sum(u["executed"] for u in us), sum(u["useful"] for u in us), sum(max(u["iterations"], 1) for u in us)
     slots = sorted(set(s_ for u in us for s_ in u["per_phase"]))
-    useful = {"sample": f"first {len(us)} problem(s) of the same batch" + ("" if N <= 11 else ", first 12 iterations"),
+    useful = {"sample": f"first {len(us)} problem(s) of the same batch" + ("" if short else ", first 12 iterations"),
               "executed_flops_per_iteration": ue / ui, "useful_flops_per_iteration": uu / ui, "useful_fraction": uu / ue,
               "stores": sum(u["stores"] for u in us), "stores_to_the_dummy_word": sum(u["dummy_stores"] for u in us), "duplicate_stores_within_a_phase": sum(u["duplicate_stores"] for u in us),
               "by_phase_slot": {str(s_): [round(sum(u["per_phase"].get(s_, (0, 0))[0] for u in us) / ui), round(sum(u["per_phase"].get(s_, (0, 0))[1] for u in us) / ui)] for s_ in slots}}

@@ -31,8 +31,10 @@ def _build(lib_name, source, flags=(), deps=()):
 
 
 def lib():
-    """the one-wave emulator: solves, the stream functions and the debug entries"""
-    return _build("libbmpc_emu.so", "bmpc_emu.cpp", ("-fopenmp", "-DBMPC_NW=1"), ("bmpc_stream.inl",))
+    """the one-wave emulator: solves, the stream functions, the library's option rule and the debug entries"""
+    L = _build("libbmpc_emu.so", "bmpc_emu.cpp", ("-fopenmp", "-DBMPC_NW=1"), ("bmpc_stream.inl",))
+    assert L.bmpc_emu_opts_size() == ctypes.sizeof(Opts), "tests/emu/emu.py Opts is not the wave program's option record"
+    return L
 
 
 def build():
@@ -45,22 +47,24 @@ def service_lib(kind):
     return _build(f"libbmpc_emu_{kind}.so", f"bmpc_emu_{kind}.cpp", (), ("bmpc_dual.inl", f"bmpc_{kind}.inl"))
 
 
-def default_opts(**kw):
-    o = Opts(1e-8, 500, 0.1, 0.1, 1e-2, 1, 0, 1e-2, 40, 0.0, 1, 6, 40, 1, 0, 0)
+def opts_for(N, opts=None, **kw):
+    """`opts`, or the defaults of a handle for this horizon -- the library's own rule (csrc/bmpc_args.h bmpc_opts_for) -- with the fields of `kw` replaced"""
+    if opts is not None:
+        return opts
+    o = Opts()
+    lib().bmpc_emu_opts_for(ctypes.c_int(N), ctypes.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
     return o
 
 
+def default_opts(**kw):
+    """the record of the short horizons"""
+    return opts_for(lib().bmpc_emu_short_nmax(), **kw)
+
+
 def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
-
-
-def opts_for(N, opts=None):
-    """`opts`, or the defaults of a handle for this horizon (long horizons: higher barrier start, restoration on breakdown only, second attempt)"""
-    if opts is not None:
-        return opts
-    return default_opts(mu_init=3.0, slack_push=0.1, stall_window=20, restoration=2, retry_cap=100) if N > 11 else default_opts()
 
 
 def _solve(entry, p, x0, N, S, h, opts, lane_order, wave_order, nthreads, state):

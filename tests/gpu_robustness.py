@@ -15,11 +15,11 @@ if not CPU:
 
 
 def opts(N, **kw):
-    return c_oracle.default_opts(max_iter=500, **kw) if N <= 11 else c_oracle.default_opts(max_iter=500, mu_init=3.0, slack_push=0.1, stall_window=20, **kw)
+    return c_oracle.opts_for(N, max_iter=500, retry_cap=0, **kw)      # (this battery has always run the oracle without the second attempt)
 
 
 def case(name, P, X, N=10):
-    rm = 1 if N <= 11 else 2
+    rm = c_oracle.opts_for(N).restoration
     o = c_oracle.solve(P, X, N, 4, 0.1, opts=opts(N, restoration=rm), nthreads=16)
     o1 = c_oracle.solve(P, X, N, 4, 0.1, opts=opts(N, restoration=rm, start_rollout=0), nthreads=16)
     o0 = c_oracle.solve(P, X, N, 4, 0.1, opts=opts(N, restoration=0, start_rollout=0), nthreads=16)

@@ -69,3 +69,24 @@ def test_team_and_pair_emulators_make_the_second_attempt(nw, mode):
     assert np.array_equal(e0["status"], ref0["status"]) and (e0["status"] == 2).sum() == 11 and np.abs(e0["iters"] - ref0["iters"]).max() <= 2
     ok = ref["status"] == 0
     assert eps.rms_q(e["x"][ok], ref["x"][ok], N).max() < 1e-5
+
+
+# what the library's option record (csrc/bmpc_wave.inl Opts, read through the emulator) and the oracle's (oracle/bmpc_oracle.c) both have
+SHARED_OPTION_FIELDS = ("tol", "max_iter", "mu_init", "mu_min_fac", "slack_push", "exact_hessian", "mu_warm", "stall_window", "restoration", "resto_short",
+                        "resto_cap", "start_rollout", "hold_mu", "retry_cap")
+
+
+@pytest.mark.parametrize("N", [1, 11, 12, 40])
+def test_the_library_and_the_oracle_state_the_same_horizon_rule(N):
+    """The defaults of a handle of horizon N exist once per implementation -- bmpc_opts_for (csrc/bmpc_args.h; what bmpc_create, bmpc_default_options_for
+    and the emulators run) and c_oracle.opts_for, an independent restatement -- and nothing else holds them together: on both sides of the cliff at
+    N = 11 / 12 and at the ends of the range they agree on every field both records have.  Literals on both sides: equality, no tolerance."""
+    from oracle import c_oracle
+    lib, ora = emu.opts_for(N), c_oracle.opts_for(N)
+    assert {f for f, _ in ora._fields_} - {"verbose"} == set(SHARED_OPTION_FIELDS) <= {f for f, _ in lib._fields_}
+    for f in SHARED_OPTION_FIELDS:
+        assert getattr(lib, f) == getattr(ora, f), (N, f, getattr(lib, f), getattr(ora, f))
+    if N == 11:
+        d = emu.default_opts()
+        for f, _ in emu.Opts._fields_:
+            assert getattr(d, f) == getattr(lib, f), f

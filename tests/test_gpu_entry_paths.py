@@ -262,3 +262,57 @@ def test_null_status_and_iters_with_the_restoration_phase_on_while_the_stand_ins
         assert np.array_equal(o["status"].cpu().numpy(), r["status"][idx])
     finally:
         s.close(); ref.close()
+
+
+def _settings_of(lib, h, N):
+    """everything the ABI has a getter for, as a dict keyed like the option record (plus queue_order)"""
+    from boundmpc_amd import _lib
+    o, e, s_, c = _lib.Options(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+    assert lib.bmpc_default_options_for(N, ctypes.byref(o)) == 0 and lib.bmpc_get_restoration(h, ctypes.byref(e), ctypes.byref(s_), ctypes.byref(c)) == 0
+    got = {f: getattr(o, f) for f, _ in _lib.Options._fields_}
+    got.update(restoration=e.value, resto_short=s_.value, resto_cap=c.value, retry_cap=lib.bmpc_get_second_attempt(h),
+               start_rollout=lib.bmpc_get_start_rollout(h), queue_order=lib.bmpc_get_queue_order(h))
+    return got
+
+
+@pytest.mark.parametrize("N,queue_order", [(11, 0), (12, 1)])
+def test_a_handle_created_without_options_runs_the_horizon_rule(N, queue_order):
+    """bmpc_create(opts = NULL) on both sides of the horizon cliff: what the getters of the ABI give back is the record of bmpc_opts_for
+    (csrc/bmpc_args.h), read through the emulator, plus the queue order of that horizon.  Handle creation only, no solve."""
+    from boundmpc_amd import _lib
+    from tests.emu import emu
+    lib, h = _lib.load(), ctypes.c_void_p()
+    assert lib.bmpc_create(N, 4, 0.1, None, ctypes.byref(h)) == 0
+    try:
+        got, want = _settings_of(lib, h, N), emu.opts_for(N)
+        assert got.pop("queue_order") == queue_order
+        assert got == {f: getattr(want, f) for f in got}, (got, {f: getattr(want, f) for f in got})
+    finally:
+        lib.bmpc_destroy(h)
+
+
+def test_explicit_options_replace_the_public_fields_only():
+    """bmpc_create with a caller's bmpc_options at N = 12: what the public struct does not carry keeps the long horizon's defaults (restoration
+    after a breakdown only, second attempt of 100 iterations, queue order on), and the public fields are the caller's.  The ABI has no getter for
+    a handle's public fields (bmpc_default_options_for is a function of N alone), so one of them is read off one problem: with max_iter = 2
+    the solve of a cold start ends after exactly 2 iterations as status 1."""
+    import torch
+    from boundmpc_amd import _lib, workload
+    from tests.emu import emu
+    lib, h = _lib.load(), ctypes.c_void_p()
+    mine = _lib.Options(1e-8, 2, 0.5, 0.1, 0.05, 1, 1, 1e-2, 12, 0.0)
+    assert lib.bmpc_create(12, 4, 0.1, ctypes.byref(mine), ctypes.byref(h)) == 0
+    try:
+        got, rule = _settings_of(lib, h, 12), emu.opts_for(12)
+        for f in ("restoration", "resto_short", "resto_cap", "retry_cap", "start_rollout"):
+            assert got[f] == getattr(rule, f), f
+        assert got["restoration"] == 2 and got["resto_cap"] == 40 and got["retry_cap"] == 100 and got["queue_order"] == 1
+        P, X, _ = workload.make_batch(1, seed=0, N=12, workers=1)
+        p, x0 = torch.tensor(P, device="cuda"), torch.tensor(X, device="cuda")
+        x, it, st = torch.empty_like(x0), torch.zeros(1, dtype=torch.int32, device="cuda"), torch.zeros(1, dtype=torch.int32, device="cuda")
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+        assert lib.bmpc_solve_batch(h, 1, ptr(p), ptr(x0), ptr(x), None, None, None, None, ptr(it), ptr(st), None, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+        torch.cuda.synchronize()
+        assert int(it[0]) == 2 and int(st[0]) == 1, (int(it[0]), int(st[0]))
+    finally:
+        lib.bmpc_destroy(h)
