@@ -1,12 +1,17 @@
 """Build the HIP extension in-tree: boundmpc_amd/csrc/libboundmpc_hip.so (gfx950 only)."""
+import collections
+import glob
+import hashlib
 import os
 import re
+import shlex
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libboundmpc_hip.so")
+ISA_DIR = os.path.join(HERE, "..", "build", "isa")      # <unit>.o, <unit>_gfx950.s (the device listing of the same compilation), <unit>.d
 SOURCES = [os.path.join(CSRC, "bmpc_hip.hip"), os.path.join(CSRC, "bmpc_wave.inl"), os.path.join(CSRC, "bmpc_stream.inl"),
            os.path.join(HERE, "..", "include", "boundmpc_hip.h"), os.path.join(CSRC, "bmpc_team.hip"), os.path.join(CSRC, "bmpc_gpu_common.h"),
            os.path.join(CSRC, "bmpc_resto.hip"), os.path.join(CSRC, "bmpc_tick.hip"), os.path.join(CSRC, "bmpc_pair.hip"),
@@ -43,7 +48,6 @@ def source_hash():
     library (bmpc_build_hash(), and as the marker BMPC_BUILD_HASH=... in its bytes): build() rebuilds when the in-tree library carries another
     hash (not by file times), _lib.load() refuses a library whose hash is not the tree's, and bench.py ties the counter / flop files in
     profiles/ to it."""
-    import hashlib
     h = hashlib.sha256()
     for p in sorted(SOURCES, key=os.path.basename):
         h.update(os.path.basename(p).encode()); h.update(b"\0")
@@ -66,6 +70,48 @@ def library_hash(path=None):
     return m.group(1).decode() if m else None
 
 
+Ins = collections.namedtuple("Ins", "line text note")                      # text: comment dropped, whitespace collapsed; note: the comment
+Block = collections.namedtuple("Block", "label line insns")                # label: "entry", ".LBB0_7" or "bb.7" (a fall-through block)
+Function = collections.namedtuple("Function", "name line blocks resources")
+
+
+def read_listing(asm_path):
+    """The functions of a device listing, each with its basic blocks and its resource record: the integer fields of its `amdhsa.kernels`
+    metadata entry (vgpr_count, sgpr_spill_count, private_segment_fixed_size, ...) and of its `; Kernel info:` trailer (NumVgprs, NumAgprs,
+    Occupancy, ...); empty for a function that is no kernel.  A function runs from its `_Z...:` label to `.Lfunc_end`; `.LBB...:` labels and
+    `; %bb.N:` comments open blocks (the listing a full compile saves names the IR block behind them: `.LBB0_7:  ; %Flow5015`); other
+    labels, directives and comment lines are no instructions."""
+    with open(asm_path) as f:
+        listing = f.read()
+    funcs, inside = [], False
+    for n, s in enumerate(listing.split("\n"), 1):
+        s = s.strip()
+        m = re.match(r"(_Z\w+):|(\.LBB\w+):|; %bb\.(\d+):", s)
+        if m and m.group(1):
+            funcs.append(Function(m.group(1), n, [Block("entry", n, [])], {}))
+            inside = True
+        elif s.startswith(".Lfunc_end"):
+            inside = False
+        elif not inside:
+            m = re.match(r"; (\w+): (\d+)", s)
+            if m and funcs:
+                funcs[-1].resources[m.group(1)] = int(m.group(2))
+        elif m:
+            funcs[-1].blocks.append(Block(m.group(2) or "bb." + m.group(3), n, []))
+        else:
+            text, _, note = s.partition(";")
+            text = " ".join(text.split())
+            if text and text[0] != "." and text[-1] != ":":
+                funcs[-1].blocks[-1].insns.append(Ins(n, text, note.strip()))
+    by_name = {fn.name: fn for fn in funcs}
+    # the metadata (YAML): one `  - .key: value` entry per kernel, its own keys at indent 4, those of its arguments deeper
+    for entry in re.split(r"\n  - (?=\.)", listing.partition("\namdhsa.kernels:")[2].partition("\namdhsa.target:")[0])[1:]:
+        fields = dict(re.findall(r"^(?:    )?\.(\w+): +(\S+)$", entry, re.M))
+        if fields.get("name") in by_name:
+            by_name[fields["name"]].resources.update((k, int(v)) for k, v in fields.items() if v.isdigit())
+    return funcs
+
+
 def lint_isa(asm_path):
     """Static check of the compiled ISA for one register-allocator defect of this toolchain (ROCm 7.2 LLVM) that silently
     corrupts results: a live-range split / spill copy placed at the top of a control-flow join block BEFORE the instruction
@@ -74,31 +120,16 @@ def lint_isa(asm_path):
     the mask of lanes 21..31; DESIGN.md 4, lesson 10): N=30 solves converged to other local minima, nothing crashed.
     Signature: a basic block whose instructions ahead of its first exec restore are only scalar ops and register copies, with
     at least one vector copy among them.  Returns the list of offending (function, block, line, copies)."""
-    hits, func, name, line0, block = [], None, None, 0, []
-
-    def check():
-        for j, s in enumerate(block):
-            if s.startswith("s_or_b64 exec, exec, s["):
-                head = block[:j]
-                copies = [t for t in head if _COPY.match(t)]
-                if copies and all(_COPY.match(t) or _HARMLESS.match(t) for t in head):
-                    hits.append((func, name, line0, copies))
-                return
-
-    with open(asm_path) as f:
-        for n, raw in enumerate(f, 1):
-            s = raw.strip()
-            m = re.match(r"^(_Z\w+):", s)
-            if m:
-                check(); func, name, line0, block = m.group(1), "entry", n, []
-                continue
-            m = re.match(r"^(\.LBB\w+):|^; %bb\.(\d+):", s)
-            if m:
-                check(); name, line0, block = (m.group(1) or "bb." + m.group(2)), n, []
-                continue
-            if s and s[0] not in ";.":
-                block.append(s)
-    check()
+    hits = []
+    for fn in read_listing(asm_path):
+        for b in fn.blocks:
+            texts = [i.text for i in b.insns]
+            for j, s in enumerate(texts):
+                if s.startswith("s_or_b64 exec, exec, s["):
+                    copies = [t for t in texts[:j] if _COPY.match(t)]
+                    if copies and all(_COPY.match(t) or _HARMLESS.match(t) for t in texts[:j]):
+                        hits.append((fn.name, b.label, b.line, copies))
+                    break
     return hits
 
 
@@ -138,9 +169,13 @@ def lint_isa_masked_loads(asm_path, window=400):
     Returns [(function, line of the saveexec, registers, defined_earlier)]: `defined_earlier` says whether the function writes the
     register anywhere before (in listing order) -- then the register may legitimately hold the default from further back (a long-lived
     value) and the hit is only a candidate; with no earlier write at all the inactive lanes certainly read garbage."""
-    hits, func, lines = [], None, []
-
-    def flush():
+    hits = []
+    for fn in read_listing(asm_path):
+        lines = []      # of the function: (line, text, False) per instruction, (line, "", True) where a label opens a block
+        for b in fn.blocks:
+            if b.label.startswith(".LBB"):
+                lines.append((b.line, "", True))
+            lines += [(i.line, i.text, False) for i in b.insns]
         n = len(lines)
         seen = set()       # registers written so far in listing order
         written_before = []
@@ -188,69 +223,90 @@ def lint_isa_masked_loads(asm_path, window=400):
                 live -= d
                 k += 1
             if used:
-                hits.append((func, ln, sorted(used), bool(used & written_before[i]) and used <= written_before[i]))
-
-    with open(asm_path) as f:
-        for n, raw in enumerate(f, 1):
-            s = raw.strip()
-            m = re.match(r"^(_Z\w+):", s)
-            if m:
-                flush(); func, lines = m.group(1), []
-                continue
-            if re.match(r"^(\.LBB\w+):", s):
-                lines.append((n, "", True))
-                continue
-            if s and s[0] not in ";.":
-                lines.append((n, s.split(";")[0].strip(), False))
-    flush()
+                hits.append((fn.name, ln, sorted(used), bool(used & written_before[i]) and used <= written_before[i]))
     return hits
 
 
-def _lint_unit(src, asm, verbose):
-    # same flags, device ISA only; a hit fails the build (the compiled code would compute wrong numbers for some lanes)
-    subprocess.check_call([hipcc()] + unit_flags(src) + ["-S", "--cuda-device-only", "-o", asm, src], cwd=CSRC, stderr=subprocess.DEVNULL)
-    bad = lint_isa(asm)
-    if bad:
-        raise RuntimeError("ISA lint: register copies ahead of an exec-mask restore (compiler defect, results would be wrong): %r" % (bad,))
-    # masked loads read after their join: fatal in EVERY kernel of the library (round 4: the last source pattern that produced a candidate
-    # -- `cond ? plan[...] : value` in the stream post-processing -- loads unconditionally behind an opaque barrier now, so the listing of
-    # the shipped text has no hit at all and a new one is a change worth stopping for)
-    ml = lint_isa_masked_loads(asm)
-    if ml:
-        raise RuntimeError("ISA lint: load under an exec mask whose result is read after the join (results may be wrong for the masked-off "
-                           "lanes; `defined_earlier` = the register has an earlier definition in listing order): %r" % (ml,))
-
-
-def _compile_unit(args):
-    src, obj, asm, verbose, lint = args
-    if lint:
-        _lint_unit(src, asm, verbose)
+def compile_unit(src, out_dir, defines=(), lint=True, verbose=False):
+    """ONE compiler run for a translation unit: leaves in out_dir the object <unit>.o (returned), the device listing of that same compilation
+    <unit>_gfx950.s (`-save-temps=obj`: the object's device code is assembled from exactly this text) and the dependency file <unit>.d.
+    The lints read that listing; a hit fails the build (the compiled code would compute wrong numbers for some lanes)."""
+    stem = os.path.splitext(os.path.basename(src))[0]
+    obj, asm, dep = (os.path.join(out_dir, stem + e) for e in (".o", "_gfx950.s", ".d"))
+    os.makedirs(out_dir, exist_ok=True)
     # -amdgpu-sched-strategy=iterative-ilp: the solver runs at one wave per SIMD, so the scheduler should chase instruction-level
     # parallelism (loads hoisted ahead of their uses), not occupancy; measured 12.7 -> 10.8 ms at B=1024 (profiles/, DESIGN.md 4)
-    cmd = [hipcc()] + unit_flags(src) + ["-DBMPC_BUILD_HASH_STR=\"%s\"" % source_hash(), "-fPIC", "-c", "-o", obj, src]
+    cmd = [hipcc()] + unit_flags(src) + ["-DBMPC_BUILD_HASH_STR=\"%s\"" % source_hash()] + list(defines) + \
+          ["-fPIC", "-save-temps=obj", "-MD", "-MF", dep, "-c", "-o", obj, src]
     if verbose:
-        cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
         print(" ".join(cmd))
     subprocess.check_call(cmd, cwd=CSRC)
+    os.replace(os.path.join(out_dir, stem + "-hip-amdgcn-amd-amdhsa-gfx950.s"), asm)
+    for pat in (stem + "-hip-amdgcn-*", stem + "-host-*", os.path.basename(src) + "-hip-*"):      # the other temporaries (.hipi, .bc, host .s, ...)
+        for tmp in glob.glob(os.path.join(out_dir, pat)):
+            os.remove(tmp)
+    if lint:
+        bad = lint_isa(asm)
+        if bad:
+            raise RuntimeError("ISA lint: register copies ahead of an exec-mask restore (compiler defect, results would be wrong): %r" % (bad,))
+        # masked loads read after their join: fatal in EVERY kernel of the library (round 4: the last source pattern that produced a candidate
+        # -- `cond ? plan[...] : value` in the stream post-processing -- loads unconditionally behind an opaque barrier now, so the listing of
+        # the shipped text has no hit at all and a new one is a change worth stopping for)
+        ml = lint_isa_masked_loads(asm)
+        if ml:
+            raise RuntimeError("ISA lint: load under an exec mask whose result is read after the join (results may be wrong for the masked-off "
+                               "lanes; `defined_earlier` = the register has an earlier definition in listing order): %r" % (ml,))
     return obj
 
 
-def build(force=False, verbose=False, lint=True):
-    if not force and library_hash() == source_hash():      # the library in the tree was built from exactly this text with these flags
-        return LIB
+def sources_mismatch(deps, sources=None):
+    """SOURCES against what the compiler read: (missing, superfluous) = the files of this tree among `deps` (paths as in the dependency
+    files, relative ones taken from csrc/) that SOURCES lacks -- a change to one would not change source_hash(), and a stale library would
+    load -- and the files of SOURCES that no unit read."""
+    root = os.path.realpath(os.path.join(HERE, ".."))
+    read = {os.path.realpath(os.path.join(CSRC, d)) for d in deps}
+    read = {d for d in read if d.startswith(root + os.sep)}
+    listed = {os.path.realpath(p) for p in (SOURCES if sources is None else sources)}
+    return sorted(os.path.relpath(d, root) for d in read - listed), sorted(os.path.relpath(d, root) for d in listed - read)
+
+
+def build(force=False, verbose=False, lint=True, lib=LIB, out_dir=ISA_DIR, defines=()):
+    """The units side by side, one compile_unit() each, the SOURCES check on their dependency files, and the link (lib, out_dir, defines: the
+    diagnostic builds of tests/)."""
+    if not force and library_hash(lib) == source_hash():      # the library in the tree was built from exactly this text with these flags
+        return lib
     from concurrent.futures import ThreadPoolExecutor
-    out_dir = os.path.join(HERE, "..", "build", "isa")
-    os.makedirs(out_dir, exist_ok=True)
-    jobs = []
-    for src in UNITS:
-        stem = os.path.splitext(os.path.basename(src))[0]
-        jobs.append((src, os.path.join(out_dir, stem + ".o"), os.path.join(out_dir, stem + "_gfx950.s"), verbose, lint))
-    with ThreadPoolExecutor(len(jobs)) as ex:      # the two units compile side by side (each: ISA for the lints, then the object)
-        objs = list(ex.map(_compile_unit, jobs))
-    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-o", LIB] + objs, cwd=CSRC)
-    return LIB
+    with ThreadPoolExecutor(len(UNITS)) as ex:
+        objs = list(ex.map(lambda src: compile_unit(src, out_dir, defines, lint, verbose), UNITS))
+    deps = []
+    for obj in objs:
+        with open(obj[:-2] + ".d") as f:      # make syntax: `<object>: file file \` and so on, blanks in names escaped
+            deps += shlex.split(f.read().replace("\\\n", " "))[1:]
+    missing, superfluous = sources_mismatch(deps)
+    if missing or superfluous:
+        raise RuntimeError("build.SOURCES is not what the units read: missing %r, superfluous %r" % (missing, superfluous))
+    subprocess.check_call([hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-o", lib] + objs, cwd=CSRC)
+    return lib
+
+
+def digest(asm_dir=ISA_DIR):
+    """[(listing, kernel, instructions, digest)] for every function with instructions in the listings of asm_dir: the first 16 hex digits
+    of the SHA-256 of its block labels and instruction texts as read_listing() normalises them (no comments, directives or `__hip_cuid_*`
+    label, whitespace collapsed).  Equal digests are what "the device listings equal the parent's" means."""
+    rows = []
+    for asm in sorted(glob.glob(os.path.join(asm_dir, "*_gfx950.s"))):
+        for fn in read_listing(asm):
+            stream = [t for b in fn.blocks for t in [b.label + ":"] * b.label.startswith(".LBB") + [i.text for i in b.insns]]
+            count = sum(len(b.insns) for b in fn.blocks)
+            if count:
+                rows.append((os.path.basename(asm), fn.name, count, hashlib.sha256("\n".join(stream).encode()).hexdigest()[:16]))
+    return rows
 
 
 if __name__ == "__main__":
-    build(force="--force" in sys.argv, verbose=True)
-    print(LIB)
+    if "--digest" in sys.argv:
+        for row in digest(*sys.argv[sys.argv.index("--digest") + 1:][:1]):
+            print("%s %s %d %s" % row)
+    else:
+        build(force="--force" in sys.argv, verbose=True)
+        print(LIB)

@@ -1,25 +1,19 @@
 """Diagnostic (GPU box): per-phase cycle shares of the solver kernel from the -DBMPC_PROFILE build
 (libboundmpc_hip_prof.so, built here on the fly; never used by the product)."""
-import ctypes, os, subprocess, sys, time
+import ctypes, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from boundmpc_amd import workload
 
-csrc = os.path.join(ROOT, "boundmpc_amd", "csrc")
 # BMPC_PROF_LIB: a profile library built ahead of the GPU call (python tests/gpu_profile_phases.py --build-only, on the CPU box: build/ travels)
 prof_lib = os.environ.get("BMPC_PROF_LIB") or os.path.join(ROOT, "build", "prof", "libboundmpc_hip_prof.so")
 if "--build-only" in sys.argv or not os.path.exists(prof_lib):
     from boundmpc_amd import build as _b
-    os.makedirs(os.path.dirname(prof_lib), exist_ok=True)
-    objs = []
-    procs = []
-    for src in _b.UNITS:      # the translation units of the library, side by side, each with the product's flags (stamps only in the batch kernels)
-        unit = os.path.splitext(os.path.basename(src))[0]
-        objs.append(os.path.join(os.path.dirname(prof_lib), unit + "_prof.o"))
-        procs.append(subprocess.Popen([_b.hipcc()] + _b.unit_flags(src) + ["-fPIC", "-DBMPC_PROFILE"] + os.environ.get("BMPC_PROF_DEFS", "").split() + ["-c", "-o", objs[-1], src]))
-    assert all(pr.wait() == 0 for pr in procs)
-    subprocess.check_call([_b.hipcc(), "--offload-arch=gfx950", "-fPIC", "-shared", "-o", prof_lib] + objs)
+    # the translation units of the library, each compiled as the product's (stamps only in the batch kernels).  lint=False: with the stamps the
+    # pair kernel trips lint_isa (profiles/build_refactor.txt): ('_Z22bmpc_pair_solve_kernel6KArgsTIN5bmpcp4OptsEE', 'bb.587', 19360,
+    # ['v_mov_b64_e32 v[208:209], v[214:215]', ... six copies]) -- a block of copies under its own `s_and_saveexec` that ends in the restore
+    _b.build(force=True, lint=False, lib=prof_lib, out_dir=os.path.dirname(prof_lib), defines=["-DBMPC_PROFILE"] + os.environ.get("BMPC_PROF_DEFS", "").split())
     if "--build-only" in sys.argv:
         print(prof_lib); sys.exit(0)
 import torch

@@ -1,46 +1,38 @@
 """Diagnostic (CPU, needs hipcc): static statistics of the solver kernel's ISA per phase.
 
-The kernel text is compiled with -DBMPC_MARKS (bmpc_hip.hip: every BMPC_PROF stamp becomes an `s_nop ; BMPCMARK id` comment in the
-listing) and the listing of one kernel is cut at the marks; the instructions ahead of mark `id` belong to phase slot `id`
+The kernel text is compiled with -DBMPC_MARKS (boundmpc_amd.build.compile_unit on bmpc_hip.hip, linted like the product: every BMPC_PROF
+stamp becomes an `s_nop ; BMPCMARK id` comment in the listing) and the listing of one kernel is cut at the marks; the instructions ahead of mark `id` belong to phase slot `id`
 (names: tests/gpu_profile_phases.py).  Three views ("Reading the ISA per phase"):
   mix    instruction mix per phase: fp64 VALU, other VALU, AGPR moves, MFMA, LDS, global loads / stores, scratch, waits, branches, SALU
   trips  `s_waitcnt vmcnt` that follow at least one load since the previous one = dependent round trips to the workspace, per phase
   ops    opcode histogram of the phases given with --slots (e.g. the Riccati stage: 6,24,5,11,21,22,12,19,20,23,14,17,30,13)
 Usage: python tests/isa_phase_stats.py {mix|trips|ops} [--kernel true|false|tick] [--slots a,b,...] [--asm listing.s]"""
-import argparse, collections, os, re, subprocess, sys, tempfile
+import argparse, collections, os, re, sys, tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 KERNELS = {"true": "_Z17bmpc_solve_kernelILb1EE", "false": "_Z17bmpc_solve_kernelILb0EE", "tick": "_Z23bmpc_stream_tick_kernelILb1EE"}      # prefixes of the mangled names
 
 
-def listing(path):
-    if path:
-        return open(path).read().split("\n")
+def kernel(path, name):
+    """the function `name` (prefix of the mangled name) of the listing at `path`, or of a fresh -DBMPC_MARKS compile of bmpc_hip.hip"""
     from boundmpc_amd import build
-    out = os.path.join(tempfile.mkdtemp(), "marks.s")
-    subprocess.check_call([build.hipcc()] + build.FLAGS + ["-DBMPC_MARKS", "-S", "--cuda-device-only", "-o", out, os.path.join(ROOT, "boundmpc_amd", "csrc", "bmpc_hip.hip")],
-                          stderr=subprocess.DEVNULL)
-    return open(out).read().split("\n")
+    if not path:
+        out = tempfile.mkdtemp()
+        build.compile_unit(os.path.join(build.CSRC, "bmpc_hip.hip"), out, ["-DBMPC_MARKS"])
+        path = os.path.join(out, "bmpc_hip_gfx950.s")
+    return next(fn for fn in build.read_listing(path) if fn.name.startswith(name))
 
 
-def kernel_lines(src, name):
-    start = next(i for i, l in enumerate(src) if l.startswith(name))
-    end = next(i for i in range(start, len(src)) if src[i].startswith(".Lfunc_end"))
-    return src[start:end]
-
-
-def phases(lines):
+def phases(fn):
     """[(slot id, [instruction text, ...])] in listing order"""
     out, cur = [], []
-    for l in lines:
-        m = re.search(r"BMPCMARK (\d+)", l)
+    for ins in (i for b in fn.blocks for i in b.insns):
+        m = re.search(r"BMPCMARK (\d+)", ins.note)
         if m:
             out.append((int(m.group(1)), cur)); cur = []
-            continue
-        t = l.strip()
-        if t and t[0] not in ";." and not t.endswith(":"):
-            cur.append(t.split(";")[0].strip())
+        else:
+            cur.append(ins.text)
     out.append((-1, cur))
     return out
 
@@ -68,7 +60,7 @@ def main():
     ap.add_argument("--slots", default="")
     ap.add_argument("--asm", default=None)
     a = ap.parse_args()
-    ph = phases(kernel_lines(listing(a.asm), KERNELS[a.kernel]))
+    ph = phases(kernel(a.asm, KERNELS[a.kernel]))
     if a.view == "mix":
         keys = ["f64", "valu", "agpr", "mfma", "lds", "gld", "gst", "scr", "wait", "br", "salu"]
         print("slot " + " ".join("%6s" % k for k in keys) + "   VALU total")
