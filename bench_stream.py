@@ -57,85 +57,79 @@ def main():
     import torch
     from boundmpc_amd import BatchedOCPSolver, workload, stream as bstream
     B, T = args.batch, args.ticks
-    q0s = workload.random_q0(B, seed=3)
-    mpcs, recs = [], []
-    for q0 in q0s:
-        m, p0fk = workload.make_mpc(q0)
-        mpcs.append(m)
-        recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0.0, 0.0]), np.zeros(7)))
-    recs = np.stack(recs)
-    solver = BatchedOCPSolver(10, 4, 0.1, tol=args.tol, mu_warm=args.mu_warm, max_iter=args.max_iter, stall_window=args.stall_window or None)
-    solver.set_timing(True)
-    if args.no_restoration:
-        solver.set_restoration(False)
-    elif args.resto_cap:
-        solver.set_restoration(cap=args.resto_cap)
-    # real-time modes: loose tolerance + hard iteration cap per tick, COLD duals (the barrier restarts centred every tick: carrying a
-    # small mu jams the iterate against the constraints that change with the shifted horizon)
-    rt = {}
-    for cap in (8, 7, 6, 5):
-        rt[cap] = BatchedOCPSolver(10, 4, 0.1, tol=args.rt_tol, max_iter=cap)
-        rt[cap].set_timing(True)
-    # warm real-time modes: the same, but the dual state is carried (shifted with the plan on the device) and the barrier restarts at
-    # a MODERATE level (mu_warm 3e-2): active rows keep their multipliers, nothing is jammed; mean 4.4 iterations per tick
-    rtw = {}
-    for cap in (7, 6, 5, 4, 3):
-        rtw[cap] = BatchedOCPSolver(10, 4, 0.1, tol=args.rt_tol, max_iter=cap, mu_warm=args.rt_mu_warm)
-        rtw[cap].set_timing(True)
-    # warm real-time modes with the Gauss-Newton Hessian (the classical choice of real-time iteration schemes): positive semidefinite by
-    # construction, so no tick ever repeats a Riccati sweep after a failed factorisation
-    rtgn = {}
-    for cap in (6, 5, 4, 3):
-        rtgn[cap] = BatchedOCPSolver(10, 4, 0.1, tol=args.rt_tol, max_iter=cap, mu_warm=args.rt_mu_warm, exact_hessian=False)
-        rtgn[cap].set_timing(True)
-    # time-budgeted real-time modes (round 4): no fixed iteration count -- the fused tick starts no further iteration once the budget (from
-    # kernel entry) is used up; loose tolerance, dual state carried
-    rtb = {}
-    for us in (600, 700, 800):
-        for gn in (False, True):
-            rtb[(us, gn)] = BatchedOCPSolver(10, 4, 0.1, tol=args.rt_tol, max_iter=30, mu_warm=args.rt_mu_warm, exact_hessian=not gn, bound_margin=args.rt_bound_margin)
-            rtb[(us, gn)].set_timing(True)
-    # time-budgeted modes on a FIXED barrier level (round 5; the classical real-time iteration of an interior-point method): mu_init = mu_warm = final
-    # level = MU, so a tick spends its few iterations as Newton steps on ONE barrier problem whose solution the previous tick left nearby, instead of
-    # restarting the barrier at mu_warm and re-converging through its levels; tol never fires (the complementarity stays at MU): every tick uses its
-    # budget and the reference's acceptance rule (threshold rt_feas_tol) decides.  Larger MU: plans further from the tube / limit rows, more robust.
-    rtf = {}
-    for us in [int(v) for v in args.rtfix_budgets.split(",") if v]:
-        for MU in [float(v) for v in args.rtfix_mu.split(",") if v]:
-            rtf[(us, MU)] = BatchedOCPSolver(10, 4, 0.1, tol=args.rt_tol, max_iter=30, fixed_barrier=MU, bound_margin=args.rt_bound_margin)
-            rtf[(us, MU)].set_timing(True); rtf[(us, MU)].set_rt_position_row_cap(args.rt_row_cap)
-    # converged loops with a barrier-level fallback (round 5; StreamBatch.tick_with_fallback): every tick is solved to tolerance with at most 24 iterations (no
-    # restoration phase); the streams that did not converge are solved again from the same warm start on the fixed barrier level 1 (14 Newton steps) and
-    # the reference's acceptance rule at the reference's threshold 1e-4 decides
-    cfb_main = BatchedOCPSolver(10, 4, 0.1, tol=args.tol, mu_warm=args.mu_warm, max_iter=args.max_iter, stall_window=args.stall_window or None)
-    cfb_main.set_restoration(False); cfb_main.set_timing(True)
+    mpcs, recs = workload.make_streams(B, seed=3)
+    RT = dict(tol=args.rt_tol)
+    made = {}
+
+    def handle(key):
+        """One solver handle per key, constructed when a selected mode first asks for it (`--only` runs create what they use)."""
+        if key in made:
+            return made[key]
+        kind = key[0]
+        if kind in ("solver", "cfb_main"):
+            # cfb_main: converged loops with a barrier-level fallback (round 5; StreamBatch.tick_with_fallback): every tick is solved to tolerance with at most 24
+            # iterations (no restoration phase); the streams that did not converge are solved again from the same warm start on the fixed barrier level 1
+            # (cfb_level: 14 Newton steps) and the reference's acceptance rule at the reference's threshold 1e-4 decides
+            s = BatchedOCPSolver(10, 4, 0.1, tol=args.tol, mu_warm=args.mu_warm, max_iter=args.max_iter, stall_window=args.stall_window or None)
+            if kind == "cfb_main" or args.no_restoration:
+                s.set_restoration(False)
+            elif args.resto_cap:
+                s.set_restoration(cap=args.resto_cap)
+        elif kind == "cfb_level":
+            s = BatchedOCPSolver(10, 4, 0.1, tol=1e-3, max_iter=cfb_k, fixed_barrier=cfb_mu)
+            s.set_restoration(False)
+        elif kind == "rt":
+            # real-time modes: loose tolerance + hard iteration cap per tick, COLD duals (the barrier restarts centred every tick: carrying a
+            # small mu jams the iterate against the constraints that change with the shifted horizon, DESIGN.md 5b)
+            s = BatchedOCPSolver(10, 4, 0.1, max_iter=key[1], **RT)
+        elif kind in ("rtw", "rtgn"):
+            # warm real-time modes: the same, but the dual state is carried (shifted with the plan on the device) and the barrier restarts at
+            # a MODERATE level (mu_warm 3e-2): active rows keep their multipliers, nothing is jammed; mean 4.4 iterations per tick
+            # rtgn: with the Gauss-Newton Hessian (the classical choice of real-time iteration schemes): positive semidefinite by
+            # construction, so no tick ever repeats a Riccati sweep after a failed factorisation
+            s = BatchedOCPSolver(10, 4, 0.1, max_iter=key[1], mu_warm=args.rt_mu_warm, exact_hessian=kind == "rtw", **RT)
+        elif kind == "rtb":
+            # time-budgeted real-time modes (round 4): no fixed iteration count -- the fused tick starts no further iteration once the budget (from
+            # kernel entry) is used up; loose tolerance, dual state carried
+            s = BatchedOCPSolver(10, 4, 0.1, max_iter=30, mu_warm=args.rt_mu_warm, exact_hessian=not key[2], bound_margin=args.rt_bound_margin, **RT)
+        elif kind in ("rtf", "rtfc", "rtfa"):
+            # a FIXED barrier level (round 5; the classical real-time iteration of an interior-point method): mu_init = mu_warm = final level = MU, so a tick
+            # spends its few iterations as Newton steps on ONE barrier problem whose solution the previous tick left nearby, instead of restarting the
+            # barrier at mu_warm and re-converging through its levels; tol never fires (the complementarity stays at MU): every tick uses its budget and the
+            # reference's acceptance rule (threshold rt_feas_tol) decides.  Larger MU: plans further from the tube / limit rows, more robust.
+            # rtf: under a time budget; rtfc: with an ITERATION cap instead, every stream takes exactly that many Newton steps -- no clock in the result;
+            # rtfa: the level that sets itself per stream (round 6)
+            s = BatchedOCPSolver(10, 4, 0.1, max_iter=30, fixed_barrier="auto" if kind == "rtfa" else key[-1], bound_margin=args.rt_bound_margin, **RT)
+            s.set_rt_position_row_cap(args.rt_row_cap)
+        elif kind == "evaluate":
+            s = BatchedOCPSolver(10, 4, 0.1, max_iter=0)       # f, g at a given point (no iteration)
+        elif kind == "reference":
+            s = BatchedOCPSolver(10, 4, 0.1, tol=args.tol, max_iter=args.max_iter, start_rollout=False)    # every tick's problem solved to tolerance, untimed; x0 taken as given, like every stream solve
+        if kind not in ("cfb_level", "evaluate", "reference"):
+            s.set_timing(True)
+        made[key] = s
+        return s
+    budgets = [int(v) for v in args.rtfix_budgets.split(",") if v]
+    levels = [float(v) for v in args.rtfix_mu.split(",") if v]
     cfb_cap, cfb_k, cfb_mu = int(args.cfb.split(",")[0]), int(args.cfb.split(",")[1]), float(args.cfb.split(",")[2])
-    cfb_level = BatchedOCPSolver(10, 4, 0.1, tol=1e-3, max_iter=cfb_k, fixed_barrier=cfb_mu)
-    cfb_level.set_restoration(False)
-    rtfc = {}      # the fixed-level modes with an ITERATION cap instead of a time budget: every stream takes exactly that many Newton steps -- no clock in the result
-    for MU in [float(v) for v in args.rtfix_mu.split(",") if v][:1]:
-        rtfc[MU] = BatchedOCPSolver(10, 4, 0.1, tol=args.rt_tol, max_iter=30, fixed_barrier=MU, bound_margin=args.rt_bound_margin)
-        rtfc[MU].set_timing(True); rtfc[MU].set_rt_position_row_cap(args.rt_row_cap)
-    rtfa = BatchedOCPSolver(10, 4, 0.1, tol=args.rt_tol, max_iter=30, fixed_barrier="auto", bound_margin=args.rt_bound_margin)      # the level that sets itself per stream (round 6)
-    rtfa.set_timing(True); rtfa.set_rt_position_row_cap(args.rt_row_cap)
-    evaluate = BatchedOCPSolver(10, 4, 0.1, max_iter=0)       # f, g at a given point (no iteration)
-    reference = BatchedOCPSolver(10, 4, 0.1, tol=args.tol, max_iter=args.max_iter, start_rollout=False)    # every tick's problem solved to tolerance, untimed; x0 taken as given, like every stream solve
     res, ref_q = [], None
     FT = args.rt_feas_tol
-    modes = [("converged", solver, 0, False, None), ("warm", solver, 0, True, None)] \
-        + [(f"rtw-tol{args.rt_tol:g}-cap{c}-feas{FT:g}", rtw[c], 0, True, FT) for c in (7, 5, 4)] \
-        + [(f"rtgn-tol{args.rt_tol:g}-cap{c}-feas{FT:g}", rtgn[c], 0, True, FT) for c in (6, 5, 4, 3)] \
-        + [(f"rtgn-tol{args.rt_tol:g}-cap4-feas1e-4(reference rule)", rtgn[4], 0, True, 1e-4)] \
-        + [(f"rt-tol{args.rt_tol:g}-cap{c}-feas{FT:g}", rt[c], 0, False, FT) for c in (8, 6)] \
-        + [("rti-3-feas%g" % FT, solver, 3, True, FT)] \
-        + [("warm-continue-feas1e-4 (converged solves; a stalled tick's iterate is the next warm start; reference acceptance rule + variable bounds)", solver, 0, True, 1e-4)] \
-        + [(f"rtb{'gn' if gn else 'w'}-tol{args.rt_tol:g}-budget{us}us-feas{FT:g}", rtb[(us, gn)], 0, True, FT) for (us, gn) in sorted(rtb)]
-    modes += [(f"rtfix-mu{MU:g}-tol{args.rt_tol:g}-budget{us}us-feas{FT:g}", rtf[(us, MU)], 0, True, FT) for (us, MU) in sorted(rtf)]
-    modes += [(f"rtfixcap-mu{MU:g}-cap{c}-feas{FT:g} (fixed barrier level, exactly {c} Newton steps per tick, no clock: reproducible bit for bit)", rtfc[MU], c, True, FT) for MU in sorted(rtfc) for c in (5, 6, 7)]
-    modes += [(f"rtfixcap-muauto-cap{c}-feas{FT:g} (barrier level held inside the tick, set per stream: clamp(0.02 (phi_max - phi), 0.01, 0.1); exactly {c} Newton steps per tick; the mode bench.py reports for configs[4])", rtfa, c, True, FT) for c in (5, 6)]
-    modes += [(f"converged-fallback-cap{cfb_cap}-level{cfb_mu:g}-k{cfb_k}-feas1e-4 (solved to tolerance within {cfb_cap} iterations, else {cfb_k} steps on the barrier level {cfb_mu:g}; the reference's rule at 1e-4)", cfb_main, cfb_cap, True, 1e-4)]
+    SOLVER = ("solver",)
+    # (mode, key of its handle, iteration cap of a tick, dual state carried, acceptance threshold)
+    modes = [("converged", SOLVER, 0, False, None), ("warm", SOLVER, 0, True, None)] \
+        + [(f"rtw-tol{args.rt_tol:g}-cap{c}-feas{FT:g}", ("rtw", c), 0, True, FT) for c in (7, 5, 4)] \
+        + [(f"rtgn-tol{args.rt_tol:g}-cap{c}-feas{FT:g}", ("rtgn", c), 0, True, FT) for c in (6, 5, 4, 3)] \
+        + [(f"rtgn-tol{args.rt_tol:g}-cap4-feas1e-4(reference rule)", ("rtgn", 4), 0, True, 1e-4)] \
+        + [(f"rt-tol{args.rt_tol:g}-cap{c}-feas{FT:g}", ("rt", c), 0, False, FT) for c in (8, 6)] \
+        + [("rti-3-feas%g" % FT, SOLVER, 3, True, FT)] \
+        + [("warm-continue-feas1e-4 (converged solves; a stalled tick's iterate is the next warm start; reference acceptance rule + variable bounds)", SOLVER, 0, True, 1e-4)] \
+        + [(f"rtb{'gn' if gn else 'w'}-tol{args.rt_tol:g}-budget{us}us-feas{FT:g}", ("rtb", us, gn), 0, True, FT) for us in (600, 700, 800) for gn in (False, True)]
+    modes += [(f"rtfix-mu{MU:g}-tol{args.rt_tol:g}-budget{us}us-feas{FT:g}", ("rtf", us, MU), 0, True, FT) for us in sorted(set(budgets)) for MU in sorted(set(levels))]
+    modes += [(f"rtfixcap-mu{MU:g}-cap{c}-feas{FT:g} (fixed barrier level, exactly {c} Newton steps per tick, no clock: reproducible bit for bit)", ("rtfc", MU), c, True, FT) for MU in levels[:1] for c in (5, 6, 7)]
+    modes += [(f"rtfixcap-muauto-cap{c}-feas{FT:g} (barrier level held inside the tick, set per stream: clamp(0.02 (phi_max - phi), 0.01, 0.1); exactly {c} Newton steps per tick; the mode bench.py reports for configs[4])", ("rtfa",), c, True, FT) for c in (5, 6)]
+    modes += [(f"converged-fallback-cap{cfb_cap}-level{cfb_mu:g}-k{cfb_k}-feas1e-4 (solved to tolerance within {cfb_cap} iterations, else {cfb_k} steps on the barrier level {cfb_mu:g}; the reference's rule at 1e-4)", ("cfb_main",), cfb_cap, True, 1e-4)]
     if args.unsafe_too:
-        modes += [(f"UNSAFE rtgn-tol{args.rt_tol:g}-cap{c} (every capped iterate applied)", rtgn[c], 0, True, 1e30) for c in (4, 3)]
+        modes += [(f"UNSAFE rtgn-tol{args.rt_tol:g}-cap{c} (every capped iterate applied)", ("rtgn", c), 0, True, 1e30) for c in (4, 3)]
     from boundmpc_amd.robot_model import RobotModel
     qlim = np.array(RobotModel().q_lim_upper)
     # Everything below runs on an explicit HIP stream.  On the legacy null stream, a hipGraph replay followed by further kernel launches
@@ -143,39 +137,30 @@ def main():
     # same sequence with direct launches instead of the graph, or on any explicit stream, is clean.
     torch.cuda.set_stream(torch.cuda.Stream())
     only = [k for k in args.only.split(",") if k]
-    budget_of = {id(rtb[k]): k[0] for k in rtb}
-    budget_of.update({id(rtf[k]): k[0] for k in rtf})
-    for mode, slv, cap, warm, feas in modes:
+    for mode, key, cap, warm, feas in modes:
         if only and mode != "converged" and not any(k in mode for k in only):
             continue
-        budget = budget_of.get(id(slv), 0)
+        slv = handle(key)
+        budget = key[1] if key[0] in ("rtb", "rtf") else None
         capped = feas is not None
         if capped:
             slv.set_rt_feasibility_tol(feas)          # read when the tick graph is captured
         sb = bstream.StreamBatch(slv, mpcs)
         sb.set_robot(recs)
-        ms, its, Q, ok, wall, tick_dq, tick_df, alive, gviol, tube_p, tube_r, skipped, maxit, row_p, row_r = [], [], [], [], [], [], [], [], [], [], [], [], [], [], []
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for t in range(T):
+        ms, its, Q, ok, wall, tick_dq, tick_df, alive, gviol, tubes, skipped, maxit = [], [], [], [], [], [], [], [], [], [], [], []
+        # (the fallback tick: three launches + a host read of the failed count, not a graph; its second handle is made here, outside the timed ticks)
+        own_tick = None
+        if mode.startswith("converged-fallback"):
+            fb = handle(("cfb_level",))
+            own_tick = lambda: sb.tick_with_fallback(fb, max_iter=cap, simulate=True)      # noqa: E731
+        reference, evaluate = (handle(("reference",)), handle(("evaluate",))) if mode != "converged" else (None, None)
+        # the first tick of every stream is its cold start from rest: solved to tolerance in all modes (not timed); the others: whole tick {pack, queue
+        # reset, solve, post, plant}, HIP events around the graph launch
+        for t in sb.closed_loop(T, cap=cap, warm=warm, accept_capped=capped, budget_us=budget, timed=True, tick=own_tick):
             if os.environ.get("BENCH_STREAM_TRACE"):
                 print("trace", mode, t, file=sys.stderr, flush=True)
-            # the first tick of every stream is its cold start from rest: solved to tolerance in all modes (not timed)
-            if t == 0:
-                if budget:
-                    slv.set_time_budget_us(0)
-                sb.tick(max_iter=100, warm_dual=True, simulate=True)
-                if not warm:
-                    sb.dual.zero_()
-                if budget:
-                    slv.set_time_budget_us(budget)      # read when the tick graph is captured (next tick)
-            else:
-                ev0.record()
-                if mode.startswith("converged-fallback"):
-                    sb.tick_with_fallback(cfb_level, max_iter=cap, simulate=True)      # (three launches + a host read of the failed count: not a graph)
-                else:
-                    sb.tick_graph(max_iter=cap, warm_dual=warm, simulate=True, accept_capped=capped)
-                ev1.record(); ev1.synchronize()
-                wall.append(ev0.elapsed_time(ev1))         # whole tick {pack, queue reset, solve, post, plant}: HIP events around the graph launch
+            if t > 0:
+                wall.append(sb.tick_ms)
             ms.append(slv.last_kernel_ms())
             if t > 0 and mode != "converged":
                 # this tick's problem solved to 1e-8 from the same warm start (untimed): how far is the applied plan from its minimiser?
@@ -190,25 +175,18 @@ def main():
             its.append(float(sb.iters.double().mean().item()))
             maxit.append(int(sb.iters.max().item()))
             if t > 0:
-                # BoundMPC's contract: is the MEASURED state of this tick inside its tubes?  (the packed p holds the measured pose, phi and the tube
-                # quartics: stream.tube_excess_of_state evaluates the five tube rows of casadi_ocp_formulation.py:316-349 at node 0; streams that
-                # have lost their plan -- skipped by the fused tick, their p is stale -- are left out and counted)
-                has_plan = (sb.state[:, bstream.SS["ERRCNT"]] < 10).cpu().numpy()
-                ex_p, ex_r = bstream.tube_excess_of_state(sb.p.cpu().numpy())
-                tube_p.append(np.where(has_plan[:, None], ex_p, -np.inf).max(axis=1)); tube_r.append(np.where(has_plan[:, None], ex_r, -np.inf).max(axis=1))
-                skipped.append(int((~has_plan).sum()))
+                # BoundMPC's contract: is the MEASURED state of this tick inside its tubes?  (stream.tick_tube_figures: the five tube rows of
+                # casadi_ocp_formulation.py:316-349 at node 0 of the packed problem; streams that have lost their plan are left out and counted)
                 # ... and as the reference's own logging shows it (BoundMPC.py:614-752: err_data against the bounds, per stage of the APPLIED plan, in
-                # the tick's own linearisation of the orientation error): the tube rows of the plan's first stage -- the state the plant reaches next --
-                # in the reference's form l^2 - w^2 (rows 38..42 of g), over the ticks whose plan was applied
-                g0 = sb.g.reshape(B, 10, 43)[:, 0, 38:43].cpu().numpy(); app = (sb.traj[:, -2] > 0.5).cpu().numpy()
-                row_p.append(np.where(app, g0[:, 1:3].max(axis=1), -np.inf)); row_r.append(np.where(app, g0[:, [0, 3, 4]].max(axis=1), -np.inf))
+                # the tick's own linearisation of the orientation error): the tube rows of the plan's first stage, over the ticks whose plan was applied
+                tubes.append(sb.tick_tube_figures())
+                skipped.append(int((~sb.has_plan()).sum().item()))
+                gviol.append(sb.g_viol().cpu().numpy())
             Q.append(sb.robot[:, :7].clone())
-            ok.append(float((sb.traj[:, -2] > 0.5).double().mean().item()))
-            alive.append(float((sb.state[:, bstream.SS["VALID"]] > 0.5).double().mean().item()))
-            if t > 0:
-                gviol.append(sb.traj[:, -1].cpu().numpy())
+            ok.append(float(sb.applied().double().mean().item()))
+            alive.append(float(sb.valid().double().mean().item()))
         Q = torch.stack(Q).cpu().numpy()
-        phi = sb.state[:, bstream.SS["PHI"]].cpu().numpy()
+        phi = sb.phi().cpu().numpy()
         if ref_q is None:
             ref_q = Q
         ms = np.array(ms[1:]); its = np.array(its[1:]); wall = np.array(wall)
@@ -219,20 +197,12 @@ def main():
             dq_all, df_all = np.concatenate(tick_dq), np.concatenate(tick_df)
             pt = {"per_tick_joint_rms_vs_own_minimiser_rad": {"median": float(np.median(dq_all)), "p90": float(np.percentile(dq_all, 90)), "p99": float(np.percentile(dq_all, 99))},
                   "per_tick_relative_objective_excess": {"median": float(np.median(df_all)), "p90": float(np.percentile(df_all, 90)), "p99": float(np.percentile(df_all, 99))}}
-        tube_p, tube_r = np.array(tube_p), np.array(tube_r)      # [ticks][streams]: largest excess over the rows, -inf where the stream had no plan
-        n_samples = int(np.isfinite(tube_p).sum())
-        tube = {"plant_samples": n_samples, "tolerance": 1e-6,
-                "fraction_outside_the_position_tube": float((tube_p > 1e-6).sum() / max(n_samples, 1)), "largest_position_excess_m": float(max(tube_p.max(), 0.0)),
-                "fraction_outside_the_orientation_tube": float((tube_r > 1e-6).sum() / max(n_samples, 1)), "largest_orientation_excess_rad": float(max(tube_r.max(), 0.0)),
-                "streams_ever_outside_a_tube": int(((tube_p > 1e-6) | (tube_r > 1e-6)).any(axis=0).sum()),
-                "note": "rows of casadi_ocp_formulation.py:316-349 at the MEASURED state (node 0 of the next packed problem), linear form |l| - |w|.  Position rows: exact.  "
+        tube = bstream.tube_summary(*(np.array(a) for a in zip(*tubes)))      # [ticks][streams] each
+        tube["note"] = ("rows of casadi_ocp_formulation.py:316-349 at the MEASURED state (node 0 of the next packed problem), linear form |l| - |w|.  Position rows: exact.  "
                         "Orientation rows: the exact zyx split of the measured orientation error, which the NLP only constrains through its per-tick linearisation -- "
-                        "a loop that solves every tick to 1e-8 shows the same excess (the `converged` row), so it measures the reference's formulation, not the solver"}
-        row_p, row_r = np.array(row_p), np.array(row_r); n_app = int(np.isfinite(row_p).sum())
-        tube["applied_plans_first_stage_rows_reference_form"] = {
-            "applied_plans": n_app, "fraction_with_a_position_row_above_1e-6": float((row_p > 1e-6).sum() / max(n_app, 1)), "largest_position_row_m2": float(max(row_p.max(), 0.0)),
-            "fraction_with_an_orientation_row_above_1e-6": float((row_r > 1e-6).sum() / max(n_app, 1)), "largest_orientation_row_rad2": float(max(row_r.max(), 0.0)),
-            "note": "l^2 - w^2 <= 0 (g rows 38..42 of stage 0) of every applied plan: what the reference's err_data / bounds logging shows for the state the plant reaches next"}
+                        "a loop that solves every tick to 1e-8 shows the same excess (the `converged` row), so it measures the reference's formulation, not the solver")
+        tube["applied_plans_first_stage_rows_reference_form"]["note"] = ("l^2 - w^2 <= 0 (g rows 38..42 of stage 0) of every applied plan: what the reference's err_data / "
+                                                                         "bounds logging shows for the state the plant reaches next")
         res.append({**pt, "mode": mode, "tick_ms_p50": float(np.percentile(wall, 50)), "tick_ms_p99": float(np.percentile(wall, 99)),
                     "tube_compliance_of_the_measured_states": tube, "streams_skipped_per_tick_mean": float(np.mean(skipped)), "streams_skipped_at_the_end": int(skipped[-1]),
                     "slowest_stream_iterations_per_tick": {"p50": float(np.percentile(maxit[1:], 50)), "p99": float(np.percentile(maxit[1:], 99)), "max": int(max(maxit[1:]))},

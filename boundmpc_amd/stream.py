@@ -184,6 +184,74 @@ def unpack_traj(t, N):
     return out, dict(n_valid=n, using_previous=bool(t[-3]), success=bool(t[-2]), g_viol=float(t[-1]))
 
 
+# Named reads of the stream records: pure indexing of the last axis, on numpy arrays and torch tensors alike (one row or a batch; no copy, no sync).
+def applied(traj):
+    """the success flag of a trajectory record (unpack_traj's `success`): the tick's plan was applied"""
+    return traj[..., -2] > 0.5
+
+
+def g_viol(traj):
+    """the summed violation the acceptance rule judged (unpack_traj's `g_viol`)"""
+    return traj[..., -1]
+
+
+def has_plan(state, N):
+    """error count < N: the stream still holds a plan (from N on the reference's step() returns None, BoundMPC.py:498-506, and the fused tick skips it)"""
+    return state[..., SS["ERRCNT"]] < N
+
+
+def valid(state):
+    """the VALID word stream_post wrote: has_plan as of the last post"""
+    return state[..., SS["VALID"]] > 0.5
+
+
+def phi(state):
+    return state[..., SS["PHI"]]
+
+
+def level(dual, N):
+    """the barrier level in the dual state [57 N multipliers | mu | ...]"""
+    return dual[..., 57 * N]
+
+
+def first_stage_tube_rows(g, N):
+    """rows 38..42 of stage 0 of g [..][43 N]: the tube rows (l^2 - w^2; orientation tangential, position bp1, bp2, orientation br1, br2) of the state the plant reaches next"""
+    assert g.shape[-1] == 43 * N
+    return g[..., 38:43]
+
+
+def set_continue_rejected(state, N, on=True):
+    """the word behind the `updated` flag: "the last iterate was rejected: the next pack continues from xlast" (bmpc_stream_pack_rt)"""
+    state[..., ss_updated(N) + 1] = 1.0 if on else 0.0
+
+
+def tick_tube_figures(p, state, g, traj, N, S=4):
+    """What a closed loop records per tick about the tubes, each [B], numpy: the largest position / orientation excess of the MEASURED state
+    (tube_excess_of_state of the packed `p`; -inf where the stream has no plan: the fused tick skips it, its p is stale) and the largest
+    position / orientation row of the plan's first stage (first_stage_tube_rows; -inf where the plan was not applied)."""
+    cpu = lambda a: a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
+    ex_p, ex_r = tube_excess_of_state(cpu(p), S)
+    plan, app, g0 = cpu(has_plan(state, N)), cpu(applied(traj)), cpu(first_stage_tube_rows(g, N))
+    return (np.where(plan, ex_p.max(axis=1), -np.inf), np.where(plan, ex_r.max(axis=1), -np.inf),
+            np.where(app, g0[:, 1:3].max(axis=1), -np.inf), np.where(app, g0[:, [0, 3, 4]].max(axis=1), -np.inf))
+
+
+def tube_summary(tube_p, tube_r, row_p, row_r, tol=1e-6):
+    """Summary of tick_tube_figures stacked over the ticks [ticks][B]: fractions of the plant samples outside, largest excess, streams ever outside,
+    and the first-stage rows of the applied plans."""
+    tube_p, tube_r, row_p, row_r = (np.asarray(a) for a in (tube_p, tube_r, row_p, row_r))
+    n, n_app = int(np.isfinite(tube_p).sum()), int(np.isfinite(row_p).sum())
+    return {"plant_samples": n, "tolerance": tol,
+            "fraction_outside_the_position_tube": float((tube_p > tol).sum() / max(n, 1)), "largest_position_excess_m": float(max(tube_p.max(), 0.0)),
+            "fraction_outside_the_orientation_tube": float((tube_r > tol).sum() / max(n, 1)), "largest_orientation_excess_rad": float(max(tube_r.max(), 0.0)),
+            "streams_ever_outside_a_tube": int(((tube_p > tol) | (tube_r > tol)).any(axis=0).sum()),
+            "applied_plans_first_stage_rows_reference_form": {
+                "applied_plans": n_app, "fraction_with_a_position_row_above_1e-6": float((row_p > tol).sum() / max(n_app, 1)),
+                "largest_position_row_m2": float(max(row_p.max(), 0.0)),
+                "fraction_with_an_orientation_row_above_1e-6": float((row_r > tol).sum() / max(n_app, 1)),
+                "largest_orientation_row_rad2": float(max(row_r.max(), 0.0))}}
+
+
 class StreamBatch:
     """B streams on the GPU.  `mpcs`: list of freshly constructed host `boundmpc_amd.bound_mpc.BoundMPC` objects (used only to
     read their path and initial state; they are not advanced)."""
@@ -219,6 +287,7 @@ class StreamBatch:
         self.kkt = torch.zeros((self.B,), dtype=torch.float64, device=device)
         self.traj = torch.zeros((self.B, self.tr_len), dtype=torch.float64, device=device)
         self._graphs = {}
+        self.tick_ms = None      # closed_loop(timed=True): HIP-event time of the tick just run
         solver._children.add(self)
 
     def update(self, b, *args, **kw):
@@ -315,6 +384,68 @@ class StreamBatch:
         # (a replay requested on the legacy null stream is run by the library on a stream of the handle, bracketed by events:
         # bmpc_graph_launch)
         _lib.check(self.solver._lib.bmpc_graph_launch(self._graphs[key], self._stream(stream)), "bmpc_graph_launch")
+
+    def closed_loop(self, ticks, cap=0, warm=True, accept_capped=False, first_cap=100, budget_us=None, graph=True, fused=True, timed=False, tick=None):
+        """THE closed loop of BASELINE configs[4], as a generator over the tick index: `for t in sb.closed_loop(ticks, ...)`.
+        Tick 0 is every stream's cold start from rest, solved out (`first_cap` iterations, dual state kept, the reference's acceptance rule,
+        no time budget); warm=False zeroes the dual state behind it (cold duals on every tick).  Later ticks run at most `cap` iterations
+        (0 = the handle's) under the real-time acceptance rule if accept_capped.  What runs on a later tick:
+          tick=f        f(), a caller's own tick body (graph is not looked at);
+          graph=True    the replay of the captured graph;
+          graph=False   a direct launch of self.tick.
+        fused is passed on to every self.tick the driver calls, tick 0 included (False: the three-kernel tick); a graph is always the fused tick.
+        budget_us: time budget of the fused ticks after the first (the handle's setting is read at capture: off for tick 0, set behind it).
+        timed=True: HIP events around every tick after the first, `self.tick_ms` holds the time of the tick just run (None for tick 0).  The
+        launch stream has been synchronised when the loop body runs; what to record there is the caller's business."""
+        import torch
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timed else None
+        for t in range(ticks):
+            self.tick_ms = None
+            if t == 0:
+                if budget_us is not None:
+                    self.solver.set_time_budget_us(0)
+                self.tick(max_iter=first_cap, warm_dual=True, simulate=True, fused=fused)
+                if not warm:
+                    self.dual.zero_()
+                if budget_us is not None:
+                    self.solver.set_time_budget_us(budget_us)
+            else:
+                if timed:
+                    ev[0].record()
+                if tick is not None:
+                    tick()
+                elif graph:
+                    self.tick_graph(max_iter=cap, warm_dual=warm, simulate=True, accept_capped=accept_capped)
+                else:
+                    self.tick(max_iter=cap, warm_dual=warm, simulate=True, accept_capped=accept_capped, fused=fused)
+                if timed:
+                    ev[1].record(); ev[1].synchronize()
+                    self.tick_ms = ev[0].elapsed_time(ev[1])
+            if self.tick_ms is None:
+                torch.cuda.current_stream(self.state.device).synchronize()
+            yield t
+
+    # the named reads (module functions above) on this batch's own buffers
+    def applied(self):
+        return applied(self.traj)
+
+    def g_viol(self):
+        return g_viol(self.traj)
+
+    def has_plan(self):
+        return has_plan(self.state, self.N)
+
+    def valid(self):
+        return valid(self.state)
+
+    def phi(self):
+        return phi(self.state)
+
+    def level(self):
+        return level(self.dual, self.N)
+
+    def tick_tube_figures(self):
+        return tick_tube_figures(self.p, self.state, self.g, self.traj, self.N, self.S)
 
     def close(self):
         for g in self._graphs.values():

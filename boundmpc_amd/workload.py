@@ -104,6 +104,19 @@ def random_q0(B, seed):
     return np.clip(Q0_EXP1 + rng.uniform(-0.3, 0.3, (B, 7)), -qlim, qlim)
 
 
+def make_streams(B, seed=3, N=10, S=4, dt=0.1, take=None):
+    """The closed-loop streams of BASELINE configs[4]: random_q0(B, seed), every stream at rest at its q0 with its own experiment1-pattern path
+    and the end of that path as its goal -> (fresh host BoundMPC objects, robot records [B][RB_LEN]), what StreamBatch(...) and set_robot take.
+    take: only the first `take` of the B streams (random_q0 is prefix-stable in B)."""
+    from .stream import robot_record
+    mpcs, recs = [], []
+    for q0 in random_q0(B, seed)[:take]:
+        m, p0fk = make_mpc(q0, N, S, dt)
+        mpcs.append(m)
+        recs.append(robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0.0, 0.0]), np.zeros(7)))
+    return mpcs, np.stack(recs)
+
+
 def _chunk(args):
     q0s, N, S, dt, tight = args
     P = np.empty((len(q0s), 141 + 91 * S)); X = np.empty((len(q0s), 44 * N))

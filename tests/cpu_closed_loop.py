@@ -17,29 +17,21 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from boundmpc_amd import stream as bstream, workload  # noqa: E402
-from oracle import c_oracle, nlp  # noqa: E402
-from tests.emu import emu  # noqa: E402
+from oracle import nlp  # noqa: E402
+from tests.closed_loop import cpu_mirror_loop  # noqa: E402
 
 N, S, H = 10, 4, 0.1
 
 
 def run_stream(args):
-    b, q0, ticks, max_iter, opts_kw = args
-    mpc, p0fk = workload.make_mpc(q0)
-    T, M = bstream.path_table(mpc.ref_path)
-    ss = bstream.initial_state(mpc, N); ss[bstream.SS["NENT"]] = M
-    rb = bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([mpc.phi_max[0], 0.0, 0.0]), np.zeros(7))
-    o = c_oracle.default_opts(max_iter=max_iter, **opts_kw)
+    b, mpc, rec, ticks, max_iter, opts_kw = args
     rows = []
-    for t in range(ticks):
-        p, x0 = emu.stream_pack(N, S, T, ss, rb)
-        r = c_oracle.solve(p, x0, N, S, H, opts=o, nthreads=1)
-        x, g, st, it = r["x"][0], r["g"][0], int(r["status"][0]), int(r["iters"][0])
-        tr = emu.stream_post(N, S, H, T, ss, rb, x, g, st, simulate=True)
-        _, fl = bstream.unpack_traj(tr, N)
-        rows.append(dict(b=b, t=t, status=st, iters=it, kkt=float(r["kkt"][0]), success=fl["success"], using_previous=fl["using_previous"],
-                         n_valid=fl["n_valid"], g_viol=fl["g_viol"], phi=float(ss[bstream.SS["PHI"]]), phi_max=float(ss[bstream.SS["PHIMAX"]]),
-                         errcnt=int(ss[bstream.SS["ERRCNT"]]), valid=bool(ss[bstream.SS["VALID"]] > 0.5), p=p, x0=x0, x=x))
+    for c in cpu_mirror_loop(mpc, rec, ticks, N, S, H, cap=max_iter, first_cap=max_iter, opts_kw=opts_kw):
+        ss = c["ss"]
+        _, fl = bstream.unpack_traj(c["traj"], N)
+        rows.append(dict(b=b, t=c["t"], status=c["status"], iters=c["iters"], kkt=c["kkt"], success=fl["success"], using_previous=fl["using_previous"],
+                         n_valid=fl["n_valid"], g_viol=fl["g_viol"], phi=float(bstream.phi(ss)), phi_max=float(ss[bstream.SS["PHIMAX"]]),
+                         errcnt=int(ss[bstream.SS["ERRCNT"]]), valid=bool(bstream.valid(ss)), p=c["p"], x0=c["x0"], x=c["x"]))
         if not rows[-1]["valid"]:
             break
     return rows
@@ -67,9 +59,9 @@ def main():
     ap.add_argument("--first-only", action="store_true", help="hand only the FIRST failing tick of every stream to SLSQP (what follows is a warm start from an outdated plan)")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "g13_hard_ticks.npz"))
     a = ap.parse_args()
-    q0s = workload.random_q0(256, seed=3)[:a.streams]
+    mpcs, recs = workload.make_streams(256, seed=3, take=a.streams)
     with mp.get_context("fork").Pool(a.procs) as pool:
-        allrows = pool.map(run_stream, [(b, q0s[b], a.ticks, a.max_iter, {}) for b in range(a.streams)], chunksize=1)
+        allrows = pool.map(run_stream, [(b, mpcs[b], recs[b], a.ticks, a.max_iter, {}) for b in range(a.streams)], chunksize=1)
     rows = [r for rr in allrows for r in rr]
     its = np.array([r["iters"] for r in rows]); st = np.array([r["status"] for r in rows])
     lost = [rr[-1] for rr in allrows if not rr[-1]["valid"]]

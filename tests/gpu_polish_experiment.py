@@ -15,15 +15,8 @@ import torch  # noqa: E402
 from boundmpc_amd import BatchedOCPSolver, stream as bstream, workload  # noqa: E402
 
 B, T, N = 256, 131, 10
-q0s = workload.random_q0(256, seed=3)
-mpcs, recs = [], []
-for q0 in q0s:
-    m, p0fk = workload.make_mpc(q0)
-    mpcs.append(m)
-    recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0.0, 0.0]), np.zeros(7)))
-recs = np.stack(recs)
+mpcs, recs = workload.make_streams(B, seed=3)
 torch.cuda.set_stream(torch.cuda.Stream())
-FLAG = 32 + 56 * N + 1      # ss_updated(N) + 1: "the last iterate was rejected: continue from xlast"
 
 
 def loop(mode, KL=5, P=0, carrier=False, level="auto", pol_tol=1e-3):
@@ -35,36 +28,32 @@ def loop(mode, KL=5, P=0, carrier=False, level="auto", pol_tol=1e-3):
             s.set_rt_feasibility_tol(1e-2); s.set_rt_position_row_cap(1e-5); s.set_start_rollout(False)
     sb = bstream.StreamBatch(slv, mpcs); sb.set_robot(recs)
     Q, ms, tube = [], [], []
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     outp = {}
-    for t in range(T):
-        if t == 0 or conv:
-            sb.tick(max_iter=100 if t == 0 else 0, warm_dual=True, simulate=True, fused=False, accept_capped=not conv and t > 0)
-        else:
-            e0.record()
+
+    def polished_tick():      # pack / solve on the level / polish / post
+        if carrier:
+            bstream.set_continue_rejected(sb.state, N)      # always continue from sb.x (the carrier)
+        sb.pack(True, None, continue_rejected=True)
+        out = dict(x=sb.x, g=sb.g, iters=sb.iters, status=sb.status, kkt=sb.kkt)
+        slv.solve_batch(sb.p, sb.x0, out=out, want=("g", "iters", "status", "kkt"), state=sb.dual, max_iter=KL)      # the carrier: sb.x, sb.dual
+        if P:
+            stp = sb.dual.clone()
+            o = pol.solve_batch(sb.p, sb.x, out=outp, want=("g", "iters", "status", "kkt"), state=stp, max_iter=P)
+            xc = sb.x.clone()
+            sb.x.copy_(o["x"]); sb.g.copy_(o["g"]); sb.status.copy_(o["status"])
+            sb.post(True, None, True)
             if carrier:
-                sb.state[:, FLAG] = 1.0      # always continue from sb.x (the carrier)
-            sb.pack(True, None, continue_rejected=True)
-            out = dict(x=sb.x, g=sb.g, iters=sb.iters, status=sb.status, kkt=sb.kkt)
-            slv.solve_batch(sb.p, sb.x0, out=out, want=("g", "iters", "status", "kkt"), state=sb.dual, max_iter=KL)      # the carrier: sb.x, sb.dual
-            if P:
-                stp = sb.dual.clone()
-                o = pol.solve_batch(sb.p, sb.x, out=outp, want=("g", "iters", "status", "kkt"), state=stp, max_iter=P)
-                xc = sb.x.clone()
-                sb.x.copy_(o["x"]); sb.g.copy_(o["g"]); sb.status.copy_(o["status"])
-                sb.post(True, None, True)
-                if carrier:
-                    sb.x.copy_(xc)
-            else:
-                sb.post(True, None, True)
-            e1.record(); e1.synchronize(); ms.append(e0.elapsed_time(e1))
-        torch.cuda.synchronize()
+                sb.x.copy_(xc)
+        else:
+            sb.post(True, None, True)
+    # (the converged loops: the three-kernel tick to the handle's tolerance on every tick)
+    for t in sb.closed_loop(T, graph=False, fused=False, timed=not conv, tick=None if conv else polished_tick):
+        if sb.tick_ms is not None:
+            ms.append(sb.tick_ms)
         Q.append(sb.robot[:, :7].cpu().numpy().copy())
         if t > 0:
-            has_plan = (sb.state[:, bstream.SS["ERRCNT"]] < 10).cpu().numpy()
-            ex_p, ex_r = bstream.tube_excess_of_state(sb.p.cpu().numpy())
-            tube.append(np.where(has_plan[:, None], ex_p, -np.inf).max())
-    alive = float((sb.state[:, bstream.SS["VALID"]] > 0.5).double().mean()); phi = float(sb.state[:, bstream.SS["PHI"]].mean())
+            tube.append(sb.tick_tube_figures()[0].max())
+    alive = float(sb.valid().double().mean()); phi = float(sb.phi().mean())
     sb.close(); slv.close()
     if pol is not None:
         pol.close()

@@ -12,13 +12,7 @@ from boundmpc_amd.robot_model import RobotModel
 
 T = int(sys.argv[1]) if len(sys.argv) > 1 else 130
 B = 256
-q0s = workload.random_q0(B, seed=3)
-mpcs, recs = [], []
-for q0 in q0s:
-    m, p0fk = workload.make_mpc(q0)
-    mpcs.append(m)
-    recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0.0, 0.0]), np.zeros(7)))
-recs = np.stack(recs)
+mpcs, recs = workload.make_streams(B, seed=3)
 qlim = np.array(RobotModel().q_lim_upper)
 torch.cuda.set_stream(torch.cuda.Stream())
 
@@ -27,21 +21,15 @@ def run(name, slv, cap, warm, capped, tol):
     if tol is not None:
         slv.set_rt_feasibility_tol(tol)
     sb = bstream.StreamBatch(slv, mpcs); sb.set_robot(recs)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     Q, ms, ok, valid, viol, its = [], [], [], [], [], []
-    for t in range(T):
-        if t == 0:
-            sb.tick(max_iter=100, warm_dual=True, simulate=True)
-            if not warm:
-                sb.dual.zero_()
-        else:
-            e0.record(); sb.tick_graph(max_iter=cap, warm_dual=warm, simulate=True, accept_capped=capped); e1.record(); e1.synchronize()
-            ms.append(e0.elapsed_time(e1))
-            ok.append((sb.traj[:, -2] > 0.5).double().mean().item()); valid.append((sb.state[:, bstream.SS["VALID"]] > 0.5).double().mean().item())
-            viol.append(sb.traj[:, -1].cpu().numpy()); its.append(sb.iters.double().mean().item())
+    for t in sb.closed_loop(T, cap=cap, warm=warm, accept_capped=capped, timed=True):
+        if t > 0:
+            ms.append(sb.tick_ms)
+            ok.append(sb.applied().double().mean().item()); valid.append(sb.valid().double().mean().item())
+            viol.append(sb.g_viol().cpu().numpy()); its.append(sb.iters.double().mean().item())
         Q.append(sb.robot[:, :7].clone())
     Q = torch.stack(Q).cpu().numpy()
-    phi = sb.state[:, bstream.SS["PHI"]].cpu().numpy()
+    phi = sb.phi().cpu().numpy()
     sb.close()
     return dict(name=name, Q=Q, ms=np.array(ms), ok=np.array(ok), valid=np.array(valid), viol=np.array(viol), its=np.array(its), phi=phi)
 

@@ -9,36 +9,15 @@ pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
 
 
-def _mpcs():
-    from boundmpc_amd import workload
-    from boundmpc_amd.bound_mpc import BoundMPC
-    from tests.test_stream import _Oracle
-    out = []
-    for which in (1, 2):
-        d6 = np.load(os.path.join(G, f"g6_pack_exp{which}_tick0.npz"))
-        mk = lambda k: [np.array(v) for v in d6[k]]
-        out.append((BoundMPC(mk("p_via"), mk("r_via"), [mk("p_lower"), mk("p_upper")], [mk("r_lower"), mk("r_upper")], mk("bp1_in"), mk("br1_in"),
-                             list(d6["s_in"]), list(d6["e_p_min_in"]), list(d6["e_r_min_in"]), list(d6["e_p_max_in"]), list(d6["e_r_max_in"]),
-                             p0=d6["p0fk"].copy(), params=workload.Params(weights=d6["weights_f64"]), solver=_Oracle()), d6))
-    return out
-
-
-def _robot0(mpc, d6):
-    from boundmpc_amd import stream as bstream
-    from boundmpc_amd.robot_model import RobotModel
-    q = d6["q0"].copy()
-    return bstream.robot_record(q, np.zeros(7), np.zeros(7), RobotModel().forward_kinematics(q, np.zeros(7))[0], np.zeros(6),
-                                np.array([mpc.phi_max[0], 0, 0]), np.zeros(7))
-
-
 @pytest.mark.parametrize("graph", [False, True])
 def test_device_closed_loop_retraces_fixtures(graph):
     import torch
     from boundmpc_amd import BatchedOCPSolver, stream as bstream
-    ms = _mpcs()
+    from tests.closed_loop import reference_experiment_streams
+    mpcs, recs, _ = reference_experiment_streams()
     solver = BatchedOCPSolver(10, 4, 0.1)
-    sb = bstream.StreamBatch(solver, [m for m, _ in ms] * 2)          # 4 streams: exp1, exp2, exp1, exp2
-    sb.set_robot(np.stack([_robot0(m, d) for m, d in ms] * 2))
+    sb = bstream.StreamBatch(solver, mpcs * 2)          # 4 streams: exp1, exp2, exp1, exp2
+    sb.set_robot(np.concatenate([recs, recs]))
     d7 = [np.load(os.path.join(G, f"g7_closedloop_exp{w}.npz")) for w in (1, 2)]
     for t in range(59):
         (sb.tick_graph if graph else sb.tick)(simulate=True)
@@ -50,7 +29,7 @@ def test_device_closed_loop_retraces_fixtures(graph):
             assert fl["success"] and fl["n_valid"] == 10
             np.testing.assert_allclose(td["q"], f["traj_q"][t], atol=2e-5, err_msg=f"tick {t} stream {b}")
             np.testing.assert_allclose(td["p"], f["traj_p"][t], atol=2e-5)
-            assert abs(st[b, bstream.SS["PHI"]] - f["phi_current"][t]) < 1e-6 and int(st[b, 0]) == int(f["sector"][t])
+            assert abs(bstream.phi(st[b]) - f["phi_current"][t]) < 1e-6 and int(st[b, 0]) == int(f["sector"][t])
             if t + 1 < f["q"].shape[0]:
                 np.testing.assert_allclose(rb[b, :7], f["q"][t + 1], atol=2e-6)
         assert np.abs(sb.iters.cpu().numpy()[:2] - np.array([d7[0]["iters"][t], d7[1]["iters"][t]])).max() <= 1
@@ -64,8 +43,9 @@ def test_device_pack_and_post_equal_cpu_build_of_the_same_text():
     import torch
     from boundmpc_amd import BatchedOCPSolver, stream as bstream
     from oracle import c_oracle
+    from tests.closed_loop import fixture_mpc
     from tests.emu import emu
-    (mpc, d6), _ = _mpcs()
+    mpc, d6 = fixture_mpc(1)
     d7 = np.load(os.path.join(G, "g7_closedloop_exp1.npz"))
     solver = BatchedOCPSolver(10, 4, 0.1)
     sb = bstream.StreamBatch(solver, [mpc])
@@ -165,13 +145,7 @@ def test_256_streams_real_time_mode_is_safeguarded_and_tracks_the_converged_loop
     from boundmpc_amd import BatchedOCPSolver, stream as bstream, workload
     from boundmpc_amd.robot_model import RobotModel
     B, T, FEAS = 256, 40, 1e-2
-    q0s = workload.random_q0(B, seed=3)
-    mpcs, recs = [], []
-    for q0 in q0s:
-        m, p0fk = workload.make_mpc(q0)
-        mpcs.append(m)
-        recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0.0, 0.0]), np.zeros(7)))
-    recs = np.stack(recs)
+    mpcs, recs = workload.make_streams(B, seed=3)
     st = torch.cuda.Stream()
     runs = {}
     with torch.cuda.stream(st):
@@ -182,24 +156,17 @@ def test_256_streams_real_time_mode_is_safeguarded_and_tracks_the_converged_loop
             sb = bstream.StreamBatch(slv, mpcs)
             sb.set_robot(recs)
             Q, ms, applied, viol_applied, alive = [], [], [], [], []
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            for t in range(T):
-                if t == 0:      # cold start from rest: to tolerance in both runs
-                    sb.tick(max_iter=100, warm_dual=True, simulate=True)
-                    if not capped:
-                        sb.dual.zero_()
-                else:
-                    e0.record(); sb.tick_graph(simulate=True, warm_dual=capped, accept_capped=capped); e1.record(); e1.synchronize()
-                    ms.append(e0.elapsed_time(e1))
-                    ok = (sb.traj[:, -2] > 0.5)
+            for t in sb.closed_loop(T, warm=capped, accept_capped=capped, timed=True):      # (tick 0, the cold start from rest: to tolerance in both runs)
+                if t > 0:
+                    ms.append(sb.tick_ms)
+                    ok = sb.applied()
                     applied.append(float(ok.double().mean().item()))
                     if capped:
-                        bad = ok & (sb.status != 0) & (sb.traj[:, -1] >= FEAS)
+                        bad = ok & (sb.status != 0) & (sb.g_viol() >= FEAS)
                         viol_applied.append(int(bad.sum().item()))
-                    alive.append(float((sb.state[:, bstream.SS["VALID"]] > 0.5).double().mean().item()))
+                    alive.append(float(sb.valid().double().mean().item()))
                 Q.append(sb.robot[:, :7].clone())
-            runs[name] = (torch.stack(Q).cpu().numpy(), np.array(ms), np.array(applied), np.array(viol_applied), np.array(alive),
-                          sb.state[:, bstream.SS["PHI"]].cpu().numpy())
+            runs[name] = (torch.stack(Q).cpu().numpy(), np.array(ms), np.array(applied), np.array(viol_applied), np.array(alive), sb.phi().cpu().numpy())
             sb.close(); slv.close()
     Qc, msc, apc, _, alc, phic = runs["converged"]
     Qr, msr, apr, bad, alr, phir = runs["rtgn"]
@@ -232,7 +199,8 @@ def test_replanning_on_the_device_matches_reference_update_g11():
     import torch
     from boundmpc_amd import BatchedOCPSolver, stream as bstream
     from oracle import c_oracle
-    (mpc, d6), _ = _mpcs()
+    from tests.closed_loop import fixture_mpc
+    mpc, d6 = fixture_mpc(1)
     d7 = np.load(os.path.join(G, "g7_closedloop_exp1.npz"))
     d = np.load(os.path.join(G, "g11_update.npz"))
     T_UPD = int(d["t_update"])
@@ -264,7 +232,7 @@ def test_replanning_on_the_device_matches_reference_update_g11():
         st = sb.state.cpu().numpy()[0]
         td, _ = bstream.unpack_traj(sb.traj.cpu().numpy()[0], 10)
         np.testing.assert_allclose(td["q"], d["traj_q"][i], atol=1e-11)
-        assert abs(st[bstream.SS["PHI"]] - d["phi_current"][i]) < 1e-11 and int(st[0]) == int(d["sector"][i])
+        assert abs(bstream.phi(st) - d["phi_current"][i]) < 1e-11 and int(st[0]) == int(d["sector"][i])
         np.testing.assert_allclose(st[10:13], d["iw_ref"][i], atol=1e-11)
     sb.close(); solver.close()
 
@@ -274,17 +242,12 @@ def test_device_tick_other_horizons_and_windows_g12(N, S):
     """The whole device tick {pack, solve, post} for other (n, nr_segs) than the experiments': closed loop against the reference's own
     step() driven with the CPU oracle (fixture G12) -- parameter layout 141 + 91 S, warm start 44 N, N <= 11 and N > 11 kernels."""
     import torch
-    from boundmpc_amd import BatchedOCPSolver, stream as bstream, workload
-    from boundmpc_amd.bound_mpc import BoundMPC
-    from tests.test_stream import _Oracle
-    d6 = np.load(os.path.join(G, "g6_pack_exp2_tick0.npz"))
+    from boundmpc_amd import BatchedOCPSolver, stream as bstream
+    from tests.closed_loop import fixture_mpc
     d = np.load(os.path.join(G, "g12_pack_other_sizes.npz"))
     k = f"n{N}s{S}_"
     dt, mask = float(d[k + "dt"]), d[k + "mask"]
-    mk = lambda key: [np.array(v) for v in d6[key]]
-    mpc = BoundMPC(mk("p_via"), mk("r_via"), [mk("p_lower"), mk("p_upper")], [mk("r_lower"), mk("r_upper")], mk("bp1_in"), mk("br1_in"),
-                   list(d6["s_in"]), list(d6["e_p_min_in"]), list(d6["e_r_min_in"]), list(d6["e_p_max_in"]), list(d6["e_r_max_in"]),
-                   p0=d6["p0fk"].copy(), params=workload.Params(n=N, dt=dt, nr_segs=S, weights=d["weights"]), solver=_Oracle())
+    mpc, _ = fixture_mpc(2, n=N, dt=dt, nr_segs=S, weights=d["weights"])
     solver = BatchedOCPSolver(N, S, dt)
     sb = bstream.StreamBatch(solver, [mpc])
     sb.set_robot(bstream.robot_record(d[k + "q"][0], d[k + "dq"][0], d[k + "ddq"][0], d[k + "p_lie"][0], d[k + "v"][0],
@@ -297,7 +260,7 @@ def test_device_tick_other_horizons_and_windows_g12(N, S):
         td, fl = bstream.unpack_traj(sb.traj.cpu().numpy()[0], N)
         assert fl["success"] and fl["n_valid"] == N
         np.testing.assert_allclose(td["q"], d[k + "traj_q"][i], atol=2e-6)
-        assert abs(sb.state.cpu().numpy()[0][bstream.SS["PHI"]] - d[k + "phi_current"][i]) < 1e-6
+        assert abs(float(sb.phi()[0]) - d[k + "phi_current"][i]) < 1e-6
     sb.close(); solver.close()
 
 
@@ -311,16 +274,11 @@ def test_fused_tick_runs_the_restoration_mode_of_the_handle(mode):
     import torch
     from boundmpc_amd import BatchedOCPSolver, stream as bstream, workload
     B, T = 48, 130
-    q0s = workload.random_q0(256, seed=3)[:B]
-    mpcs, recs = [], []
-    for q0 in q0s:
-        m, p0fk = workload.make_mpc(q0)
-        mpcs.append(m)
-        recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0.0, 0.0]), np.zeros(7)))
+    mpcs, recs = workload.make_streams(256, seed=3, take=B)
     sa, sb_ = BatchedOCPSolver(10, 4, 0.1, max_iter=100), BatchedOCPSolver(10, 4, 0.1, max_iter=100)
     sa.set_restoration(mode); sb_.set_restoration(mode)
     a, b = bstream.StreamBatch(sa, mpcs), bstream.StreamBatch(sb_, mpcs)
-    a.set_robot(np.stack(recs)); b.set_robot(np.stack(recs))
+    a.set_robot(recs); b.set_robot(recs)
     nd, ns, worst, n2 = 0, 0, 0, 0
     for t in range(T):
         for k in ("state", "robot", "dual", "x", "traj"):      # the unfused loop starts every tick from the fused loop's state
@@ -344,27 +302,17 @@ def test_long_closed_loops_through_the_hard_part_of_the_path():
     import torch
     from boundmpc_amd import BatchedOCPSolver, stream as bstream, workload
     B, T = 64, 130
-    q0s = workload.random_q0(256, seed=3)[:B]
-    mpcs, recs = [], []
-    for q0 in q0s:
-        m, p0fk = workload.make_mpc(q0)
-        mpcs.append(m)
-        recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0.0, 0.0]), np.zeros(7)))
+    mpcs, recs = workload.make_streams(256, seed=3, take=B)
     slv = BatchedOCPSolver(10, 4, 0.1, max_iter=100)
     sb = bstream.StreamBatch(slv, mpcs)
-    sb.set_robot(np.stack(recs))
+    sb.set_robot(recs)
     side = torch.cuda.Stream()
     phis, ecs, oks = [], [], []
     with torch.cuda.stream(side):
-        for t in range(T):
-            if t == 0:
-                sb.tick(max_iter=100, warm_dual=True, simulate=True)
-            else:
-                sb.tick_graph(warm_dual=True, simulate=True)
-            side.synchronize()
-            phis.append(sb.state[:, bstream.SS["PHI"]].cpu().numpy().copy())
+        for t in sb.closed_loop(T):
+            phis.append(sb.phi().cpu().numpy().copy())
             ecs.append(sb.state[:, bstream.SS["ERRCNT"]].cpu().numpy().copy())
-            oks.append((sb.traj[:, -2] > 0.5).cpu().numpy().copy())
+            oks.append(sb.applied().cpu().numpy().copy())
             assert bool(torch.isfinite(sb.state).all()) and bool(torch.isfinite(sb.robot).all()) and bool(torch.isfinite(sb.x).all()), t
     phis, ecs, oks = np.array(phis), np.array(ecs), np.array(oks)
     # no jump backwards on healthy ticks (a stream may creep back: dphi has no lower bound).  A stream that is replaying a plan it accepted on the reference's
@@ -374,7 +322,7 @@ def test_long_closed_loops_through_the_hard_part_of_the_path():
     assert dphi[ecs[1:] == 0].min() > -0.05 and dphi.min() > -0.3, (dphi[ecs[1:] == 0].min(), dphi.min())
     assert phis[-1].max() > 5.0 and np.median(phis[-1]) > 3.0       # the loops got through the later segments
     assert oks.mean() > 0.9
-    stuck = ecs[-1] >= 10                                           # error count past N: no plan is returned any more
+    stuck = ~sb.has_plan().cpu().numpy()                            # error count past N: no plan is returned any more
     assert stuck.any(), ecs[-1].max()
     assert np.abs(phis[-1][stuck] - phis[-5][stuck]).max() == 0.0   # ... and the stream stays where it is
     sb.close(); slv.close()
@@ -429,17 +377,12 @@ def test_streams_at_36_stages_fused_tick_matches_the_three_kernel_tick():
     import torch
     from boundmpc_amd import BatchedOCPSolver, stream as bstream, workload
     N = 36
-    q0s = workload.random_q0(6, seed=11)
     runs = []
     for fused in (True, False):
         s = BatchedOCPSolver(N, 4, 0.1)
-        mpcs, recs = [], []
-        for q0 in q0s:
-            m, p0fk = workload.make_mpc(q0, N=N)
-            mpcs.append(m)
-            recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0, 0]), np.zeros(7)))
+        mpcs, recs = workload.make_streams(6, seed=11, N=N)
         sb = bstream.StreamBatch(s, mpcs)
-        sb.set_robot(np.stack(recs))
+        sb.set_robot(recs)
         for t in range(5):
             sb.tick(simulate=True, fused=fused)
         torch.cuda.synchronize()
@@ -459,39 +402,26 @@ def _budgeted_closed_loops(slv, budget_us, cap=0, row_cap=0.0):
     import torch
     from boundmpc_amd import stream as bstream, workload
     B, T = 256, 131
-    q0s = workload.random_q0(B, seed=3)
-    mpcs, recs = [], []
-    for q0 in q0s:
-        m, p0fk = workload.make_mpc(q0)
-        mpcs.append(m)
-        recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0.0, 0.0]), np.zeros(7)))
+    mpcs, recs = workload.make_streams(B, seed=3)
     slv.set_rt_feasibility_tol(1e-2)
     slv.set_rt_position_row_cap(row_cap)
     st = torch.cuda.Stream()
     with torch.cuda.stream(st):
         sb = bstream.StreamBatch(slv, mpcs)
-        sb.set_robot(np.stack(recs))
+        sb.set_robot(recs)
         assert slv.team_info(B)["waves"] == 4      # 256 streams = the resident teams of an MI355X
-        ms, Q, applied, tube_p, tube_r, row_p = [], [], [], [], [], []
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for t in range(T):
-            if t == 0:      # cold start from rest: to tolerance, without a budget
-                sb.tick(max_iter=100, warm_dual=True, simulate=True)
-                slv.set_time_budget_us(budget_us)      # read when the tick graph is captured
-            else:
-                e0.record(); sb.tick_graph(max_iter=cap, simulate=True, warm_dual=True, accept_capped=True); e1.record(); e1.synchronize()
-                ms.append(e0.elapsed_time(e1))
-                applied.append(float((sb.traj[:, -2] > 0.5).double().mean().item()))
-                has_plan = (sb.state[:, bstream.SS["ERRCNT"]] < 10).cpu().numpy()
-                ex_p, ex_r = bstream.tube_excess_of_state(sb.p.cpu().numpy())
-                tube_p.append(np.where(has_plan, ex_p.max(axis=1), -np.inf)); tube_r.append(np.where(has_plan, ex_r.max(axis=1), -np.inf))
-                app = (sb.traj[:, -2] > 0.5).cpu().numpy()
-                row_p.append(np.where(app, sb.g.reshape(B, 10, 43)[:, 0, 39:41].cpu().numpy().max(axis=1), -np.inf))
+        ms, Q, applied, tubes = [], [], [], []
+        for t in sb.closed_loop(T, cap=cap, accept_capped=True, budget_us=budget_us, timed=True):
+            if t > 0:
+                ms.append(sb.tick_ms)
+                applied.append(float(sb.applied().double().mean().item()))
+                tubes.append(sb.tick_tube_figures())
             Q.append(sb.robot[:, :7].clone())
-        alive = float((sb.state[:, bstream.SS["VALID"]] > 0.5).double().mean().item())
+        alive = float(sb.valid().double().mean().item())
         Q = torch.stack(Q).cpu().numpy()
         sb.close(); slv.close()
-    return np.array(ms), alive, float(np.mean(applied)), Q, np.array(tube_p), np.array(tube_r), np.array(row_p)
+    tube_p, tube_r, row_p, _ = (np.array(a) for a in zip(*tubes))
+    return np.array(ms), alive, float(np.mean(applied)), Q, tube_p, tube_r, row_p
 
 
 @pytest.mark.gpu
@@ -561,24 +491,19 @@ def test_tick_with_a_barrier_level_fallback():
     import torch
     from boundmpc_amd import BatchedOCPSolver, stream as bstream, workload
     B = 32
-    q0s = workload.random_q0(256, seed=3)[:B]
-    mpcs, recs = [], []
-    for q0 in q0s:
-        m, p0fk = workload.make_mpc(q0)
-        mpcs.append(m)
-        recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0.0, 0.0]), np.zeros(7)))
+    mpcs, recs = workload.make_streams(256, seed=3, take=B)
     def loop(with_fallback, ticks=60, fail_at=30):
         slv = BatchedOCPSolver(10, 4, 0.1, max_iter=100, stall_window=16); slv.set_restoration(False); slv.set_rt_feasibility_tol(1e-4)
         level = BatchedOCPSolver(10, 4, 0.1, tol=1e-3, max_iter=14, fixed_barrier=1.0); level.set_restoration(False)
-        sb = bstream.StreamBatch(slv, mpcs); sb.set_robot(np.stack(recs)); X, applied, nfb = [], [], []
+        sb = bstream.StreamBatch(slv, mpcs); sb.set_robot(recs); X, applied, nfb = [], [], []
         for t in range(ticks):
             cap = 2 if t == fail_at else 24      # a tick on which no solve can converge
             if with_fallback:
                 nfb.append(sb.tick_with_fallback(level, max_iter=cap))
             else:
                 sb.tick(max_iter=cap, warm_dual=True, simulate=True, fused=False, accept_capped=True); nfb.append(0)
-            X.append(sb.x.clone()); applied.append((sb.traj[:, -2] > 0.5).cpu().numpy())
-        alive = (sb.state[:, bstream.SS["VALID"]] > 0.5).cpu().numpy()
+            X.append(sb.x.clone()); applied.append(sb.applied().cpu().numpy())
+        alive = sb.valid().cpu().numpy()
         sb.close(); slv.close(); level.close()
         return torch.stack(X), np.array(applied), np.array(nfb), alive
     Xa, app_a, nfb_a, alive_a = loop(True)
@@ -625,41 +550,23 @@ def test_fixed_barrier_level_loops_on_the_gpu_retrace_the_cpu_mirror(level):
     graph -- against the CPU mirror: the g++ build of the stream functions (tests/emu) around the CPU oracle with the same options.  Plant joint positions
     to 1e-6 rad on every tick, the same ticks applied.  level "auto": the level sets itself per stream (clamp(0.02 (phi_max - phi), 0.01, 0.1), written into the
     dual state by the device-side pack, held inside the tick): mirrored by the CPU build of stream_pack with the same rule and the oracle's hold_mu."""
-    import torch
     from boundmpc_amd import BatchedOCPSolver, stream as bstream, workload
-    from oracle import c_oracle
-    from tests.emu import emu
+    from tests.closed_loop import cpu_mirror_loop
     B, T, N, S, H = 6, 40, 10, 4, 0.1
-    q0s = workload.random_q0(256, seed=3)[:B]
-    mpcs, recs = [], []
-    for q0 in q0s:
-        m, p0fk = workload.make_mpc(q0)
-        mpcs.append(m)
-        recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0.0, 0.0]), np.zeros(7)))
+    mpcs, recs = workload.make_streams(256, seed=3, take=B)
     slv = BatchedOCPSolver(N, S, H, tol=1e-3, max_iter=30, fixed_barrier=level); slv.set_rt_feasibility_tol(1e-2)
-    sb = bstream.StreamBatch(slv, mpcs); sb.set_robot(np.stack(recs))
+    sb = bstream.StreamBatch(slv, mpcs); sb.set_robot(recs)
     Qg, Ag = [], []
-    for t in range(T):
-        if t == 0:
-            sb.tick(max_iter=100, warm_dual=True, simulate=True)
-        else:
-            sb.tick_graph(max_iter=5, warm_dual=True, simulate=True, accept_capped=True)
-        torch.cuda.synchronize()
-        Qg.append(sb.robot[:, :7].cpu().numpy().copy()); Ag.append((sb.traj[:, -2] > 0.5).cpu().numpy().copy())
+    for t in sb.closed_loop(T, cap=5, accept_capped=True):
+        Qg.append(sb.robot[:, :7].cpu().numpy().copy()); Ag.append(sb.applied().cpu().numpy().copy())
     sb.close(); slv.close()
     auto = level == "auto"
     kw = dict(tol=1e-3, mu_init=0.1, mu_warm=0.01, mu_min_fac=10.0, hold_mu=1) if auto else dict(tol=1e-3, mu_init=0.1, mu_warm=0.1, mu_min_fac=100.0)
     rule = (0.02, 0.01, 0.1) if auto else (0.0, 0.0, 0.0)
     for b in range(B):
-        Tb, M = bstream.path_table(mpcs[b].ref_path)
-        ss = bstream.initial_state(mpcs[b], N); ss[bstream.SS["NENT"]] = M
-        rb = recs[b].copy(); state = np.zeros((1, c_oracle.state_len(N))); xlast = None
-        for t in range(T):
-            p, x0 = emu.stream_pack(N, S, Tb, ss, rb, dual=state[0], xlast=xlast, level_rule=rule)
-            r = c_oracle.solve(p, x0, N, S, H, opts=c_oracle.default_opts(max_iter=100 if t == 0 else 5, **kw), nthreads=1, state=state)
-            tr = emu.stream_post(N, S, H, Tb, ss, rb, r["x"][0], r["g"][0], int(r["status"][0]), simulate=True, flags=0 if t == 0 else 2, rt_tol=1e-2)
-            _, fl = bstream.unpack_traj(tr, N)
-            xlast = r["x"][0]
+        for c in cpu_mirror_loop(mpcs[b], recs[b], T, N, S, H, cap=5, accept_capped=True, rt_tol=1e-2, level_rule=rule, opts_kw=kw):
+            t, rb = c["t"], c["rb"]
+            _, fl = bstream.unpack_traj(c["traj"], N)
             assert bool(fl["success"]) == bool(Ag[t][b]), (b, t)
             np.testing.assert_allclose(rb[bstream.RB["Q"]:bstream.RB["Q"] + 7], Qg[t][b], atol=1e-6, err_msg=f"stream {b} tick {t}")
 
@@ -671,27 +578,22 @@ def test_fixed_level_loops_reach_the_goals_of_the_reference_experiments():
     155 / 59 -- with >= 97 % of the ticks applied and no failed stream; on the level 0.1 (the robust choice for the 130-tick benchmark loops) they stay
     alive but stall short of the end point.  The level that sets itself (fixed_barrier="auto": clamp(0.02 (phi_max - phi), 0.01, 0.1) per stream) reaches both
     goals after 161 / 64 ticks -- and keeps 94.9 % of the 256 benchmark plans (the next test): one default for both tasks."""
-    import torch
     from boundmpc_amd import BatchedOCPSolver, stream as bstream
-    ms = _mpcs()
+    from tests.closed_loop import reference_experiment_streams
+    mpcs, recs, _ = reference_experiment_streams()
 
     def run(level, K=8, ticks=200):
         slv = BatchedOCPSolver(10, 4, 0.1, tol=1e-3, max_iter=30, fixed_barrier=level); slv.set_rt_feasibility_tol(1e-2)
-        sb = bstream.StreamBatch(slv, [m for m, _ in ms]); sb.set_robot(np.stack([_robot0(m, d) for m, d in ms]))
+        sb = bstream.StreamBatch(slv, mpcs); sb.set_robot(recs)
         done, app = [None, None], []
-        for t in range(ticks):
-            if t == 0:
-                sb.tick(max_iter=100, warm_dual=True, simulate=True)
-            else:
-                sb.tick_graph(max_iter=K, warm_dual=True, simulate=True, accept_capped=True)
-            torch.cuda.synchronize()
-            st = sb.state.cpu().numpy(); app.append((sb.traj[:, -2] > 0.5).cpu().numpy().copy())
+        for t in sb.closed_loop(ticks, cap=K, accept_capped=True):
+            phi = sb.phi().cpu().numpy(); app.append(sb.applied().cpu().numpy().copy())
             for b in range(2):
-                if done[b] is None and ms[b][0].phi_max[0] - st[b, bstream.SS["PHI"]] <= 0.01:
+                if done[b] is None and mpcs[b].phi_max[0] - phi[b] <= 0.01:
                     done[b] = t + 1
             if all(d is not None for d in done):
                 break
-        valid = st[:, bstream.SS["VALID"]].copy(); phi = st[:, bstream.SS["PHI"]].copy()
+        valid = sb.valid().cpu().numpy()
         sb.close(); slv.close()
         return done, np.mean(app, axis=0), valid, phi
     done, app, valid, phi = run(0.01)
@@ -701,3 +603,41 @@ def test_fixed_level_loops_reach_the_goals_of_the_reference_experiments():
     done, app, valid, phi = run(0.1)
     assert done == [None, None] and valid.all() and app.min() >= 0.97 and phi[0] > 6.0 and phi[1] > 1.0      # alive, applied, short of the end point
 
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("warm,graph", [(True, True), (False, False)], ids=["warm-graph", "cold-direct"])
+def test_closed_loop_driver_equals_the_protocol_written_out_by_hand(warm, graph):
+    """StreamBatch.closed_loop against the tick protocol it stands for, written out here: tick 0 solved out (100 iterations, dual state kept, the
+    reference's rule), then the captured graph of the capped real-time tick.  6 streams x 12 ticks on the self-setting barrier level, five Newton steps
+    per tick, acceptance at 1e-2: no clock in these ticks, so every buffer of the two batches is equal bit for bit after the last tick.
+    cold-direct: the other branches of the driver -- the dual state zeroed behind tick 0, direct launches, timed -- on loops solved to tolerance
+    (1e-8, at most 100 iterations per tick: no clock either)."""
+    import torch
+    from boundmpc_amd import BatchedOCPSolver, stream as bstream, workload
+    B, T, N = 6, 12, 10
+    cap = 5 if warm else 0      # (an iteration cap needs the dual state)
+    ends = []
+    for driver in (True, False):
+        mpcs, recs = workload.make_streams(B, seed=3, N=N)
+        slv = BatchedOCPSolver(N, 4, 0.1, tol=1e-3, max_iter=30, fixed_barrier="auto") if warm else BatchedOCPSolver(N, 4, 0.1, max_iter=100, stall_window=16)
+        slv.set_rt_feasibility_tol(1e-2)
+        sb = bstream.StreamBatch(slv, mpcs); sb.set_robot(recs)
+        if driver:
+            ms = [sb.tick_ms for t in sb.closed_loop(T, cap=cap, warm=warm, accept_capped=warm, graph=graph, timed=not graph)]
+            assert len(ms) == T and ms[0] is None and all((m is not None and m > 0.0) != graph for m in ms[1:])
+        else:
+            for t in range(T):
+                if t == 0:
+                    sb.tick(max_iter=100, warm_dual=True, simulate=True)
+                    if not warm:
+                        sb.dual.zero_()
+                elif graph:
+                    sb.tick_graph(max_iter=cap, warm_dual=warm, simulate=True, accept_capped=warm)
+                else:
+                    sb.tick(max_iter=cap, warm_dual=warm, simulate=True, accept_capped=warm)
+            torch.cuda.synchronize()
+        ends.append({k: getattr(sb, k).clone() for k in ("robot", "state", "x", "dual", "traj")})
+        sb.close(); slv.close()
+    assert bool(bstream.applied(ends[0]["traj"]).any())      # (plans were applied: the loops ran)
+    for k, v in ends[0].items():
+        assert torch.equal(v, ends[1][k]), k

@@ -165,26 +165,19 @@ def test_team_kernel_warm_entry_iteration_cap_and_other_horizons():
 def test_team_tick_equals_one_wave_tick_in_closed_loop():
     """The fused closed-loop tick {pack, solve, post} by teams (wave 0 packs and post-processes, the team solves) against the one-wave tick
     over 12 ticks of 16 streams: same plant trajectories."""
-    import torch
     from boundmpc_amd import workload
     from boundmpc_amd import stream as bstream
-    q0s = workload.random_q0(16, seed=3)
     outs = []
     for waves in (1, 4):
         from boundmpc_amd import BatchedOCPSolver
         s = BatchedOCPSolver(10, 4, 0.1)
         s.set_team_waves(waves)
-        mpcs, recs = [], []
-        for q0 in q0s:
-            m, p0fk = workload.make_mpc(q0)
-            mpcs.append(m)
-            recs.append(bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([m.phi_max[0], 0, 0]), np.zeros(7)))
+        mpcs, recs = workload.make_streams(16, seed=3)
         sb = bstream.StreamBatch(s, mpcs)
-        sb.set_robot(np.stack(recs))
+        sb.set_robot(recs)
         try:
-            for t in range(12):
-                sb.tick(warm_dual=True, simulate=True)
-            torch.cuda.synchronize()
+            for t in sb.closed_loop(12, first_cap=0, graph=False):      # direct fused ticks, every one to the handle's tolerance
+                pass
             outs.append((sb.robot.cpu().numpy().copy(), sb.iters.cpu().numpy().copy(), sb.status.cpu().numpy().copy(), sb.traj.cpu().numpy().copy()))
         finally:
             sb.close(); s.close()

@@ -9,38 +9,13 @@ import numpy as np
 import pytest
 
 from boundmpc_amd import stream as bstream, workload
-from boundmpc_amd.bound_mpc import BoundMPC, integrate_joint
+from boundmpc_amd.bound_mpc import integrate_joint
 from boundmpc_amd.robot_model import RobotModel
 from oracle import c_oracle
+from tests.closed_loop import Oracle, cpu_mirror_loop, fixture_mpc, fixture_robot_record, stream_arrays
 from tests.emu import emu
 
 G = os.path.join(os.path.dirname(__file__), "golden")
-
-
-class _Oracle:
-    """nlpsol-shaped solver backed by the CPU oracle; `fail_at` ticks report failure with a wildly infeasible g."""
-
-    def __init__(self, fail_at=()):
-        self.calls, self.fail_at = 0, set(fail_at)
-
-    def generate_dependencies(self, *a, **k):
-        pass
-
-    def solve(self, p, x0):
-        r = c_oracle.solve(p, x0, 10, 4, 0.1, nthreads=1)
-        x, g, st = r["x"][0], r["g"][0].copy(), int(r["status"][0])
-        if self.calls in self.fail_at:
-            g[:] = 1.0; st = 3
-        self.calls += 1
-        return x, g, st, int(r["iters"][0])
-
-    def __call__(self, x0=None, lbx=None, ubx=None, lbg=None, ubg=None, p=None):
-        x, g, st, it = self.solve(np.asarray(p, dtype=float), np.asarray(x0, dtype=float))
-        self._st = dict(iter_count=it, success=st == 0, return_status="x")
-        return dict(x=x, g=g, lam_g=np.zeros_like(g), lam_x=np.zeros_like(x), f=0.0)
-
-    def stats(self):
-        return self._st
 
 
 def _same_rotation(rv_a, rv_b, tol):
@@ -49,44 +24,26 @@ def _same_rotation(rv_a, rv_b, tol):
     np.testing.assert_allclose(R.from_rotvec(rv_a).as_matrix(), R.from_rotvec(rv_b).as_matrix(), atol=tol)
 
 
-def _fixture_mpc(which, solver):
-    d6 = np.load(os.path.join(G, f"g6_pack_exp{which}_tick0.npz"))
-    mk = lambda k: [np.array(v) for v in d6[k]]
-    mpc = BoundMPC(mk("p_via"), mk("r_via"), [mk("p_lower"), mk("p_upper")], [mk("r_lower"), mk("r_upper")], mk("bp1_in"), mk("br1_in"),
-                   list(d6["s_in"]), list(d6["e_p_min_in"]), list(d6["e_r_min_in"]), list(d6["e_p_max_in"]), list(d6["e_r_max_in"]),
-                   p0=d6["p0fk"].copy(), params=workload.Params(weights=d6["weights_f64"]), solver=solver)
-    return mpc, d6
-
-
 @pytest.mark.parametrize("which,ticks", [(1, 155), (2, 59)])
 def test_stream_closed_loop_retraces_reference_fixture(which, ticks):
     """pack -> (oracle) solve -> post with the plant simulation, nothing else: every tick's p and x0 equal what the reference's
     step() assembled, the trajectory and the advanced phi / rotation-reference state equal compute_return_data's."""
-    mpc, d6 = _fixture_mpc(which, _Oracle())
+    mpc, d6 = fixture_mpc(which, Oracle())
     d7 = np.load(os.path.join(G, f"g7_closedloop_exp{which}.npz"))
-    T, M = bstream.path_table(mpc.ref_path)
-    ss = bstream.initial_state(mpc, 10); ss[bstream.SS["NENT"]] = M
-    rm = RobotModel()
-    q = d6["q0"].copy()
-    rb = bstream.robot_record(q, np.zeros(7), np.zeros(7), rm.forward_kinematics(q, np.zeros(7))[0], np.zeros(6),
-                              np.array([mpc.phi_max[0], 0, 0]), np.zeros(7))
-    sol = _Oracle()
     mask = d6["p_defined_mask"]        # row S of a4..a0 is uninitialised memory in the reference (SURVEY A.9); defined here as row S-1
     worst_p = worst_x0 = 0.0
-    for t in range(ticks):
-        np.testing.assert_allclose(rb[:7], d7["q"][t], atol=2e-6)
-        p, x0 = emu.stream_pack(10, 4, T, ss, rb)
+    for c in cpu_mirror_loop(mpc, fixture_robot_record(mpc, d6), ticks, solve=Oracle().solve):
+        t, p, x0, ss = c["t"], c["p"], c["x0"], c["ss"]
+        np.testing.assert_allclose(c["q"], d7["q"][t], atol=2e-6)
         worst_p = max(worst_p, np.abs(p - d7["p"][t])[mask].max()); worst_x0 = max(worst_x0, np.abs(x0 - d7["x0"][t]).max())
-        x, g, st, _ = sol.solve(p, x0)
-        tr = emu.stream_post(10, 4, 0.1, T, ss, rb, x, g, st, simulate=True)
-        td, fl = bstream.unpack_traj(tr, 10)
+        td, fl = bstream.unpack_traj(c["traj"], 10)
         assert fl["success"] and fl["n_valid"] == 10 and not fl["using_previous"]
         for k in ("q", "dq", "ddq", "dddq", "p", "v", "a", "phi", "dphi", "ddphi", "dddphi"):
             # the loop feeds the solver's 1e-8-tolerance round-off back into the next problem; jerks are the weakly determined
             # variables (w_jerk = 1e-4), everything integrated from them is smoother
             tol = 2e-3 if k in ("dddq", "dddphi") else (2e-4 if k in ("ddq", "a", "ddphi") else 2e-5)
             np.testing.assert_allclose(td[k], d7["traj_" + k][t], atol=tol, err_msg=f"tick {t} {k}")
-        assert abs(ss[bstream.SS["PHI"]] - d7["phi_current"][t]) < 1e-6
+        assert abs(bstream.phi(ss) - d7["phi_current"][t]) < 1e-6
         _same_rotation(ss[7:10], d7["pr_ref"][t], 1e-6)
         np.testing.assert_allclose(ss[10:13], d7["iw_ref"][t], atol=1e-6)
         assert int(ss[0]) == int(d7["sector"][t])
@@ -97,10 +54,9 @@ def test_stream_closed_loop_retraces_reference_fixture(which, ticks):
 @pytest.mark.parametrize("which", [1, 2])
 def test_stream_pack_is_exact_given_the_reference_state(which):
     """Open loop: feed the recorded robot state and the recorded previous solution of each tick -> p and x0 to round-off."""
-    mpc, d6 = _fixture_mpc(which, _Oracle())
+    mpc, d6 = fixture_mpc(which, Oracle())
     d7 = np.load(os.path.join(G, f"g7_closedloop_exp{which}.npz"))
-    T, M = bstream.path_table(mpc.ref_path)
-    ss = bstream.initial_state(mpc, 10); ss[bstream.SS["NENT"]] = M
+    T, ss = stream_arrays(mpc, 10)
     xphid = np.array([mpc.phi_max[0], 0, 0])
     mask = d6["p_defined_mask"]
     n = d7["p"].shape[0]
@@ -111,7 +67,7 @@ def test_stream_pack_is_exact_given_the_reference_state(which):
         np.testing.assert_allclose(x0, d7["x0"][t], atol=1e-13)
         g = c_oracle.eval_fg(d7["p"][t], d7["x"][t], 10, 4, 0.1)[1]
         emu.stream_post(10, 4, 0.1, T, ss, rb.copy(), d7["x"][t], g, int(d7["status"][t]), simulate=False)
-        assert abs(ss[bstream.SS["PHI"]] - d7["phi_current"][t]) < 1e-12
+        assert abs(bstream.phi(ss) - d7["phi_current"][t]) < 1e-12
         _same_rotation(ss[7:10], d7["pr_ref"][t], 1e-11)
         np.testing.assert_allclose(ss[10:13], d7["iw_ref"][t], atol=1e-12)
 
@@ -121,27 +77,21 @@ def test_stream_matches_host_mirror_with_failures():
     (error count, fallback to the previous plan, shortened trajectories) follows the host mirror's."""
     q0 = workload.random_q0(3, seed=5)[2]
     fails = (3, 4, 9)
-    mpc, p0fk = workload.make_mpc(q0, solver=_Oracle(fails))
-    ref, _ = workload.make_mpc(q0, solver=_Oracle())
-    T, M = bstream.path_table(ref.ref_path)
-    ss = bstream.initial_state(ref, 10); ss[bstream.SS["NENT"]] = M
+    mpc, p0fk = workload.make_mpc(q0, solver=Oracle(fails))
+    ref, _ = workload.make_mpc(q0, solver=Oracle())
     rm = RobotModel()
     q, dq, ddq, jerk, v = q0.copy(), np.zeros(7), np.zeros(7), np.zeros(7), np.zeros(6)
     x_phi_d = np.array([mpc.phi_max[0], 0, 0])
-    rb = bstream.robot_record(q, dq, ddq, p0fk, v, x_phi_d, jerk)
-    sol = _Oracle(fails)
-    for t in range(14):
+    for c in cpu_mirror_loop(ref, bstream.robot_record(q, dq, ddq, p0fk, v, x_phi_d, jerk), 14, solve=Oracle(fails).solve):
+        t, ss, rb = c["t"], c["ss"], c["rb"]
         p_lie = rm.forward_kinematics(q, dq)[0]
         w0, params, _ = mpc.pack(q, dq, ddq, p_lie, v, x_phi_d, jerk)
         # undo the side effects of the extra pack() call?  none: pack() only reads/updates the window, which step() repeats identically
         traj, _, _, _, _ = mpc.step(q, dq, ddq, p_lie, v, x_phi_d, jerk)
-        p, x0 = emu.stream_pack(10, 4, T, ss, rb)
         # two independent closed loops: each solve's 1e-8-level freedom in the jerks feeds the next tick
-        np.testing.assert_allclose(p, params, atol=2e-6, rtol=1e-9, err_msg=f"tick {t}")
-        np.testing.assert_allclose(x0, np.array(w0), atol=2e-6)
-        x, g, st, _ = sol.solve(p, x0)
-        tr = emu.stream_post(10, 4, 0.1, T, ss, rb, x, g, st, simulate=True)
-        td, fl = bstream.unpack_traj(tr, 10)
+        np.testing.assert_allclose(c["p"], params, atol=2e-6, rtol=1e-9, err_msg=f"tick {t}")
+        np.testing.assert_allclose(c["x0"], np.array(w0), atol=2e-6)
+        td, fl = bstream.unpack_traj(c["traj"], 10)
         assert int(ss[bstream.SS["ERRCNT"]]) == mpc.error_count
         assert fl["using_previous"] == (t in fails)
         assert fl["n_valid"] == 10 - mpc.error_count
@@ -184,12 +134,11 @@ def test_stream_replanning_matches_reference_update_g11():
     """Re-planning on the stream functions: the recorded experiment-1 loop up to the tick of the update, `apply_update` (the state part
     of BoundMPC.update), then the ticks after it -- whose warm start goes through the re-projection branch with the Cartesian
     derivatives of the previous plan kept by stream_post -- against what the REFERENCE's own update()/step() produced (fixture G11)."""
-    mpc, d6 = _fixture_mpc(1, _Oracle())
+    mpc, d6 = fixture_mpc(1, Oracle())
     d7 = np.load(os.path.join(G, "g7_closedloop_exp1.npz"))
     d = np.load(os.path.join(G, "g11_update.npz"))
     T_UPD = int(d["t_update"])
-    T, M = bstream.path_table(mpc.ref_path)
-    ss = bstream.initial_state(mpc, 10); ss[bstream.SS["NENT"]] = M
+    T, ss = stream_arrays(mpc, 10)
     xphid = np.array([mpc.phi_max[0], 0, 0])
     for t in range(T_UPD):          # open loop over the recorded ticks (states and solutions of G7)
         rb = bstream.robot_record(d7["q"][t], d7["dq"][t], d7["ddq"][t], d7["p_lie"][t], d7["v"][t], xphid, d7["jerk"][t])
@@ -216,7 +165,7 @@ def test_stream_replanning_matches_reference_update_g11():
         td, fl = bstream.unpack_traj(tr, 10)
         np.testing.assert_allclose(td["q"], d["traj_q"][i], atol=1e-12)
         np.testing.assert_allclose(td["phi"], d["traj_phi"][i], atol=1e-12)
-        assert abs(ss[bstream.SS["PHI"]] - d["phi_current"][i]) < 1e-12 and int(ss[0]) == int(d["sector"][i])
+        assert abs(bstream.phi(ss) - d["phi_current"][i]) < 1e-12 and int(ss[0]) == int(d["sector"][i])
         _same_rotation(ss[7:10], d["pr_ref"][i], 1e-11)
         np.testing.assert_allclose(ss[10:13], d["iw_ref"][i], atol=1e-12)
 
@@ -224,16 +173,11 @@ def test_stream_replanning_matches_reference_update_g11():
 @pytest.mark.parametrize("N,S", [(5, 2), (8, 3), (20, 4), (6, 5), (12, 6)])
 def test_stream_functions_other_horizons_and_windows_g12(N, S):
     """stream_pack / stream_post for other (n, nr_segs) against the reference's own step() (fixture G12), open loop over its ticks."""
-    d6 = np.load(os.path.join(G, "g6_pack_exp2_tick0.npz"))
     d = np.load(os.path.join(G, "g12_pack_other_sizes.npz"))
     k = f"n{N}s{S}_"
     dt, mask = float(d[k + "dt"]), d[k + "mask"]
-    mk = lambda key: [np.array(v) for v in d6[key]]
-    mpc = BoundMPC(mk("p_via"), mk("r_via"), [mk("p_lower"), mk("p_upper")], [mk("r_lower"), mk("r_upper")], mk("bp1_in"), mk("br1_in"),
-                   list(d6["s_in"]), list(d6["e_p_min_in"]), list(d6["e_r_min_in"]), list(d6["e_p_max_in"]), list(d6["e_r_max_in"]),
-                   p0=d6["p0fk"].copy(), params=workload.Params(n=N, dt=dt, nr_segs=S, weights=d["weights"]), solver=_Oracle())
-    T, M = bstream.path_table(mpc.ref_path)
-    ss = bstream.initial_state(mpc, N); ss[bstream.SS["NENT"]] = M
+    mpc, _ = fixture_mpc(2, n=N, dt=dt, nr_segs=S, weights=d["weights"])
+    T, ss = stream_arrays(mpc, N)
     xphid = np.array([mpc.phi_max[0], 0, 0])
     for i in range(len(d[k + "x"])):
         rb = bstream.robot_record(d[k + "q"][i], d[k + "dq"][i], d[k + "ddq"][i], d[k + "p_lie"][i], d[k + "v"][i], xphid, d[k + "jerk"][i])
@@ -245,7 +189,7 @@ def test_stream_functions_other_horizons_and_windows_g12(N, S):
         td, fl = bstream.unpack_traj(tr, N)
         np.testing.assert_allclose(td["q"], d[k + "traj_q"][i], atol=1e-12)
         np.testing.assert_allclose(td["p"], d[k + "traj_p"][i], atol=1e-11)
-        assert abs(ss[bstream.SS["PHI"]] - d[k + "phi_current"][i]) < 1e-12
+        assert abs(bstream.phi(ss) - d[k + "phi_current"][i]) < 1e-12
         _same_rotation(ss[7:10], d[k + "pr_ref"][i], 1e-11)
 
 
@@ -255,12 +199,9 @@ def test_realtime_continuation_rule_of_stream_pack():
     (bmpc_stream_pack_rt / the fused and the unfused tick), while plain stream_pack (xlast = NULL) restarts from the last accepted plan as the
     reference does (BoundMPC.py:322-375,468-489).  A numerical failure (status 3) is never continued from."""
     N = 10
-    q0 = workload.random_q0(3, seed=7)[1]
-    mpc, p0fk = workload.make_mpc(q0, solver=_Oracle())
-    T, M = bstream.path_table(mpc.ref_path)
-    ss = bstream.initial_state(mpc, N); ss[bstream.SS["NENT"]] = M
-    rb = bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([mpc.phi_max[0], 0, 0]), np.zeros(7))
-    sol = _Oracle()
+    (mpc,), (rb,) = (a[1:] for a in workload.make_streams(3, seed=7, take=2))
+    T, ss = stream_arrays(mpc, N)
+    sol = Oracle()
     for t in range(3):      # three accepted ticks (converged solves)
         p, x0 = emu.stream_pack(N, 4, T, ss, rb)
         x, g, st, _ = sol.solve(p, x0)
@@ -293,12 +234,9 @@ def test_realtime_acceptance_counts_the_variable_bounds():
     """Real-time mode: a capped iterate whose g passes the rule but whose plan leaves a joint limit is NOT applied (the reference's rule looks at
     g only -- Ipopt iterates satisfy the variable bounds by construction; an iteration-capped interior-point iterate of this solver need not)."""
     N = 10
-    q0 = workload.random_q0(3, seed=7)[1]
-    mpc, p0fk = workload.make_mpc(q0)
-    T, M = bstream.path_table(mpc.ref_path)
-    ss = bstream.initial_state(mpc, N); ss[bstream.SS["NENT"]] = M
-    rb = bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([mpc.phi_max[0], 0, 0]), np.zeros(7))
-    sol = _Oracle()
+    (mpc,), (rb,) = (a[1:] for a in workload.make_streams(3, seed=7, take=2))
+    T, ss = stream_arrays(mpc, N)
+    sol = Oracle()
     p, x0 = emu.stream_pack(N, 4, T, ss, rb)
     x, g, st, _ = sol.solve(p, x0)
     emu.stream_post(N, 4, 0.1, T, ss, rb, x, g, st, simulate=True, flags=2)
@@ -323,32 +261,18 @@ def test_stream_functions_at_the_longest_horizons_match_the_host_mirror():
     functions against the host mirror (which fixture G12 pins against the reference for other (n, nr_segs)) at N = 36, with one forced failure."""
     N = 36
     q0 = workload.random_q0(3, seed=11)[0]
-
-    class Orc(_Oracle):
-        def solve(self, p, x0):
-            r = c_oracle.solve(p, x0, N, 4, 0.1, nthreads=4)
-            x, g, st = r["x"][0], r["g"][0].copy(), int(r["status"][0])
-            if self.calls in self.fail_at:
-                g[:] = 1.0; st = 3
-            self.calls += 1
-            return x, g, st, int(r["iters"][0])
+    Orc = lambda fail_at=(): Oracle(fail_at, N=N, nthreads=4)
     fails = (2,)
     mpc, p0fk = workload.make_mpc(q0, N=N, solver=Orc(fails))
     ref, _ = workload.make_mpc(q0, N=N, solver=Orc())
-    T, M = bstream.path_table(ref.ref_path)
-    ss = bstream.initial_state(ref, N); ss[bstream.SS["NENT"]] = M
     rm = RobotModel()
     q, dq, ddq, jerk, v = q0.copy(), np.zeros(7), np.zeros(7), np.zeros(7), np.zeros(6)
     x_phi_d = np.array([mpc.phi_max[0], 0, 0])
-    rb = bstream.robot_record(q, dq, ddq, p0fk, v, x_phi_d, jerk)
-    sol = Orc(fails)
-    for t in range(4):
+    for c in cpu_mirror_loop(ref, bstream.robot_record(q, dq, ddq, p0fk, v, x_phi_d, jerk), 4, N=N, solve=Orc(fails).solve):
+        t, ss, rb = c["t"], c["ss"], c["rb"]
         p_lie = rm.forward_kinematics(q, dq)[0]
         traj, _, _, _, _ = mpc.step(q, dq, ddq, p_lie, v, x_phi_d, jerk)
-        p, x0 = emu.stream_pack(N, 4, T, ss, rb)
-        x, g, st, _ = sol.solve(p, x0)
-        tr = emu.stream_post(N, 4, 0.1, T, ss, rb, x, g, st, simulate=True)
-        td, fl = bstream.unpack_traj(tr, N)
+        td, fl = bstream.unpack_traj(c["traj"], N)
         assert int(ss[bstream.SS["ERRCNT"]]) == mpc.error_count and fl["using_previous"] == (t in fails) and fl["n_valid"] == N - mpc.error_count
         for k in ("q", "dq", "p", "v", "phi", "dphi"):
             np.testing.assert_allclose(td[k], traj[k], atol=5e-5, err_msg=f"tick {t} {k}")      # two closed loops of 36-stage solves (tol 1e-8 each)
@@ -364,17 +288,14 @@ def test_level_rule_of_the_pack_and_held_barrier_level_in_oracle_and_kernel_text
     take the same iterations to the same point and hand the level back unchanged."""
     from boundmpc_amd import stream as bstream, workload
     N, S, H = 10, 4, 0.1
-    q0 = workload.random_q0(4, seed=3)[1]
-    mpc, p0fk = workload.make_mpc(q0)
-    T, M = bstream.path_table(mpc.ref_path)
-    ss = bstream.initial_state(mpc, N); ss[bstream.SS["NENT"]] = M
-    rb = bstream.robot_record(q0, np.zeros(7), np.zeros(7), p0fk, np.zeros(6), np.array([mpc.phi_max[0], 0.0, 0.0]), np.zeros(7))
-    dist = float(mpc.phi_max[0] - ss[bstream.SS["PHI"]])
+    (mpc,), (rb,) = (a[1:] for a in workload.make_streams(4, seed=3, take=2))
+    T, ss = stream_arrays(mpc, N)
+    dist = float(mpc.phi_max[0] - bstream.phi(ss))
     for mu0, rule, want in ((0.0, (0.02, 0.01, 0.1), 0.0), (0.05, (0.02, 0.01, 0.1), min(max(0.02 * dist, 0.01), 0.1)), (0.05, (1e-4, 0.01, 0.1), 0.01),
                             (0.05, (0.0, 0.0, 0.0), 0.05)):
         dual = np.zeros(c_oracle.state_len(N)); dual[57 * N] = mu0
         p, x0 = emu.stream_pack(N, S, T, ss.copy(), rb, dual=dual, level_rule=rule)
-        assert abs(dual[57 * N] - want) < 1e-15, (mu0, rule, dual[57 * N], want)
+        assert abs(bstream.level(dual, N) - want) < 1e-15, (mu0, rule, dual[57 * N], want)
     # (b) one solve on a held level from a warm state: oracle == kernel text
     P, X, _ = workload.make_batch(4, seed=0)
     for level in (0.05, 0.02):
