@@ -17,6 +17,7 @@
 #include "bmpc_gpu_common.h"
 #include "bmpc_wave.inl"
 #include "bmpc_stream.inl"
+#include "bmpc_stream_log.inl"
 #include "bmpc_dual.inl"
 #include "bmpc_kkt.inl"
 #include "bmpc_sens.inl"
@@ -750,6 +751,14 @@ __global__ void __launch_bounds__(64) bmpc_stream_post_kernel(int N, int S, int 
     bmpcs::stream_post(N, S, h, path + (long long)b * path_stride, path_stride / bmpcs::PT_LEN, ss + (long long)b * bmpcs::ss_len(N), rb + (long long)b * bmpcs::RB_LEN,
                        x + (long long)b * 44 * N, g + (long long)b * 43 * N, status[b], traj + (long long)b * bmpcs::tr_len(N), flags, rt_tol, sh, threadIdx.x, 64, rt_row_cap);
 }
+// the logging records (ref_data / err_data) of the plan a tick left behind; reads p, traj, the state and the path table, writes the log row only
+__global__ void __launch_bounds__(64) bmpc_stream_log_kernel(int N, int S, int B, double h, const double *path, int path_stride, const double *ss, const double *p,
+                                                            const double *traj, double *log) {
+    __shared__ double sh[bmpcs::LSH_LEN];
+    const int b = blockIdx.x;
+    bmpcs::stream_log(N, S, h, path + (long long)b * path_stride, path_stride / bmpcs::PT_LEN, ss + (long long)b * bmpcs::ss_len(N), p + (long long)b * (141 + 91 * S),
+                      traj + (long long)b * bmpcs::tr_len(N), log + (long long)b * bmpcs::log_len(N), sh, threadIdx.x, 64);
+}
 // (the fused one-launch tick kernels of one wave per stream live in bmpc_tick.hip, those of the teams in bmpc_team.hip)
 // The argument test of the four stream entry points (max_iter: 0 where the entry point has none; need: the arrays it cannot do without, looked
 // at for B > 0 only).  False: BMPC_ERR_ARG.
@@ -844,6 +853,16 @@ extern "C" int bmpc_stream_post(bmpc_handle *h, int B, const double *path, int p
     if (B == 0) return BMPC_OK;
     hipLaunchKernelGGL(bmpc_stream_post_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, h->h, path,
                        path_entries * bmpcs::PT_LEN, sstate, robot, x, g, status, traj, flags, h->rt_viol_tol, h->rt_row_cap);
+    HIPCHK(hipGetLastError());
+    return BMPC_OK;
+}
+extern "C" int bmpc_stream_log_len(const bmpc_handle *h) { return h ? bmpcs::log_len(h->N) : -1; }
+// (no workspace of the handle is touched: no ordering event, and the launch may sit inside a capture of the caller's stream)
+extern "C" int bmpc_stream_log(bmpc_handle *h, int B, const double *path, int path_entries, const double *sstate, const double *p, const double *traj, double *log,
+                               void *hip_stream) {
+    if (!stream_args_ok(h, B, 0, path_entries, {path, sstate, p, traj, log})) return BMPC_ERR_ARG;
+    if (B == 0) return BMPC_OK;
+    hipLaunchKernelGGL(bmpc_stream_log_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, h->h, path, path_entries * bmpcs::PT_LEN, sstate, p, traj, log);
     HIPCHK(hipGetLastError());
     return BMPC_OK;
 }

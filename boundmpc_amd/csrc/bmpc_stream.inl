@@ -15,7 +15,8 @@
 // stream_pack takes the re-projection branch of step() (:335-369: the path-parameter states of the warm start are re-projected
 // from the Cartesian position / velocity / acceleration / jerk of the previous plan, no shift), for which stream_post keeps those
 // four 3 x N arrays of the last plan in the state (:557-566; J, dJ and the second time derivative of J of the geometric chain).
-// Not covered: the RViz logging dictionaries (host mirror).
+// The logging dictionaries ref_data / err_data (BoundMPC.py:614-752) are a third function, stream_log in bmpc_stream_log.inl, run behind stream_post.
+// Not covered: the ROS message types built from them.
 //
 // Rotation conversions follow scipy.spatial.transform.Rotation's algorithms (from_rotvec / as_matrix / from_matrix /
 // as_rotvec / as_euler('zyx')) so that the parameters agree with the host mirror to round-off.

@@ -184,6 +184,33 @@ def unpack_traj(t, N):
     return out, dict(n_valid=n, using_previous=bool(t[-3]), success=bool(t[-2]), g_viol=float(t[-1]))
 
 
+# csrc/bmpc_stream_log.inl: the keys of the reference's ref_data / err_data (BoundMPC.py:614-752) with their widths, in row order
+LOG_REF = (("p", 6), ("dp", 6), ("ddp", 6), ("dp_normed", 3), ("r_par_bound", 1), ("bound_lower", 4), ("bound_upper", 4), ("e_p_off", 2), ("e_r_off", 2),
+           ("bp1", 3), ("bp2", 3), ("br1", 3), ("br2", 3), ("v1", 3), ("v2", 3), ("v3", 3))
+LOG_ERR = tuple((k, 3) for k in ("e_p", "de_p", "e_p_par", "e_p_orth", "de_p_par", "de_p_orth", "e_r", "de_r", "e_r_par", "e_r_orth1", "e_r_orth2"))
+LOG_STAGE = sum(w for _, w in LOG_REF + LOG_ERR)
+
+
+def log_len(N):
+    """[N][LOG_STAGE] | n_valid | error_count | 2 pad"""
+    return N * LOG_STAGE + 4
+
+
+def unpack_log(row, N):
+    """Log row (bmpc_stream_log) -> (ref_data, err_data), the reference's logging dictionaries as the host mirror returns them: lists of flat
+    arrays, one entry per stage of the plan (n_valid of them).  (None, None) for a stream without a plan (n_valid == 0)."""
+    row = np.asarray(row)
+    assert row.shape == (log_len(N),)
+    n = int(row[-4])
+    if n == 0:
+        return None, None
+    body, o, out = row[:N * LOG_STAGE].reshape(N, LOG_STAGE)[:n], 0, ({}, {})
+    for d, keys in zip(out, (LOG_REF, LOG_ERR)):
+        for k, w in keys:
+            d[k] = [body[i, o:o + w].copy() for i in range(n)]; o += w
+    return out
+
+
 # Named reads of the stream records: pure indexing of the last axis, on numpy arrays and torch tensors alike (one row or a batch; no copy, no sync).
 def applied(traj):
     """the success flag of a trajectory record (unpack_traj's `success`): the tick's plan was applied"""
@@ -287,6 +314,7 @@ class StreamBatch:
         self.kkt = torch.zeros((self.B,), dtype=torch.float64, device=device)
         self.traj = torch.zeros((self.B, self.tr_len), dtype=torch.float64, device=device)
         self._graphs = {}
+        self._log = None         # log(): allocated on first use
         self.tick_ms = None      # closed_loop(timed=True): HIP-event time of the tick just run
         solver._children.add(self)
 
@@ -328,6 +356,19 @@ class StreamBatch:
         _lib.check(self.solver._lib.bmpc_stream_post(self.solver._h, self.B, _ptr(self.path), self.entries, _ptr(self.state), _ptr(self.robot), _ptr(self.x),
                                                      _ptr(self.g), _ptr(self.status), _ptr(self.traj), self._flags(simulate, accept_capped),
                                                      self._stream(stream)), "bmpc_stream_post")
+
+    def log(self, stream=None):
+        """The logging records of the plans the last tick left behind (bmpc_stream_log): the tensor [B][log_len(N)], rows for `unpack_log`.
+        Call it after post(), tick() or tick_graph() and before the next pack; asynchronous on `stream` like them.  A stream without a plan
+        has n_valid = 0 and a NaN body.  The buffer is allocated on first use and reused."""
+        if self._log is None:
+            import torch
+            n = self.solver._lib.bmpc_stream_log_len(self.solver._h)
+            assert n == log_len(self.N)
+            self._log = torch.empty((self.B, n), dtype=torch.float64, device=self.path.device)
+        _lib.check(self.solver._lib.bmpc_stream_log(self.solver._h, self.B, _ptr(self.path), self.entries, _ptr(self.state), _ptr(self.p), _ptr(self.traj),
+                                                    _ptr(self._log), self._stream(stream)), "bmpc_stream_log")
+        return self._log
 
     def tick(self, max_iter=0, warm_dual=False, simulate=True, stream=None, accept_capped=False, fused=True):
         """pack -> solve -> post of one tick: one fused launch (bmpc_stream_tick; N <= 11, B within the resident waves) or, with

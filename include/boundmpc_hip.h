@@ -263,6 +263,21 @@ int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int path_entries
 int bmpc_stream_graph_create(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
                              double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj,
                              int flags, bmpc_graph **out);
+/* The logging records of step() (ref_data / err_data, BoundMPC.py:614-752) of the plan a tick left behind, one row per stream:
+ *   log [B][bmpc_stream_log_len] = [N][88] | n_valid | error_count | 2 pad,  a stage being
+ *     ref (55): p 6, dp 6, ddp 6, dp_normed 3, r_par_bound 1, bound_lower 4, bound_upper 4, e_p_off 2, e_r_off 2, bp1, bp2, br1, br2, v1, v2, v3 (3 each)
+ *     err (33): e_p, de_p, e_p_par, e_p_orth, de_p_par, de_p_orth, e_r, de_r, e_r_par, e_r_orth1, e_r_orth2 (3 each)
+ *   in the key order of the reference's dictionaries.  ref p[3:] and e_r are the values of the reference's second pass (:712-752): the rotation
+ *   reference integrated along the plan, and the orientation error log(R(p) R(ref)^T) against it.
+ * Stages at or beyond n_valid are NaN.  A stream without a plan (error count >= N; the fused tick skips it) gets n_valid = 0 and an all-NaN
+ * body.  Non-finite inputs give non-finite records.
+ * Call it after bmpc_stream_post, after bmpc_stream_tick or after a graph replay of the tick, and BEFORE the next pack (which overwrites p and may
+ * move the window of the path).  p and traj are the arrays of that tick, sstate the state behind its post.  After a real-time tick (flags bit 1) it
+ * logs the plan traj holds: the applied or the replayed one.  All pointers are DEVICE pointers; asynchronous on hip_stream; no workspace of the
+ * handle is used, so the call may also be enqueued inside a capture of the caller's stream.  BMPC_ERR_ARG on a missing array. */
+int bmpc_stream_log_len(const bmpc_handle *h);      /* 88 N + 4 */
+int bmpc_stream_log(bmpc_handle *h, int B, const double *path, int path_entries, const double *sstate, const double *p, const double *traj,
+                    double *log, void *hip_stream);
 
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
