@@ -36,6 +36,7 @@ SIGNATURES = {
     "bmpc_stream_lengths": (_ci, [_vp] + [_P(_ci)] * 4), "bmpc_stream_pack": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 6), "bmpc_stream_pack_rt": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 7),
     "bmpc_stream_post": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 6 + [_ci, _vp]), "bmpc_stream_tick": (_ci, _TICK + [_vp]), "bmpc_stream_graph_create": (_ci, _TICK + [_P(_vp)]),
     "bmpc_stream_log_len": (_ci, [_vp]), "bmpc_stream_log": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 5),
+    "bmpc_stream_replan_len": (_ci, [_vp, _ci]), "bmpc_stream_update": (_ci, [_vp, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _ci, _vp]),
     "bmpc_stream_set_rt_feasibility_tol": (_ci, [_vp, _cd]), "bmpc_stream_set_rt_position_row_cap": (_ci, [_vp, _cd]), "bmpc_stream_set_time_budget": (_ci, [_vp, _cd]),
     "bmpc_stream_set_level_rule": (_ci, [_vp, _cd, _cd, _cd]), "bmpc_set_barrier_hold": (_ci, [_vp, _ci]),
     "bmpc_set_latency_buffer": (_ci, [_vp, _vp]), "bmpc_set_timing": (_ci, [_vp, _ci]), "bmpc_last_kernel_ms": (_ci, [_vp, _P(ctypes.c_float)]), "bmpc_kernel_ms": (_ci, [_vp, _ci, _P(ctypes.c_float)]),

@@ -18,6 +18,7 @@
 #include "bmpc_wave.inl"
 #include "bmpc_stream.inl"
 #include "bmpc_stream_log.inl"
+#include "bmpc_stream_update.inl"
 #include "bmpc_dual.inl"
 #include "bmpc_kkt.inl"
 #include "bmpc_sens.inl"
@@ -759,6 +760,14 @@ __global__ void __launch_bounds__(64) bmpc_stream_log_kernel(int N, int S, int B
     bmpcs::stream_log(N, S, h, path + (long long)b * path_stride, path_stride / bmpcs::PT_LEN, ss + (long long)b * bmpcs::ss_len(N), p + (long long)b * (141 + 91 * S),
                       traj + (long long)b * bmpcs::tr_len(N), log + (long long)b * bmpcs::log_len(N), sh, threadIdx.x, 64);
 }
+// re-planning (ReferencePath.__init__ and the state part of BoundMPC.update()): reads the re-plan records, writes the path table blocks, the state scalars
+// update() sets and the goal of the robot records of the streams whose record carries a raised flag
+__global__ void __launch_bounds__(64) bmpc_stream_update_kernel(int N, int S, int B, double *replan, double *path, int path_stride, double *ss, double *rb, int *info,
+                                                               int flags) {
+    const int b = blockIdx.x, cap = path_stride / bmpcs::PT_LEN;
+    bmpcs::stream_update(N, S, replan + (long long)b * bmpcs::replan_len(S, cap), path + (long long)b * path_stride, cap, ss + (long long)b * bmpcs::ss_len(N),
+                         rb ? rb + (long long)b * bmpcs::RB_LEN : nullptr, info ? info + b : nullptr, flags, threadIdx.x, 64);
+}
 // (the fused one-launch tick kernels of one wave per stream live in bmpc_tick.hip, those of the teams in bmpc_team.hip)
 // The argument test of the four stream entry points (max_iter: 0 where the entry point has none; need: the arrays it cannot do without, looked
 // at for B > 0 only).  False: BMPC_ERR_ARG.
@@ -863,6 +872,16 @@ extern "C" int bmpc_stream_log(bmpc_handle *h, int B, const double *path, int pa
     if (!stream_args_ok(h, B, 0, path_entries, {path, sstate, p, traj, log})) return BMPC_ERR_ARG;
     if (B == 0) return BMPC_OK;
     hipLaunchKernelGGL(bmpc_stream_log_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, h->h, path, path_entries * bmpcs::PT_LEN, sstate, p, traj, log);
+    HIPCHK(hipGetLastError());
+    return BMPC_OK;
+}
+extern "C" int bmpc_stream_replan_len(const bmpc_handle *h, int path_entries) { return (h && path_entries >= h->S + 1) ? bmpcs::replan_len(h->S, path_entries) : -1; }
+// (like the log: no workspace of the handle, no ordering event, and the launch may sit inside a capture of the caller's stream)
+extern "C" int bmpc_stream_update(bmpc_handle *h, int B, double *replan, double *path, int path_entries, double *sstate, double *robot, int *info, int flags,
+                                  void *hip_stream) {
+    if (B < 1 || !stream_args_ok(h, B, 0, path_entries, {replan, path, sstate})) return BMPC_ERR_ARG;
+    hipLaunchKernelGGL(bmpc_stream_update_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, replan, path, path_entries * bmpcs::PT_LEN, sstate, robot,
+                       info, flags);
     HIPCHK(hipGetLastError());
     return BMPC_OK;
 }

@@ -10,8 +10,9 @@
 //                joint and path states from the optimal jerks (:513-555), Cartesian trajectory (:568-587), advance of the
 //                path-parameter state and of the rotation reference (:594-611, util_functions.py:88-99), optional kinematic
 //                plant step (util_functions.py:152-161) so that a closed loop runs without leaving the device.
-// Re-planning (BoundMPC.update, BoundMPC.py:163-217): the host writes the new path table and the handful of state scalars update()
-// sets (boundmpc_amd.stream.apply_update), and raises SS_UPDATED; from then on -- the reference never clears `self.updated` --
+// Re-planning (BoundMPC.update, BoundMPC.py:163-217): the new path table and the handful of state scalars update() sets are written, and
+// SS_UPDATED raised, either by a fourth function on the device (stream_update in bmpc_stream_update.inl: one launch over the batch, from
+// re-plan records) or by the host one stream at a time (boundmpc_amd.stream.apply_update); from then on -- the reference never clears `self.updated` --
 // stream_pack takes the re-projection branch of step() (:335-369: the path-parameter states of the warm start are re-projected
 // from the Cartesian position / velocity / acceleration / jerk of the previous plan, no shift), for which stream_post keeps those
 // four 3 x N arrays of the last plan in the state (:557-566; J, dJ and the second time derivative of J of the geometric chain).

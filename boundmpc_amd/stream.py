@@ -8,6 +8,8 @@ solution).  Per tick the device runs  pack -> solve -> post  (csrc/bmpc_stream.i
 optionally as one captured hipGraph and optionally with the node's kinematic plant simulation, so a closed loop
 needs no host round trip.  Re-planning (`BoundMPC.update`, BoundMPC.py:163-217): `StreamBatch.update` / `apply_update` write the
 new path table and the state scalars update() sets, from then on the device takes the re-projection branch of step() (:335-369).
+`StreamBatch.update_device` does the same on the device for the whole batch in one launch, from re-plan records (`replan_record`;
+csrc/bmpc_stream_update.inl), without a synchronisation; `apply_update` is its specification.
 """
 import ctypes
 
@@ -107,6 +109,47 @@ def apply_update(ss, N, S, pos_points, rot_points, pos_lim, rot_lim, bp1, br1, s
     if ss[SS["ERRCNT"]] >= N:
         ss[SS["ERRCNT"]] = N - 1
     return T, M
+
+
+# csrc/bmpc_stream_update.inl: the re-plan record [header 32 | n_max via entries of 32]
+RP = dict(FLAG=0, N=1, NB=2, P0=3, V=6, A=9, JERK=12, W=15, HEAD=32)
+RV = dict(P=0, R=3, PLO=12, PUP=14, RLO=16, RUP=18, BP1=20, BR1=23, S=26, EPMIN=27, ERMIN=28, EPMAX=29, ERMAX=30, LEN=32)
+
+
+def replan_len(S, entries):
+    """length of a re-plan record for a path table of `entries` rows: a path of n via points fills n + S - 1 of them"""
+    return RP["HEAD"] + RV["LEN"] * (entries - S + 1)
+
+
+def replan_record(S, entries, pos_points, rot_points, pos_lim, rot_lim, bp1, br1, s, e_p_min, e_r_min, e_p_max, e_r_max, p, v, a, jerk, p0, weights):
+    """The re-plan record of one stream for bmpc_stream_update (StreamBatch.update_device): a numpy row [replan_len(S, entries)] with the flag
+    raised.  Arguments as apply_update after (ss, N, S); rot_points are rotation matrices.  Limit and scalar lists shorter than the via-point list
+    are extended by their last entry, as ReferencePath pads them; len(bp1) basis entries are computed on the device, the last one serves the rest.
+    Raises the ValueError of apply_update when the path does not fit into `entries`."""
+    n, nb = len(pos_points), len(bp1)
+    if n + S - 1 > entries:
+        raise ValueError(f"the new path has {n + S - 1} table entries, the stream batch was built for {entries}: construct the StreamBatch "
+                         "with the longest path it will ever follow")
+    if n < 2 or len(rot_points) != n or not 1 <= nb <= n or len(br1) != nb:
+        raise ValueError(f"a path needs at least two via points, one rotation each and 1..n basis vectors (n = {n}, rotations {len(rot_points)}, "
+                         f"bp1 {nb}, br1 {len(br1)})")
+    rec = np.zeros(replan_len(S, entries))
+    rec[RP["FLAG"]], rec[RP["N"]], rec[RP["NB"]] = 1.0, n, nb
+    for key, val in (("P0", p0), ("V", v), ("A", a), ("JERK", jerk)):
+        rec[RP[key]:RP[key] + 3] = np.asarray(val, dtype=float)[:3]
+    rec[RP["W"]:RP["W"] + 15] = np.asarray(weights, dtype=float)
+    via = rec[RP["HEAD"]:RP["HEAD"] + n * RV["LEN"]].reshape(n, RV["LEN"])
+    at = lambda lst, j: lst[min(j, len(lst) - 1)]
+    for j in range(n):
+        e = via[j]
+        e[RV["P"]:RV["P"] + 3] = pos_points[j]
+        e[RV["R"]:RV["R"] + 9] = np.asarray(rot_points[j], dtype=float).reshape(9)
+        e[RV["PLO"]:RV["PLO"] + 2], e[RV["PUP"]:RV["PUP"] + 2] = at(pos_lim[0], j), at(pos_lim[1], j)
+        e[RV["RLO"]:RV["RLO"] + 2], e[RV["RUP"]:RV["RUP"] + 2] = at(rot_lim[0], j), at(rot_lim[1], j)
+        if j < nb:
+            e[RV["BP1"]:RV["BP1"] + 3], e[RV["BR1"]:RV["BR1"] + 3] = bp1[j], br1[j]
+        e[RV["S"]], e[RV["EPMIN"]], e[RV["ERMIN"]], e[RV["EPMAX"]], e[RV["ERMAX"]] = at(s, j), at(e_p_min, j), at(e_r_min, j), at(e_p_max, j), at(e_r_max, j)
+    return rec
 
 
 def _poff(S):
@@ -315,6 +358,7 @@ class StreamBatch:
         self.traj = torch.zeros((self.B, self.tr_len), dtype=torch.float64, device=device)
         self._graphs = {}
         self._log = None         # log(): allocated on first use
+        self.replan = self.replan_info = None      # update_device(): record buffer [B][replan_len] and info [B], allocated on first use
         self.tick_ms = None      # closed_loop(timed=True): HIP-event time of the tick just run
         solver._children.add(self)
 
@@ -328,6 +372,30 @@ class StreamBatch:
         self.path[b].copy_(torch.as_tensor(T, dtype=torch.float64))
         self.state[b].copy_(torch.as_tensor(row, dtype=torch.float64))
         return float(row[SS["PHIMAX"]])
+
+    def update_device(self, records, set_goal=True, stream=None):
+        """Re-plan on the device (bmpc_stream_update): `records` [B][replan_len(S, entries)], a tensor or an array of `replan_record` rows; a
+        row whose flag is 0 leaves its stream alone.  One launch over the batch, asynchronous on `stream`, no synchronisation and no host copy of
+        the state: call it after post(), tick(), tick_graph() or log() and before the next pack.  The records are copied into a device buffer
+        allocated on first use (`self.replan`; a caller that captures the launch raises flags in that buffer, the launch clears them) -- passing
+        `self.replan` itself copies nothing.  set_goal: also robot[x_phi_d] = (phi_max, 0, 0), as the node does right after update().
+        Returns the `info` tensor [B] (int32; 1: invalid record, stream untouched), valid once `stream` has run the launch."""
+        import torch
+        if self.replan is None:
+            n = self.solver._lib.bmpc_stream_replan_len(self.solver._h, self.entries)
+            assert n == replan_len(self.S, self.entries)
+            self.replan = torch.zeros((self.B, n), dtype=torch.float64, device=self.path.device)
+            self.replan_info = torch.zeros((self.B,), dtype=torch.int32, device=self.path.device)
+        if records is not self.replan:
+            if not torch.is_tensor(records):
+                records = torch.as_tensor(np.ascontiguousarray(records, dtype=np.float64))
+            if tuple(records.shape) != tuple(self.replan.shape):
+                raise ValueError(f"records must be [{self.B}][{self.replan.shape[1]}] (replan_len(S, entries)), got {tuple(records.shape)}")
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.path.device)):      # the copy ahead of the launch, same stream
+                self.replan.copy_(records)
+        _lib.check(self.solver._lib.bmpc_stream_update(self.solver._h, self.B, _ptr(self.replan), _ptr(self.path), self.entries, _ptr(self.state), _ptr(self.robot),
+                                                       _ptr(self.replan_info), int(bool(set_goal)), self._stream(stream)), "bmpc_stream_update")
+        return self.replan_info
 
     def set_robot(self, rec):
         import torch

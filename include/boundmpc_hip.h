@@ -224,8 +224,9 @@ int bmpc_graph_destroy(bmpc_graph *g);
  *                        acc, jerk of the previous plan 4 x 3 x N | updated flag, pad]
  *   robot  [B][robot]   q dq ddq p_lie v x_phi_d jerk = the arguments of step() (read; written when simulate)
  *   traj   [B][traj]    q dq ddq dddq (7 x N) | p v a (6 x N) | phi dphi ddphi dddphi (N) | n_valid using_previous success g_viol
- * Re-planning (BoundMPC.update, BoundMPC.py:163-217): the host writes the new path table and the state scalars and raises the `updated` flag
- * (boundmpc_amd.stream.apply_update); bmpc_stream_pack then takes the re-projection branch of step() (:335-369). */
+ * Re-planning (BoundMPC.update, BoundMPC.py:163-217): bmpc_stream_update (below; one launch over the batch) or the host (one stream at a time,
+ * boundmpc_amd.stream.apply_update) writes the new path table and the state scalars and raises the `updated` flag; bmpc_stream_pack then takes
+ * the re-projection branch of step() (:335-369). */
 int bmpc_stream_lengths(const bmpc_handle *h, int *path_entry, int *state, int *robot, int *traj);
 int bmpc_stream_pack(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, const double *robot, double *p, double *x0,
                      double *dual_state, void *hip_stream);
@@ -255,7 +256,7 @@ int bmpc_stream_set_time_budget(bmpc_handle *h, double microseconds);
 /* One whole tick {pack, warm-started solve with max_iter (0 = options), post} of B streams.  For B within the resident workgroups of the device
  * (bmpc_launch_info; teams: bmpc_team_info) it is ONE kernel launch, whatever N and S; otherwise the three kernels are enqueued.  In the fused
  * launch a stream that has lost its plan (error count >= N: step() returns five Nones there, BoundMPC.py:498-506) is skipped (status 3, 0
- * iterations): re-plan it (StreamBatch.update) or restart it. */
+ * iterations): re-plan it (bmpc_stream_update / StreamBatch.update_device, or StreamBatch.update from the host) or restart it. */
 int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
                      double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
                      void *hip_stream);
@@ -278,6 +279,30 @@ int bmpc_stream_graph_create(bmpc_handle *h, int B, const double *path, int path
 int bmpc_stream_log_len(const bmpc_handle *h);      /* 88 N + 4 */
 int bmpc_stream_log(bmpc_handle *h, int B, const double *path, int path_entries, const double *sstate, const double *p, const double *traj,
                     double *log, void *hip_stream);
+/* Re-planning of closed-loop streams on the device: ReferencePath.__init__ (ReferencePath.py:10-163) and the state part of BoundMPC.update()
+ * (BoundMPC.py:163-217) for every stream whose record carries a raised flag, one launch over the batch (host mirror, one stream at a time:
+ * boundmpc_amd.stream.apply_update).  One re-plan record per stream:
+ *   replan [B][bmpc_stream_replan_len] = header (32) | n_max via entries (32 each),  n_max = path_entries - S + 1
+ *     header:    flag | n (via points) | nb (basis entries: the first nb bp1 / br1 are read) | p0 3 | v 3 | a 3 | jerk 3 (the linear parts of the
+ *                measured Cartesian state, as update() uses them) | weights 15 | 2 pad
+ *     via entry: p 3 | R 9 (rotation matrix, row-major) | p_lower 2 | p_upper 2 | r_lower 2 | r_upper 2 | bp1 3 | br1 3 | s | e_p_min | e_r_min |
+ *                e_p_max | e_r_max | 1 pad
+ *   (builder: boundmpc_amd.stream.replan_record).  Written for a re-planned stream: its whole block of the path table (n + S - 1 slots as
+ *   ReferencePath pads its lists, the rows behind them copy the last slot), and of its state row the window start (0), the path-parameter state
+ *   projected onto the new first segment, the rotation reference, phi_max, the weights, the entry count and the `updated` flag; an error count
+ *   >= N goes back to N - 1, so the next tick solves a stream that had lost its plan.  The previous solution and its Cartesian arrays stay.
+ *   flags bit 0 (set_goal) with robot != NULL: also robot[x_phi_d] = (phi_max, 0, 0), what the node does right after update()
+ *   (bound_mpc_node.py:164).  The node's splice of the measured pose into the first via point (:125-137) is the caller's business.
+ * Flag protocol: flag == 0 leaves the stream alone, bit for bit.  A raised flag is CLEARED by the launch that consumed it, so a captured graph
+ * that holds this launch re-plans only when someone raises a flag in the record buffer again.  n < 2, n > n_max, nb < 1, nb > n or a non-finite
+ * n / nb: invalid record -- stream untouched, flag cleared, info[b] = 1; otherwise info[b] = 0 (info may be NULL).  Non-finite numbers elsewhere,
+ * or a basis vector parallel to its direction, give non-finite table or state entries, as the host mirror does.
+ * Ordering: the call belongs BETWEEN a tick's post (or log) and the next pack.  All pointers are DEVICE pointers; asynchronous on hip_stream; no
+ * workspace of the handle is used, so the call may also be enqueued inside a capture of the caller's stream.  BMPC_ERR_ARG on a missing
+ * replan / path / sstate, on B < 1 or on path_entries < S + 1. */
+int bmpc_stream_replan_len(const bmpc_handle *h, int path_entries);      /* 32 + 32 (path_entries - S + 1); <= 0 on bad arguments */
+int bmpc_stream_update(bmpc_handle *h, int B, double *replan, double *path, int path_entries, double *sstate, double *robot /* may be NULL */,
+                       int *info /* may be NULL */, int flags, void *hip_stream);
 
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
