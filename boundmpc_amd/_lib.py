@@ -35,6 +35,7 @@ SIGNATURES = {
     "bmpc_sens_len": (_ci, []), "bmpc_sens_batch": (_ci, [_vp, _ci] + [_vp] * 5 + [_cd] + [_vp] * 5), "bmpc_sens_batch_host": (_ci, [_vp, _ci] + [_vp] * 5 + [_cd] + [_vp] * 4),
     "bmpc_stream_lengths": (_ci, [_vp] + [_P(_ci)] * 4), "bmpc_stream_pack": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 6), "bmpc_stream_pack_rt": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 7),
     "bmpc_stream_post": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 6 + [_ci, _vp]), "bmpc_stream_tick": (_ci, _TICK + [_vp]), "bmpc_stream_graph_create": (_ci, _TICK + [_P(_vp)]),
+    "bmpc_stream_rollout_len": (_ci, []), "bmpc_stream_rollout": (_ci, _TICK[:2] + [_ci] + _TICK[2:] + [_cd, _vp, _vp, _vp, _vp]),      # handle, B, ticks, path ... flags, goal_tol, hist, traj_hist, ticks_run, stream
     "bmpc_stream_log_len": (_ci, [_vp]), "bmpc_stream_log": (_ci, [_vp, _ci, _vp, _ci] + [_vp] * 5),
     "bmpc_stream_replan_len": (_ci, [_vp, _ci]), "bmpc_stream_update": (_ci, [_vp, _ci, _vp, _vp, _ci, _vp, _vp, _vp, _ci, _vp]),
     "bmpc_stream_set_rt_feasibility_tol": (_ci, [_vp, _cd]), "bmpc_stream_set_rt_position_row_cap": (_ci, [_vp, _cd]), "bmpc_stream_set_time_budget": (_ci, [_vp, _cd]),

@@ -82,3 +82,9 @@ struct ServiceArgsT {
 struct SArgs {
     const double *path; int path_stride; double *ss, *rb, *traj; int flags; double rt_tol; double rt_row_cap; double lvl_c, lvl_lo, lvl_hi;
 };
+// what a rollout adds to the arguments of a fused tick (bmpc_rollout_kernel.inl): the ticks of every stream, the goal rule and the history
+struct RArgs {
+    int ticks; double goal_tol;      // goal_tol > 0: a stream stops behind the post that leaves phi_max - phi <= goal_tol
+    double *hist, *traj_hist;        // [ticks][B][bmpcs::RH_LEN], [ticks][B][tr_len(N)]; either may be NULL
+    int *ticks_run;                  // [B] or NULL
+};

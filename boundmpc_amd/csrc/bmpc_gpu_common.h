@@ -5,7 +5,7 @@
 // fused tick of the one-wave tick and team units).  bmpc_hip.hip holds the one-wave-per-problem batch kernel, the service kernel (one entry
 // over the jobs of bmpc_dual.inl, bmpc_kkt.inl and bmpc_sens.inl, each of which slices its own batch) and the C ABI, bmpc_team.hip the team
 // kernels (NW cooperating waves per problem), bmpc_pair.hip the pair kernel, bmpc_resto.hip the restoration kernels, bmpc_tick.hip the
-// one-wave fused ticks.
+// one-wave fused ticks, bmpc_rollout.hip the rollouts (many ticks per stream in one launch; kernel text bmpc_rollout_kernel.inl).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -95,6 +95,9 @@ hipError_t bmpc_resto_launch(bool zlds, const void *kargs, int grid, hipStream_t
 
 // ---- fused closed-loop tick, one wave per stream (bmpc_tick.hip); resto: the instantiation that carries the restoration phase ----
 hipError_t bmpc_tick_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, int B, hipStream_t st);
+
+// ---- rollout: many ticks of every stream in one launch, one wave per stream striding over the batch (bmpc_rollout.hip, bmpc_rollout_kernel.inl) ----
+hipError_t bmpc_rollout_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 
 // ---- team kernels (bmpc_team.hip); `kargs` points at a KArgsT<...> record (the layouts are identical across instantiations) ----
 // resident workgroups per CU of the team solver kernel with `nw` waves (0: no such instantiation)

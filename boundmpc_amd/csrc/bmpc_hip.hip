@@ -779,6 +779,12 @@ static bool stream_args_ok(const bmpc_handle *h, int B, int max_iter, int path_e
 static bool tick_args_ok(const bmpc_handle *h, int B, const SolveIO &s, const StreamIO &t) {
     return stream_args_ok(h, B, s.max_iter, t.path_entries, {t.path, t.sstate, t.robot, s.p, s.x0, s.x, s.g, s.status, t.traj});
 }
+// the stream arguments of a fused launch (tick, rollout): the caller's stream record and the handle's real-time settings and level rule, read now
+static SArgs stream_sargs(const bmpc_handle *h, const StreamIO &t) {
+    SArgs s; s.path = t.path; s.path_stride = t.path_entries * bmpcs::PT_LEN; s.ss = t.sstate; s.rb = t.robot; s.traj = t.traj; s.flags = t.flags;
+    s.rt_tol = h->rt_viol_tol; s.rt_row_cap = h->rt_row_cap; s.lvl_c = h->level_c; s.lvl_lo = h->level_lo; s.lvl_hi = h->level_hi;
+    return s;
+}
 // enqueues the fused tick on `st` (direct launch or inside a capture)
 static int enqueue_tick(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, hipStream_t st, bool capturing) {
     if (h->closed) return BMPC_ERR_ARG;
@@ -786,7 +792,7 @@ static int enqueue_tick(bmpc_handle *h, int B, const SolveIO &io, const StreamIO
     KArgs a = handle_kargs(h, B, io);
     a.o.retry_cap = 0; a.budget_ticks = (long long)(h->rt_budget_us * 100.0);
     if (B > h->scr_waves) return BMPC_ERR_ARG;
-    SArgs s; s.path = t.path; s.path_stride = t.path_entries * bmpcs::PT_LEN; s.ss = t.sstate; s.rb = t.robot; s.traj = t.traj; s.flags = t.flags; s.rt_tol = h->rt_viol_tol; s.rt_row_cap = h->rt_row_cap; s.lvl_c = h->level_c; s.lvl_lo = h->level_lo; s.lvl_hi = h->level_hi;
+    const SArgs s = stream_sargs(h, t);
     const bool timed = !capturing && h->timing != 0;
     hipEvent_t *pair = nullptr;
     if (timed) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
@@ -820,6 +826,36 @@ extern "C" int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int p
     if (B == 0) return BMPC_OK;
     { const int rc_ = reserve_for_batch(h, B); if (rc_ != BMPC_OK) return rc_; }
     return enqueue_stream_tick(h, B, io, t, (hipStream_t)hip_stream, false);
+}
+
+// ---- rollout: `ticks` ticks of every stream in one launch (bmpc_rollout.hip), a direct launch on the caller's stream ----
+extern "C" int bmpc_stream_rollout_len(void) { return BMPC_ROLL_LEN; }
+extern "C" int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                                   double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                                   double goal_tol, double *hist, double *traj_hist, int *ticks_run, void *hip_stream) {
+    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
+    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (!tick_args_ok(h, B, io, t) || ticks < 1) return BMPC_ERR_ARG;
+    if (!(flags & 1)) return BMPC_ERR_ARG;                            // without the plant in the loop a second tick repeats the first
+    if (!(goal_tol >= 0.0) || !std::isfinite(goal_tol)) return BMPC_ERR_ARG;
+    if (h->rt_budget_us > 0.0) return BMPC_ERR_ARG;                   // a rollout is not real time, and budgeted results depend on the clock
+    if (h->closed || caller_is_capturing(st)) return BMPC_ERR_ARG;    // (a direct launch: the workspace may grow, and the ordering events are recorded)
+    if (B == 0) return BMPC_OK;
+    // one wave per stream whatever bmpc_set_team_waves says: workgroup w strides over the streams on workspace slab w
+    const int grid = service_grid(h, B);
+    { int rc_ = reserve_for_batch(h, B); if (rc_ == BMPC_OK) rc_ = ensure_scratch(h, grid); if (rc_ != BMPC_OK) return rc_; }
+    { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
+    KArgs a = handle_kargs(h, B, io);
+    a.o.retry_cap = 0; a.budget_ticks = 0;
+    const bool resto = h->o.restoration != 0;      // inside the kernel, as in the fused tick: the post needs the final solution
+    const SArgs s = stream_sargs(h, t);
+    const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run};
+    hipEvent_t *pair = nullptr;
+    if (h->timing) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
+    HIPCHK(bmpc_rollout_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    if (h->timing) { HIPCHK(hipEventRecord(pair[1], st)); h->n_timed++; }
+    return order_after(h, st);
 }
 
 extern "C" int bmpc_stream_set_rt_feasibility_tol(bmpc_handle *h, double tol) {

@@ -1,0 +1,112 @@
+// bmpc_rollout_kernel.inl -- a ROLLOUT of closed-loop streams: `ticks` whole ticks {pack, solve, post} of every stream in ONE launch, one wave
+// per stream (bmpc_rollout.hip: bmpc_stream_rollout_kernel<ZLDS, RESTO>).  Included after the wave program and the stream functions; the unit
+// defines KArgs.
+// A loop of fused ticks (bmpc_tick_kernel.inl) joins the whole grid once per tick: "a tick lasts as long as its slowest stream", so a batch of
+// closed loops costs the sum over the ticks of the slowest stream's solve.  The streams of a batch are independent -- with the plant in the loop
+// (flags bit 0) tick t + 1 of stream b needs only what tick t of stream b left behind -- so here every stream runs at its own pace and the batch
+// costs the slowest stream's SUM.  Workgroup w serves streams w, w + grid, w + 2 grid, ... on workspace slab w: a plain stride (no queue word, no
+// atomic, no reset kernel; the streams have comparable total work, and the result does not depend on scheduling), so any B is served.
+// The body of a tick is the fused tick's, line for line, with the same arguments (xlast = x under flags bit 1, no time budget, no second attempt);
+// what one tick stores -- ss, rb, x, the dual state -- the pack of the next one reads back from global memory behind a workgroup barrier, the
+// hand-over the fused tick already uses between its own three steps (p, x0 -> solver -> x, g -> post).
+// Behind every tick's post the stream's history row is written; the stop rules of the node's loop are applied per stream:
+//   lost plan   ss[SS_ERRCNT] >= N at the start of a tick: what the fused tick writes for a skipped stream (status 3, iters 0, kkt 0) is written
+//               once, everything else keeps its last value, the stream stops;
+//   goal        goal_tol > 0 and phi_max - phi <= goal_tol behind a post (NodeLoop.run, the reference's experiment runners): the stream stops.
+// The history rows of the ticks a stream did not run are NaN.  With goal_tol = 0 every tick array holds afterwards what `ticks` launches of the
+// one-wave fused tick leave, bit for bit.
+// The same text is compiled by g++ for the CPU tests (tests/emu/bmpc_emu_rollout.cpp: one lane for the stream functions, the wave program's lane
+// loops inside the solve).
+#pragma once
+
+namespace bmpcs {
+// history row of one tick of one stream (BMPC_ROLL_* of include/boundmpc_hip.h): the robot record behind the post, then the named scalars, then the
+// four trailer words of the tick's trajectory record
+enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH_NVALID, RH_USINGPREV, RH_SUCCESS, RH_GVIOL, RH_LEN };
+}  // namespace bmpcs
+
+// What the kernel entry names of the launch: on the GPU the HIP words; a host build of this text (tests/emu) defines them before it includes the
+// file -- one workgroup of one lane, BMPCR_WAVE_HOOK(W, pr) for what its wave carries beside the kernels' (the lane order of the solver's phases).
+#ifndef BMPC_EMU
+#define BMPCR_KERNEL __global__ void __launch_bounds__(64, 1)
+#define BMPCR_LDS __shared__
+#define BMPCR_LANE threadIdx.x
+#define BMPCR_NL 64
+#define BMPCR_BLOCK blockIdx.x
+#define BMPCR_GRID gridDim.x
+#define BMPCR_UNIFORM(i) __builtin_amdgcn_readfirstlane(i)      // a wave-uniform decision as a scalar: the barriers of the loops sit in uniform control flow
+// The tick loop must not become a reason to hoist: what the solver derives from the wave's and the problem's scalars (strides, table offsets, address
+// arithmetic) is invariant over the ticks of a stream, and hoisted out of the loop it would stay live across the whole solve (the register pressure
+// LANES_BEGIN guards against per phase).  Opaque per tick, the body allocates like the fused tick's.
+#define BMPCR_WAVE_HOOK(W, pr) asm volatile("" : "+s"((W).N), "+s"((W).S), "+s"((W).h), "+s"((W).G.b), "+s"((pr).p), "+s"((pr).x0), "+s"((pr).x), "+s"((pr).g), "+s"((pr).state))
+#define BMPCR_OPAQUE2(x, y) asm volatile("" : "+s"(x), "+s"(y))      // the same for what the stream functions are given
+#else
+#define BMPCR_OPAQUE2(x, y)
+#endif
+
+// (the body of a tick in the kernel itself, as in bmpc_tick_kernel.inl: behind a function that takes `a` the argument loads lose their no-clobber
+// property -- bmpc_args.h, BMPC_PROBLEM)
+template <bool ZLDS, bool RESTO>
+BMPCR_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
+    BMPCR_LDS double lds[BMPC_NAMESPACE::L_SIZE];
+    BMPC_STRIDES(a);
+    double *sh = lds + BMPC_NAMESPACE::L_RED;
+    static_assert(bmpcs::SH_LEN <= 6 * 64, "the stream functions' LDS words must fit into the solver's reduction area");
+    const int TRN = bmpcs::tr_len(a.N);
+    const double nan_ = __builtin_nan("");
+    for (int b = BMPCR_BLOCK; b < a.B; b += BMPCR_GRID) {
+        const double *path = s.path + (long long)b * s.path_stride;
+        double *ss = s.ss + (long long)b * bmpcs::ss_len(a.N), *rb = s.rb + (long long)b * bmpcs::RB_LEN, *traj = s.traj + (long long)b * TRN;
+        double *p = const_cast<double *>(a.p) + (long long)b * np, *x0 = const_cast<double *>(a.x0) + (long long)b * nw;
+        double *dual = a.state ? a.state + (long long)b * (a.N * BMPC_NAMESPACE::NI + 2) : nullptr;
+        long long busy = 0;      // counts of the 100 MHz clock spent in the stream's solves
+        int t = 0;
+        for (; t < r.ticks; t++) {
+            // (the lost-plan test of the fused tick: BoundMPC.step() returns five Nones there and the reference node stops)
+            if (BMPCR_UNIFORM((int)(ss[bmpcs::SS_ERRCNT] >= (double)a.N))) {
+                if (BMPCR_LANE == 0) { a.status[b] = 3; if (a.iters) a.iters[b] = 0; if (a.kkt) a.kkt[b] = 0.0; }
+                break;
+            }
+            int N_ = a.N, S_ = a.S;
+            BMPCR_OPAQUE2(N_, S_);
+            bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCR_LANE, BMPCR_NL, s.lvl_c, s.lvl_lo, s.lvl_hi);
+            BMPCS_SYNC();
+            BMPC_WAVE_INIT(W, a, lds, a.scratch + (long long)BMPCR_BLOCK * a.scr_stride, 0);
+            BMPC_TICK_PROBLEM(pr, a, b, p, x0, dual);
+            BMPCR_WAVE_HOOK(W, pr);
+            const long long t0_ = a.latency_us ? BMPC_NOW() : 0;
+            BMPC_NAMESPACE::wave_solve<ZLDS, true, RESTO>(W, pr);
+            BMPCS_SYNC();
+            if (a.latency_us) busy += BMPC_NOW() - t0_;
+            BMPCR_OPAQUE2(N_, S_);
+            bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, s.rt_tol, sh, BMPCR_LANE, BMPCR_NL, s.rt_row_cap);
+            BMPCS_SYNC();      // the history and the next pack read ss, rb, x, traj and the dual state that other lanes have just stored
+            const long long row = (long long)t * a.B + b;
+            if (r.hist) {
+                double *hr = r.hist + row * bmpcs::RH_LEN;
+                for (int i = BMPCR_LANE; i < bmpcs::RB_LEN; i += BMPCR_NL) hr[bmpcs::RH_ROBOT + i] = rb[i];
+                for (int i = BMPCR_LANE; i < 4; i += BMPCR_NL) hr[bmpcs::RH_NVALID + i] = traj[TRN - 4 + i];
+                if (BMPCR_LANE == 0) {
+                    hr[bmpcs::RH_PHI] = ss[bmpcs::SS_PHI]; hr[bmpcs::RH_ERRCNT] = ss[bmpcs::SS_ERRCNT]; hr[bmpcs::RH_STATUS] = (double)a.status[b];
+                    hr[bmpcs::RH_ITERS] = nan_; hr[bmpcs::RH_KKT] = nan_;
+                    if (a.iters) hr[bmpcs::RH_ITERS] = (double)a.iters[b];
+                    if (a.kkt) hr[bmpcs::RH_KKT] = a.kkt[b];
+                }
+            }
+            if (r.traj_hist) { double *th = r.traj_hist + row * TRN; for (int i = BMPCR_LANE; i < TRN; i += BMPCR_NL) th[i] = traj[i]; }
+            if (BMPCR_UNIFORM((int)(r.goal_tol > 0.0 && ss[bmpcs::SS_PHIMAX] - ss[bmpcs::SS_PHI] <= r.goal_tol))) { t++; break; }
+        }
+        // t ticks were run; the rows behind them stay without a tick
+        for (int u = t; u < r.ticks; u++) {
+            const long long row = (long long)u * a.B + b;
+            if (r.hist) for (int i = BMPCR_LANE; i < bmpcs::RH_LEN; i += BMPCR_NL) r.hist[row * bmpcs::RH_LEN + i] = nan_;
+            if (r.traj_hist) for (int i = BMPCR_LANE; i < TRN; i += BMPCR_NL) r.traj_hist[row * TRN + i] = nan_;
+        }
+        if (BMPCR_LANE == 0) {
+            if (r.ticks_run) r.ticks_run[b] = t;
+            if (a.latency_us) a.latency_us[b] = (double)busy * 0.01;
+        }
+        BMPCS_SYNC();      // the next stream's pack reuses the LDS words this stream's last phase read
+    }
+}
+

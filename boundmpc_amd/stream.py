@@ -254,6 +254,31 @@ def unpack_log(row, N):
     return out
 
 
+# csrc/bmpc_rollout_kernel.inl: the history row of one tick of one stream (BMPC_ROLL_* of include/boundmpc_hip.h)
+ROLL = dict(ROBOT=0, PHI=43, ERRCNT=44, ITERS=45, STATUS=46, KKT=47, NVALID=48, USINGPREV=49, SUCCESS=50, GVIOL=51, LEN=52)
+
+
+def rollout_len():
+    """[robot record 43 | phi | error count | iters | status | kkt | n_valid | using_previous | success | g_viol]"""
+    return ROLL["LEN"]
+
+
+def unpack_rollout(row):
+    """History row of a rollout (StreamBatch.rollout()["hist"][t, b], numpy) -> dict: the fields of the robot record behind the tick's post
+    (q, dq, ddq, p, v, x_phi_d, jerk) and the named scalars.  None for a tick the stream did not run (a NaN row)."""
+    row = np.asarray(row)
+    assert row.shape == (ROLL["LEN"],)
+    if np.isnan(row[ROLL["STATUS"]]):
+        return None
+    names = [k for k in sorted(RB, key=RB.get) if k != "LEN"]
+    out = {k.lower(): row[RB[k]:RB[names[i + 1]] if i + 1 < len(names) else RB["LEN"]].copy() for i, k in enumerate(names)}
+    out["x_phi_d"] = out.pop("xphid")
+    out.update(phi=float(row[ROLL["PHI"]]), error_count=int(row[ROLL["ERRCNT"]]), status=int(row[ROLL["STATUS"]]), kkt=float(row[ROLL["KKT"]]),
+               iters=None if np.isnan(row[ROLL["ITERS"]]) else int(row[ROLL["ITERS"]]), n_valid=int(row[ROLL["NVALID"]]),
+               using_previous=bool(row[ROLL["USINGPREV"]]), success=bool(row[ROLL["SUCCESS"]]), g_viol=float(row[ROLL["GVIOL"]]))
+    return out
+
+
 # Named reads of the stream records: pure indexing of the last axis, on numpy arrays and torch tensors alike (one row or a batch; no copy, no sync).
 def applied(traj):
     """the success flag of a trajectory record (unpack_traj's `success`): the tick's plan was applied"""
@@ -494,6 +519,33 @@ class StreamBatch:
         # bmpc_graph_launch)
         _lib.check(self.solver._lib.bmpc_graph_launch(self._graphs[key], self._stream(stream)), "bmpc_graph_launch")
 
+    def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None):
+        """`ticks` closed-loop ticks (plant simulation on) of every stream in ONE launch (bmpc_stream_rollout): each stream runs at its own pace, so
+        the launch lasts as long as the slowest stream's SUM of solves, where a loop of tick() / tick_graph() pays the slowest stream of every tick.
+        For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, re-planning, a time
+        budget) use the ticks.  One wave per stream always (set_team_waves does not apply).  A stream stops once it has lost its plan (status 3, as
+        the fused tick leaves a skipped stream) or, with goal_tol > 0, behind the tick that leaves phi_max - phi <= goal_tol (NodeLoop.run's rule).
+        With goal_tol = 0 the batch's buffers hold afterwards what `ticks` calls of tick(fused=True) on one wave per stream leave, bit for bit.
+        The protocol of closed_loop -- tick 0 solved out with first_cap, later ticks capped -- is
+            sb.tick(first_cap, warm_dual=True); sb.rollout(T - 1, cap, warm_dual=True, accept_capped=...)
+        Returns device tensors, valid once `stream` has run the launch (asynchronous, no synchronisation):
+          hist [ticks][B][rollout_len()]   the history row of stream b behind tick t (slots ROLL, unpack_rollout); NaN for a tick it did not run
+          ticks_run [B] int32              ticks the stream ran
+          traj_hist [ticks][B][tr_len]     want_traj: the trajectory record of every tick (unpack_traj); NaN likewise"""
+        import torch
+        if max_iter and not warm_dual:
+            raise ValueError("an iteration cap needs the dual state (warm_dual=True): the multipliers must be shifted with the plan")
+        assert self.solver._lib.bmpc_stream_rollout_len() == ROLL["LEN"]
+        n, dev = max(int(ticks), 0), self.path.device
+        out = {"hist": torch.empty((n, self.B, ROLL["LEN"]), dtype=torch.float64, device=dev), "ticks_run": torch.zeros((self.B,), dtype=torch.int32, device=dev)}
+        if want_traj:
+            out["traj_hist"] = torch.empty((n, self.B, self.tr_len), dtype=torch.float64, device=dev)
+        args = self._tick_args(max_iter, warm_dual, True, accept_capped)
+        _lib.check(self.solver._lib.bmpc_stream_rollout(self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]),
+                                                        _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]), self._stream(stream)),
+                   "bmpc_stream_rollout")
+        return out
+
     def closed_loop(self, ticks, cap=0, warm=True, accept_capped=False, first_cap=100, budget_us=None, graph=True, fused=True, timed=False, tick=None):
         """THE closed loop of BASELINE configs[4], as a generator over the tick index: `for t in sb.closed_loop(ticks, ...)`.
         Tick 0 is every stream's cold start from rest, solved out (`first_cap` iterations, dual state kept, the reference's acceptance rule,
@@ -505,7 +557,8 @@ class StreamBatch:
         fused is passed on to every self.tick the driver calls, tick 0 included (False: the three-kernel tick); a graph is always the fused tick.
         budget_us: time budget of the fused ticks after the first (the handle's setting is read at capture: off for tick 0, set behind it).
         timed=True: HIP events around every tick after the first, `self.tick_ms` holds the time of the tick just run (None for tick 0).  The
-        launch stream has been synchronised when the loop body runs; what to record there is the caller's business."""
+        launch stream has been synchronised when the loop body runs; what to record there is the caller's business.
+        Where nothing is read between the ticks, the same protocol in two launches is tick(first_cap, warm_dual=True) + rollout(ticks - 1, cap, ...)."""
         import torch
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timed else None
         for t in range(ticks):

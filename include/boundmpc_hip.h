@@ -264,6 +264,38 @@ int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int path_entries
 int bmpc_stream_graph_create(bmpc_handle *h, int B, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
                              double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj,
                              int flags, bmpc_graph **out);
+/* Rollout: `ticks` whole ticks of every stream in ONE launch, for closed loops run in bulk (Monte-Carlo runs, tuning, robustness batteries) where
+ * the throughput of whole loops counts, not the latency of a tick.  A loop of bmpc_stream_tick launches joins the grid once per tick, so it costs
+ * the sum over the ticks of the slowest stream's solve; here every stream runs at its own pace and the launch lasts as long as the slowest
+ * stream's sum.  The tick arrays and their argument test are those of bmpc_stream_tick.  One wave per stream ALWAYS: bmpc_set_team_waves does not
+ * apply, workgroup w serves streams w, w + grid, w + 2 grid, ... (grid = min(B, bmpc_launch_info's grid)), so any B is served.
+ * Per stream, tick after tick:
+ *   lost plan  error count >= N at the start of a tick: what a fused tick writes for a skipped stream (status 3, iters 0, kkt 0) is written
+ *              once, everything else keeps its last value, the stream stops;
+ *   goal       goal_tol > 0: the stream stops behind the post that leaves phi_max - phi <= goal_tol (the rule of the node's loop); 0 = never.
+ * With goal_tol = 0 every tick array (sstate, robot, p, x0, dual_state, x, g, iters, status, kkt, traj) holds afterwards what `ticks` successive
+ * bmpc_stream_tick launches on one wave per stream (bmpc_set_team_waves(h, 1)) leave, bit for bit.
+ *   hist [ticks][B][BMPC_ROLL_LEN] (may be NULL): row [t][b] describes stream b BEHIND tick t: the robot record, phi, the error count, the
+ *     solve's iters / status / kkt (NaN where that array is NULL) and the four trailer words of the tick's trajectory record;
+ *   traj_hist [ticks][B][traj] (may be NULL): the whole trajectory record of that tick;
+ *   ticks_run [B] (may be NULL): the ticks the stream ran.  Rows of ticks a stream did not run -- from its stop on, all of them if it was lost on
+ *     entry -- are NaN in both arrays.
+ * The barrier hold, the level rule, the real-time feasibility tolerance, the position-row cap and the restoration mode are read from the handle
+ * at launch time, as for a tick; the second attempt is off.  A registered latency buffer receives the SUM of the stream's solve durations;
+ * bmpc_set_timing brackets the launch like a tick.  The launch uses the handle's workspace and is ordered against the handle's other launches.
+ * A direct launch: not to be enqueued inside a stream capture (BMPC_ERR_ARG).  All pointers are DEVICE pointers; asynchronous on hip_stream.
+ * First tick: a loop whose tick 0 is solved out and whose later ticks are capped is bmpc_stream_tick (first cap) followed by a rollout of
+ * ticks - 1.  BMPC_ERR_ARG, nothing launched: ticks < 1, a missing tick array, flags bit 0 (simulate) clear -- without the plant in the loop a
+ * second tick repeats the first --, a negative or non-finite goal_tol, a time budget set on the handle (bmpc_stream_set_time_budget: a rollout
+ * is not real time, and budgeted results depend on the clock). */
+enum { BMPC_ROLL_ROBOT = 0 /* 43: the robot record behind the tick's post */, BMPC_ROLL_PHI = 43, BMPC_ROLL_ERRCNT = 44, BMPC_ROLL_ITERS = 45,
+       BMPC_ROLL_STATUS = 46, BMPC_ROLL_KKT = 47, BMPC_ROLL_NVALID = 48, BMPC_ROLL_USINGPREV = 49, BMPC_ROLL_SUCCESS = 50, BMPC_ROLL_GVIOL = 51,
+       BMPC_ROLL_LEN = 52 };
+int bmpc_stream_rollout_len(void);
+int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                        double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                        double goal_tol, double *hist /* [ticks][B][52] or NULL */, double *traj_hist /* [ticks][B][traj] or NULL */,
+                        int *ticks_run /* [B] or NULL */, void *hip_stream);
 /* The logging records of step() (ref_data / err_data, BoundMPC.py:614-752) of the plan a tick left behind, one row per stream:
  *   log [B][bmpc_stream_log_len] = [N][88] | n_valid | error_count | 2 pad,  a stage being
  *     ref (55): p 6, dp 6, ddp 6, dp_normed 3, r_par_bound 1, bound_lower 4, bound_upper 4, e_p_off 2, e_r_off 2, bp1, bp2, br1, br2, v1, v2, v3 (3 each)
@@ -329,7 +361,8 @@ int bmpc_set_latency_buffer(bmpc_handle *h, double *latency_us);
  * else one wave per problem; (h, 1): always one wave; (h, 2): pairs whatever the batch; (h, 4): teams whatever the batch (an error where the
  * instantiation does not exist).  Results agree with the one-wave kernels up to the order of a few sums (same iterates unless a filter
  * decision sits on a rounding error).  bmpc_team_info: waves per problem a batch of B would get, resident teams / pairs of that kind, LDS
- * bytes of its workgroup.  The fused closed-loop ticks run on teams or on one wave per stream. */
+ * bytes of its workgroup.  The fused closed-loop ticks run on teams or on one wave per stream; a rollout (bmpc_stream_rollout) always runs one
+ * wave per stream, whatever is set here. */
 int bmpc_set_team_waves(bmpc_handle *h, int waves);
 int bmpc_team_info(const bmpc_handle *h, int B, int *waves, int *resident_teams, int *lds_bytes);
 

@@ -1,0 +1,137 @@
+"""The rollout -- many closed-loop ticks of a stream in one launch -- as device code (csrc/bmpc_rollout_kernel.inl compiled for the CPU, tests/emu)
+against its exact checker: a loop of the existing emulator entries emu.stream_pack -> the in-kernel solve of the fused tick -> emu.stream_post,
+one tick at a time (tests/emu/emu_rollout.py per_tick_loop).  Bit for bit on every tick array, `hist` and `traj_hist` against the per-tick values,
+and the stop rules: a lost plan, the goal.  Every case asserts that each stream ran at least one tick."""
+import numpy as np
+import pytest
+
+from boundmpc_amd import stream as bstream
+from tests.emu import emu_rollout as er
+
+SS, ROLL = bstream.SS, bstream.ROLL
+H = 0.1
+
+
+def _compare(N, S, T, A0, ticks, what, goal_tol=0.0, **kw):
+    """rollout(ticks) on a copy of the arrays A0 against `ticks` single ticks on another; returns (rollout result, its arrays, per-tick rows, snapshots)"""
+    A, B = er.copy_arrays(A0), er.copy_arrays(A0)
+    rows, trajs, snaps = er.per_tick_loop(N, S, H, T, A, ticks, **kw)
+    r = er.rollout(N, S, H, T, B, ticks, goal_tol=goal_tol, **kw)
+    assert r["ticks_run"] >= 1, what
+    if goal_tol == 0.0:
+        er.assert_arrays_equal(A, B, what)
+        assert r["ticks_run"] == int(np.isfinite(rows[:, ROLL["STATUS"]]).sum()), what
+        assert np.array_equal(r["hist"], rows, equal_nan=True) and np.array_equal(r["traj_hist"], trajs, equal_nan=True), what
+    return r, B, rows, snaps
+
+
+@pytest.mark.parametrize("N,S", [(2, 2), (1, 2)])
+def test_rollout_equals_the_per_tick_loop_bit_for_bit(N, S):
+    """T = 4 converged ticks with the dual state carried, from the cold start; every tick runs."""
+    _, rec, T, ss = er.small_stream(N, S)
+    r, B, rows, _ = _compare(N, S, T, er.fresh_arrays(N, S, ss, rec), 4, f"N {N} S {S}", warm_dual=True)
+    assert r["ticks_run"] == 4 and np.isfinite(r["hist"]).all() and (r["hist"][:, ROLL["STATUS"]] == 0).all()
+    assert (np.diff(r["hist"][:, ROLL["PHI"]]) > 0).all()                   # the plant moves: a second tick does not repeat the first
+    # the history row: the robot record and the named scalars of the arrays behind the last tick, the trailer of its trajectory record
+    last = bstream.unpack_rollout(r["hist"][3])
+    assert np.array_equal(last["q"], B["rb"][:7]) and np.array_equal(last["jerk"], B["rb"][36:43]) and last["phi"] == B["ss"][SS["PHI"]]
+    assert last["iters"] == B["iters"][0] > 0 and last["status"] == 0 and last["kkt"] == B["kkt"][0] and last["error_count"] == 0
+    _, fl = bstream.unpack_traj(B["traj"], N)
+    assert (last["n_valid"], last["using_previous"], last["success"], last["g_viol"]) == (fl["n_valid"], fl["using_previous"], fl["success"], fl["g_viol"])
+    assert np.array_equal(r["traj_hist"][3], B["traj"])
+
+
+def test_rollout_without_the_dual_state_and_in_any_lane_order():
+    """cold duals on every tick (dual_state NULL), and the solver's phases with their lanes reversed and scrambled: the same bits"""
+    N, S = 2, 2
+    _, rec, T, ss = er.small_stream(N, S)
+    A0 = er.fresh_arrays(N, S, ss, rec)
+    r, B, _, _ = _compare(N, S, T, A0, 4, "cold duals", warm_dual=False)
+    assert r["ticks_run"] == 4 and (B["dual"] == 0.0).all()
+    ref = er.copy_arrays(A0); want = er.rollout(N, S, H, T, ref, 4, warm_dual=True)
+    for order in (1, 2):
+        C = er.copy_arrays(A0); got = er.rollout(N, S, H, T, C, 4, warm_dual=True, lane_order=order)
+        er.assert_arrays_equal(ref, C, f"lane order {order}")
+        assert np.array_equal(got["hist"], want["hist"])
+
+
+def test_one_tick_rollout_equals_one_tick():
+    N, S = 2, 2
+    _, rec, T, ss = er.small_stream(N, S)
+    A0 = er.fresh_arrays(N, S, ss, rec)
+    r, _, _, _ = _compare(N, S, T, A0, 1, "T = 1", warm_dual=True)
+    assert r["ticks_run"] == 1 and r["hist"].shape == (1, ROLL["LEN"])
+    warm = er.copy_arrays(A0); er.tick(N, S, H, T, warm, warm_dual=True)      # ... and one tick of a stream that already holds a plan
+    r, _, _, _ = _compare(N, S, T, warm, 1, "T = 1, warm", warm_dual=True)
+    assert r["ticks_run"] == 1
+
+
+def test_a_stream_that_loses_its_plan_stops():
+    """Tick 0 solved out, then two iterations per tick without the real-time rule: every capped iterate fails the reference's acceptance rule, the error
+    count climbs to N and the stream stops.  At (10, 4): the two-iteration ticks of the smallest shape stay feasible (summed violation 0) and never fail."""
+    N, S, ticks = 10, 4, 13                                               # T > N + 1
+    _, rec, T, ss = er.small_stream(N, S)
+    A0 = er.fresh_arrays(N, S, ss, rec)
+    er.tick(N, S, H, T, A0, max_iter=100, warm_dual=True)
+    assert A0["status"][0] == 0 and A0["ss"][SS["ERRCNT"]] == 0
+    r, B, rows, snaps = _compare(N, S, T, A0, ticks, "lost plan", max_iter=2, warm_dual=True)
+    ec = rows[:, ROLL["ERRCNT"]]
+    implied = int(np.argmax(ec >= N)) + 1                                  # the tick that raises the error count to N is the last one run
+    assert (ec >= N).any() and 1 <= implied < ticks and r["ticks_run"] == implied
+    assert np.array_equal(ec[:implied], np.arange(1, implied + 1)) and (rows[:implied, ROLL["STATUS"]] == 1).all()
+    assert np.isnan(r["hist"][implied:]).all() and np.isnan(r["traj_hist"][implied:]).all() and np.isfinite(r["hist"][:implied]).all()
+    assert B["status"][0] == 3 and B["iters"][0] == 0 and B["kkt"][0] == 0.0 and B["ss"][SS["ERRCNT"]] == N
+    # everything else keeps its last value: the arrays behind the last tick that ran, but for the three words above
+    keep = er.copy_arrays(snaps[implied - 1]); keep["status"][0], keep["iters"][0], keep["kkt"][0] = 3, 0, 0.0
+    er.assert_arrays_equal(keep, B, "behind the stop")
+    # lost on entry: no tick, all rows NaN, the same three words
+    C = er.copy_arrays(B); C["status"][0], C["iters"][0], C["kkt"][0] = 7, 7, 7.0
+    r2 = er.rollout(N, S, H, T, C, 3, max_iter=2, warm_dual=True)
+    assert r2["ticks_run"] == 0 and np.isnan(r2["hist"]).all() and np.isnan(r2["traj_hist"]).all()
+    er.assert_arrays_equal(B, C, "lost on entry")
+
+
+def test_a_stream_stops_at_its_goal():
+    """goal_tol from the per-tick loop's own phi trace, so that the stop falls strictly inside the T ticks on the reference path alone: ticks_run is
+    the first crossing and the state is that of the per-tick loop stopped there."""
+    N, S, ticks = 2, 2, 4
+    _, rec, T, ss = er.small_stream(N, S)
+    A0 = er.fresh_arrays(N, S, ss, rec)
+    A = er.copy_arrays(A0)
+    rows, trajs, snaps = er.per_tick_loop(N, S, H, T, A, ticks, warm_dual=True)
+    gap = A0["ss"][SS["PHIMAX"]] - rows[:, ROLL["PHI"]]
+    assert (np.diff(gap) < 0).all()
+    goal_tol = float(gap[1])                                               # reached behind tick 1, not behind tick 0
+    first = int(np.argmax(gap <= goal_tol)) + 1
+    assert first == 2 < ticks
+    B = er.copy_arrays(A0)
+    r = er.rollout(N, S, H, T, B, ticks, goal_tol=goal_tol, warm_dual=True)
+    assert r["ticks_run"] == first
+    er.assert_arrays_equal(snaps[first - 1], B, "stopped at the goal")
+    assert np.array_equal(r["hist"][:first], rows[:first]) and np.array_equal(r["traj_hist"][:first], trajs[:first])
+    assert np.isnan(r["hist"][first:]).all() and np.isnan(r["traj_hist"][first:]).all()
+    C = er.copy_arrays(A0)                                                 # a tolerance nobody reaches stops nobody
+    assert er.rollout(N, S, H, T, C, ticks, goal_tol=float(gap[-1]) * 0.5, warm_dual=True)["ticks_run"] == ticks
+    er.assert_arrays_equal(A, C, "goal never reached")
+
+
+def test_argument_errors_of_the_entry():
+    """what the C ABI refuses, on the entry of the CPU build (the time budget lives on a handle: tests/test_gpu_stream_rollout.py)"""
+    N, S = 2, 2
+    _, rec, T, ss = er.small_stream(N, S)
+    A0 = er.fresh_arrays(N, S, ss, rec)
+    for kw in (dict(ticks=0), dict(ticks=-1), dict(ticks=2, simulate=False), dict(ticks=2, goal_tol=-1e-3), dict(ticks=2, goal_tol=np.nan), dict(ticks=2, goal_tol=np.inf)):
+        A = er.copy_arrays(A0)
+        assert er.rollout(N, S, H, T, A, warm_dual=True, want_rc=True, **kw) == 1, kw
+        er.assert_arrays_equal(A0, A, f"{kw}: nothing runs")
+    assert er.rollout(N, S, H, T, er.copy_arrays(A0), ticks=2, warm_dual=True, want_rc=True) == 0
+
+
+def test_history_slots_and_unpack():
+    assert bstream.rollout_len() == ROLL["LEN"] == 52 and ROLL["PHI"] == bstream.RB["LEN"] == 43
+    assert [ROLL[k] for k in ("ROBOT", "PHI", "ERRCNT", "ITERS", "STATUS", "KKT", "NVALID", "USINGPREV", "SUCCESS", "GVIOL")] == [0] + list(range(43, 52))
+    row = np.arange(52, dtype=float)
+    d = bstream.unpack_rollout(row)
+    assert d["q"].tolist() == list(range(7)) and d["p"].tolist() == list(range(21, 27)) and d["x_phi_d"].tolist() == [33, 34, 35] and d["jerk"].tolist() == list(range(36, 43))
+    assert (d["phi"], d["error_count"], d["iters"], d["status"], d["kkt"], d["n_valid"], d["g_viol"]) == (43.0, 44, 45, 46, 47.0, 48, 51.0)
+    assert bstream.unpack_rollout(np.full(52, np.nan)) is None
