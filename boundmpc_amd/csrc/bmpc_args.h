@@ -59,6 +59,12 @@ inline void bmpc_opts_for(int N, OPTS &o) {
     pr.p = (p_); pr.x0 = (x0_); pr.x = (a).x + (long long)(b) * nw; pr.g = (a).g + (long long)(b) * ng; pr.lam_g = nullptr; pr.lam_x = nullptr; \
     pr.f = nullptr; pr.kkt = (a).kkt ? (a).kkt + (b) : nullptr; pr.iters = (a).iters ? (a).iters + (b) : nullptr; pr.status = (a).status + (b); \
     pr.state = (dual_); pr.resto_from = -1
+// Stream b of a fused launch (tick, rollout): its path table, state, robot and trajectory records, packed problem and dual state (NULL stays NULL)
+#define BMPC_STREAM_SLICES(a, s, b) \
+    const double *path = (s).path + (long long)(b) * (s).path_stride; \
+    double *ss = (s).ss + (long long)(b) * bmpcs::ss_len((a).N), *rb = (s).rb + (long long)(b) * bmpcs::RB_LEN, *traj = (s).traj + (long long)(b) * bmpcs::tr_len((a).N); \
+    double *p = const_cast<double *>((a).p) + (long long)(b) * np, *x0 = const_cast<double *>((a).x0) + (long long)(b) * nw; \
+    double *dual = (a).state ? (a).state + (long long)(b) * ((a).N * BMPC_NAMESPACE::NI + 2) : nullptr
 
 // kernel arguments of a solve; OPTS = the Opts type of the wave program's namespace (same layout in every instantiation)
 template <class OPTS>

@@ -1,8 +1,8 @@
 // bmpc_gpu_common.h -- what the translation units of libboundmpc_hip.so share: the device math macros the wave program
 // (bmpc_wave.inl) is written in, its lane and phase macros (one set per BMPC_NW: one wave, or a workgroup of cooperating waves), the phase
-// stamps and the prologue of a one-wave kernel; bmpc_args.h holds the kernel argument records and the per-problem slicing of a batch.  The
-// kernel entry texts shared between units are bmpc_multi_batch.inl (the batch kernel of the team and pair units) and bmpc_tick_kernel.inl (the
-// fused tick of the one-wave tick and team units).  bmpc_hip.hip holds the one-wave-per-problem batch kernel, the service kernel (one entry
+// stamps, the prologue of a one-wave kernel and the entry words (BMPCK_*) of the kernel entries the CPU tests compile whole (bmpc_tick_kernel.inl,
+// bmpc_rollout_kernel.inl); bmpc_args.h holds the kernel argument records and the per-problem / per-stream slicing of a batch.  The kernel entry texts shared between
+// units are bmpc_multi_batch.inl (team and pair batch kernel) and bmpc_tick_kernel.inl (one-wave and team fused tick).  bmpc_hip.hip holds the one-wave-per-problem batch kernel, the service kernel (one entry
 // over the jobs of bmpc_dual.inl, bmpc_kkt.inl and bmpc_sens.inl, each of which slices its own batch) and the C ABI, bmpc_team.hip the team
 // kernels (NW cooperating waves per problem), bmpc_pair.hip the pair kernel, bmpc_resto.hip the restoration kernels, bmpc_tick.hip the
 // one-wave fused ticks, bmpc_rollout.hip the rollouts (many ticks per stream in one launch; kernel text bmpc_rollout_kernel.inl).
@@ -34,6 +34,18 @@
 #define BMPC_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #define BMPC_NOW() ((long long)wall_clock64())      // constant 100 MHz counter
 #define BMPCS_OPAQUE(x) asm volatile("" : "+v"(x))      // stream functions: keeps a loaded value out of the optimiser's reach (no re-sinking of the load under a branch)
+
+// What a kernel entry names of its launch (bmpc_tick_kernel.inl, bmpc_rollout_kernel.inl): the HIP words; tests/emu/bmpc_emu_host.h has a host build's
+#define BMPCK_KERNEL __global__ void __launch_bounds__(64 * BMPC_NW, 1)
+#define BMPCK_LDS __shared__
+#define BMPCK_LANE threadIdx.x
+#define BMPCK_NL 64                 // lanes that run the stream functions (one wave)
+#define BMPCK_BLOCK blockIdx.x
+#define BMPCK_GRID gridDim.x
+#define BMPCK_WAVE (BMPC_NW == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)))      // this wave's index in the workgroup
+#define BMPCK_UNIFORM(i) __builtin_amdgcn_readfirstlane(i)      // a wave-uniform decision as a scalar: the barriers behind it sit in uniform control flow
+#define BMPCK_SYNC() __syncthreads()      // WORKGROUP barrier for every BMPC_NW (BMPCS_SYNC is a wave fence in a team unit)
+#define BMPCK_WAVE_HOOK(W)          // behind BMPC_WAVE_INIT; a host build gives the wave its lane and wave order here
 
 #if BMPC_NW > 1
 // ---- a workgroup of BMPC_NW cooperating waves per problem (bmpc_team.hip, bmpc_pair.hip) ----

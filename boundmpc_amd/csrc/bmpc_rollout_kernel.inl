@@ -15,8 +15,7 @@
 //   goal        goal_tol > 0 and phi_max - phi <= goal_tol behind a post (NodeLoop.run, the reference's experiment runners): the stream stops.
 // The history rows of the ticks a stream did not run are NaN.  With goal_tol = 0 every tick array holds afterwards what `ticks` launches of the
 // one-wave fused tick leave, bit for bit.
-// The same text is compiled by g++ for the CPU tests (tests/emu/bmpc_emu_rollout.cpp: one lane for the stream functions, the wave program's lane
-// loops inside the solve).
+// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp).
 #pragma once
 
 namespace bmpcs {
@@ -25,88 +24,74 @@ namespace bmpcs {
 enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH_NVALID, RH_USINGPREV, RH_SUCCESS, RH_GVIOL, RH_LEN };
 }  // namespace bmpcs
 
-// What the kernel entry names of the launch: on the GPU the HIP words; a host build of this text (tests/emu) defines them before it includes the
-// file -- one workgroup of one lane, BMPCR_WAVE_HOOK(W, pr) for what its wave carries beside the kernels' (the lane order of the solver's phases).
-#ifndef BMPC_EMU
-#define BMPCR_KERNEL __global__ void __launch_bounds__(64, 1)
-#define BMPCR_LDS __shared__
-#define BMPCR_LANE threadIdx.x
-#define BMPCR_NL 64
-#define BMPCR_BLOCK blockIdx.x
-#define BMPCR_GRID gridDim.x
-#define BMPCR_UNIFORM(i) __builtin_amdgcn_readfirstlane(i)      // a wave-uniform decision as a scalar: the barriers of the loops sit in uniform control flow
 // The tick loop must not become a reason to hoist: what the solver derives from the wave's and the problem's scalars (strides, table offsets, address
 // arithmetic) is invariant over the ticks of a stream, and hoisted out of the loop it would stay live across the whole solve (the register pressure
-// LANES_BEGIN guards against per phase).  Opaque per tick, the body allocates like the fused tick's.
-#define BMPCR_WAVE_HOOK(W, pr) asm volatile("" : "+s"((W).N), "+s"((W).S), "+s"((W).h), "+s"((W).G.b), "+s"((pr).p), "+s"((pr).x0), "+s"((pr).x), "+s"((pr).g), "+s"((pr).state))
-#define BMPCR_OPAQUE2(x, y) asm volatile("" : "+s"(x), "+s"(y))      // the same for what the stream functions are given
+// LANES_BEGIN guards against per phase).  Opaque per tick, the body allocates like the fused tick's.  Code generation of this kernel on the GPU only.
+#ifndef BMPC_EMU
+#define BMPCR_OPAQUE(...) asm volatile("" : __VA_ARGS__)
 #else
-#define BMPCR_OPAQUE2(x, y)
+#define BMPCR_OPAQUE(...)
 #endif
-
 // (the body of a tick in the kernel itself, as in bmpc_tick_kernel.inl: behind a function that takes `a` the argument loads lose their no-clobber
 // property -- bmpc_args.h, BMPC_PROBLEM)
 template <bool ZLDS, bool RESTO>
-BMPCR_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
-    BMPCR_LDS double lds[BMPC_NAMESPACE::L_SIZE];
+BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
+    BMPCK_LDS double lds[BMPC_NAMESPACE::L_SIZE];
     BMPC_STRIDES(a);
     double *sh = lds + BMPC_NAMESPACE::L_RED;
     static_assert(bmpcs::SH_LEN <= 6 * 64, "the stream functions' LDS words must fit into the solver's reduction area");
     const int TRN = bmpcs::tr_len(a.N);
     const double nan_ = __builtin_nan("");
-    for (int b = BMPCR_BLOCK; b < a.B; b += BMPCR_GRID) {
-        const double *path = s.path + (long long)b * s.path_stride;
-        double *ss = s.ss + (long long)b * bmpcs::ss_len(a.N), *rb = s.rb + (long long)b * bmpcs::RB_LEN, *traj = s.traj + (long long)b * TRN;
-        double *p = const_cast<double *>(a.p) + (long long)b * np, *x0 = const_cast<double *>(a.x0) + (long long)b * nw;
-        double *dual = a.state ? a.state + (long long)b * (a.N * BMPC_NAMESPACE::NI + 2) : nullptr;
+    for (int b = BMPCK_BLOCK; b < a.B; b += BMPCK_GRID) {
+        BMPC_STREAM_SLICES(a, s, b);
         long long busy = 0;      // counts of the 100 MHz clock spent in the stream's solves
         int t = 0;
         for (; t < r.ticks; t++) {
             // (the lost-plan test of the fused tick: BoundMPC.step() returns five Nones there and the reference node stops)
-            if (BMPCR_UNIFORM((int)(ss[bmpcs::SS_ERRCNT] >= (double)a.N))) {
-                if (BMPCR_LANE == 0) { a.status[b] = 3; if (a.iters) a.iters[b] = 0; if (a.kkt) a.kkt[b] = 0.0; }
+            if (BMPCK_UNIFORM((int)(ss[bmpcs::SS_ERRCNT] >= (double)a.N))) {
+                if (BMPCK_LANE == 0) { a.status[b] = 3; if (a.iters) a.iters[b] = 0; if (a.kkt) a.kkt[b] = 0.0; }
                 break;
             }
             int N_ = a.N, S_ = a.S;
-            BMPCR_OPAQUE2(N_, S_);
-            bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCR_LANE, BMPCR_NL, s.lvl_c, s.lvl_lo, s.lvl_hi);
-            BMPCS_SYNC();
-            BMPC_WAVE_INIT(W, a, lds, a.scratch + (long long)BMPCR_BLOCK * a.scr_stride, 0);
+            BMPCR_OPAQUE("+s"(N_), "+s"(S_));      // (what the stream functions are given)
+            bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCK_LANE, BMPCK_NL, s.lvl_c, s.lvl_lo, s.lvl_hi);
+            BMPCK_SYNC();
+            BMPC_WAVE_INIT(W, a, lds, a.scratch + (long long)BMPCK_BLOCK * a.scr_stride, 0); BMPCK_WAVE_HOOK(W);
             BMPC_TICK_PROBLEM(pr, a, b, p, x0, dual);
-            BMPCR_WAVE_HOOK(W, pr);
+            BMPCR_OPAQUE("+s"(W.N), "+s"(W.S), "+s"(W.h), "+s"(W.G.b), "+s"(pr.p), "+s"(pr.x0), "+s"(pr.x), "+s"(pr.g), "+s"(pr.state));
             const long long t0_ = a.latency_us ? BMPC_NOW() : 0;
             BMPC_NAMESPACE::wave_solve<ZLDS, true, RESTO>(W, pr);
-            BMPCS_SYNC();
+            BMPCK_SYNC();
             if (a.latency_us) busy += BMPC_NOW() - t0_;
-            BMPCR_OPAQUE2(N_, S_);
-            bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, s.rt_tol, sh, BMPCR_LANE, BMPCR_NL, s.rt_row_cap);
-            BMPCS_SYNC();      // the history and the next pack read ss, rb, x, traj and the dual state that other lanes have just stored
+            BMPCR_OPAQUE("+s"(N_), "+s"(S_));
+            bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, s.rt_tol, sh, BMPCK_LANE, BMPCK_NL, s.rt_row_cap);
+            BMPCK_SYNC();      // the history and the next pack read ss, rb, x, traj and the dual state that other lanes have just stored
             const long long row = (long long)t * a.B + b;
             if (r.hist) {
                 double *hr = r.hist + row * bmpcs::RH_LEN;
-                for (int i = BMPCR_LANE; i < bmpcs::RB_LEN; i += BMPCR_NL) hr[bmpcs::RH_ROBOT + i] = rb[i];
-                for (int i = BMPCR_LANE; i < 4; i += BMPCR_NL) hr[bmpcs::RH_NVALID + i] = traj[TRN - 4 + i];
-                if (BMPCR_LANE == 0) {
+                for (int i = BMPCK_LANE; i < bmpcs::RB_LEN; i += BMPCK_NL) hr[bmpcs::RH_ROBOT + i] = rb[i];
+                for (int i = BMPCK_LANE; i < 4; i += BMPCK_NL) hr[bmpcs::RH_NVALID + i] = traj[TRN - 4 + i];
+                if (BMPCK_LANE == 0) {
                     hr[bmpcs::RH_PHI] = ss[bmpcs::SS_PHI]; hr[bmpcs::RH_ERRCNT] = ss[bmpcs::SS_ERRCNT]; hr[bmpcs::RH_STATUS] = (double)a.status[b];
                     hr[bmpcs::RH_ITERS] = nan_; hr[bmpcs::RH_KKT] = nan_;
                     if (a.iters) hr[bmpcs::RH_ITERS] = (double)a.iters[b];
                     if (a.kkt) hr[bmpcs::RH_KKT] = a.kkt[b];
                 }
             }
-            if (r.traj_hist) { double *th = r.traj_hist + row * TRN; for (int i = BMPCR_LANE; i < TRN; i += BMPCR_NL) th[i] = traj[i]; }
-            if (BMPCR_UNIFORM((int)(r.goal_tol > 0.0 && ss[bmpcs::SS_PHIMAX] - ss[bmpcs::SS_PHI] <= r.goal_tol))) { t++; break; }
+            if (r.traj_hist) { double *th = r.traj_hist + row * TRN; for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) th[i] = traj[i]; }
+            if (BMPCK_UNIFORM((int)(r.goal_tol > 0.0 && ss[bmpcs::SS_PHIMAX] - ss[bmpcs::SS_PHI] <= r.goal_tol))) { t++; break; }
         }
         // t ticks were run; the rows behind them stay without a tick
         for (int u = t; u < r.ticks; u++) {
             const long long row = (long long)u * a.B + b;
-            if (r.hist) for (int i = BMPCR_LANE; i < bmpcs::RH_LEN; i += BMPCR_NL) r.hist[row * bmpcs::RH_LEN + i] = nan_;
-            if (r.traj_hist) for (int i = BMPCR_LANE; i < TRN; i += BMPCR_NL) r.traj_hist[row * TRN + i] = nan_;
+            if (r.hist) for (int i = BMPCK_LANE; i < bmpcs::RH_LEN; i += BMPCK_NL) r.hist[row * bmpcs::RH_LEN + i] = nan_;
+            if (r.traj_hist) for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) r.traj_hist[row * TRN + i] = nan_;
         }
-        if (BMPCR_LANE == 0) {
+        if (BMPCK_LANE == 0) {
             if (r.ticks_run) r.ticks_run[b] = t;
             if (a.latency_us) a.latency_us[b] = (double)busy * 0.01;
         }
-        BMPCS_SYNC();      // the next stream's pack reuses the LDS words this stream's last phase read
+        BMPCK_SYNC();      // the next stream's pack reuses the LDS words this stream's last phase read
     }
 }
 

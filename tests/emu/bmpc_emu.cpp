@@ -5,8 +5,8 @@
 // as a loop over its waves in a caller-chosen order (bmpc_emu_host.h), and runs per problem the lines the kernel entries run: the argument
 // record, the wave initialiser and the slicers of csrc/bmpc_args.h.  It exists so the kernel's indexing, phase structure and numerics can be
 // unit-tested in a container without a GPU (pytest -m "not gpu"), and so that intra-phase cross-lane (and cross-wave) dependences show up as
-// order-dependent results.  It is NOT part of the product: boundmpc_amd never builds, loads or falls back to it.
-#include <cstdlib>
+// order-dependent results.  The fused tick is run as its kernel entry text (csrc/bmpc_tick_kernel.inl, both of its instantiations), launched as a
+// loop over the blocks.  It is NOT part of the product: boundmpc_amd never builds, loads or falls back to it.
 #include <cstring>
 #include <cstdio>
 #ifdef _OPENMP
@@ -30,15 +30,16 @@ extern "C" int bmpc_emu_team_lds_doubles() { return ns::L_SIZE; }
 #else
 #define EMU_SOLVE bmpc_emu_solve
 #endif
-// A batch of B problems, each on a workgroup of its own.  BMPC_EMU_POISON=1: LDS and workspace hold NaN before every problem (emu_wave).
+// A batch of B problems, each on a workgroup of its own.  mode bit 0 (poison): LDS and workspace hold NaN before every problem (emu_wave).
 // One wave: what the one-wave batch kernel and the restoration kernel behind it compute (bmpc_hip.hip bmpc_solve_kernel, bmpc_resto.hip).
-// One wave with BMPC_EMU_INKERNEL=1: the solve of a fused tick (bmpc_tick_kernel.inl), with the restoration phase inside and only the outputs
-// a tick has -- x, g, kkt, iters, status; x, g and status must be given.
+// One wave with mode bit 1 (in-kernel): the solve of a fused tick on raw (p, x0) -- the instantiation the tick calls (real-time text, no deadline),
+// with the restoration phase inside and only the outputs a tick has -- x, g, kkt, iters, status; x, g and status must be given.
 // Teams: the multi-wave batch kernel's call (bmpc_multi_batch.inl) on the text with the restoration phase inside, as the fused team tick runs
 // it; the team BATCH kernel hands jammed problems to the one-wave restoration kernel, which no emulator build runs behind a team.
 extern "C" int EMU_SOLVE(int N, int S, double h, const ns::Opts *opts, int B, const double *p, const double *x0, double *state, double *x, double *g,
-                         double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt, int lane_order, int wave_order, int nthreads) {
-    if (!ns::emu_shape_ok(N, S)) return 1;
+                         double *lam_g, double *lam_x, double *f, int *iters, int *status, double *kkt, int lane_order, int wave_order, int nthreads, int mode) {
+    const bool poison = mode & 1, inkernel = mode & 2;
+    if (!ns::emu_shape_ok(N, S) || (inkernel && (BMPC_NW > 1 || !x || !g || !status))) return 1;
     KArgs a = ns::emu_args(N, S, B, h, *opts);
     a.p = p; a.x0 = x0; a.state = state; a.x = x; a.g = g; a.lam_g = lam_g; a.lam_x = lam_x; a.f = f; a.iters = iters; a.status = status; a.kkt = kkt;
     const ns::Scr sc = ns::make_scr(N);
@@ -47,9 +48,7 @@ extern "C" int EMU_SOLVE(int N, int S, double h, const ns::Opts *opts, int B, co
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
 #endif
-    const bool poison = getenv("BMPC_EMU_POISON") != nullptr;
 #if BMPC_NW == 1
-    const bool inkernel = getenv("BMPC_EMU_INKERNEL") != nullptr;
     // The batch kernel leaves a jammed problem (internal status 4) with its iterate in x, and the restoration kernel continues it from there: for
     // both, x, iters and status are always there -- private ones here, copied to the caller's (where given) behind the hand-over.
     std::vector<double> xb((size_t)B * nw); std::vector<int> itb(B, 0), stb(B, 0);
@@ -67,7 +66,7 @@ extern "C" int EMU_SOLVE(int N, int S, double h, const ns::Opts *opts, int B, co
 #else
             if (inkernel) {
                 BMPC_TICK_PROBLEM(pr, a, b, p + (size_t)b * np, x0 + (size_t)b * nw, state ? state + (size_t)b * (N * ns::NI + 2) : nullptr);
-                if (zl) ns::wave_solve<true, false, true>(W, pr); else ns::wave_solve<false, false, true>(W, pr);
+                if (zl) ns::wave_solve<true, true, true>(W, pr); else ns::wave_solve<false, true, true>(W, pr);
                 continue;
             }
             BMPC_PROBLEM(pr, a, b);
@@ -86,10 +85,53 @@ extern "C" int EMU_SOLVE(int N, int S, double h, const ns::Opts *opts, int B, co
     return 0;
 }
 
-#if BMPC_NW == 1
-#define BMPCS_SYNC()
+#ifndef BMPC_WSG      // (the pair has no stream kernels)
 #include "../../boundmpc_amd/csrc/bmpc_stream.inl"
+#include "../../boundmpc_amd/csrc/bmpc_tick_kernel.inl"
 
+// ONE fused tick of B streams as the kernel entry text runs it: the arguments of bmpc_stream_tick (path [B][path_entries][48]), behind the option record
+// and in front of what the handle holds (real-time tolerance, position-row cap, level rule) and the lane and wave orders.  Returns 1 where the C ABI
+// returns BMPC_ERR_ARG (tick_args_ok).  The launch is a loop over the blocks 0 ... B -- one more than there are streams: that one meets the kernel's own
+// guard -- on one workspace slab; the instantiation is chosen as bmpc_tick_launch / bmpc_team_launch_tick are called: the iterate in LDS by the horizon
+// rule (teams: always), the restoration phase by the option record.  No clock here: no time budget.
+#if BMPC_NW > 1
+#define EMU_STREAM_TICK bmpc_emu_team_stream_tick
+#else
+#define EMU_STREAM_TICK bmpc_emu_stream_tick
+#endif
+extern "C" int EMU_STREAM_TICK(int N, int S, double h, const ns::Opts *opts, int B, const double *path, int path_entries, double *ss, double *rb, double *p, double *x0,
+                               double *dual, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags, double rt_tol,
+                               double rt_row_cap, double lvl_c, double lvl_lo, double lvl_hi, int lane_order, int wave_order) {
+    if (!ns::emu_shape_ok(N, S) || B < 0 || max_iter < 0 || path_entries < S + 1 || N > bmpcs::STREAM_NMAX) return 1;
+    if (B > 0 && (!path || !ss || !rb || !p || !x0 || !x || !g || !status || !traj)) return 1;
+#if BMPC_NW > 1
+    if (N > ns::TEAM_NMAX) return 1;      // (the library ticks such a horizon with one wave per stream)
+#endif
+    KArgs a = ns::emu_args(N, S, B, h, *opts);
+    if (max_iter > 0) a.o.max_iter = max_iter;
+    a.o.verbose = 0; a.o.retry_cap = 0;
+    a.p = p; a.x0 = x0; a.state = dual; a.x = x; a.g = g; a.iters = iters; a.status = status; a.kkt = kkt;
+    const SArgs s{path, path_entries * bmpcs::PT_LEN, ss, rb, traj, flags, rt_tol, rt_row_cap, lvl_c, lvl_lo, lvl_hi};
+    std::vector<double> scr(ns::make_scr(N).size, 0.0);
+    a.scratch = scr.data(); a.scr_stride = 0;
+    const bool resto = a.o.restoration != 0;
+    for (int b = 0; b <= B; b++) {
+        emu_launch = EmuLaunch{b, B + 1, lane_order, wave_order};
+#if BMPC_NW > 1
+        if (resto) bmpc_team_tick_kernel<true>(a, s); else bmpc_team_tick_kernel<false>(a, s);
+#else
+        const bool zl = ns::emu_zlds(N, S);
+        if (zl && resto) bmpc_stream_tick_kernel<true, true>(a, s);
+        else if (zl) bmpc_stream_tick_kernel<true, false>(a, s);
+        else if (resto) bmpc_stream_tick_kernel<false, true>(a, s);
+        else bmpc_stream_tick_kernel<false, false>(a, s);
+#endif
+    }
+    return 0;
+}
+#endif
+
+#if BMPC_NW == 1
 // CPU build of the stream functions (same text as the device kernels), one call per stream
 extern "C" void bmpc_emu_stream_lengths(int N, int *out) { out[0] = bmpcs::PT_LEN; out[1] = bmpcs::ss_len(N); out[2] = bmpcs::RB_LEN; out[3] = bmpcs::tr_len(N); }
 extern "C" void bmpc_emu_stream_pack(int N, int S, const double *path, double *ss, const double *rb, double *p, double *x0, double *dual, const double *xlast, double lvl_c, double lvl_lo, double lvl_hi) {

@@ -1,28 +1,17 @@
 // TEST-ONLY: CPU build of the rollout (boundmpc_amd/csrc/bmpc_rollout_kernel.inl), the same text the GPU kernels bmpc_stream_rollout_kernel<ZLDS, RESTO>
-// run: the stream functions with one lane, the wave program inside with its phases as loops over the 64 lanes (bmpc_emu_host.h), one stream per call.
+// run, in the host's entry words (bmpc_emu_host.h: the stream functions with one lane, the wave program inside with its phases as loops over the 64
+// lanes), one stream per call.
 // Used by tests/test_stream_rollout.py and tests/test_gpu_stream_rollout.py; never built, loaded or fallen back to by the product.
 // With -DBMPC_EMU_ROLLOUT_MAIN a stand-alone program for a sanitizer build: it reads a case file (tests/emu/emu_rollout.py write_case), runs the
-// rollout and prints ticks_run and a checksum.
+// fused tick's text (bmpc_emu.cpp, compiled beside this file) and the rollout and prints ticks_run and a checksum.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 
-#define BMPC_NOW() 0LL      // no clock here: no time budget, and a latency buffer is never registered
 #include "bmpc_emu_host.h"
-#define BMPCS_SYNC()
 #include "../../boundmpc_amd/csrc/bmpc_stream.inl"
 
 typedef KArgsT<bmpc::Opts> KArgs;
-static int emu_lane_order = 0;      // of the solver's phases: 0 forward, 1 reverse, 2 scrambled (emu_wave's orders)
-#define BMPCR_WAVE_HOOK(W, pr) for (int i_ = 0; i_ < 64; i_++) (W).order[i_] = emu_lane_order == 0 ? i_ : (emu_lane_order == 1 ? 63 - i_ : (i_ * 37 + 11) % 64)
-// the launch of the kernel entry: one workgroup of one lane (the stream functions' phases run on lane 0 of 1), its LDS array a static one
-#define BMPCR_KERNEL static void
-#define BMPCR_LDS static
-#define BMPCR_LANE 0
-#define BMPCR_NL 1
-#define BMPCR_BLOCK 0
-#define BMPCR_GRID 1
-#define BMPCR_UNIFORM(i) (i)
 #include "../../boundmpc_amd/csrc/bmpc_rollout_kernel.inl"
 
 extern "C" int bmpc_emu_stream_rollout_len() { return bmpcs::RH_LEN; }
@@ -44,7 +33,7 @@ extern "C" int bmpc_emu_stream_rollout(int N, int S, double h, const bmpc::Opts 
     const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run};
     std::vector<double> scr(bmpc::make_scr(N).size, 0.0);
     a.scratch = scr.data(); a.scr_stride = (long long)scr.size();
-    emu_lane_order = lane_order;
+    emu_launch = EmuLaunch{0, 1, lane_order, 0};      // one workgroup
     const bool zl = bmpc::emu_zlds(N, S), resto = opts->restoration != 0;
     if (zl && resto) bmpc_stream_rollout_kernel<true, true>(a, s, r);
     else if (zl) bmpc_stream_rollout_kernel<true, false>(a, s, r);
@@ -54,8 +43,11 @@ extern "C" int bmpc_emu_stream_rollout(int N, int S, double h, const bmpc::Opts 
 }
 
 #ifdef BMPC_EMU_ROLLOUT_MAIN
-// case file (doubles): N S h ticks cap flags goal_tol max_iter tick0_cap | path [cap][48] | ss | rb.  Tick 0 is solved with tick0_cap (a rollout of one
-// tick), then `ticks` ticks with max_iter; every array is exactly as long as the kernel text may index it, so that an access outside is seen.
+// case file (doubles): N S h ticks cap flags goal_tol max_iter tick0_cap | path [cap][48] | ss | rb.  Tick 0 is solved with tick0_cap by the fused tick's
+// text, then `ticks` ticks with max_iter by the rollout's; every array is exactly as long as the kernel text may index it, so that an access outside is seen.
+extern "C" int bmpc_emu_stream_tick(int N, int S, double h, const bmpc::Opts *opts, int B, const double *path, int path_entries, double *ss, double *rb, double *p, double *x0,
+                                    double *dual, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags, double rt_tol,
+                                    double rt_row_cap, double lvl_c, double lvl_lo, double lvl_hi, int lane_order, int wave_order);
 int main(int argc, char **argv) {
     if (argc < 2) { fprintf(stderr, "usage: %s case.bin\n", argv[0]); return 2; }
     FILE *f = fopen(argv[1], "rb");
@@ -71,8 +63,8 @@ int main(int argc, char **argv) {
     bmpc::Opts o; bmpc_opts_for(N, o); o.start_rollout = 0;
     std::vector<double> p(141 + 91 * S), x0(44 * N), dual(57 * N + 2, 0.0), x(44 * N), g(43 * N), traj(TRN), hist((size_t)ticks * bmpcs::RH_LEN), th((size_t)ticks * TRN);
     int iters = 0, status = 0, run = 0; double kkt = 0.0;
-    int rc = bmpc_emu_stream_rollout(N, S, hd[2], &o, 1, path.data(), cap, ss.data(), rb.data(), p.data(), x0.data(), dual.data(), cap0, x.data(), g.data(), &iters, &status,
-                                     &kkt, traj.data(), 1, 0.0, nullptr, nullptr, nullptr, 1e-4, 0.0, 0.0, 0.0, 0.0, 0);
+    int rc = bmpc_emu_stream_tick(N, S, hd[2], &o, 1, path.data(), cap, ss.data(), rb.data(), p.data(), x0.data(), dual.data(), cap0, x.data(), g.data(), &iters, &status,
+                                  &kkt, traj.data(), 1, 1e-4, 0.0, 0.0, 0.0, 0.0, 0, 0);
     if (rc == 0) rc = bmpc_emu_stream_rollout(N, S, hd[2], &o, ticks, path.data(), cap, ss.data(), rb.data(), p.data(), x0.data(), dual.data(), max_iter, x.data(), g.data(),
                                               &iters, &status, &kkt, traj.data(), flags, hd[6], hist.data(), th.data(), &run, 1e-4, 0.0, 0.0, 0.0, 0.0, 0);
     double sum = 0.0;

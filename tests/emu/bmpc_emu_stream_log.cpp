@@ -3,7 +3,6 @@
 #include <cstdio>
 
 #include "bmpc_emu_host.h"
-#define BMPCS_SYNC()
 #include "../../boundmpc_amd/csrc/bmpc_stream.inl"
 #include "../../boundmpc_amd/csrc/bmpc_stream_log.inl"
 

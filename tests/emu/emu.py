@@ -1,5 +1,6 @@
-"""TEST-ONLY: ctypes bindings of the CPU lane emulators of the wave program (tests/emu/*.cpp) and the one place that builds them.
-Not part of the product; see the header of bmpc_emu.cpp."""
+"""TEST-ONLY: ctypes bindings of the CPU lane emulators of the wave program (tests/emu/*.cpp) and the one place that builds them: solves, the stream
+functions one by one, and the fused tick as its kernel entry text (stream_tick, one wave or a team).  Modes of a solve (poison, in_kernel) are
+arguments, nothing is read from the environment.  Not part of the product; see the header of bmpc_emu.cpp."""
 import ctypes
 import functools
 import os
@@ -11,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "..", "..", "boundmpc_amd", "csrc")
 # what every emulator is built from beside its own source: the host header, the kernels' entry records and slicers, the wave program
 _COMMON = [os.path.join(_HERE, "bmpc_emu_host.h"), os.path.join(_CSRC, "bmpc_args.h"), os.path.join(_CSRC, "bmpc_wave.inl")]
+_STREAM = ("bmpc_stream.inl", "bmpc_tick_kernel.inl")      # what bmpc_emu.cpp reads of csrc beside them
 
 
 class Opts(ctypes.Structure):
@@ -32,7 +34,7 @@ def _build(lib_name, source, flags=(), deps=()):
 
 def lib():
     """the one-wave emulator: solves, the stream functions, the library's option rule and the debug entries"""
-    L = _build("libbmpc_emu.so", "bmpc_emu.cpp", ("-fopenmp", "-DBMPC_NW=1"), ("bmpc_stream.inl",))
+    L = _build("libbmpc_emu.so", "bmpc_emu.cpp", ("-fopenmp", "-DBMPC_NW=1"), _STREAM)
     assert L.bmpc_emu_opts_size() == ctypes.sizeof(Opts), "tests/emu/emu.py Opts is not the wave program's option record"
     return L
 
@@ -67,7 +69,7 @@ def _p(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None else None
 
 
-def _solve(entry, p, x0, N, S, h, opts, lane_order, wave_order, nthreads, state):
+def _solve(entry, p, x0, N, S, h, opts, lane_order, wave_order, nthreads, state, poison=False, in_kernel=False):
     p = np.ascontiguousarray(np.atleast_2d(p), dtype=np.float64)
     x0 = np.ascontiguousarray(np.atleast_2d(x0), dtype=np.float64)
     B = p.shape[0]
@@ -75,30 +77,31 @@ def _solve(entry, p, x0, N, S, h, opts, lane_order, wave_order, nthreads, state)
                f=np.zeros(B), iters=np.zeros(B, dtype=np.int32), status=np.zeros(B, dtype=np.int32), kkt=np.zeros(B))
     rc = entry(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), ctypes.byref(opts_for(N, opts)), ctypes.c_int(B), _p(p), _p(x0), _p(state),
                _p(out["x"]), _p(out["g"]), _p(out["lam_g"]), _p(out["lam_x"]), _p(out["f"]), _p(out["iters"]), _p(out["status"]), _p(out["kkt"]),
-               ctypes.c_int(lane_order), ctypes.c_int(wave_order), ctypes.c_int(nthreads))
+               ctypes.c_int(lane_order), ctypes.c_int(wave_order), ctypes.c_int(nthreads), ctypes.c_int(int(bool(poison)) | 2 * int(bool(in_kernel))))
     assert rc == 0
     return out
 
 
-def solve(p, x0, N, S, h, opts=None, lane_order=0, nthreads=0, state=None):
-    """The one-wave program on the CPU, lanes in `lane_order` (0 forward, 1 reverse, 2 scrambled).  With BMPC_EMU_INKERNEL set it runs the
-    solve of a fused tick, which yields only x, g, kkt, iters and status: lam_g, lam_x and f stay zero and are no results."""
-    return _solve(lib().bmpc_emu_solve, p, x0, N, S, h, opts, lane_order, 0, nthreads, state)
+def solve(p, x0, N, S, h, opts=None, lane_order=0, nthreads=0, state=None, poison=False, in_kernel=False):
+    """The one-wave program on the CPU, lanes in `lane_order` (0 forward, 1 reverse, 2 scrambled).  poison: LDS and workspace hold NaN before every
+    problem.  in_kernel: the solve of a fused tick (its instantiation, the restoration phase inside) on raw (p, x0), which yields only x, g, kkt,
+    iters and status: lam_g, lam_x and f stay zero and are no results."""
+    return _solve(lib().bmpc_emu_solve, p, x0, N, S, h, opts, lane_order, 0, nthreads, state, poison, in_kernel)
 
 
 # ---- team variant of the wave program (tests/emu/bmpc_emu.cpp with BMPC_NW cooperating waves per problem) ----
 def team_lib(nw=4):
     """nw = 4 / 2: teams (workspace rows in LDS); nw = "pair": the two-wave team with the workspace in the global slab (BMPC_WSG, csrc/bmpc_pair.hip)"""
     pair = nw == "pair"
-    L = _build("libbmpc_emu_pair.so" if pair else f"libbmpc_emu_team{nw}.so", "bmpc_emu.cpp", ("-fopenmp",) + (("-DBMPC_NW=2", "-DBMPC_WSG") if pair else (f"-DBMPC_NW={nw}",)))
+    L = _build("libbmpc_emu_pair.so" if pair else f"libbmpc_emu_team{nw}.so", "bmpc_emu.cpp", ("-fopenmp",) + (("-DBMPC_NW=2", "-DBMPC_WSG") if pair else (f"-DBMPC_NW={nw}",)), _STREAM)
     assert L.bmpc_emu_team_waves() == (2 if pair else nw)
     return L
 
 
-def solve_team(p, x0, N, S, h, nw=4, opts=None, lane_order=0, wave_order=0, nthreads=0, state=None):
+def solve_team(p, x0, N, S, h, nw=4, opts=None, lane_order=0, wave_order=0, nthreads=0, state=None, poison=False):
     """The team program (nw waves per problem) on the CPU: wide phases run wave after wave in `wave_order` (0 forward, 1 reverse,
-    2 scrambled), lanes in `lane_order`."""
-    return _solve(team_lib(nw).bmpc_emu_team_solve, p, x0, N, S, h, opts, lane_order, wave_order, nthreads, state)
+    2 scrambled), lanes in `lane_order`; poison as in solve."""
+    return _solve(team_lib(nw).bmpc_emu_team_solve, p, x0, N, S, h, opts, lane_order, wave_order, nthreads, state, poison)
 
 
 # ---- CPU build of the stream functions (boundmpc_amd/csrc/bmpc_stream.inl) ----
@@ -124,6 +127,25 @@ def stream_post(N, S, h, path, ss, rb, x, g, status, simulate=True, rt_tol=1e-4,
     lib().bmpc_emu_stream_post(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), _p(path), _p(ss), _p(rb), _p(x), _p(g), ctypes.c_int(int(status)),
                                _p(traj), ctypes.c_int(int(simulate) | int(flags)), ctypes.c_double(rt_tol), ctypes.c_double(rt_row_cap))
     return traj
+
+
+def stream_tick(N, S, h, T, A, max_iter=0, warm_dual=True, accept_capped=False, simulate=True, opts=None, rt_tol=1e-4, rt_row_cap=0.0, level_rule=(0.0, 0.0, 0.0),
+                lane_order=0, wave_order=0, nw=1, want_rc=False):
+    """ONE fused tick as the kernel entry text runs it (csrc/bmpc_tick_kernel.inl; nw = 1: one wave per stream, else the team's) on the tick arrays `A`
+    (tests/emu/emu_rollout.py fresh_arrays; B streams: every array with a leading axis of B, T [B][M][48]), advanced in place.  Returns the entry's
+    return code with want_rc (1: the arguments the C ABI refuses; A[k] = None passes NULL), else asserts it 0."""
+    T = np.ascontiguousarray(T, dtype=np.float64)
+    B = 1 if T.ndim == 2 else T.shape[0]
+    assert all(v is None or v.flags.c_contiguous for v in A.values())
+    c = ctypes
+    entry = lib().bmpc_emu_stream_tick if nw == 1 else team_lib(nw).bmpc_emu_team_stream_tick
+    rc = entry(c.c_int(N), c.c_int(S), c.c_double(h), c.byref(opts_for(N, opts)), c.c_int(B), _p(T), c.c_int(T.shape[-2]), _p(A["ss"]), _p(A["rb"]), _p(A["p"]),
+               _p(A["x0"]), _p(A["dual"]) if warm_dual else None, c.c_int(int(max_iter)), _p(A["x"]), _p(A["g"]), _p(A["iters"]), _p(A["status"]), _p(A["kkt"]),
+               _p(A["traj"]), c.c_int(int(bool(simulate)) | (2 if accept_capped else 0)), c.c_double(rt_tol), c.c_double(rt_row_cap), c.c_double(level_rule[0]),
+               c.c_double(level_rule[1]), c.c_double(level_rule[2]), c.c_int(lane_order), c.c_int(wave_order))
+    if want_rc:
+        return rc
+    assert rc == 0
 
 
 def jacobian_lin_ddot(q, dq, ddq):

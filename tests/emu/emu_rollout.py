@@ -1,7 +1,9 @@
 """TEST-ONLY: the CPU build of the rollout (boundmpc_amd/csrc/bmpc_rollout_kernel.inl through tests/emu/bmpc_emu_rollout.cpp) and what the CPU and
-the GPU tests of the rollout share: the per-tick loop of the existing emulator entries that is its exact checker, and the small streams.
+the GPU tests of the rollout and of the fused tick share: the per-tick loop of the fused tick's own kernel text (emu.stream_tick) that is the
+rollout's exact checker, and the small streams.
 
-  python -m tests.emu.emu_rollout --sanitize    builds bmpc_emu_rollout.cpp as a stand-alone program with -fsanitize=address,undefined and runs it
+  python -m tests.emu.emu_rollout --sanitize    builds bmpc_emu_rollout.cpp (with bmpc_emu.cpp beside it: tick 0 of every case runs the fused tick's
+                                                text) as a stand-alone program with -fsanitize=address,undefined and runs it
 """
 import ctypes
 import os
@@ -66,32 +68,12 @@ def rollout(N, S, h, T, A, ticks, max_iter=0, warm_dual=True, accept_capped=Fals
     return dict(hist=hist, traj_hist=th, ticks_run=int(run[0]))
 
 
-def tick(N, S, h, T, A, max_iter=0, warm_dual=True, accept_capped=False, opts=None, rt_tol=1e-4, rt_row_cap=0.0, level_rule=(0.0, 0.0, 0.0)):
-    """ONE fused tick of the existing emulator entries on the tick arrays `A` (advanced in place): emu.stream_pack -> the in-kernel solve of the fused
-    tick (emu.solve under BMPC_EMU_INKERNEL) -> emu.stream_post with the plant step, with the skip of a stream that has lost its plan.  Returns the
-    history row the rollout would write behind this tick (None for a skipped stream)."""
-    if A["ss"][bstream.SS["ERRCNT"]] >= N:
-        A["status"][0], A["iters"][0], A["kkt"][0] = 3, 0, 0.0
-        return None
-    dual = A["dual"] if warm_dual else None
-    p, x0 = emu.stream_pack(N, S, T, A["ss"], A["rb"], dual=dual, xlast=A["x"].copy() if accept_capped else None, level_rule=level_rule)
-    A["p"][:], A["x0"][:] = p, x0
-    o = emu.opts_for(N, opts)
-    o2 = emu.Opts.from_buffer_copy(o)
-    if max_iter > 0:
-        o2.max_iter = max_iter
-    os.environ["BMPC_EMU_INKERNEL"] = "1"
-    try:
-        r = emu.solve(p, x0, N, S, h, opts=o2, state=dual[None] if dual is not None else None)
-    finally:
-        del os.environ["BMPC_EMU_INKERNEL"]
-    A["x"][:], A["g"][:], A["iters"][0], A["status"][0], A["kkt"][0] = r["x"][0], r["g"][0], r["iters"][0], r["status"][0], r["kkt"][0]
-    # (the emulator's own entry, not emu.stream_post: that one hands out a fresh record per call, while a stream's record persists -- a shortened
-    # trajectory leaves the columns behind it as the tick before wrote them)
-    c = ctypes
-    emu.lib().bmpc_emu_stream_post(c.c_int(N), c.c_int(S), c.c_double(h), emu._p(T), emu._p(A["ss"]), emu._p(A["rb"]), emu._p(A["x"]), emu._p(A["g"]),
-                                   c.c_int(int(A["status"][0])), emu._p(A["traj"]), c.c_int(1 | (2 if accept_capped else 0)), c.c_double(rt_tol), c.c_double(rt_row_cap))
-    return history_row(A)
+def tick(N, S, h, T, A, **kw):
+    """ONE fused tick -- the kernel entry text, emu.stream_tick -- on the tick arrays `A` (advanced in place).  Returns the history row the rollout would
+    write behind this tick (None for a stream that has lost its plan, which the tick skips)."""
+    lost = A["ss"][bstream.SS["ERRCNT"]] >= N
+    emu.stream_tick(N, S, h, T, A, **kw)
+    return None if lost else history_row(A)
 
 
 def history_row(A):
@@ -124,7 +106,7 @@ def write_case(path, N, S, h, T, ss, rb, ticks, flags=1, goal_tol=0.0, max_iter=
 
 
 def run_sanitized(cases=((2, 2, 6, 0, 0.0), (10, 4, 13, 2, 0.0), (10, 4, 3, 0, 0.0), (2, 2, 6, 0, 6.9242), (1, 2, 4, 0, 0.0)), keep=None):
-    """bmpc_emu_rollout.cpp with its own main under AddressSanitizer and UndefinedBehaviorSanitizer, on (N, S, ticks, max_iter, goal_tol) cases:
+    """bmpc_emu_rollout.cpp with its own main (and bmpc_emu.cpp for the tick text of tick 0) under AddressSanitizer and UndefinedBehaviorSanitizer, on (N, S, ticks, max_iter, goal_tol) cases:
     a converged loop, the reference's shape capped at two iterations (runs into the lost-plan stop, NaN rows behind it), converged, a goal that is
     reached inside the ticks, the smallest horizon.  Returns the program's output lines; raises when the build fails, a run returns non-zero or a
     sanitizer reports."""
@@ -134,7 +116,7 @@ def run_sanitized(cases=((2, 2, 6, 0, 0.0), (10, 4, 13, 2, 0.0), (10, 4, 3, 0, 0
         tmp = keep or tmp
         exe = os.path.join(tmp, "bmpc_emu_rollout_san")
         subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer", "-Wno-unknown-pragmas",
-                               "-Wno-enum-compare", "-DBMPC_EMU_ROLLOUT_MAIN", "-o", exe, os.path.join(here, "bmpc_emu_rollout.cpp")])
+                               "-Wno-enum-compare", "-DBMPC_EMU_ROLLOUT_MAIN", "-o", exe, os.path.join(here, "bmpc_emu_rollout.cpp"), os.path.join(here, "bmpc_emu.cpp")])
         for i, (N, S, ticks, max_iter, goal_tol) in enumerate(cases):
             _, rec, T, ss = small_stream(N, S)
             case = os.path.join(tmp, f"case{i}.bin")

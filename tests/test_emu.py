@@ -176,30 +176,25 @@ def test_infeasible_problem_ends_as_status_2_in_oracle_and_emulator():
 
 def test_no_solve_reads_what_it_has_not_written():
     """LDS and the workspace slab are reused from problem to problem on the GPU.  With both filled with NaN before every problem
-    (BMPC_EMU_POISON) every output must stay bit-identical: cold solves, evaluation only (max_iter 0), capped Gauss-Newton ticks,
+    (poison=True) every output must stay bit-identical: cold solves, evaluation only (max_iter 0), capped Gauss-Newton ticks,
     warm-started ticks, the long-horizon instantiation."""
     from boundmpc_amd import workload
     d = np.load(os.path.join(G, "g7_closedloop_exp1.npz"))
 
-    def run():
+    def run(poison):
         outs = []
         P, X, _ = workload.make_batch(8, seed=0, N=10)
-        outs.append(emu.solve(P, X, 10, 4, 0.1, nthreads=4))
-        outs.append(emu.solve(P, X, 10, 4, 0.1, emu.default_opts(max_iter=0), nthreads=4))
-        outs.append(emu.solve(P, X, 10, 4, 0.1, emu.default_opts(exact_hessian=0, tol=1e-3, max_iter=4), nthreads=4))
+        outs.append(emu.solve(P, X, 10, 4, 0.1, nthreads=4, poison=poison))
+        outs.append(emu.solve(P, X, 10, 4, 0.1, emu.default_opts(max_iter=0), nthreads=4, poison=poison))
+        outs.append(emu.solve(P, X, 10, 4, 0.1, emu.default_opts(exact_hessian=0, tol=1e-3, max_iter=4), nthreads=4, poison=poison))
         st = np.zeros((1, c_oracle.state_len(10)))
         for t in range(4):
-            outs.append(emu.solve(d["p"][t:t + 1], d["x0"][t:t + 1], 10, 4, 0.1, emu.default_opts(tol=1e-3, max_iter=4, mu_warm=3e-2), state=st, nthreads=1))
+            outs.append(emu.solve(d["p"][t:t + 1], d["x0"][t:t + 1], 10, 4, 0.1, emu.default_opts(tol=1e-3, max_iter=4, mu_warm=3e-2), state=st, nthreads=1, poison=poison))
             nu = st[0, :570].reshape(10, 57); nu[:-1] = nu[1:].copy()
         P3, X3, _ = workload.make_batch(2, seed=2, N=30, tight=True)
-        outs.append(emu.solve(P3, X3, 30, 4, 0.1, nthreads=2))
+        outs.append(emu.solve(P3, X3, 30, 4, 0.1, nthreads=2, poison=poison))
         return outs
-    plain = run()
-    os.environ["BMPC_EMU_POISON"] = "1"
-    try:
-        poisoned = run()
-    finally:
-        del os.environ["BMPC_EMU_POISON"]
+    plain, poisoned = run(False), run(True)
     for a, b in zip(plain, poisoned):
         for k in ("x", "g", "lam_g", "lam_x", "f", "kkt", "iters", "status"):
             assert np.array_equal(a[k], b[k], equal_nan=True), k
@@ -255,11 +250,7 @@ def test_team_program_matches_oracle_and_is_order_invariant(nw):
     P, X, _ = workload.make_batch(1024, seed=0, rows=(0, 24), workers=1)
     ref = c_oracle.solve(P, X, 10, 4, 0.1, nthreads=4)
     one = emu.solve(P, X, 10, 4, 0.1, nthreads=4)
-    os.environ["BMPC_EMU_POISON"] = "1"      # LDS and workspace of every problem start as NaN: a read of a word nobody wrote shows
-    try:
-        t = emu.solve_team(P, X, 10, 4, 0.1, nw=nw, nthreads=4)
-    finally:
-        del os.environ["BMPC_EMU_POISON"]
+    t = emu.solve_team(P, X, 10, 4, 0.1, nw=nw, nthreads=4, poison=True)      # LDS and workspace of every problem start as NaN: a read of a word nobody wrote shows
     assert (t["status"] == ref["status"]).all() and (t["status"] == 0).all()
     assert np.abs(t["iters"] - ref["iters"]).max() <= 1
     d = (t["x"] - ref["x"]).reshape(-1, 10, 44)[:, :, 8:15]
@@ -300,11 +291,7 @@ def test_restoration_phase_kernel_text_follows_the_oracle_on_g13b():
     d = np.load(os.path.join(G, "g13b_first_failures_256_streams.npz"))
     ref = c_oracle.solve(d["p"], d["x0"], 10, 4, 0.1, opts=c_oracle.default_opts(max_iter=500, start_rollout=0), nthreads=4)
     a = emu.solve(d["p"], d["x0"], 10, 4, 0.1, opts=emu.default_opts(max_iter=500, start_rollout=0), nthreads=4)
-    os.environ["BMPC_EMU_INKERNEL"] = "1"
-    try:
-        b = emu.solve(d["p"], d["x0"], 10, 4, 0.1, opts=emu.default_opts(max_iter=500, start_rollout=0), nthreads=4)
-    finally:
-        del os.environ["BMPC_EMU_INKERNEL"]
+    b = emu.solve(d["p"], d["x0"], 10, 4, 0.1, opts=emu.default_opts(max_iter=500, start_rollout=0), nthreads=4, in_kernel=True)
     c = emu.solve_team(d["p"], d["x0"], 10, 4, 0.1, opts=emu.default_opts(max_iter=500, start_rollout=0), nthreads=4)
     assert np.array_equal(a["x"], b["x"]) and np.array_equal(a["iters"], b["iters"]) and np.array_equal(a["status"], b["status"])
     for r in (a, c):

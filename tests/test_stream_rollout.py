@@ -1,6 +1,6 @@
 """The rollout -- many closed-loop ticks of a stream in one launch -- as device code (csrc/bmpc_rollout_kernel.inl compiled for the CPU, tests/emu)
-against its exact checker: a loop of the existing emulator entries emu.stream_pack -> the in-kernel solve of the fused tick -> emu.stream_post,
-one tick at a time (tests/emu/emu_rollout.py per_tick_loop).  Bit for bit on every tick array, `hist` and `traj_hist` against the per-tick values,
+against its exact checker: a loop of the fused tick's own kernel text (csrc/bmpc_tick_kernel.inl compiled for the CPU, emu.stream_tick), one tick at
+a time (tests/emu/emu_rollout.py per_tick_loop; tests/test_stream_tick.py holds that text to the separate pack, solve and post).  Bit for bit on every tick array, `hist` and `traj_hist` against the per-tick values,
 and the stop rules: a lost plan, the goal.  Every case asserts that each stream ran at least one tick."""
 import numpy as np
 import pytest
