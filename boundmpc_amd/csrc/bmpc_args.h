@@ -93,4 +93,10 @@ struct RArgs {
     int ticks; double goal_tol;      // goal_tol > 0: a stream stops behind the post that leaves phi_max - phi <= goal_tol
     double *hist, *traj_hist;        // [ticks][B][bmpcs::RH_LEN], [ticks][B][tr_len(N)]; either may be NULL
     int *ticks_run;                  // [B] or NULL
+    // events behind a tick's post (the EV instantiations, bmpc_stream_rollout_events); NULL = off, what an initialiser of the members above leaves
+    double *replan;                  // [B][replan_len]: the record of stream b is consumed behind tick replan_tick[b]
+    const int *replan_tick;          // [B]; required with replan
+    int *replan_info;                // [B] or NULL: -1 = not consumed, else the info of stream_update
+    int update_flags;                // the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice, bit 2 poor bounds
+    const double *disturb;           // [ticks][B][bmpcs::DIST_LEN]
 };

@@ -19,6 +19,7 @@
 #include "bmpc_stream.inl"
 #include "bmpc_stream_log.inl"
 #include "bmpc_stream_update.inl"
+#include "bmpc_stream_events.inl"
 #include "bmpc_dual.inl"
 #include "bmpc_kkt.inl"
 #include "bmpc_sens.inl"
@@ -768,6 +769,21 @@ __global__ void __launch_bounds__(64) bmpc_stream_update_kernel(int N, int S, in
     bmpcs::stream_update(N, S, replan + (long long)b * bmpcs::replan_len(S, cap), path + (long long)b * path_stride, cap, ss + (long long)b * bmpcs::ss_len(N),
                          rb ? rb + (long long)b * bmpcs::RB_LEN : nullptr, info ? info + b : nullptr, flags, threadIdx.x, 64);
 }
+// the same behind the splice of the measured state into the raised records (flags bit 1; bit 2: the poor-bounds rule): the spliced words stay in the record
+__global__ void __launch_bounds__(64) bmpc_stream_update_splice_kernel(int N, int S, int B, double h, double *replan, double *path, int path_stride, double *ss, double *rb,
+                                                                      int *info, int flags) {
+    const int b = blockIdx.x, cap = path_stride / bmpcs::PT_LEN;
+    double *rec = replan + (long long)b * bmpcs::replan_len(S, cap);
+    bmpcs::stream_splice(h, S, cap, rec, rb + (long long)b * bmpcs::RB_LEN, flags, threadIdx.x, 64);
+    __syncthreads();
+    bmpcs::stream_update(N, S, rec, path + (long long)b * path_stride, cap, ss + (long long)b * bmpcs::ss_len(N), rb + (long long)b * bmpcs::RB_LEN, info ? info + b : nullptr,
+                         flags & 1, threadIdx.x, 64);
+}
+// plant disturbance: one LANE per stream (the work of a stream is one pass over its kinematic chain)
+__global__ void __launch_bounds__(64) bmpc_stream_disturb_kernel(int B, double *rb, const double *d) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b < B) bmpcs::stream_disturb(rb + (long long)b * bmpcs::RB_LEN, d + (long long)b * bmpcs::DIST_LEN, 0, 1);
+}
 // (the fused one-launch tick kernels of one wave per stream live in bmpc_tick.hip, those of the teams in bmpc_team.hip)
 // The argument test of the four stream entry points (max_iter: 0 where the entry point has none; need: the arrays it cannot do without, looked
 // at for B > 0 only).  False: BMPC_ERR_ARG.
@@ -830,12 +846,11 @@ extern "C" int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int p
 
 // ---- rollout: `ticks` ticks of every stream in one launch (bmpc_rollout.hip), a direct launch on the caller's stream ----
 extern "C" int bmpc_stream_rollout_len(void) { return BMPC_ROLL_LEN; }
-extern "C" int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
-                                   double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
-                                   double goal_tol, double *hist, double *traj_hist, int *ticks_run, void *hip_stream) {
-    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
-    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
-    hipStream_t st = (hipStream_t)hip_stream;
+// the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice (needs the robot records), bit 2 poor bounds (with bit 1 only)
+static bool update_flags_ok(int flags, const void *robot) { return !(flags & ~7) && !((flags & 4) && !(flags & 2)) && !((flags & 2) && !robot); }
+// both rollout entries: the argument test, then the launch of the kernels without (events = false: r holds no event) or with the event code
+static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, const RArgs &r, bool events, hipStream_t st) {
+    const int ticks = r.ticks, flags = t.flags; const double goal_tol = r.goal_tol;
     if (!tick_args_ok(h, B, io, t) || ticks < 1) return BMPC_ERR_ARG;
     if (!(flags & 1)) return BMPC_ERR_ARG;                            // without the plant in the loop a second tick repeats the first
     if (!(goal_tol >= 0.0) || !std::isfinite(goal_tol)) return BMPC_ERR_ARG;
@@ -850,12 +865,32 @@ extern "C" int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const doubl
     a.o.retry_cap = 0; a.budget_ticks = 0;
     const bool resto = h->o.restoration != 0;      // inside the kernel, as in the fused tick: the post needs the final solution
     const SArgs s = stream_sargs(h, t);
-    const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run};
     hipEvent_t *pair = nullptr;
     if (h->timing) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
-    HIPCHK(bmpc_rollout_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    if (events) HIPCHK(bmpc_rollout_events_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    else HIPCHK(bmpc_rollout_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     if (h->timing) { HIPCHK(hipEventRecord(pair[1], st)); h->n_timed++; }
     return order_after(h, st);
+}
+extern "C" int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                                   double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                                   double goal_tol, double *hist, double *traj_hist, int *ticks_run, void *hip_stream) {
+    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
+    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
+    const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run};
+    return rollout_launch(h, B, io, t, r, false, (hipStream_t)hip_stream);
+}
+// with events behind every tick's post (bmpc_rollout_events.hip): disturbances of the plant and one scheduled re-plan per stream
+extern "C" int bmpc_stream_rollout_events(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                                          double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                                          double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan, const int *replan_tick, int *replan_info,
+                                          int update_flags, const double *disturb, void *hip_stream) {
+    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
+    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
+    if ((replan && !replan_tick) || !update_flags_ok(update_flags, robot)) return BMPC_ERR_ARG;
+    // (the table is written by a re-plan: the caller's `path` is not const where a record may be consumed)
+    const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb};
+    return rollout_launch(h, B, io, t, r, true, (hipStream_t)hip_stream);
 }
 
 extern "C" int bmpc_stream_set_rt_feasibility_tol(bmpc_handle *h, double tol) {
@@ -915,9 +950,19 @@ extern "C" int bmpc_stream_replan_len(const bmpc_handle *h, int path_entries) { 
 // (like the log: no workspace of the handle, no ordering event, and the launch may sit inside a capture of the caller's stream)
 extern "C" int bmpc_stream_update(bmpc_handle *h, int B, double *replan, double *path, int path_entries, double *sstate, double *robot, int *info, int flags,
                                   void *hip_stream) {
-    if (B < 1 || !stream_args_ok(h, B, 0, path_entries, {replan, path, sstate})) return BMPC_ERR_ARG;
-    hipLaunchKernelGGL(bmpc_stream_update_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, replan, path, path_entries * bmpcs::PT_LEN, sstate, robot,
-                       info, flags);
+    if (B < 1 || !stream_args_ok(h, B, 0, path_entries, {replan, path, sstate}) || !update_flags_ok(flags, robot)) return BMPC_ERR_ARG;
+    if (flags & 2) hipLaunchKernelGGL(bmpc_stream_update_splice_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, h->h, replan, path,
+                                      path_entries * bmpcs::PT_LEN, sstate, robot, info, flags);
+    else hipLaunchKernelGGL(bmpc_stream_update_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, replan, path, path_entries * bmpcs::PT_LEN, sstate, robot,
+                            info, flags);
+    HIPCHK(hipGetLastError());
+    return BMPC_OK;
+}
+// (no workspace of the handle either: may sit inside a capture)
+extern "C" int bmpc_stream_disturb_len(void) { return BMPC_DIST_LEN; }
+extern "C" int bmpc_stream_disturb(bmpc_handle *h, int B, double *robot, const double *d, void *hip_stream) {
+    if (!h || B < 1 || !robot || !d) return BMPC_ERR_ARG;
+    hipLaunchKernelGGL(bmpc_stream_disturb_kernel, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)hip_stream, B, robot, d);
     HIPCHK(hipGetLastError());
     return BMPC_OK;
 }

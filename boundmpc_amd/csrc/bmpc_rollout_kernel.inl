@@ -15,8 +15,18 @@
 //   goal        goal_tol > 0 and phi_max - phi <= goal_tol behind a post (NodeLoop.run, the reference's experiment runners): the stream stops.
 // The history rows of the ticks a stream did not run are NaN.  With goal_tol = 0 every tick array holds afterwards what `ticks` launches of the
 // one-wave fused tick leave, bit for bit.
-// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp).
+// EVENTS (the instantiations with EV, bmpc_stream_rollout_events; bmpc_stream_events.inl, bmpc_stream_update.inl): behind the history rows of tick t
+// and ahead of the goal test, the plant of a stream may be disturbed (r.disturb[t][b]) and, behind tick r.replan_tick[b], the stream re-planned from
+// its record, the measured state spliced in on the device -- what only the device knows inside a rollout.  The goal test and the next tick's lost-plan
+// test see what the re-plan left: a new phi_max lets a stream that has reached its old goal go on (a second leg), an error count back at N - 1
+// rescues a stream whose plan the post has just exhausted.  A stream that stops first never consumes its record.  With goal_tol = 0 the arrays hold
+// what the loop {one-wave fused tick, bmpc_stream_disturb, bmpc_stream_update of the records due} leaves, bit for bit.  Without EV no event line is
+// compiled and the kernels are the ones from before the events.
+// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp,
+// bmpc_emu_rollout_events.cpp).
 #pragma once
+
+#include "bmpc_stream_events.inl"
 
 namespace bmpcs {
 // history row of one tick of one stream (BMPC_ROLL_* of include/boundmpc_hip.h): the robot record behind the post, then the named scalars, then the
@@ -34,7 +44,7 @@ enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH
 #endif
 // (the body of a tick in the kernel itself, as in bmpc_tick_kernel.inl: behind a function that takes `a` the argument loads lose their no-clobber
 // property -- bmpc_args.h, BMPC_PROBLEM)
-template <bool ZLDS, bool RESTO>
+template <bool ZLDS, bool RESTO, bool EV = false>
 BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
     BMPCK_LDS double lds[BMPC_NAMESPACE::L_SIZE];
     BMPC_STRIDES(a);
@@ -46,6 +56,7 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
         BMPC_STREAM_SLICES(a, s, b);
         long long busy = 0;      // counts of the 100 MHz clock spent in the stream's solves
         int t = 0;
+        if (EV) { if (r.replan_info && BMPCK_LANE == 0) r.replan_info[b] = -1; }
         for (; t < r.ticks; t++) {
             // (the lost-plan test of the fused tick: BoundMPC.step() returns five Nones there and the reference node stops)
             if (BMPCK_UNIFORM((int)(ss[bmpcs::SS_ERRCNT] >= (double)a.N))) {
@@ -79,6 +90,22 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
                 }
             }
             if (r.traj_hist) { double *th = r.traj_hist + row * TRN; for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) th[i] = traj[i]; }
+            if (EV) {
+                // (the stream and the tick opaque: what the events address is computed here, behind the solve, not carried across it)
+                int b_ = b, t_ = t, cap_ = s.path_stride / bmpcs::PT_LEN;
+                BMPCR_OPAQUE("+s"(b_), "+s"(t_), "+s"(cap_), "+s"(S_));
+                if (r.disturb) {
+                    bmpcs::stream_disturb(rb, r.disturb + ((long long)t_ * a.B + b_) * bmpcs::DIST_LEN, BMPCK_LANE, BMPCK_NL);
+                    BMPCK_SYNC();
+                }
+                if (r.replan && BMPCK_UNIFORM((int)(r.replan_tick[b_] == t_))) {
+                    double *rec = r.replan + (long long)b_ * bmpcs::replan_len(S_, cap_);
+                    if (r.update_flags & 2) { bmpcs::stream_splice(a.h, S_, cap_, rec, rb, r.update_flags, BMPCK_LANE, BMPCK_NL); BMPCK_SYNC(); }
+                    bmpcs::stream_update(N_, S_, rec, const_cast<double *>(path), cap_, ss, rb, r.replan_info ? r.replan_info + b_ : nullptr, r.update_flags & 1,
+                                         BMPCK_LANE, BMPCK_NL);
+                    BMPCK_SYNC();      // the goal test, the lost-plan test and the next pack read what the re-plan stored
+                }
+            }
             if (BMPCK_UNIFORM((int)(r.goal_tol > 0.0 && ss[bmpcs::SS_PHIMAX] - ss[bmpcs::SS_PHI] <= r.goal_tol))) { t++; break; }
         }
         // t ticks were run; the rows behind them stay without a tick

@@ -259,7 +259,9 @@ BMPC_HD inline void forward_kinematics(const double *q, const double *dq, Fk &F)
 // sums, v_ang, a_ang the totals of its two prefix sums.  No Jacobian array is formed: the two functions together kept ~280 doubles live
 // (J, dJ, ddJ and nine 7x3 work arrays: 600-750 B of scratch per lane in the post / fused-tick kernels), this one 84 (axes, lever arms and
 // the two prefix sums per joint).  dJ_v of forward_kinematics and dw_j here are the same vector by the Jacobi identity.
+// JK2 (stream_splice of bmpc_stream_events.inl): jk = J u + 2 dJ ddq + ddJ dq instead, the time derivative of a.
 struct FkMotion { double p[6], v[6], a[6], jk[3]; };
+template <bool JK2 = false>
 BMPC_HD inline void fk_motion(const double *q, const double *dq, const double *ddq, const double *u, FkMotion &M) {
     const int ax[7] = {2, 1, 2, -1, 2, 1, 2};
     const double pre[7] = {0.0, 0.1575 + 0.2025, 0.0, 0.2375 + 0.1825, 0.0, 0.2175 + 0.1825, 0.0};
@@ -305,7 +307,8 @@ BMPC_HD inline void fk_motion(const double *q, const double *dq, const double *d
         cross3s(dom[j], A[j], u1); cross3s(om[j], da, u2); for (int c = 0; c < 3; c++) dda[c] = u1[c] + u2[c];
         cross3s(dom[j], r[j], u1); cross3s(om[j], dr, u2); for (int c = 0; c < 3; c++) ddr[c] = u1[c] + u2[c] + suf2[c];
         cross3s(dda, r[j], u1); cross3s(da, dr, u2); cross3s(A[j], ddr, u3);
-        for (int c = 0; c < 3; c++) jk[c] += u[j] * w[c] + ddq[j] * dw[c] + dq[j] * (u1[c] + 2.0 * u2[c] + u3[c]);
+        const double f = JK2 ? 2.0 * ddq[j] : ddq[j];
+        for (int c = 0; c < 3; c++) jk[c] += u[j] * w[c] + f * dw[c] + dq[j] * (u1[c] + 2.0 * u2[c] + u3[c]);
     }
     for (int c = 0; c < 3; c++) { M.v[c] = suf[c]; M.a[c] = suf2[c]; M.jk[c] = jk[c]; }
 }

@@ -13,6 +13,7 @@ The solver is whatever `BoundMPC` is given: the GPU solver behind `NlpSolverShim
 import time
 
 import numpy as np
+from scipy.spatial.transform import Rotation as R
 
 from .bound_mpc import BoundMPC, integrate_joint
 from .robot_model import RobotModel
@@ -41,6 +42,7 @@ class NodeLoop:
         self.x_phi_d = np.array([self.mpc.phi_max[0], 0.0, 0.0])
         self.q, self.dq, self.ddq, self.jerk = self.q0.copy(), np.zeros(7), np.zeros(7), np.zeros(7)
         self.p_lie, self.v = self.p0.copy(), np.zeros(6)
+        self.a, self.j_cart = np.zeros(6), np.zeros(6)      # (the node has them from its first plant step on)
         self.t_current, self.t0 = 0.0, 0.0
         self.t_mpc, self.t_overhead = 0.0, 0.0
         self.fails, self.t_switch, self.phi_switch = [], [], []
@@ -71,6 +73,35 @@ class NodeLoop:
         if self.publish is not None:
             self.publish(self.mpc_data(traj_data, iters, t_loop))
         return traj_data, ref_data, err_data
+
+    def update(self, p_via, r_via, p_limits, r_limits, bp1, br1, s, e_p_min, e_r_min, e_p_max, e_r_max, params=None, update=True, scenario=0):
+        """A later Trajectory request, bound_mpc_node.py:92-167 (callback_trajectory once the node is initialised): the new trajectory is kept, and with
+        `update` (msg.update) the measured state is spliced into it -- the first via point becomes p_lie[:3] + 0.5 dt v[:3] (:131; scenario 0, the
+        node's constant: lowered by 0.05 in z when v[2] < 0 and p_lie[1] * p_via[1][1] < 0, "adapting to poor bounds", :126-129; any other scenario:
+        p_lie[:3]) with the measured orientation (:134), p0 and q0 the measured pose and joints -- and BoundMPC.update is called with the Cartesian
+        state of the node's own plant step (p_lie, v, a, j_cart of integrate_joint), then x_phi_d = [phi_max, 0, 0] (:164).  The device counterpart
+        is the splice of bmpc_stream_update (stream.splice_record), which differs in the jerk alone.  Arguments as the constructor's; params: new
+        MPCParams or None (the node passes the ones it holds).  Returns the spliced (p_via, r_via), or None without `update`."""
+        p_via, r_via = [np.array(p, dtype=float) for p in p_via], [np.array(r, dtype=float) for r in r_via]
+        self.traj = dict(p_via=p_via, r_via=r_via, p_limits=p_limits, r_limits=r_limits, bp1=bp1, br1=br1, s=s,
+                         e_p_min=e_p_min, e_r_min=e_r_min, e_p_max=e_p_max, e_r_max=e_r_max)
+        if params is not None:
+            self.params = params
+        if not update:
+            return None
+        if scenario == 0:
+            poor = self.v[2] < 0 and self.p_lie[1] * p_via[1][1] < 0
+            p_via[0] = self.p_lie[:3] + 0.5 * self.mpc.dt * self.v[:3]
+            if poor:
+                p_via[0][2] -= 0.05
+        else:
+            p_via[0] = self.p_lie[:3].copy()
+        r_via[0] = R.from_rotvec(self.p_lie[3:]).as_matrix()
+        self.p0, self.q0 = self.p_lie.copy(), self.q.copy()
+        self.mpc.update(p_via, r_via, p_limits, r_limits, bp1, br1, s, e_p_min, e_r_min, e_p_max, e_r_max, self.p_lie, self.v, self.a, self.j_cart,
+                        p0=self.p0, params=self.params)
+        self.x_phi_d = np.array([self.mpc.phi_max[0], 0.0, 0.0])
+        return p_via, r_via
 
     def mpc_data(self, traj_data, iters, t_loop):
         """The fields of the MPCData message the node fills per tick (publish_mpc_data, :169-289), without the logging lists of ref_data."""

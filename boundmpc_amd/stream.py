@@ -9,7 +9,9 @@ optionally as one captured hipGraph and optionally with the node's kinematic pla
 needs no host round trip.  Re-planning (`BoundMPC.update`, BoundMPC.py:163-217): `StreamBatch.update` / `apply_update` write the
 new path table and the state scalars update() sets, from then on the device takes the re-projection branch of step() (:335-369).
 `StreamBatch.update_device` does the same on the device for the whole batch in one launch, from re-plan records (`replan_record`;
-csrc/bmpc_stream_update.inl), without a synchronisation; `apply_update` is its specification.
+csrc/bmpc_stream_update.inl), without a synchronisation; `apply_update` is its specification.  The node's splice of the measured state into such a
+record and disturbances of the plant are device code too (csrc/bmpc_stream_events.inl; mirrors `splice_record`, `disturb_robot`), on their own
+launches (`update_device(splice=True)`, `disturb`) or as events behind the ticks of a rollout (`rollout(replan=, replan_tick=, disturb=)`).
 """
 import ctypes
 
@@ -150,6 +152,55 @@ def replan_record(S, entries, pos_points, rot_points, pos_lim, rot_lim, bp1, br1
             e[RV["BP1"]:RV["BP1"] + 3], e[RV["BR1"]:RV["BR1"] + 3] = bp1[j], br1[j]
         e[RV["S"]], e[RV["EPMIN"]], e[RV["ERMIN"]], e[RV["EPMAX"]], e[RV["ERMAX"]] = at(s, j), at(e_p_min, j), at(e_r_min, j), at(e_p_max, j), at(e_r_max, j)
     return rec
+
+
+def splice_record(rec, robot_row, dt, S, poor_bounds=False):
+    """The device splice (csrc/bmpc_stream_events.inl stream_splice; bmpc_stream_update flags bit 1) as numpy over `RobotModel`: the words of a raised,
+    valid re-plan record that the node takes from the plant (bound_mpc_node.py:121-137,158-162), from the robot record `robot_row` behind a post.
+    Returns the spliced copy of `rec`: via[0].p = p_lie[:3] + 0.5 dt v[:3] (poor_bounds: the node's scenario 0, z lowered by 0.05 when v[2] < 0 and
+    p_lie[1] * via[1].p[1] < 0), via[0].R = the matrix of the rotation vector p_lie[3:], header p0 = p_lie[:3], v = v[:3], a = J ddq + dJ dq,
+    jerk = J u + 2 dJ ddq + ddJ dq (linear rows) -- the time derivative of a, where the node's j_cart (integrate_joint) takes ddJ at the state before
+    the plant step and J ddq in the place of J u.  A record whose flag is 0 and an invalid record (bmpc_stream_update: info 1) come back unchanged."""
+    from .robot_model import RobotModel
+    rec, rb = np.array(rec, dtype=float), np.asarray(robot_row, dtype=float)
+    n_max = (rec.shape[0] - RP["HEAD"]) // RV["LEN"]
+    n, nb = rec[RP["N"]], rec[RP["NB"]]
+    if rec[RP["FLAG"]] == 0.0 or not (2.0 <= n <= n_max) or not (1.0 <= nb <= int(n)):
+        return rec
+    model = RobotModel()
+    q, dq, ddq, u = rb[RB["Q"]:RB["Q"] + 7], rb[RB["DQ"]:RB["DQ"] + 7], rb[RB["DDQ"]:RB["DDQ"] + 7], rb[RB["JERK"]:RB["JERK"] + 7]
+    p_lie, v = rb[RB["P"]:RB["P"] + 6], rb[RB["V"]:RB["V"] + 6]
+    _, J, dJ = model.forward_kinematics(q, dq)
+    ddJ = model.ddjacobian_fk(q, dq, ddq)
+    via = rec[RP["HEAD"]:].reshape(-1, RV["LEN"])
+    lower = bool(poor_bounds) and v[2] < 0 and p_lie[1] * via[1, RV["P"] + 1] < 0
+    via[0, RV["P"]:RV["P"] + 3] = p_lie[:3] + 0.5 * dt * v[:3]
+    if lower:
+        via[0, RV["P"] + 2] -= 0.05
+    via[0, RV["R"]:RV["R"] + 9] = R.from_rotvec(p_lie[3:]).as_matrix().reshape(9)
+    rec[RP["P0"]:RP["P0"] + 3], rec[RP["V"]:RP["V"] + 3] = p_lie[:3], v[:3]
+    rec[RP["A"]:RP["A"] + 3] = (J @ ddq + dJ @ dq)[:3]
+    rec[RP["JERK"]:RP["JERK"] + 3] = (J @ u + 2 * dJ @ ddq + ddJ @ dq)[:3]
+    return rec
+
+
+# csrc/bmpc_stream_events.inl: a disturbance row [delta q 7 | delta dq 7 | delta ddq 7]
+DIST_LEN = 21
+
+
+def disturb_robot(robot_row, d):
+    """The device disturbance (stream_disturb; bmpc_stream_disturb) as numpy over `RobotModel`: d [DIST_LEN] added to q, dq, ddq of the robot record,
+    p_lie and v recomputed from the disturbed joint state.  Non-finite entries count as 0, an all-zero row returns the record unchanged.  Returns a copy."""
+    from .robot_model import RobotModel
+    rb, d = np.array(robot_row, dtype=float), np.asarray(d, dtype=float)
+    assert d.shape == (DIST_LEN,)
+    d = np.where(np.isfinite(d), d, 0.0)
+    if not d.any():
+        return rb
+    rb[RB["Q"]:RB["Q"] + 21] += d
+    p, J, _ = RobotModel().forward_kinematics(rb[RB["Q"]:RB["Q"] + 7], rb[RB["DQ"]:RB["DQ"] + 7])
+    rb[RB["P"]:RB["P"] + 6], rb[RB["V"]:RB["V"] + 6] = p, J @ rb[RB["DQ"]:RB["DQ"] + 7]
+    return rb
 
 
 def _poff(S):
@@ -398,13 +449,8 @@ class StreamBatch:
         self.state[b].copy_(torch.as_tensor(row, dtype=torch.float64))
         return float(row[SS["PHIMAX"]])
 
-    def update_device(self, records, set_goal=True, stream=None):
-        """Re-plan on the device (bmpc_stream_update): `records` [B][replan_len(S, entries)], a tensor or an array of `replan_record` rows; a
-        row whose flag is 0 leaves its stream alone.  One launch over the batch, asynchronous on `stream`, no synchronisation and no host copy of
-        the state: call it after post(), tick(), tick_graph() or log() and before the next pack.  The records are copied into a device buffer
-        allocated on first use (`self.replan`; a caller that captures the launch raises flags in that buffer, the launch clears them) -- passing
-        `self.replan` itself copies nothing.  set_goal: also robot[x_phi_d] = (phi_max, 0, 0), as the node does right after update().
-        Returns the `info` tensor [B] (int32; 1: invalid record, stream untouched), valid once `stream` has run the launch."""
+    def _replan_buffer(self, records, stream):
+        """the device record buffer (allocated on first use) holding `records`; `self.replan` itself is taken as it is"""
         import torch
         if self.replan is None:
             n = self.solver._lib.bmpc_stream_replan_len(self.solver._h, self.entries)
@@ -418,9 +464,47 @@ class StreamBatch:
                 raise ValueError(f"records must be [{self.B}][{self.replan.shape[1]}] (replan_len(S, entries)), got {tuple(records.shape)}")
             with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.path.device)):      # the copy ahead of the launch, same stream
                 self.replan.copy_(records)
+        return self.replan
+
+    @staticmethod
+    def _update_flags(set_goal, splice, poor_bounds):
+        if poor_bounds and not splice:
+            raise ValueError("poor_bounds is a rule of the splice (splice=True)")
+        return int(bool(set_goal)) | (2 if splice else 0) | (4 if poor_bounds else 0)
+
+    def update_device(self, records, set_goal=True, stream=None, splice=False, poor_bounds=False):
+        """Re-plan on the device (bmpc_stream_update): `records` [B][replan_len(S, entries)], a tensor or an array of `replan_record` rows; a
+        row whose flag is 0 leaves its stream alone.  One launch over the batch, asynchronous on `stream`, no synchronisation and no host copy of
+        the state: call it after post(), tick(), tick_graph() or log() and before the next pack.  The records are copied into a device buffer
+        allocated on first use (`self.replan`; a caller that captures the launch raises flags in that buffer, the launch clears them) -- passing
+        `self.replan` itself copies nothing.  set_goal: also robot[x_phi_d] = (phi_max, 0, 0), as the node does right after update().
+        splice: the device first writes what the node takes from the plant into every raised record, from the stream's robot record (the first via
+        point, p0, v, a, jerk: `splice_record` is the mirror; poor_bounds: the node's scenario-0 rule with it); the spliced words stay in `self.replan`.
+        Returns the `info` tensor [B] (int32; 1: invalid record, stream untouched), valid once `stream` has run the launch."""
+        flags = self._update_flags(set_goal, splice, poor_bounds)
+        self._replan_buffer(records, stream)
         _lib.check(self.solver._lib.bmpc_stream_update(self.solver._h, self.B, _ptr(self.replan), _ptr(self.path), self.entries, _ptr(self.state), _ptr(self.robot),
-                                                       _ptr(self.replan_info), int(bool(set_goal)), self._stream(stream)), "bmpc_stream_update")
+                                                       _ptr(self.replan_info), flags, self._stream(stream)), "bmpc_stream_update")
         return self.replan_info
+
+    def disturb(self, d, stream=None):
+        """Disturb the plants (bmpc_stream_disturb): d [B][DIST_LEN] (tensor or array) = delta q | delta dq | delta ddq, added to the robot records;
+        pose and Cartesian velocity follow (`disturb_robot` is the mirror).  Between a tick's post (or log, or update) and the next pack; one launch,
+        asynchronous on `stream`."""
+        assert self.solver._lib.bmpc_stream_disturb_len() == DIST_LEN
+        d = self._dev64(d, (self.B, DIST_LEN), "d", stream)
+        _lib.check(self.solver._lib.bmpc_stream_disturb(self.solver._h, self.B, _ptr(self.robot), _ptr(d), self._stream(stream)), "bmpc_stream_disturb")
+
+    def _dev64(self, a, shape, name, stream, dtype=None):
+        """`a` as a contiguous device tensor of `shape` (float64 unless dtype), copied on `stream` when it is not one already"""
+        import torch
+        dtype = dtype or torch.float64
+        if not torch.is_tensor(a):
+            a = torch.as_tensor(np.ascontiguousarray(a))
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError(f"{name} must be {list(shape)}, got {list(a.shape)}")
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.path.device)):
+            return a.to(device=self.path.device, dtype=dtype).contiguous()
 
     def set_robot(self, rec):
         import torch
@@ -519,10 +603,11 @@ class StreamBatch:
         # bmpc_graph_launch)
         _lib.check(self.solver._lib.bmpc_graph_launch(self._graphs[key], self._stream(stream)), "bmpc_graph_launch")
 
-    def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None):
+    def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None,
+                replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None):
         """`ticks` closed-loop ticks (plant simulation on) of every stream in ONE launch (bmpc_stream_rollout): each stream runs at its own pace, so
         the launch lasts as long as the slowest stream's SUM of solves, where a loop of tick() / tick_graph() pays the slowest stream of every tick.
-        For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, re-planning, a time
+        For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, a time
         budget) use the ticks.  One wave per stream always (set_team_waves does not apply).  A stream stops once it has lost its plan (status 3, as
         the fused tick leaves a skipped stream) or, with goal_tol > 0, behind the tick that leaves phi_max - phi <= goal_tol (NodeLoop.run's rule).
         With goal_tol = 0 the batch's buffers hold afterwards what `ticks` calls of tick(fused=True) on one wave per stream leave, bit for bit.
@@ -531,7 +616,15 @@ class StreamBatch:
         Returns device tensors, valid once `stream` has run the launch (asynchronous, no synchronisation):
           hist [ticks][B][rollout_len()]   the history row of stream b behind tick t (slots ROLL, unpack_rollout); NaN for a tick it did not run
           ticks_run [B] int32              ticks the stream ran
-          traj_hist [ticks][B][tr_len]     want_traj: the trajectory record of every tick (unpack_traj); NaN likewise"""
+          traj_hist [ticks][B][tr_len]     want_traj: the trajectory record of every tick (unpack_traj); NaN likewise
+        EVENTS behind a tick's post (bmpc_stream_rollout_events; with replan, replan_tick and disturb all None the plain rollout runs):
+          disturb [ticks][B][DIST_LEN]     row [t][b] disturbs the plant of stream b behind tick t (as disturb()); hist[t][b] shows the plant before it
+          replan [B][replan_len], replan_tick [B]   the record of stream b (`replan_record`; `self.replan` itself is taken as it is) is consumed behind
+                                           tick replan_tick[b] as update_device(set_goal, splice, poor_bounds) consumes it; splice (default here: the
+                                           state behind that tick exists on the device only) writes the measured state into the record first.
+        The goal test and the next tick's lost-plan test see what the re-plan left: a second leg starts behind the tick that reaches the old goal, a
+        re-plan behind the post that exhausted the plan rescues the stream.  A stream that stops before its tick keeps its record's flag raised.
+        Then the result also holds  replan_info [B] int32: -1 not consumed, 0 consumed, 1 invalid record."""
         import torch
         if max_iter and not warm_dual:
             raise ValueError("an iteration cap needs the dual state (warm_dual=True): the multipliers must be shifted with the plan")
@@ -541,9 +634,26 @@ class StreamBatch:
         if want_traj:
             out["traj_hist"] = torch.empty((n, self.B, self.tr_len), dtype=torch.float64, device=dev)
         args = self._tick_args(max_iter, warm_dual, True, accept_capped)
-        _lib.check(self.solver._lib.bmpc_stream_rollout(self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]),
-                                                        _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]), self._stream(stream)),
-                   "bmpc_stream_rollout")
+        if replan is None and replan_tick is None and disturb is None:
+            _lib.check(self.solver._lib.bmpc_stream_rollout(self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]),
+                                                            _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]), self._stream(stream)),
+                       "bmpc_stream_rollout")
+            return out
+        if (replan is None) != (replan_tick is None):
+            raise ValueError("replan and replan_tick go together")
+        flags = self._update_flags(set_goal, splice, poor_bounds)
+        if replan is not None:
+            self._replan_buffer(replan, stream)
+            replan_tick = self._dev64(replan_tick, (self.B,), "replan_tick", stream, dtype=torch.int32)
+        if disturb is not None:
+            disturb = self._dev64(disturb, (n, self.B, DIST_LEN), "disturb", stream)
+        out["replan_info"] = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
+        _lib.check(self.solver._lib.bmpc_stream_rollout_events(self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]),
+                                                               _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]),
+                                                               _ptr(self.replan) if replan is not None else None, _ptr(replan_tick) if replan is not None else None,
+                                                               _ptr(out["replan_info"]), flags, _ptr(disturb) if disturb is not None else None, self._stream(stream)),
+                   "bmpc_stream_rollout_events")
+        self._event_inputs = (replan_tick, disturb)      # the launch is asynchronous: its inputs live until the next one replaces them
         return out
 
     def closed_loop(self, ticks, cap=0, warm=True, accept_capped=False, first_cap=100, budget_us=None, graph=True, fused=True, timed=False, tick=None):

@@ -324,7 +324,17 @@ int bmpc_stream_log(bmpc_handle *h, int B, const double *path, int path_entries,
  *   projected onto the new first segment, the rotation reference, phi_max, the weights, the entry count and the `updated` flag; an error count
  *   >= N goes back to N - 1, so the next tick solves a stream that had lost its plan.  The previous solution and its Cartesian arrays stay.
  *   flags bit 0 (set_goal) with robot != NULL: also robot[x_phi_d] = (phi_max, 0, 0), what the node does right after update()
- *   (bound_mpc_node.py:164).  The node's splice of the measured pose into the first via point (:125-137) is the caller's business.
+ *   (bound_mpc_node.py:164).
+ *   flags bit 1 (splice; needs robot != NULL): the words the node takes from the plant (bound_mpc_node.py:121-137,158-162) are written into every
+ *   raised, valid record from the stream's robot record before it is consumed:
+ *     via[0].p = p_lie[0:3] + 0.5 h v[0:3],  via[0].R = rotation matrix of the rotation vector p_lie[3:6],
+ *     header p0 = p_lie[0:3], v = v[0:3], a = J ddq + dJ dq, jerk = J u + 2 dJ ddq + ddJ dq (linear rows; q, dq, ddq and u = jerk of the record).
+ *   The robot record carries no Cartesian acceleration or jerk.  The node keeps both from its plant step (util_functions.py:152-161): its a is this a,
+ *   its j_cart evaluates ddJ at the state before the step and uses J ddq where the kinematics say J u; the device uses the consistent derivative
+ *   of a.  The difference reaches one state word, dddphi.  The spliced words stay in the record after the launch (only the flag word is cleared),
+ *   so the caller can read back what was spliced.  A record whose flag is 0 and an invalid record are not spliced.
+ *   flags bit 2 (poor bounds; with bit 1 only): the node's scenario 0 (:126-129): if v[2] < 0 and p_lie[1] * via[1].p[1] < 0, via[0].p[2] -= 0.05.
+ *   Any other bit, bit 2 without bit 1, bit 1 without robot: BMPC_ERR_ARG.  Without bit 1 the caller splices (boundmpc_amd.stream.splice_record).
  * Flag protocol: flag == 0 leaves the stream alone, bit for bit.  A raised flag is CLEARED by the launch that consumed it, so a captured graph
  * that holds this launch re-plans only when someone raises a flag in the record buffer again.  n < 2, n > n_max, nb < 1, nb > n or a non-finite
  * n / nb: invalid record -- stream untouched, flag cleared, info[b] = 1; otherwise info[b] = 0 (info may be NULL).  Non-finite numbers elsewhere,
@@ -335,6 +345,38 @@ int bmpc_stream_log(bmpc_handle *h, int B, const double *path, int path_entries,
 int bmpc_stream_replan_len(const bmpc_handle *h, int path_entries);      /* 32 + 32 (path_entries - S + 1); <= 0 on bad arguments */
 int bmpc_stream_update(bmpc_handle *h, int B, double *replan, double *path, int path_entries, double *sstate, double *robot /* may be NULL */,
                        int *info /* may be NULL */, int flags, void *hip_stream);
+/* Plant disturbance of closed-loop streams, one launch over the batch: d [B][BMPC_DIST_LEN] = delta q 7 | delta dq 7 | delta ddq 7 is added to q, dq
+ * and ddq of the robot records, then p_lie and v of a record are recomputed from its disturbed joint state (the kinematics of the post, with the
+ * record's jerk).  An all-zero row leaves its record untouched, bit for bit; a non-finite entry counts as 0.  The call belongs BETWEEN a tick's post
+ * (or log, or update) and the next pack.  DEVICE pointers; asynchronous on hip_stream; no workspace of the handle is used, so the call may be
+ * enqueued inside a capture of the caller's stream.  BMPC_ERR_ARG on a missing array or B < 1. */
+enum { BMPC_DIST_LEN = 21 };
+int bmpc_stream_disturb_len(void);
+int bmpc_stream_disturb(bmpc_handle *h, int B, double *robot, const double *d /* [B][21] */, void *hip_stream);
+/* Rollout with EVENTS: bmpc_stream_rollout (its arguments, tests and contract) with what a Monte-Carlo run needs between the ticks without a return
+ * to the host -- both events sit "behind tick t of stream b" and need only the stream's own records:
+ *   disturb [ticks][B][BMPC_DIST_LEN] or NULL: row [t][b] disturbs the plant of stream b behind tick t, as bmpc_stream_disturb does;
+ *   replan [B][bmpc_stream_replan_len] or NULL, replan_tick [B] (required with replan): the record of stream b is consumed behind tick
+ *     replan_tick[b] as bmpc_stream_update(update_flags) consumes it -- with bit 1 the state behind that tick is spliced in on the device, where
+ *     alone it is known.  One re-plan per stream and launch; several legs are several rollouts.  The path table is written then (the const of
+ *     `path` is the plain rollout's).
+ * Per stream and tick: pack, solve, post, the hist and traj_hist rows (as in the rollout: hist[t][b] shows the UNDISTURBED plant behind tick t),
+ * the disturbance, the re-plan, the goal test, the next tick's lost-plan test.  So a re-plan behind the tick that reaches the old goal gives the
+ * stream a new phi_max and it goes on (a second leg), and a re-plan behind the post that exhausted the plan (error count back to N - 1) rescues the
+ * stream.  Stops win over events: a stream that stops before its replan_tick -- lost on entry or at the start of an earlier tick, or at its goal --
+ * never consumes its record: the flag stays raised and replan_info[b] = -1; the same for replan_tick[b] < 0 or >= ticks.  Otherwise replan_info[b]
+ * (may be NULL) is what bmpc_stream_update writes: 0 consumed (or a record whose flag was 0), 1 invalid record (stream untouched, flag cleared).
+ * With goal_tol = 0 every tick array, the path table, the record buffer, hist, traj_hist and ticks_run hold afterwards what this loop leaves, bit
+ * for bit, events applied to the streams that still run:
+ *   for t in 0..ticks-1: bmpc_stream_tick on one wave per stream; bmpc_stream_disturb(rows of tick t);
+ *                        bmpc_stream_update(update_flags) with exactly the flags of the streams whose replan_tick == t raised
+ * BMPC_ERR_ARG, nothing launched: what the rollout refuses, replan without replan_tick, update_flags as bmpc_stream_update refuses them
+ * (update_flags without replan are checked and otherwise ignored). */
+int bmpc_stream_rollout_events(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                               double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                               double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan /* or NULL */,
+                               const int *replan_tick /* [B]; required with replan */, int *replan_info /* [B] or NULL */, int update_flags,
+                               const double *disturb /* [ticks][B][21] or NULL */, void *hip_stream);
 
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
