@@ -99,4 +99,8 @@ struct RArgs {
     int *replan_info;                // [B] or NULL: -1 = not consumed, else the info of stream_update
     int update_flags;                // the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice, bit 2 poor bounds
     const double *disturb;           // [ticks][B][bmpcs::DIST_LEN]
+    // audit of the state every tick starts from (the AU instantiations, bmpc_stream_rollout_audit); NULL = off
+    double *tube_hist;               // [ticks][B][bmpcs::TUBE_LEN]
+    double *audit;                   // [B][bmpcs::AUDIT_LEN], initialised by the kernel
+    double audit_tol;                // an excess above it counts as outside a tube
 };

@@ -5,7 +5,8 @@
 // units are bmpc_multi_batch.inl (team and pair batch kernel) and bmpc_tick_kernel.inl (one-wave and team fused tick).  bmpc_hip.hip holds the one-wave-per-problem batch kernel, the service kernel (one entry
 // over the jobs of bmpc_dual.inl, bmpc_kkt.inl and bmpc_sens.inl, each of which slices its own batch) and the C ABI, bmpc_team.hip the team
 // kernels (NW cooperating waves per problem), bmpc_pair.hip the pair kernel, bmpc_resto.hip the restoration kernels, bmpc_tick.hip the
-// one-wave fused ticks, bmpc_rollout.hip the rollouts (many ticks per stream in one launch; kernel text bmpc_rollout_kernel.inl), bmpc_rollout_events.hip the rollouts with events.
+// one-wave fused ticks, bmpc_rollout.hip the rollouts (many ticks per stream in one launch; kernel text bmpc_rollout_kernel.inl), bmpc_rollout_events.hip the rollouts with events,
+// bmpc_rollout_audit.hip the rollouts with events and the tube audit.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -112,6 +113,10 @@ hipError_t bmpc_tick_launch(bool zlds, bool resto, const void *kargs, const SArg
 hipError_t bmpc_rollout_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // ---- the same with events behind a tick's post: plant disturbances, one scheduled re-plan per stream (bmpc_rollout_events.hip; bmpc_rollout_kernel.inl, EV) ----
 hipError_t bmpc_rollout_events_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
+// ---- the same with the audit behind a tick's pack: tube and joint-limit excess of the state the tick starts from (bmpc_rollout_audit.hip; EV and AU) ----
+hipError_t bmpc_rollout_audit_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
+// ---- the measurement on its own, one wave per stream of the batch (bmpc_rollout_audit.hip; bmpc_stream_tube.inl) ----
+hipError_t bmpc_stream_tube_launch(int N, int S, int B, const double *p, const double *ss, double *tube, hipStream_t st);
 
 // ---- team kernels (bmpc_team.hip); `kargs` points at a KArgsT<...> record (the layouts are identical across instantiations) ----
 // resident workgroups per CU of the team solver kernel with `nw` waves (0: no such instantiation)

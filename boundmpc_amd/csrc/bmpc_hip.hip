@@ -779,6 +779,7 @@ __global__ void __launch_bounds__(64) bmpc_stream_update_splice_kernel(int N, in
     bmpcs::stream_update(N, S, rec, path + (long long)b * path_stride, cap, ss + (long long)b * bmpcs::ss_len(N), rb + (long long)b * bmpcs::RB_LEN, info ? info + b : nullptr,
                          flags & 1, threadIdx.x, 64);
 }
+// (the tube kernel, bmpc_stream_tube.inl, lives in bmpc_rollout_audit.hip: this unit's device text is not touched by it)
 // plant disturbance: one LANE per stream (the work of a stream is one pass over its kinematic chain)
 __global__ void __launch_bounds__(64) bmpc_stream_disturb_kernel(int B, double *rb, const double *d) {
     const int b = blockIdx.x * 64 + threadIdx.x;
@@ -848,8 +849,9 @@ extern "C" int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int p
 extern "C" int bmpc_stream_rollout_len(void) { return BMPC_ROLL_LEN; }
 // the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice (needs the robot records), bit 2 poor bounds (with bit 1 only)
 static bool update_flags_ok(int flags, const void *robot) { return !(flags & ~7) && !((flags & 4) && !(flags & 2)) && !((flags & 2) && !robot); }
-// both rollout entries: the argument test, then the launch of the kernels without (events = false: r holds no event) or with the event code
-static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, const RArgs &r, bool events, hipStream_t st) {
+// the rollout entries: the argument test, then the launch of the kernels without the event code (events = 0: r holds no event), with it (1), or with
+// the event and the audit code (2)
+static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, const RArgs &r, int events, hipStream_t st) {
     const int ticks = r.ticks, flags = t.flags; const double goal_tol = r.goal_tol;
     if (!tick_args_ok(h, B, io, t) || ticks < 1) return BMPC_ERR_ARG;
     if (!(flags & 1)) return BMPC_ERR_ARG;                            // without the plant in the loop a second tick repeats the first
@@ -867,7 +869,8 @@ static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const Stream
     const SArgs s = stream_sargs(h, t);
     hipEvent_t *pair = nullptr;
     if (h->timing) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
-    if (events) HIPCHK(bmpc_rollout_events_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    if (events == 2) HIPCHK(bmpc_rollout_audit_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    else if (events) HIPCHK(bmpc_rollout_events_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else HIPCHK(bmpc_rollout_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     if (h->timing) { HIPCHK(hipEventRecord(pair[1], st)); h->n_timed++; }
     return order_after(h, st);
@@ -878,7 +881,7 @@ extern "C" int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const doubl
     const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
     const StreamIO t{path, path_entries, sstate, robot, traj, flags};
     const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run};
-    return rollout_launch(h, B, io, t, r, false, (hipStream_t)hip_stream);
+    return rollout_launch(h, B, io, t, r, 0, (hipStream_t)hip_stream);
 }
 // with events behind every tick's post (bmpc_rollout_events.hip): disturbances of the plant and one scheduled re-plan per stream
 extern "C" int bmpc_stream_rollout_events(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
@@ -890,7 +893,22 @@ extern "C" int bmpc_stream_rollout_events(bmpc_handle *h, int B, int ticks, cons
     if ((replan && !replan_tick) || !update_flags_ok(update_flags, robot)) return BMPC_ERR_ARG;
     // (the table is written by a re-plan: the caller's `path` is not const where a record may be consumed)
     const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb};
-    return rollout_launch(h, B, io, t, r, true, (hipStream_t)hip_stream);
+    return rollout_launch(h, B, io, t, r, 1, (hipStream_t)hip_stream);
+}
+// with the audit behind every tick's pack on top (bmpc_rollout_audit.hip); without both of its arrays it IS the entry above
+extern "C" int bmpc_stream_rollout_audit(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                                         double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                                         double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan, const int *replan_tick, int *replan_info,
+                                         int update_flags, const double *disturb, double *tube_hist, double *audit, double audit_tol, void *hip_stream) {
+    if (!(audit_tol >= 0.0) || !std::isfinite(audit_tol)) return BMPC_ERR_ARG;
+    if (!tube_hist && !audit)
+        return bmpc_stream_rollout_events(h, B, ticks, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, goal_tol, hist,
+                                          traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb, hip_stream);
+    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
+    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
+    if ((replan && !replan_tick) || !update_flags_ok(update_flags, robot)) return BMPC_ERR_ARG;
+    const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb, tube_hist, audit, audit_tol};
+    return rollout_launch(h, B, io, t, r, 2, (hipStream_t)hip_stream);
 }
 
 extern "C" int bmpc_stream_set_rt_feasibility_tol(bmpc_handle *h, double tol) {
@@ -944,6 +962,13 @@ extern "C" int bmpc_stream_log(bmpc_handle *h, int B, const double *path, int pa
     if (B == 0) return BMPC_OK;
     hipLaunchKernelGGL(bmpc_stream_log_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, h->h, path, path_entries * bmpcs::PT_LEN, sstate, p, traj, log);
     HIPCHK(hipGetLastError());
+    return BMPC_OK;
+}
+extern "C" int bmpc_stream_tube_len(void) { return BMPC_TUBE_LEN; }
+// (like the log: no workspace of the handle, no ordering event, and the launch may sit inside a capture of the caller's stream)
+extern "C" int bmpc_stream_tube(bmpc_handle *h, int B, const double *p, const double *sstate, double *tube, void *hip_stream) {
+    if (!h || B < 1 || !p || !tube || h->N > bmpcs::STREAM_NMAX) return BMPC_ERR_ARG;
+    HIPCHK(bmpc_stream_tube_launch(h->N, h->S, B, p, sstate, tube, (hipStream_t)hip_stream));
     return BMPC_OK;
 }
 extern "C" int bmpc_stream_replan_len(const bmpc_handle *h, int path_entries) { return (h && path_entries >= h->S + 1) ? bmpcs::replan_len(h->S, path_entries) : -1; }

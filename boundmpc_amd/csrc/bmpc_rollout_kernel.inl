@@ -22,11 +22,16 @@
 // rescues a stream whose plan the post has just exhausted.  A stream that stops first never consumes its record.  With goal_tol = 0 the arrays hold
 // what the loop {one-wave fused tick, bmpc_stream_disturb, bmpc_stream_update of the records due} leaves, bit for bit.  Without EV no event line is
 // compiled and the kernels are the ones from before the events.
+// AUDIT (the instantiations with AU, bmpc_stream_rollout_audit; bmpc_stream_tube.inl): behind the pack of tick t and its barrier the tube row of the
+// stream's p -- the state tick t STARTS from: the plant behind tick t - 1 with that tick's disturbance and re-plan applied, what a host loop measures
+// on the p of every tick -- goes to r.tube_hist[t][b] and into the stream's record r.audit[b].  The record lives in global memory and the row in
+// global memory or LDS: nothing of the audit is carried in a register across the solve.  Without AU no audit line is compiled.
 // Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp,
 // bmpc_emu_rollout_events.cpp).
 #pragma once
 
 #include "bmpc_stream_events.inl"
+#include "bmpc_stream_tube.inl"
 
 namespace bmpcs {
 // history row of one tick of one stream (BMPC_ROLL_* of include/boundmpc_hip.h): the robot record behind the post, then the named scalars, then the
@@ -44,12 +49,13 @@ enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH
 #endif
 // (the body of a tick in the kernel itself, as in bmpc_tick_kernel.inl: behind a function that takes `a` the argument loads lose their no-clobber
 // property -- bmpc_args.h, BMPC_PROBLEM)
-template <bool ZLDS, bool RESTO, bool EV = false>
+template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false>
 BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
     BMPCK_LDS double lds[BMPC_NAMESPACE::L_SIZE];
     BMPC_STRIDES(a);
     double *sh = lds + BMPC_NAMESPACE::L_RED;
     static_assert(bmpcs::SH_LEN <= 6 * 64, "the stream functions' LDS words must fit into the solver's reduction area");
+    static_assert(bmpcs::TUBE_LEN <= 6 * 64, "and so must a tube row");
     const int TRN = bmpcs::tr_len(a.N);
     const double nan_ = __builtin_nan("");
     for (int b = BMPCK_BLOCK; b < a.B; b += BMPCK_GRID) {
@@ -57,6 +63,7 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
         long long busy = 0;      // counts of the 100 MHz clock spent in the stream's solves
         int t = 0;
         if (EV) { if (r.replan_info && BMPCK_LANE == 0) r.replan_info[b] = -1; }
+        if (AU) { if (r.audit && BMPCK_LANE == 0) bmpcs::stream_audit_init(r.audit + (long long)b * bmpcs::AUDIT_LEN); }
         for (; t < r.ticks; t++) {
             // (the lost-plan test of the fused tick: BoundMPC.step() returns five Nones there and the reference node stops)
             if (BMPCK_UNIFORM((int)(ss[bmpcs::SS_ERRCNT] >= (double)a.N))) {
@@ -67,6 +74,15 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
             BMPCR_OPAQUE("+s"(N_), "+s"(S_));      // (what the stream functions are given)
             bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCK_LANE, BMPCK_NL, s.lvl_c, s.lvl_lo, s.lvl_hi);
             BMPCK_SYNC();
+            if (AU) {
+                // (the stream and the tick opaque, as for the events: what the audit addresses is computed here and dead before the solve)
+                int b_ = b, t_ = t;
+                BMPCR_OPAQUE("+s"(b_), "+s"(t_), "+s"(N_), "+s"(S_));
+                double *row = r.tube_hist ? r.tube_hist + ((long long)t_ * a.B + b_) * bmpcs::TUBE_LEN : sh;
+                bmpcs::stream_tube(N_, S_, p, nullptr, row, BMPCK_LANE, BMPCK_NL);      // (no state row: the lost-plan test has just passed)
+                if (r.audit && BMPCK_LANE == 0) bmpcs::stream_audit(row, r.audit + (long long)b_ * bmpcs::AUDIT_LEN, t_, r.audit_tol);
+                BMPCK_SYNC();      // the solver's reductions reuse the LDS words of the row
+            }
             BMPC_WAVE_INIT(W, a, lds, a.scratch + (long long)BMPCK_BLOCK * a.scr_stride, 0); BMPCK_WAVE_HOOK(W);
             BMPC_TICK_PROBLEM(pr, a, b, p, x0, dual);
             BMPCR_OPAQUE("+s"(W.N), "+s"(W.S), "+s"(W.h), "+s"(W.G.b), "+s"(pr.p), "+s"(pr.x0), "+s"(pr.x), "+s"(pr.g), "+s"(pr.state));
@@ -113,6 +129,7 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
             const long long row = (long long)u * a.B + b;
             if (r.hist) for (int i = BMPCK_LANE; i < bmpcs::RH_LEN; i += BMPCK_NL) r.hist[row * bmpcs::RH_LEN + i] = nan_;
             if (r.traj_hist) for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) r.traj_hist[row * TRN + i] = nan_;
+            if (AU) { if (r.tube_hist) for (int i = BMPCK_LANE; i < bmpcs::TUBE_LEN; i += BMPCK_NL) r.tube_hist[row * bmpcs::TUBE_LEN + i] = nan_; }
         }
         if (BMPCK_LANE == 0) {
             if (r.ticks_run) r.ticks_run[b] = t;

@@ -12,6 +12,8 @@ new path table and the state scalars update() sets, from then on the device take
 csrc/bmpc_stream_update.inl), without a synchronisation; `apply_update` is its specification.  The node's splice of the measured state into such a
 record and disturbances of the plant are device code too (csrc/bmpc_stream_events.inl; mirrors `splice_record`, `disturb_robot`), on their own
 launches (`update_device(splice=True)`, `disturb`) or as events behind the ticks of a rollout (`rollout(replan=, replan_tick=, disturb=)`).
+The error bound itself -- how far the measured state of a tick is outside its tubes and joint limits, `tube_excess_of_state` on the host -- is
+measured on the device as well (csrc/bmpc_stream_tube.inl): `StreamBatch.tube` behind a pack or a tick, `rollout(audit=, want_tube=)` inside a rollout.
 """
 import ctypes
 
@@ -330,6 +332,30 @@ def unpack_rollout(row):
     return out
 
 
+# csrc/bmpc_stream_tube.inl: the tube row of one stream (BMPC_TUBE_* of include/boundmpc_hip.h) and the audit record of a rollout (BMPC_AUDIT_*)
+TUBE = dict(L=0, W=5, EX_POS=10, EX_ROT=11, EX_Q=12, EX_DQ=13, SEG=14, PHI=15, LEN=16)
+AUDIT = dict(SAMPLES=0, MAX_POS=1, TICK_POS=2, MAX_ROT=3, TICK_ROT=4, MAX_Q=5, MAX_DQ=6, N_POS=7, N_ROT=8, N_JOINT=9, FIRST_OUT=10, LEN=12)
+
+
+def tube_len():
+    """[l 5 | w 5 | ex_pos | ex_rot | ex_q | ex_dq | segment | phi0]: `tube_excess_of_state` of one stream in both of its forms (rows 38..42:
+    orientation tangential, position bp1, bp2, orientation br1, br2) and the joint figures max_j |q0_j| - qlim_j, max_j |dq0_j| - dqlim_j"""
+    return TUBE["LEN"]
+
+
+def unpack_audit(row):
+    """Audit record of a rollout (StreamBatch.rollout(audit=True)["audit"][b], numpy) -> dict: samples, the largest position / orientation excess
+    (metres, radians; <= 0: inside; NaN: a non-finite sample) with the tick each was measured AHEAD of (row t of tube_hist is the state tick t
+    starts from), the largest joint figures, the counts of samples outside and first_out (None: never outside a tube).  A stream lost on entry
+    has samples 0 and maxima -inf."""
+    row = np.asarray(row)
+    assert row.shape == (AUDIT["LEN"],)
+    tick = lambda k: None if row[AUDIT[k]] < 0 else int(row[AUDIT[k]])
+    return dict(samples=int(row[AUDIT["SAMPLES"]]), max_pos=float(row[AUDIT["MAX_POS"]]), tick_pos=tick("TICK_POS"), max_rot=float(row[AUDIT["MAX_ROT"]]),
+                tick_rot=tick("TICK_ROT"), max_q=float(row[AUDIT["MAX_Q"]]), max_dq=float(row[AUDIT["MAX_DQ"]]), n_pos=int(row[AUDIT["N_POS"]]),
+                n_rot=int(row[AUDIT["N_ROT"]]), n_joint=int(row[AUDIT["N_JOINT"]]), first_out=tick("FIRST_OUT"))
+
+
 # Named reads of the stream records: pure indexing of the last axis, on numpy arrays and torch tensors alike (one row or a batch; no copy, no sync).
 def applied(traj):
     """the success flag of a trajectory record (unpack_traj's `success`): the tick's plan was applied"""
@@ -434,6 +460,7 @@ class StreamBatch:
         self.traj = torch.zeros((self.B, self.tr_len), dtype=torch.float64, device=device)
         self._graphs = {}
         self._log = None         # log(): allocated on first use
+        self._tube = None        # tube(): allocated on first use
         self.replan = self.replan_info = None      # update_device(): record buffer [B][replan_len] and info [B], allocated on first use
         self.tick_ms = None      # closed_loop(timed=True): HIP-event time of the tick just run
         solver._children.add(self)
@@ -547,6 +574,18 @@ class StreamBatch:
                                                     _ptr(self._log), self._stream(stream)), "bmpc_stream_log")
         return self._log
 
+    def tube(self, stream=None):
+        """The tube and joint-limit excess of the measured state in `self.p` (bmpc_stream_tube): the tensor [B][tube_len()], slots TUBE -- what
+        `tube_excess_of_state(self.p)` computes on the host, without the copy.  Call it behind pack(), tick() or tick_graph() and before the next
+        pack; behind a tick it measures the state that tick started from.  A stream without a plan has a NaN row.  Asynchronous on `stream`; the
+        buffer is allocated on first use and reused."""
+        if self._tube is None:
+            import torch
+            assert self.solver._lib.bmpc_stream_tube_len() == TUBE["LEN"]
+            self._tube = torch.empty((self.B, TUBE["LEN"]), dtype=torch.float64, device=self.path.device)
+        _lib.check(self.solver._lib.bmpc_stream_tube(self.solver._h, self.B, _ptr(self.p), _ptr(self.state), _ptr(self._tube), self._stream(stream)), "bmpc_stream_tube")
+        return self._tube
+
     def tick(self, max_iter=0, warm_dual=False, simulate=True, stream=None, accept_capped=False, fused=True):
         """pack -> solve -> post of one tick: one fused launch (bmpc_stream_tick; N <= 11, B within the resident waves) or, with
         fused=False, the three launches of the separate entry points (see tick_graph for the captured form).
@@ -604,7 +643,7 @@ class StreamBatch:
         _lib.check(self.solver._lib.bmpc_graph_launch(self._graphs[key], self._stream(stream)), "bmpc_graph_launch")
 
     def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None,
-                replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None):
+                replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None, audit=False, audit_tol=1e-6, want_tube=False):
         """`ticks` closed-loop ticks (plant simulation on) of every stream in ONE launch (bmpc_stream_rollout): each stream runs at its own pace, so
         the launch lasts as long as the slowest stream's SUM of solves, where a loop of tick() / tick_graph() pays the slowest stream of every tick.
         For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, a time
@@ -624,7 +663,12 @@ class StreamBatch:
                                            state behind that tick exists on the device only) writes the measured state into the record first.
         The goal test and the next tick's lost-plan test see what the re-plan left: a second leg starts behind the tick that reaches the old goal, a
         re-plan behind the post that exhausted the plan rescues the stream.  A stream that stops before its tick keeps its record's flag raised.
-        Then the result also holds  replan_info [B] int32: -1 not consumed, 0 consumed, 1 invalid record."""
+        Then the result also holds  replan_info [B] int32: -1 not consumed, 0 consumed, 1 invalid record.
+        AUDIT behind a tick's pack (bmpc_stream_rollout_audit; with audit and want_tube both off the entries above run unchanged):
+          want_tube: tube_hist [ticks][B][tube_len()]   row [t][b] (slots TUBE) measures the state tick t of stream b STARTS from -- the plant behind
+                                           tick t - 1 with its disturbance and re-plan applied, what tube() behind tick t returns; NaN likewise
+          audit: audit [B][12]             the stream's verdict over its rows (slots AUDIT, unpack_audit): largest excesses and their ticks, samples
+                                           outside by more than audit_tol, joint-limit samples, the first tick outside a tube."""
         import torch
         if max_iter and not warm_dual:
             raise ValueError("an iteration cap needs the dual state (warm_dual=True): the multipliers must be shifted with the plan")
@@ -634,7 +678,12 @@ class StreamBatch:
         if want_traj:
             out["traj_hist"] = torch.empty((n, self.B, self.tr_len), dtype=torch.float64, device=dev)
         args = self._tick_args(max_iter, warm_dual, True, accept_capped)
-        if replan is None and replan_tick is None and disturb is None:
+        audited = bool(audit) or bool(want_tube)
+        if audit:
+            out["audit"] = torch.empty((self.B, AUDIT["LEN"]), dtype=torch.float64, device=dev)
+        if want_tube:
+            out["tube_hist"] = torch.empty((n, self.B, TUBE["LEN"]), dtype=torch.float64, device=dev)
+        if replan is None and replan_tick is None and disturb is None and not audited:
             _lib.check(self.solver._lib.bmpc_stream_rollout(self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]),
                                                             _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]), self._stream(stream)),
                        "bmpc_stream_rollout")
@@ -648,11 +697,14 @@ class StreamBatch:
         if disturb is not None:
             disturb = self._dev64(disturb, (n, self.B, DIST_LEN), "disturb", stream)
         out["replan_info"] = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
-        _lib.check(self.solver._lib.bmpc_stream_rollout_events(self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]),
-                                                               _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]),
-                                                               _ptr(self.replan) if replan is not None else None, _ptr(replan_tick) if replan is not None else None,
-                                                               _ptr(out["replan_info"]), flags, _ptr(disturb) if disturb is not None else None, self._stream(stream)),
-                   "bmpc_stream_rollout_events")
+        events = (self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]), _ptr(out["traj_hist"]) if want_traj else None,
+                  _ptr(out["ticks_run"]), _ptr(self.replan) if replan is not None else None, _ptr(replan_tick) if replan is not None else None,
+                  _ptr(out["replan_info"]), flags, _ptr(disturb) if disturb is not None else None)
+        if audited:
+            _lib.check(self.solver._lib.bmpc_stream_rollout_audit(*events, _ptr(out["tube_hist"]) if want_tube else None, _ptr(out["audit"]) if audit else None,
+                                                                  float(audit_tol), self._stream(stream)), "bmpc_stream_rollout_audit")
+        else:
+            _lib.check(self.solver._lib.bmpc_stream_rollout_events(*events, self._stream(stream)), "bmpc_stream_rollout_events")
         self._event_inputs = (replan_tick, disturb)      # the launch is asynchronous: its inputs live until the next one replaces them
         return out
 

@@ -377,6 +377,46 @@ int bmpc_stream_rollout_events(bmpc_handle *h, int B, int ticks, const double *p
                                double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan /* or NULL */,
                                const int *replan_tick /* [B]; required with replan */, int *replan_info /* [B] or NULL */, int update_flags,
                                const double *disturb /* [ticks][B][21] or NULL */, void *hip_stream);
+/* The error bound, measured on the device: how far is the MEASURED state of a tick outside its tubes and its joint limits?  One row per stream from
+ * the parameter vector p a pack (or a tick) left behind -- the five tube rows of the OCP (rows 38..42 of a stage) evaluated at NODE 0, the state
+ * the plant is in: segment selected by phi0 against phi_switch, the tube quartics at phi0 - phi_switch[segment], the position error
+ * p0 - (pref + dpref x) along bp1 / bp2 (which never select the last window segment), the orientation rows from the packed initial errors of the
+ * segment (host mirror and specification: boundmpc_amd.stream.tube_excess_of_state), and q0, dq0 against the reference's joint limits (those of the
+ * inequality rows, without bound_margin):
+ *   tube [B][BMPC_TUBE_LEN] = l 5 | w 5 | ex_pos | ex_rot | ex_q | ex_dq | segment | phi0
+ *     l, w    the rows in the linear form, |l| <= |w| inside (the OCP's rows are l^2 - w^2), in row order: orientation tangential, position bp1,
+ *             position bp2, orientation br1, orientation br2
+ *     ex_pos  max over the two position rows of |l| - |w|, metres; <= 0: inside.  ex_rot: the same over the three orientation rows, radians
+ *     ex_q    max over the joints of |q0_j| - qlim_j;  ex_dq: max of |dq0_j| - dqlim_j
+ * Non-finite inputs give non-finite slots (a maximum with a NaN among its terms is NaN), never a fault: the segment is clamped to 0..S-1 before it
+ * addresses anything.  sstate may be NULL; where it is given, a stream without a plan (error count not in 0..N-1: the fused tick skips it, its p is
+ * stale) gets an all-NaN row.  The call belongs BEHIND a pack or a tick and BEFORE the next pack; behind a tick it measures the state that tick
+ * started from.  One launch over the batch, one wave per stream.  DEVICE pointers; asynchronous on hip_stream; no workspace of the handle is used, so
+ * the call may be enqueued inside a capture of the caller's stream.  BMPC_ERR_ARG on a missing p or tube or on B < 1. */
+enum { BMPC_TUBE_L = 0 /* 5 */, BMPC_TUBE_W = 5 /* 5 */, BMPC_TUBE_EX_POS = 10, BMPC_TUBE_EX_ROT = 11, BMPC_TUBE_EX_Q = 12, BMPC_TUBE_EX_DQ = 13,
+       BMPC_TUBE_SEG = 14, BMPC_TUBE_PHI = 15, BMPC_TUBE_LEN = 16 };
+int bmpc_stream_tube_len(void);
+int bmpc_stream_tube(bmpc_handle *h, int B, const double *p, const double *sstate /* may be NULL */, double *tube /* [B][16] */, void *hip_stream);
+/* Rollout with the AUDIT: bmpc_stream_rollout_events (its arguments in their order, its tests and contract; NULL event pointers switch the events off)
+ * that also answers what a Monte-Carlo run asks -- did the plant leave its tube, when, and by how much?  Behind the pack of tick t the row of
+ * bmpc_stream_tube is taken from the stream's p:
+ *   tube_hist [ticks][B][BMPC_TUBE_LEN] or NULL: row [t][b] is the state tick t of stream b STARTS from -- the plant behind tick t - 1 with that
+ *     tick's disturbance and re-plan applied, which is what a host loop measures on the p of every tick.  Rows of ticks the stream did not run are NaN,
+ *     as in hist.  The state behind the LAST tick a stream runs is seen by the first pack of the next launch, not by this one.
+ *   audit [B][BMPC_AUDIT_LEN] or NULL, initialised by the kernel: SAMPLES ticks audited; MAX_POS, TICK_POS the largest position excess and its (first)
+ *     tick, MAX_ROT, TICK_ROT likewise; MAX_Q, MAX_DQ the largest joint figures; N_POS, N_ROT samples whose excess is > audit_tol; N_JOINT samples with
+ *     ex_q or ex_dq > 1e-9; FIRST_OUT the first tick with a position or an orientation excess > audit_tol, -1 for none; one pad word.  A non-finite
+ *     excess makes its maximum NaN for good and counts as outside.  A stream lost on entry has SAMPLES 0, maxima -inf, ticks and FIRST_OUT -1.
+ * The audit changes nothing else: every other array holds what bmpc_stream_rollout_events leaves, bit for bit.  With tube_hist and audit both NULL
+ * the call IS bmpc_stream_rollout_events.  BMPC_ERR_ARG, nothing launched: a negative or non-finite audit_tol, and what that entry refuses. */
+enum { BMPC_AUDIT_SAMPLES = 0, BMPC_AUDIT_MAX_POS = 1, BMPC_AUDIT_TICK_POS = 2, BMPC_AUDIT_MAX_ROT = 3, BMPC_AUDIT_TICK_ROT = 4, BMPC_AUDIT_MAX_Q = 5,
+       BMPC_AUDIT_MAX_DQ = 6, BMPC_AUDIT_N_POS = 7, BMPC_AUDIT_N_ROT = 8, BMPC_AUDIT_N_JOINT = 9, BMPC_AUDIT_FIRST_OUT = 10, BMPC_AUDIT_LEN = 12 };
+int bmpc_stream_rollout_audit(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                              double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                              double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan /* or NULL */,
+                              const int *replan_tick /* [B]; required with replan */, int *replan_info /* [B] or NULL */, int update_flags,
+                              const double *disturb /* [ticks][B][21] or NULL */, double *tube_hist /* [ticks][B][16] or NULL */,
+                              double *audit /* [B][12] or NULL */, double audit_tol, void *hip_stream);
 
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
