@@ -103,4 +103,8 @@ struct RArgs {
     double *tube_hist;               // [ticks][B][bmpcs::TUBE_LEN]
     double *audit;                   // [B][bmpcs::AUDIT_LEN], initialised by the kernel
     double audit_tol;                // an excess above it counts as outside a tube
+    // logging records behind every tick's post and the tracking record over their stage 0 (the LG instantiations, bmpc_stream_rollout_log); NULL = off
+    double *log_hist;                // [ticks][B][bmpcs::LOG_STAGE * log_stages + 4]
+    int log_stages;                  // 1..N: the stages of the plan a row keeps
+    double *track;                   // [B][bmpcs::TRACK_LEN], initialised by the kernel
 };

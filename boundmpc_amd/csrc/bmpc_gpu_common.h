@@ -6,7 +6,7 @@
 // over the jobs of bmpc_dual.inl, bmpc_kkt.inl and bmpc_sens.inl, each of which slices its own batch) and the C ABI, bmpc_team.hip the team
 // kernels (NW cooperating waves per problem), bmpc_pair.hip the pair kernel, bmpc_resto.hip the restoration kernels, bmpc_tick.hip the
 // one-wave fused ticks, bmpc_rollout.hip the rollouts (many ticks per stream in one launch; kernel text bmpc_rollout_kernel.inl), bmpc_rollout_events.hip the rollouts with events,
-// bmpc_rollout_audit.hip the rollouts with events and the tube audit.
+// bmpc_rollout_audit.hip the rollouts with events and the tube audit, bmpc_rollout_log.hip those with the logging records on top.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -115,6 +115,8 @@ hipError_t bmpc_rollout_launch(bool zlds, bool resto, const void *kargs, const S
 hipError_t bmpc_rollout_events_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // ---- the same with the audit behind a tick's pack: tube and joint-limit excess of the state the tick starts from (bmpc_rollout_audit.hip; EV and AU) ----
 hipError_t bmpc_rollout_audit_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
+// ---- the same with the logging records behind a tick's post and the tracking record over their stage 0 (bmpc_rollout_log.hip; EV, AU and LG) ----
+hipError_t bmpc_rollout_log_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // ---- the measurement on its own, one wave per stream of the batch (bmpc_rollout_audit.hip; bmpc_stream_tube.inl) ----
 hipError_t bmpc_stream_tube_launch(int N, int S, int B, const double *p, const double *ss, double *tube, hipStream_t st);
 

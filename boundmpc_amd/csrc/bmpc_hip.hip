@@ -850,7 +850,7 @@ extern "C" int bmpc_stream_rollout_len(void) { return BMPC_ROLL_LEN; }
 // the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice (needs the robot records), bit 2 poor bounds (with bit 1 only)
 static bool update_flags_ok(int flags, const void *robot) { return !(flags & ~7) && !((flags & 4) && !(flags & 2)) && !((flags & 2) && !robot); }
 // the rollout entries: the argument test, then the launch of the kernels without the event code (events = 0: r holds no event), with it (1), or with
-// the event and the audit code (2)
+// the event and the audit code (2), or with the log code on top of both (3)
 static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, const RArgs &r, int events, hipStream_t st) {
     const int ticks = r.ticks, flags = t.flags; const double goal_tol = r.goal_tol;
     if (!tick_args_ok(h, B, io, t) || ticks < 1) return BMPC_ERR_ARG;
@@ -869,7 +869,8 @@ static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const Stream
     const SArgs s = stream_sargs(h, t);
     hipEvent_t *pair = nullptr;
     if (h->timing) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
-    if (events == 2) HIPCHK(bmpc_rollout_audit_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    if (events == 3) HIPCHK(bmpc_rollout_log_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    else if (events == 2) HIPCHK(bmpc_rollout_audit_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else if (events) HIPCHK(bmpc_rollout_events_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else HIPCHK(bmpc_rollout_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     if (h->timing) { HIPCHK(hipEventRecord(pair[1], st)); h->n_timed++; }
@@ -909,6 +910,25 @@ extern "C" int bmpc_stream_rollout_audit(bmpc_handle *h, int B, int ticks, const
     if ((replan && !replan_tick) || !update_flags_ok(update_flags, robot)) return BMPC_ERR_ARG;
     const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb, tube_hist, audit, audit_tol};
     return rollout_launch(h, B, io, t, r, 2, (hipStream_t)hip_stream);
+}
+// with the logging records behind every tick's post on top (bmpc_rollout_log.hip); without both of its arrays it IS the entry above
+extern "C" int bmpc_stream_track_len(void) { return BMPC_TRACK_LEN; }
+extern "C" int bmpc_stream_rollout_log_len(const bmpc_handle *h, int log_stages) { return (h && log_stages >= 1 && log_stages <= h->N) ? bmpcs::LOG_STAGE * log_stages + 4 : -1; }
+extern "C" int bmpc_stream_rollout_log(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                                       double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                                       double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan, const int *replan_tick, int *replan_info,
+                                       int update_flags, const double *disturb, double *tube_hist, double *audit, double audit_tol, double *log_hist, int log_stages,
+                                       double *track, void *hip_stream) {
+    if (!log_hist && !track)
+        return bmpc_stream_rollout_audit(h, B, ticks, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, goal_tol, hist,
+                                         traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb, tube_hist, audit, audit_tol, hip_stream);
+    if (!h || log_stages < 1 || log_stages > h->N) return BMPC_ERR_ARG;
+    if (!(audit_tol >= 0.0) || !std::isfinite(audit_tol)) return BMPC_ERR_ARG;
+    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
+    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
+    if ((replan && !replan_tick) || !update_flags_ok(update_flags, robot)) return BMPC_ERR_ARG;
+    const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb, tube_hist, audit, audit_tol, log_hist, log_stages, track};
+    return rollout_launch(h, B, io, t, r, 3, (hipStream_t)hip_stream);
 }
 
 extern "C" int bmpc_stream_set_rt_feasibility_tol(bmpc_handle *h, double tol) {

@@ -26,12 +26,19 @@
 // stream's p -- the state tick t STARTS from: the plant behind tick t - 1 with that tick's disturbance and re-plan applied, what a host loop measures
 // on the p of every tick -- goes to r.tube_hist[t][b] and into the stream's record r.audit[b].  The record lives in global memory and the row in
 // global memory or LDS: nothing of the audit is carried in a register across the solve.  Without AU no audit line is compiled.
+// LOG (the instantiations with LG, bmpc_stream_rollout_log; bmpc_stream_log.inl): behind the post of tick t and its barrier, beside the history rows and
+// AHEAD of that tick's events -- a disturbance changes rb, a re-plan rewrites the path table and the state row --, the logging record of the tick: what
+// bmpc_stream_log writes when it is called right behind bmpc_stream_tick, cut to its first r.log_stages stages, to r.log_hist[t][b]; stage 0 of it, the
+// state the plant is in behind the tick in the path frame, goes into the stream's tracking record r.track[b].  The window exists on the device only: the
+// next pack overwrites p.  The record lives in global memory and the row in global memory or (without log_hist: stage 0 alone) in LDS, behind the log's
+// own LDS words: nothing of the log is carried in a register across the solve.  Without LG no log line is compiled.
 // Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp,
-// bmpc_emu_rollout_events.cpp).
+// bmpc_emu_rollout_events.cpp, bmpc_emu_rollout_audit.cpp, bmpc_emu_rollout_log.cpp).
 #pragma once
 
 #include "bmpc_stream_events.inl"
 #include "bmpc_stream_tube.inl"
+#include "bmpc_stream_log.inl"
 
 namespace bmpcs {
 // history row of one tick of one stream (BMPC_ROLL_* of include/boundmpc_hip.h): the robot record behind the post, then the named scalars, then the
@@ -49,13 +56,14 @@ enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH
 #endif
 // (the body of a tick in the kernel itself, as in bmpc_tick_kernel.inl: behind a function that takes `a` the argument loads lose their no-clobber
 // property -- bmpc_args.h, BMPC_PROBLEM)
-template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false>
+template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false, bool LG = false>
 BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
     BMPCK_LDS double lds[BMPC_NAMESPACE::L_SIZE];
     BMPC_STRIDES(a);
     double *sh = lds + BMPC_NAMESPACE::L_RED;
     static_assert(bmpcs::SH_LEN <= 6 * 64, "the stream functions' LDS words must fit into the solver's reduction area");
     static_assert(bmpcs::TUBE_LEN <= 6 * 64, "and so must a tube row");
+    static_assert(bmpcs::LSH_LEN + bmpcs::LOG_STAGE + 4 <= 6 * 64, "and the log's LDS words with one stage row and its trailer behind them");
     const int TRN = bmpcs::tr_len(a.N);
     const double nan_ = __builtin_nan("");
     for (int b = BMPCK_BLOCK; b < a.B; b += BMPCK_GRID) {
@@ -64,6 +72,7 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
         int t = 0;
         if (EV) { if (r.replan_info && BMPCK_LANE == 0) r.replan_info[b] = -1; }
         if (AU) { if (r.audit && BMPCK_LANE == 0) bmpcs::stream_audit_init(r.audit + (long long)b * bmpcs::AUDIT_LEN); }
+        if (LG) { if (r.track && BMPCK_LANE == 0) bmpcs::stream_track_init(r.track + (long long)b * bmpcs::TRACK_LEN); }
         for (; t < r.ticks; t++) {
             // (the lost-plan test of the fused tick: BoundMPC.step() returns five Nones there and the reference node stops)
             if (BMPCK_UNIFORM((int)(ss[bmpcs::SS_ERRCNT] >= (double)a.N))) {
@@ -106,6 +115,18 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
                 }
             }
             if (r.traj_hist) { double *th = r.traj_hist + row * TRN; for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) th[i] = traj[i]; }
+            if (LG) {
+                // (the stream and the tick opaque, as for the audit: what the log addresses is computed here, behind the solve, and dead before the next one)
+                int b_ = b, t_ = t, cap_ = s.path_stride / bmpcs::PT_LEN;
+                BMPCR_OPAQUE("+s"(b_), "+s"(t_), "+s"(cap_), "+s"(N_), "+s"(S_));
+                // the row: the caller's, or stage 0 alone behind the log's own LDS words
+                const int K_ = r.log_hist ? r.log_stages : 1;
+                double *lrow = r.log_hist ? r.log_hist + ((long long)t_ * a.B + b_) * (K_ * bmpcs::LOG_STAGE + 4) : sh + bmpcs::LSH_LEN;
+                bmpcs::stream_log_rows<true>(N_, S_, a.h, path, cap_, ss, p, traj, lrow, K_, sh, BMPCK_LANE, BMPCK_NL);
+                // (lane 0 wrote stage 0 and the trailer itself)
+                if (r.track && BMPCK_LANE == 0) bmpcs::stream_track(lrow, lrow[K_ * bmpcs::LOG_STAGE], traj[TRN - 3], r.track + (long long)b_ * bmpcs::TRACK_LEN, t_);
+                BMPCK_SYNC();      // the events and the next pack reuse the LDS words of the log
+            }
             if (EV) {
                 // (the stream and the tick opaque: what the events address is computed here, behind the solve, not carried across it)
                 int b_ = b, t_ = t, cap_ = s.path_stride / bmpcs::PT_LEN;
@@ -130,6 +151,10 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
             if (r.hist) for (int i = BMPCK_LANE; i < bmpcs::RH_LEN; i += BMPCK_NL) r.hist[row * bmpcs::RH_LEN + i] = nan_;
             if (r.traj_hist) for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) r.traj_hist[row * TRN + i] = nan_;
             if (AU) { if (r.tube_hist) for (int i = BMPCK_LANE; i < bmpcs::TUBE_LEN; i += BMPCK_NL) r.tube_hist[row * bmpcs::TUBE_LEN + i] = nan_; }
+            if (LG) {
+                const int LR = r.log_stages * bmpcs::LOG_STAGE + 4;
+                if (r.log_hist) for (int i = BMPCK_LANE; i < LR; i += BMPCK_NL) r.log_hist[row * LR + i] = nan_;
+            }
         }
         if (BMPCK_LANE == 0) {
             if (r.ticks_run) r.ticks_run[b] = t;

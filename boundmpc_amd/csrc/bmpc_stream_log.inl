@@ -43,10 +43,15 @@ BMPC_HD inline void angular_velocity(const double *q, const double *dq, double *
 }
 
 // h: the sampling time of the plan.  cap = entries the path table holds.  sh: shared workspace of LSH_LEN doubles.
-BMPC_HD inline void stream_log(int N, int S, double h, const double *path, int cap, const double *ss, const double *p, const double *traj, double *log,
-                               double *sh, int lane, int nl) {
+// The writer of the row.  CUT: only the first `stages` stages (1..N) are written, the row is  [stages][LOG_STAGE] | n_valid | error_count | 2 pad  with
+// the n_valid of the WHOLE plan, and the serial parts stop at the last stage that is kept (a stage needs only the stages ahead of it): the rows of a
+// rollout (bmpc_rollout_kernel.inl, LG).  Without CUT `stages` is not looked at and the text is the one of the whole row, N in its place.
+template <bool CUT>
+BMPC_HD inline void stream_log_rows(int N, int S, double h, const double *path, int cap, const double *ss, const double *p, const double *traj, double *log,
+                                    int stages, double *sh, int lane, int nl) {
     const double qnan = __builtin_nan("");
-    const int TRN = tr_len(N), LL = log_len(N);
+    const int K = CUT ? stages : N;                                // stages of the row
+    const int TRN = tr_len(N), LL = K * LOG_STAGE + 4;
     // the counts, read so that a non-finite word means "no plan" (the tests are written so that a NaN fails them)
     const double ecd = ss[SS_ERRCNT], nvd = traj[TRN - 4];
     const int ec = (ecd >= 0.0 && ecd < (double)N) ? (int)ecd : N;
@@ -54,9 +59,10 @@ BMPC_HD inline void stream_log(int N, int S, double h, const double *path, int c
     n = n > N - ec ? N - ec : n;
     if (lane == 0) { log[LL - 4] = (double)n; log[LL - 3] = (double)ec; log[LL - 2] = 0.0; log[LL - 1] = 0.0; }
     if (n <= 0) {                                                  // (uniform over the lanes)
-        for (int id = lane; id < N * LOG_STAGE; id += nl) log[id] = qnan;
+        for (int id = lane; id < K * LOG_STAGE; id += nl) log[id] = qnan;
         return;
     }
+    const int m = CUT ? (n < K ? n : K) : n;                       // stages the serial parts run to
     const BMPC_NAMESPACE::POff o = BMPC_NAMESPACE::make_poff(S);
     const double *Tp = traj + 4 * 7 * N, *Tv = Tp + 6 * N, *Tphi = Tv + 12 * N, *Tdphi = Tphi + N;
     const double *p0 = p + o.p0;
@@ -65,7 +71,7 @@ BMPC_HD inline void stream_log(int N, int S, double h, const double *path, int c
         // integrated angular velocity of the plan: trapezoid from omega(q0, dq0) over the angular rows of v (:574-586), sign flip after failures (:587-589)
         double om[3], acc[3] = {p0[3], p0[4], p0[5]};
         angular_velocity(p + o.q0, p + o.dq0, om);
-        for (int i = 0; i < n; i++)
+        for (int i = 0; i < m; i++)
             for (int c = 0; c < 3; c++) {
                 const double v = Tv[(3 + c) * N + i];
                 acc[c] = acc[c] + 0.5 * h * (om[c] + v); om[c] = v;
@@ -73,7 +79,7 @@ BMPC_HD inline void stream_log(int N, int S, double h, const double *path, int c
             }
         const double d0[3] = {p0[3] - sh[LSH_IW], p0[4] - sh[LSH_IW + STREAM_NMAX], p0[5] - sh[LSH_IW + 2 * STREAM_NMAX]};
         if (ec > 0 && norm3(d0) > 3.1)
-            for (int i = 0; i < n; i++) for (int c = 0; c < 3; c++) sh[LSH_IW + c * STREAM_NMAX + i] = -sh[LSH_IW + c * STREAM_NMAX + i];
+            for (int i = 0; i < m; i++) for (int c = 0; c < 3; c++) sh[LSH_IW + c * STREAM_NMAX + i] = -sh[LSH_IW + c * STREAM_NMAX + i];
         // rotation reference integrated along the plan from the advanced reference, re-anchored at the via rotations where a stage crosses
         // phi_switch[1] or [2] (:712-752)
         const double sd = ss[SS_SECTOR];
@@ -81,9 +87,9 @@ BMPC_HD inline void stream_log(int N, int S, double h, const double *path, int c
         const int e1 = sector + 1 < cap ? sector + 1 : cap - 1, e2 = sector + 2 < cap ? sector + 2 : cap - 1;      // clamped to the table
         const double sw1 = p[o.sw + 1], sw2 = p[o.sw + 2];
         double pr[3] = {ss[SS_PRREF], ss[SS_PRREF + 1], ss[SS_PRREF + 2]};
-        for (int i = 0; i < n; i++) {
+        for (int i = 0; i < m; i++) {
             for (int c = 0; c < 3; c++) sh[LSH_PR + c * STREAM_NMAX + i] = pr[c];
-            if (i + 1 < n) {
+            if (i + 1 < m) {
                 const double phi = Tphi[i], nxt = Tphi[i + 1];
                 const bool a1 = nxt > sw1 && phi < sw1, a2 = !a1 && nxt > sw2 && phi < sw2;
                 const int k = a1 ? 1 : ((a2 || nxt > sw2) ? 2 : (nxt > sw1 ? 1 : 0));
@@ -101,7 +107,7 @@ BMPC_HD inline void stream_log(int N, int S, double h, const double *path, int c
     }
     BMPCS_SYNC();
     // ---- phase 2: one lane per stage.  Every lane works on a valid stage (its own, or the last one) and the stores select NaN ----
-    for (int i = lane; i < N; i += nl) {
+    for (int i = lane; i < K; i += nl) {
         const bool live = i < n;
         const int ic = live ? i : n - 1;
         double *ref = log + i * LOG_STAGE, *err = ref + LOG_REF;
@@ -175,7 +181,7 @@ BMPC_HD inline void stream_log(int N, int S, double h, const double *path, int c
     }
     // ---- phase 3, one lane per stage: e_r of the second pass, log(R(p) R(ref)^T) against the integrated rotation reference.  (A loop of its
     //      own: with the conversions inside phase 2 the register allocator of this toolchain does not survive the function.) ----
-    for (int i = lane; i < N; i += nl) {
+    for (int i = lane; i < K; i += nl) {
         const bool live = i < n;
         const int ic = live ? i : n - 1;
         double *err = log + i * LOG_STAGE + LOG_REF;
@@ -186,6 +192,40 @@ BMPC_HD inline void stream_log(int N, int S, double h, const double *path, int c
         for (int c = 0; c < 3; c++) BMPCS_LOG_PUT(err[18 + c], er[c]);
     }
 #undef BMPCS_LOG_PUT
+}
+// the whole row  [N][LOG_STAGE] | n_valid | error_count | 2 pad  (bmpc_stream_log)
+BMPC_HD inline void stream_log(int N, int S, double h, const double *path, int cap, const double *ss, const double *p, const double *traj, double *log,
+                               double *sh, int lane, int nl) {
+    stream_log_rows<false>(N, S, h, path, cap, ss, p, traj, log, N, sh, lane, nl);
+}
+
+// stream_track_init / stream_track: the tracking record of a rollout (bmpc_rollout_kernel.inl, LG) over STAGE 0 of the log rows of its ticks -- the state
+// the plant is in behind the tick, in the path frame --,
+//   track [TRACK_LEN = 12] = samples | max, tick, sum of squares of ||e_p_orth|| | the same of ||e_p_par|| | the same of ||e_r|| | replayed | pad
+// (BMPC_TRACK_* of include/boundmpc_hip.h; host mirror and specification: boundmpc_amd.stream.track_of_rows).  Both are the work of ONE lane (lane 0,
+// which wrote stage 0 and the trailer of the row); the record lives in global memory between the ticks.
+enum { TRACK_SAMPLES = 0, TRACK_MAX_EP_ORTH, TRACK_TICK_EP_ORTH, TRACK_SUMSQ_EP_ORTH, TRACK_MAX_EP_PAR, TRACK_TICK_EP_PAR, TRACK_SUMSQ_EP_PAR, TRACK_MAX_ER,
+       TRACK_TICK_ER, TRACK_SUMSQ_ER, TRACK_REPLAYED, TRACK_PAD, TRACK_LEN };
+BMPC_HD inline void stream_track_init(double *track) {
+    const double ninf = -__builtin_inf();
+    for (int f = 0; f < 3; f++) { track[TRACK_MAX_EP_ORTH + 3 * f] = ninf; track[TRACK_TICK_EP_ORTH + 3 * f] = -1.0; track[TRACK_SUMSQ_EP_ORTH + 3 * f] = 0.0; }
+    track[TRACK_SAMPLES] = 0.0; track[TRACK_REPLAYED] = 0.0; track[TRACK_PAD] = 0.0;
+}
+// stage: stage 0 of the row of tick t; n_valid: the row's; using_previous: the word of the tick's trajectory record.  A tick without a valid stage is
+// no sample.  A larger norm replaces the maximum, a non-finite one makes it NaN for good (the audit's rule).
+BMPC_HD inline void stream_track(const double *stage, double n_valid, double using_previous, double *track, int t) {
+    if (!(n_valid >= 1.0)) return;
+    track[TRACK_SAMPLES] += 1.0;
+    if (using_previous > 0.0) track[TRACK_REPLAYED] += 1.0;
+    const int at[3] = {LOG_REF + 9, LOG_REF + 6, LOG_REF + 18};      // e_p_orth, e_p_par, e_r (second pass)
+    for (int f = 0; f < 3; f++) {
+        const double *v = stage + at[f];
+        const double sq = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2], nrm = BMPC_SQRT(sq);
+        const bool bad = !(nrm - nrm == 0.0);
+        const double mx = track[TRACK_MAX_EP_ORTH + 3 * f];
+        if (bad ? mx == mx : nrm > mx) { track[TRACK_MAX_EP_ORTH + 3 * f] = bad ? __builtin_nan("") : nrm; track[TRACK_TICK_EP_ORTH + 3 * f] = (double)t; }
+        track[TRACK_SUMSQ_EP_ORTH + 3 * f] += sq;
+    }
 }
 
 }  // namespace bmpcs

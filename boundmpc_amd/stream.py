@@ -292,18 +292,85 @@ def log_len(N):
     return N * LOG_STAGE + 4
 
 
-def unpack_log(row, N):
+def rollout_log_len(stages):
+    """a log row of a rollout, cut to the first `stages` stages of the plan: [stages][LOG_STAGE] | n_valid | error_count | 2 pad"""
+    return int(stages) * LOG_STAGE + 4
+
+
+def unpack_log(row, N, stages=None):
     """Log row (bmpc_stream_log) -> (ref_data, err_data), the reference's logging dictionaries as the host mirror returns them: lists of flat
-    arrays, one entry per stage of the plan (n_valid of them).  (None, None) for a stream without a plan (n_valid == 0)."""
+    arrays, one entry per stage of the plan (n_valid of them).  (None, None) for a stream without a plan (n_valid == 0).
+    stages: the row is a rollout's (StreamBatch.rollout(want_log=True, log_stages=stages)["log_hist"][t, b]), cut to the first `stages` stages: the
+    lists hold min(n_valid, stages) entries (n_valid is the whole plan's); (None, None) also for the NaN row of a tick the stream did not run."""
     row = np.asarray(row)
-    assert row.shape == (log_len(N),)
-    n = int(row[-4])
+    K = N if stages is None else int(stages)
+    assert 1 <= K <= N and row.shape == (K * LOG_STAGE + 4,)
+    if stages is not None and np.isnan(row[-4]):
+        return None, None
+    n = min(int(row[-4]), K)
     if n == 0:
         return None, None
-    body, o, out = row[:N * LOG_STAGE].reshape(N, LOG_STAGE)[:n], 0, ({}, {})
+    body, o, out = row[:K * LOG_STAGE].reshape(K, LOG_STAGE)[:n], 0, ({}, {})
     for d, keys in zip(out, (LOG_REF, LOG_ERR)):
         for k, w in keys:
             d[k] = [body[i, o:o + w].copy() for i in range(n)]; o += w
+    return out
+
+
+# csrc/bmpc_stream_log.inl: the tracking record of a rollout with the log (BMPC_TRACK_* of include/boundmpc_hip.h)
+TRACK = dict(SAMPLES=0, MAX_EP_ORTH=1, TICK_EP_ORTH=2, SUMSQ_EP_ORTH=3, MAX_EP_PAR=4, TICK_EP_PAR=5, SUMSQ_EP_PAR=6, MAX_ER=7, TICK_ER=8, SUMSQ_ER=9,
+             REPLAYED=10, LEN=12)
+_TRACK_FIGURES = (("EP_ORTH", "e_p_orth"), ("EP_PAR", "e_p_par"), ("ER", "e_r"))
+
+
+def track_len():
+    """[samples | max, tick, sum of squares of ||e_p_orth|| | of ||e_p_par|| | of ||e_r|| | replayed | pad]"""
+    return TRACK["LEN"]
+
+
+def unpack_track(row):
+    """Tracking record of a rollout (StreamBatch.rollout(track=True)["track"][b], numpy) -> dict: samples, and per figure (e_p_orth, e_p_par in
+    metres, e_r in radians) max_<figure> (NaN: a non-finite sample; -inf: no sample), tick_<figure> (the first tick of the maximum, None: none),
+    sumsq_<figure> and the convenience rms_<figure> = sqrt(sumsq / samples) (NaN without a sample); replayed: samples that replayed the previous plan."""
+    row = np.asarray(row)
+    assert row.shape == (TRACK["LEN"],)
+    n = int(row[TRACK["SAMPLES"]])
+    out = dict(samples=n, replayed=int(row[TRACK["REPLAYED"]]))
+    for K, k in _TRACK_FIGURES:
+        t = row[TRACK["TICK_" + K]]
+        out["max_" + k], out["tick_" + k], out["sumsq_" + k] = float(row[TRACK["MAX_" + K]]), None if t < 0 else int(t), float(row[TRACK["SUMSQ_" + K]])
+        out["rms_" + k] = float(np.sqrt(row[TRACK["SUMSQ_" + K]] / n)) if n else float("nan")
+    return out
+
+
+def track_of_rows(log_hist, hist):
+    """The numpy specification of the tracking record: log_hist [T][B][rollout_log_len(stages)] and hist [T][B][rollout_len()] of ONE rollout (its own
+    rows) -> track [B][12].  A tick is a sample when its row has n_valid >= 1 (a NaN row -- a tick the stream did not run -- has none); the figures are
+    the norms sqrt((x x + y y) + z z) of e_p_orth, e_p_par and e_r of STAGE 0: the largest with its first tick (a non-finite norm makes it NaN for
+    good, its tick the first such), the squares summed in tick order; replayed counts the samples whose hist row says using_previous."""
+    log_hist, hist = np.asarray(log_hist, dtype=np.float64), np.asarray(hist, dtype=np.float64)
+    T, B = log_hist.shape[:2]
+    assert hist.shape[:2] == (T, B) and hist.shape[2] == ROLL["LEN"] and (log_hist.shape[2] - 4) % LOG_STAGE == 0
+    w0 = sum(w for _, w in LOG_REF)
+    at = {"e_p_par": w0 + 6, "e_p_orth": w0 + 9, "e_r": w0 + 18}
+    out = np.zeros((B, TRACK["LEN"]))
+    for b in range(B):
+        r = out[b]
+        for K, _ in _TRACK_FIGURES:
+            r[TRACK["MAX_" + K]], r[TRACK["TICK_" + K]] = -np.inf, -1.0
+        for t in range(T):
+            if not log_hist[t, b, -4] >= 1.0:
+                continue
+            r[TRACK["SAMPLES"]] += 1.0
+            if hist[t, b, ROLL["USINGPREV"]] > 0.0:
+                r[TRACK["REPLAYED"]] += 1.0
+            for K, k in _TRACK_FIGURES:
+                x, y, z = log_hist[t, b, at[k]:at[k] + 3]
+                sq = (x * x + y * y) + z * z
+                nrm, mx = np.sqrt(sq), r[TRACK["MAX_" + K]]
+                if (not np.isnan(mx)) if not np.isfinite(nrm) else nrm > mx:
+                    r[TRACK["MAX_" + K]], r[TRACK["TICK_" + K]] = (nrm if np.isfinite(nrm) else np.nan), float(t)
+                r[TRACK["SUMSQ_" + K]] += sq
     return out
 
 
@@ -643,7 +710,8 @@ class StreamBatch:
         _lib.check(self.solver._lib.bmpc_graph_launch(self._graphs[key], self._stream(stream)), "bmpc_graph_launch")
 
     def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None,
-                replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None, audit=False, audit_tol=1e-6, want_tube=False):
+                replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None, audit=False, audit_tol=1e-6, want_tube=False,
+                want_log=False, log_stages=1, track=False):
         """`ticks` closed-loop ticks (plant simulation on) of every stream in ONE launch (bmpc_stream_rollout): each stream runs at its own pace, so
         the launch lasts as long as the slowest stream's SUM of solves, where a loop of tick() / tick_graph() pays the slowest stream of every tick.
         For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, a time
@@ -668,7 +736,13 @@ class StreamBatch:
           want_tube: tube_hist [ticks][B][tube_len()]   row [t][b] (slots TUBE) measures the state tick t of stream b STARTS from -- the plant behind
                                            tick t - 1 with its disturbance and re-plan applied, what tube() behind tick t returns; NaN likewise
           audit: audit [B][12]             the stream's verdict over its rows (slots AUDIT, unpack_audit): largest excesses and their ticks, samples
-                                           outside by more than audit_tol, joint-limit samples, the first tick outside a tube."""
+                                           outside by more than audit_tol, joint-limit samples, the first tick outside a tube.
+        LOG behind a tick's post, ahead of its events (bmpc_stream_rollout_log; with want_log and track both off the entries above run unchanged):
+          want_log: log_hist [ticks][B][rollout_log_len(log_stages)]   row [t][b] holds the first log_stages (1..N) stages of what log() returns
+                                           behind tick t -- path reference, tube bounds, errors in the path frame (unpack_log(row, N, log_stages)) --
+                                           with the n_valid of the whole plan; NaN likewise
+          track: track [B][12]             the stream's tracking record over stage 0 of its rows, the state the plant is in behind every tick (slots
+                                           TRACK, unpack_track): largest ||e_p_orth||, ||e_p_par||, ||e_r|| with their ticks, sums of squares, replays."""
         import torch
         if max_iter and not warm_dual:
             raise ValueError("an iteration cap needs the dual state (warm_dual=True): the multipliers must be shifted with the plan")
@@ -683,7 +757,16 @@ class StreamBatch:
             out["audit"] = torch.empty((self.B, AUDIT["LEN"]), dtype=torch.float64, device=dev)
         if want_tube:
             out["tube_hist"] = torch.empty((n, self.B, TUBE["LEN"]), dtype=torch.float64, device=dev)
-        if replan is None and replan_tick is None and disturb is None and not audited:
+        logged = bool(want_log) or bool(track)
+        if want_log:
+            if not 1 <= int(log_stages) <= self.N:
+                raise ValueError("log_stages must be in 1..N")
+            assert self.solver._lib.bmpc_stream_rollout_log_len(self.solver._h, int(log_stages)) == rollout_log_len(log_stages)
+            out["log_hist"] = torch.empty((n, self.B, rollout_log_len(log_stages)), dtype=torch.float64, device=dev)
+        if track:
+            assert self.solver._lib.bmpc_stream_track_len() == TRACK["LEN"]
+            out["track"] = torch.empty((self.B, TRACK["LEN"]), dtype=torch.float64, device=dev)
+        if replan is None and replan_tick is None and disturb is None and not audited and not logged:
             _lib.check(self.solver._lib.bmpc_stream_rollout(self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]),
                                                             _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]), self._stream(stream)),
                        "bmpc_stream_rollout")
@@ -700,7 +783,11 @@ class StreamBatch:
         events = (self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]), _ptr(out["traj_hist"]) if want_traj else None,
                   _ptr(out["ticks_run"]), _ptr(self.replan) if replan is not None else None, _ptr(replan_tick) if replan is not None else None,
                   _ptr(out["replan_info"]), flags, _ptr(disturb) if disturb is not None else None)
-        if audited:
+        if logged:
+            _lib.check(self.solver._lib.bmpc_stream_rollout_log(*events, _ptr(out["tube_hist"]) if want_tube else None, _ptr(out["audit"]) if audit else None,
+                                                                float(audit_tol), _ptr(out["log_hist"]) if want_log else None, int(log_stages),
+                                                                _ptr(out["track"]) if track else None, self._stream(stream)), "bmpc_stream_rollout_log")
+        elif audited:
             _lib.check(self.solver._lib.bmpc_stream_rollout_audit(*events, _ptr(out["tube_hist"]) if want_tube else None, _ptr(out["audit"]) if audit else None,
                                                                   float(audit_tol), self._stream(stream)), "bmpc_stream_rollout_audit")
         else:

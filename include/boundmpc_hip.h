@@ -417,6 +417,37 @@ int bmpc_stream_rollout_audit(bmpc_handle *h, int B, int ticks, const double *pa
                               const int *replan_tick /* [B]; required with replan */, int *replan_info /* [B] or NULL */, int update_flags,
                               const double *disturb /* [ticks][B][21] or NULL */, double *tube_hist /* [ticks][B][16] or NULL */,
                               double *audit /* [B][12] or NULL */, double audit_tol, void *hip_stream);
+/* Rollout with the LOG: bmpc_stream_rollout_audit (every argument up to audit_tol in its order, its tests and contract; NULL event and audit pointers
+ * switch those off) that also answers what the reference's plots are about -- how well did the loop track the path, tick by tick, in the path frame?
+ * Behind the post of tick t, AHEAD of that tick's disturbance and re-plan, the record of bmpc_stream_log is taken from the stream's path table, state
+ * row, p and traj -- the window between a tick's post and the next pack, which inside a rollout exists on the device only:
+ *   log_hist [ticks][B][88 log_stages + 4] or NULL: row [t][b] = [log_stages][88] | n_valid | error_count | 2 pad, the first log_stages (1..N) stages of
+ *     the row bmpc_stream_log writes when called right behind bmpc_stream_tick (stage layout there), with the n_valid of the WHOLE plan, not clipped
+ *     to log_stages.  Stages at or beyond n_valid are NaN; a tick whose post exhausted the plan gives n_valid = 0 and a NaN body.  The row of a
+ *     re-plan tick is taken before the table is rewritten.  Rows of ticks the stream did not run are NaN, trailer included, as in hist.
+ *   track [B][BMPC_TRACK_LEN] or NULL, initialised by the kernel, over STAGE 0 of every row -- the state the plant is in behind the tick (the robot
+ *     record of hist[t][b], ahead of the tick's disturbance); a tick is a sample when the stream ran it and its row has n_valid >= 1: SAMPLES their
+ *     number; MAX_EP_ORTH the largest ||e_p_orth|| (metres), TICK_EP_ORTH its first tick, SUMSQ_EP_ORTH the sum of its squares in tick order (rms =
+ *     sqrt(sumsq / samples)); the same three for e_p_par and for e_r (radians; the value of the log's second pass); REPLAYED the samples whose
+ *     trajectory record says using_previous; one pad word.  A norm is sqrt((x x + y y) + z z).  A non-finite norm makes its maximum NaN for good.  A
+ *     stream lost on entry has SAMPLES 0, maxima -inf, ticks -1, sums 0.
+ * The log changes nothing else: every other array holds what bmpc_stream_rollout_audit leaves, bit for bit.  With log_hist and track both NULL the call
+ * IS bmpc_stream_rollout_audit (log_stages is not looked at).  With goal_tol = 0 log_hist holds what this loop leaves, cut to log_stages:
+ *   for t in 0..ticks-1: bmpc_stream_tick on one wave per stream; bmpc_stream_log; bmpc_stream_disturb(rows of tick t); bmpc_stream_update of the
+ *                        records due
+ * BMPC_ERR_ARG, nothing launched: log_stages outside 1..N while log_hist or track is given, and what that entry refuses. */
+enum { BMPC_TRACK_SAMPLES = 0, BMPC_TRACK_MAX_EP_ORTH = 1, BMPC_TRACK_TICK_EP_ORTH = 2, BMPC_TRACK_SUMSQ_EP_ORTH = 3, BMPC_TRACK_MAX_EP_PAR = 4,
+       BMPC_TRACK_TICK_EP_PAR = 5, BMPC_TRACK_SUMSQ_EP_PAR = 6, BMPC_TRACK_MAX_ER = 7, BMPC_TRACK_TICK_ER = 8, BMPC_TRACK_SUMSQ_ER = 9,
+       BMPC_TRACK_REPLAYED = 10, BMPC_TRACK_LEN = 12 };
+int bmpc_stream_track_len(void);
+int bmpc_stream_rollout_log_len(const bmpc_handle *h, int log_stages);      /* 88 log_stages + 4; <= 0 on bad arguments (log_stages outside 1..N) */
+int bmpc_stream_rollout_log(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                            double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                            double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan /* or NULL */,
+                            const int *replan_tick /* [B]; required with replan */, int *replan_info /* [B] or NULL */, int update_flags,
+                            const double *disturb /* [ticks][B][21] or NULL */, double *tube_hist /* [ticks][B][16] or NULL */,
+                            double *audit /* [B][12] or NULL */, double audit_tol, double *log_hist /* [ticks][B][88 log_stages + 4] or NULL */,
+                            int log_stages, double *track /* [B][12] or NULL */, void *hip_stream);
 
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
