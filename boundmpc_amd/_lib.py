@@ -47,7 +47,8 @@ SIGNATURES = {
     "bmpc_stream_set_rt_feasibility_tol": (_ci, [_vp, _cd]), "bmpc_stream_set_rt_position_row_cap": (_ci, [_vp, _cd]), "bmpc_stream_set_time_budget": (_ci, [_vp, _cd]),
     "bmpc_stream_set_level_rule": (_ci, [_vp, _cd, _cd, _cd]), "bmpc_set_barrier_hold": (_ci, [_vp, _ci]),
     "bmpc_set_latency_buffer": (_ci, [_vp, _vp]), "bmpc_set_timing": (_ci, [_vp, _ci]), "bmpc_last_kernel_ms": (_ci, [_vp, _P(ctypes.c_float)]), "bmpc_kernel_ms": (_ci, [_vp, _ci, _P(ctypes.c_float)]),
-    "bmpc_set_team_waves": (_ci, [_vp, _ci]), "bmpc_team_info": (_ci, [_vp, _ci, _P(_ci), _P(_ci), _P(_ci)]),
+    "bmpc_set_team_waves": (_ci, [_vp, _ci]), "bmpc_set_rollout_waves": (_ci, [_vp, _ci]), "bmpc_get_rollout_waves": (_ci, [_vp]),
+    "bmpc_team_info": (_ci, [_vp, _ci, _P(_ci), _P(_ci), _P(_ci)]),
     "bmpc_set_restoration": (_ci, [_vp, _ci, _ci, _ci]), "bmpc_get_restoration": (_ci, [_vp, _P(_ci), _P(_ci), _P(_ci)]),
     "bmpc_set_start_rollout": (_ci, [_vp, _ci]), "bmpc_get_start_rollout": (_ci, [_vp]), "bmpc_set_queue_order": (_ci, [_vp, _ci]), "bmpc_get_queue_order": (_ci, [_vp]),
     "bmpc_set_second_attempt": (_ci, [_vp, _ci]), "bmpc_get_second_attempt": (_ci, [_vp]),

@@ -118,6 +118,7 @@ struct bmpc_handle {
     int queue_order;         // bmpc_set_queue_order: 1 = a batch beyond the resident waves is solved in the order of decreasing f(x0) (default for long horizons), 0 = natural order
     double *qkey; int *qorder; int q_cap;      // [q_cap] keys and order of the last such batch
     int team_mode;           // bmpc_set_team_waves: 0 automatic (teams when the batch fits into the resident teams), 1 never, BMPC_TEAM_NW whenever possible
+    int rollout_waves = 1;   // bmpc_set_rollout_waves: 1 one wave per stream (default), BMPC_TEAM_NW teams whatever the batch, 0 automatic (teams when the batch fits into the resident teams)
     int timing; hipEvent_t *ev; int nev; long long n_timed;   // timing = number of launches whose {start, stop} event pairs are kept (ring)
     double *latency_us;
     char *arena_d, *arena_h; size_t arena_d_cap, arena_h_cap;      // staging arena of the host-buffer calls (host_call): device and pinned host buffer, capacities in bytes
@@ -377,6 +378,14 @@ extern "C" int bmpc_set_team_waves(bmpc_handle *h, int waves) {
     h->team_mode = waves;
     return BMPC_OK;
 }
+// the waves a rollout gives each stream (bmpc_set_team_waves does not apply to rollouts): read at launch time by rollout_launch
+extern "C" int bmpc_set_rollout_waves(bmpc_handle *h, int waves) {
+    if (!h || (waves != 0 && waves != 1 && waves != BMPC_TEAM_NW)) return BMPC_ERR_ARG;
+    if (waves == BMPC_TEAM_NW && h->team_grid <= 0) return BMPC_ERR_ARG;      // no team instantiation for this horizon / window
+    h->rollout_waves = waves;
+    return BMPC_OK;
+}
+extern "C" int bmpc_get_rollout_waves(const bmpc_handle *h) { return h ? h->rollout_waves : -1; }
 extern "C" int bmpc_team_info(const bmpc_handle *h, int B, int *waves, int *resident_teams, int *lds_bytes) {
     if (!h) return BMPC_ERR_ARG;
     const int w = solve_waves(h, B);
@@ -859,8 +868,10 @@ static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const Stream
     if (h->rt_budget_us > 0.0) return BMPC_ERR_ARG;                   // a rollout is not real time, and budgeted results depend on the clock
     if (h->closed || caller_is_capturing(st)) return BMPC_ERR_ARG;    // (a direct launch: the workspace may grow, and the ordering events are recorded)
     if (B == 0) return BMPC_OK;
-    // one wave per stream whatever bmpc_set_team_waves says: workgroup w strides over the streams on workspace slab w
-    const int grid = service_grid(h, B);
+    // bmpc_set_rollout_waves, not bmpc_set_team_waves: one wave per stream (the default), or a team per stream -- whatever the batch, or (automatic)
+    // when every stream has a resident team; either way workgroup w strides over the streams on workspace slab w
+    const bool team = h->team_grid > 0 && (h->rollout_waves == BMPC_TEAM_NW || (h->rollout_waves == 0 && B <= h->team_grid));
+    const int grid = team ? (B < h->team_grid ? B : h->team_grid) : service_grid(h, B);
     { int rc_ = reserve_for_batch(h, B); if (rc_ == BMPC_OK) rc_ = ensure_scratch(h, grid); if (rc_ != BMPC_OK) return rc_; }
     { const int rc_ = order_before(h, st); if (rc_ != BMPC_OK) return rc_; }
     KArgs a = handle_kargs(h, B, io);
@@ -869,7 +880,8 @@ static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const Stream
     const SArgs s = stream_sargs(h, t);
     hipEvent_t *pair = nullptr;
     if (h->timing) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
-    if (events == 3) HIPCHK(bmpc_rollout_log_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    if (team) HIPCHK(bmpc_team_rollout_launch(BMPC_TEAM_NW, resto, events != 0, &a, &s, &r, grid, st));      // (one kernel with everything serves the three entries with events)
+    else if (events == 3) HIPCHK(bmpc_rollout_log_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else if (events == 2) HIPCHK(bmpc_rollout_audit_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else if (events) HIPCHK(bmpc_rollout_events_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else HIPCHK(bmpc_rollout_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));

@@ -32,8 +32,15 @@
 // state the plant is in behind the tick in the path frame, goes into the stream's tracking record r.track[b].  The window exists on the device only: the
 // next pack overwrites p.  The record lives in global memory and the row in global memory or (without log_hist: stage 0 alone) in LDS, behind the log's
 // own LDS words: nothing of the log is carried in a register across the solve.  Without LG no log line is compiled.
+// TEAMS (bmpc_team_rollout.hip: BMPC_NW waves per stream, namespace bmpct, ZLDS always): the same text, as bmpc_tick_kernel.inl serves a team -- wave 0
+// runs the stream functions and stores the rows, the workgroup solves, BMPCK_SYNC is a workgroup barrier.  The tick loop holds those barriers and
+// leaves through data-dependent exits (lost plan, goal, replan_tick[b] == t), so all waves must take every exit together: each wave reads every
+// such decision itself from memory that does not change between the last barrier ahead of the read and the first barrier behind it -- ss[SS_ERRCNT],
+// ss[SS_PHI], ss[SS_PHIMAX] (written by wave 0 in stream_post and stream_update, each followed by a barrier; the only word of ss the next pack writes
+// is SS_SECTOR, and the post behind it sits behind the solve's barriers, which need every wave), r.replan_tick (never written) and the kernel
+// arguments.  No decision is taken from a value that only wave 0 holds.
 // Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp,
-// bmpc_emu_rollout_events.cpp, bmpc_emu_rollout_audit.cpp, bmpc_emu_rollout_log.cpp).
+// bmpc_emu_rollout_events.cpp, bmpc_emu_rollout_audit.cpp, bmpc_emu_rollout_log.cpp; the team's: bmpc_emu_team_rollout.cpp).
 #pragma once
 
 #include "bmpc_stream_events.inl"
@@ -58,8 +65,11 @@ enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH
 // property -- bmpc_args.h, BMPC_PROBLEM)
 template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false, bool LG = false>
 BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
+    static_assert(BMPC_NW == 1 || ZLDS, "a team keeps the iterate in LDS");
     BMPCK_LDS double lds[BMPC_NAMESPACE::L_SIZE];
     BMPC_STRIDES(a);
+    const int wv = BMPCK_WAVE;
+    const bool w0 = BMPC_NW == 1 || wv == 0;      // the wave that runs the stream functions and stores the rows (a team: wave 0)
     double *sh = lds + BMPC_NAMESPACE::L_RED;
     static_assert(bmpcs::SH_LEN <= 6 * 64, "the stream functions' LDS words must fit into the solver's reduction area");
     static_assert(bmpcs::TUBE_LEN <= 6 * 64, "and so must a tube row");
@@ -81,18 +91,18 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
             }
             int N_ = a.N, S_ = a.S;
             BMPCR_OPAQUE("+s"(N_), "+s"(S_));      // (what the stream functions are given)
-            bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCK_LANE, BMPCK_NL, s.lvl_c, s.lvl_lo, s.lvl_hi);
+            if (w0) bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCK_LANE, BMPCK_NL, s.lvl_c, s.lvl_lo, s.lvl_hi);
             BMPCK_SYNC();
             if (AU) {
                 // (the stream and the tick opaque, as for the events: what the audit addresses is computed here and dead before the solve)
                 int b_ = b, t_ = t;
                 BMPCR_OPAQUE("+s"(b_), "+s"(t_), "+s"(N_), "+s"(S_));
                 double *row = r.tube_hist ? r.tube_hist + ((long long)t_ * a.B + b_) * bmpcs::TUBE_LEN : sh;
-                bmpcs::stream_tube(N_, S_, p, nullptr, row, BMPCK_LANE, BMPCK_NL);      // (no state row: the lost-plan test has just passed)
+                if (w0) bmpcs::stream_tube(N_, S_, p, nullptr, row, BMPCK_LANE, BMPCK_NL);      // (no state row: the lost-plan test has just passed)
                 if (r.audit && BMPCK_LANE == 0) bmpcs::stream_audit(row, r.audit + (long long)b_ * bmpcs::AUDIT_LEN, t_, r.audit_tol);
                 BMPCK_SYNC();      // the solver's reductions reuse the LDS words of the row
             }
-            BMPC_WAVE_INIT(W, a, lds, a.scratch + (long long)BMPCK_BLOCK * a.scr_stride, 0); BMPCK_WAVE_HOOK(W);
+            BMPC_WAVE_INIT(W, a, lds, a.scratch + (long long)BMPCK_BLOCK * a.scr_stride, wv); BMPCK_WAVE_HOOK(W);
             BMPC_TICK_PROBLEM(pr, a, b, p, x0, dual);
             BMPCR_OPAQUE("+s"(W.N), "+s"(W.S), "+s"(W.h), "+s"(W.G.b), "+s"(pr.p), "+s"(pr.x0), "+s"(pr.x), "+s"(pr.g), "+s"(pr.state));
             const long long t0_ = a.latency_us ? BMPC_NOW() : 0;
@@ -100,10 +110,10 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
             BMPCK_SYNC();
             if (a.latency_us) busy += BMPC_NOW() - t0_;
             BMPCR_OPAQUE("+s"(N_), "+s"(S_));
-            bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, s.rt_tol, sh, BMPCK_LANE, BMPCK_NL, s.rt_row_cap);
+            if (w0) bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, s.rt_tol, sh, BMPCK_LANE, BMPCK_NL, s.rt_row_cap);
             BMPCK_SYNC();      // the history and the next pack read ss, rb, x, traj and the dual state that other lanes have just stored
             const long long row = (long long)t * a.B + b;
-            if (r.hist) {
+            if (r.hist && w0) {
                 double *hr = r.hist + row * bmpcs::RH_LEN;
                 for (int i = BMPCK_LANE; i < bmpcs::RB_LEN; i += BMPCK_NL) hr[bmpcs::RH_ROBOT + i] = rb[i];
                 for (int i = BMPCK_LANE; i < 4; i += BMPCK_NL) hr[bmpcs::RH_NVALID + i] = traj[TRN - 4 + i];
@@ -114,7 +124,7 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
                     if (a.kkt) hr[bmpcs::RH_KKT] = a.kkt[b];
                 }
             }
-            if (r.traj_hist) { double *th = r.traj_hist + row * TRN; for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) th[i] = traj[i]; }
+            if (r.traj_hist && w0) { double *th = r.traj_hist + row * TRN; for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) th[i] = traj[i]; }
             if (LG) {
                 // (the stream and the tick opaque, as for the audit: what the log addresses is computed here, behind the solve, and dead before the next one)
                 int b_ = b, t_ = t, cap_ = s.path_stride / bmpcs::PT_LEN;
@@ -122,7 +132,7 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
                 // the row: the caller's, or stage 0 alone behind the log's own LDS words
                 const int K_ = r.log_hist ? r.log_stages : 1;
                 double *lrow = r.log_hist ? r.log_hist + ((long long)t_ * a.B + b_) * (K_ * bmpcs::LOG_STAGE + 4) : sh + bmpcs::LSH_LEN;
-                bmpcs::stream_log_rows<true>(N_, S_, a.h, path, cap_, ss, p, traj, lrow, K_, sh, BMPCK_LANE, BMPCK_NL);
+                if (w0) bmpcs::stream_log_rows<true>(N_, S_, a.h, path, cap_, ss, p, traj, lrow, K_, sh, BMPCK_LANE, BMPCK_NL);
                 // (lane 0 wrote stage 0 and the trailer itself)
                 if (r.track && BMPCK_LANE == 0) bmpcs::stream_track(lrow, lrow[K_ * bmpcs::LOG_STAGE], traj[TRN - 3], r.track + (long long)b_ * bmpcs::TRACK_LEN, t_);
                 BMPCK_SYNC();      // the events and the next pack reuse the LDS words of the log
@@ -132,13 +142,13 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
                 int b_ = b, t_ = t, cap_ = s.path_stride / bmpcs::PT_LEN;
                 BMPCR_OPAQUE("+s"(b_), "+s"(t_), "+s"(cap_), "+s"(S_));
                 if (r.disturb) {
-                    bmpcs::stream_disturb(rb, r.disturb + ((long long)t_ * a.B + b_) * bmpcs::DIST_LEN, BMPCK_LANE, BMPCK_NL);
+                    if (w0) bmpcs::stream_disturb(rb, r.disturb + ((long long)t_ * a.B + b_) * bmpcs::DIST_LEN, BMPCK_LANE, BMPCK_NL);
                     BMPCK_SYNC();
                 }
                 if (r.replan && BMPCK_UNIFORM((int)(r.replan_tick[b_] == t_))) {
                     double *rec = r.replan + (long long)b_ * bmpcs::replan_len(S_, cap_);
-                    if (r.update_flags & 2) { bmpcs::stream_splice(a.h, S_, cap_, rec, rb, r.update_flags, BMPCK_LANE, BMPCK_NL); BMPCK_SYNC(); }
-                    bmpcs::stream_update(N_, S_, rec, const_cast<double *>(path), cap_, ss, rb, r.replan_info ? r.replan_info + b_ : nullptr, r.update_flags & 1,
+                    if (r.update_flags & 2) { if (w0) bmpcs::stream_splice(a.h, S_, cap_, rec, rb, r.update_flags, BMPCK_LANE, BMPCK_NL); BMPCK_SYNC(); }
+                    if (w0) bmpcs::stream_update(N_, S_, rec, const_cast<double *>(path), cap_, ss, rb, r.replan_info ? r.replan_info + b_ : nullptr, r.update_flags & 1,
                                          BMPCK_LANE, BMPCK_NL);
                     BMPCK_SYNC();      // the goal test, the lost-plan test and the next pack read what the re-plan stored
                 }
@@ -146,7 +156,7 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
             if (BMPCK_UNIFORM((int)(r.goal_tol > 0.0 && ss[bmpcs::SS_PHIMAX] - ss[bmpcs::SS_PHI] <= r.goal_tol))) { t++; break; }
         }
         // t ticks were run; the rows behind them stay without a tick
-        for (int u = t; u < r.ticks; u++) {
+        for (int u = t; w0 && u < r.ticks; u++) {
             const long long row = (long long)u * a.B + b;
             if (r.hist) for (int i = BMPCK_LANE; i < bmpcs::RH_LEN; i += BMPCK_NL) r.hist[row * bmpcs::RH_LEN + i] = nan_;
             if (r.traj_hist) for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) r.traj_hist[row * TRN + i] = nan_;

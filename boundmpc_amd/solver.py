@@ -218,6 +218,16 @@ class BatchedOCPSolver:
         1 never teams; 2 pairs whatever the batch (N <= 11, S <= 4); 4 teams whenever the kernel exists (N <= 10, S <= 4).  Re-capture graphs after changing it."""
         _lib.check(self._lib.bmpc_set_team_waves(self._h, int(waves)), "bmpc_set_team_waves")
 
+    def set_rollout_waves(self, waves=1):
+        """Waves per stream of StreamBatch.rollout (include/boundmpc_hip.h bmpc_set_rollout_waves; set_team_waves does not apply there): 1 (default)
+        one wave per stream; 4 a team of cooperating waves per stream whatever the batch, striding over the resident teams (N <= 10, S <= 4, else
+        refused); 0 automatic -- teams when the batch fits into the resident teams, else one wave.  Read at launch time."""
+        _lib.check(self._lib.bmpc_set_rollout_waves(self._h, int(waves)), "bmpc_set_rollout_waves")
+
+    @property
+    def rollout_waves(self):
+        return int(self._lib.bmpc_get_rollout_waves(self._h))
+
     def team_info(self, B):
         w, r, l = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         _lib.check(self._lib.bmpc_team_info(self._h, int(B), ctypes.byref(w), ctypes.byref(r), ctypes.byref(l)), "bmpc_team_info")

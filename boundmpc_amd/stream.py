@@ -711,11 +711,15 @@ class StreamBatch:
 
     def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None,
                 replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None, audit=False, audit_tol=1e-6, want_tube=False,
-                want_log=False, log_stages=1, track=False):
+                want_log=False, log_stages=1, track=False, waves=None):
         """`ticks` closed-loop ticks (plant simulation on) of every stream in ONE launch (bmpc_stream_rollout): each stream runs at its own pace, so
         the launch lasts as long as the slowest stream's SUM of solves, where a loop of tick() / tick_graph() pays the slowest stream of every tick.
         For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, a time
-        budget) use the ticks.  One wave per stream always (set_team_waves does not apply).  A stream stops once it has lost its plan (status 3, as
+        budget) use the ticks.  Waves per stream: the solver's set_rollout_waves (set_team_waves does not apply) -- 1, the default, one wave per
+        stream; 4 a team of cooperating waves per stream whatever B is, striding over the resident teams (N <= 10, S <= 4; what pays up to 256 streams,
+        where one wave per stream leaves three SIMDs of four idle); 0 teams when B fits into the resident teams, else one wave.  waves=None takes that
+        setting; another value is set for this launch and the former one put back behind it (read at launch time: the launch stays asynchronous).  On
+        teams "one wave per stream" below reads "a team per stream": the ticks of set_team_waves(4).  A stream stops once it has lost its plan (status 3, as
         the fused tick leaves a skipped stream) or, with goal_tol > 0, behind the tick that leaves phi_max - phi <= goal_tol (NodeLoop.run's rule).
         With goal_tol = 0 the batch's buffers hold afterwards what `ticks` calls of tick(fused=True) on one wave per stream leave, bit for bit.
         The protocol of closed_loop -- tick 0 solved out with first_cap, later ticks capped -- is
@@ -744,6 +748,14 @@ class StreamBatch:
           track: track [B][12]             the stream's tracking record over stage 0 of its rows, the state the plant is in behind every tick (slots
                                            TRACK, unpack_track): largest ||e_p_orth||, ||e_p_par||, ||e_r|| with their ticks, sums of squares, replays."""
         import torch
+        if waves is not None:
+            former = self.solver.rollout_waves
+            self.solver.set_rollout_waves(waves)      # (a refused value raises here, the setting intact)
+            try:
+                return self.rollout(ticks, max_iter, warm_dual, accept_capped, goal_tol, want_traj, stream, replan, replan_tick, splice, poor_bounds, set_goal,
+                                    disturb, audit, audit_tol, want_tube, want_log, log_stages, track)
+            finally:
+                self.solver.set_rollout_waves(former)
         if max_iter and not warm_dual:
             raise ValueError("an iteration cap needs the dual state (warm_dual=True): the multipliers must be shifted with the plan")
         assert self.solver._lib.bmpc_stream_rollout_len() == ROLL["LEN"]

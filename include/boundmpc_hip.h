@@ -267,14 +267,16 @@ int bmpc_stream_graph_create(bmpc_handle *h, int B, const double *path, int path
 /* Rollout: `ticks` whole ticks of every stream in ONE launch, for closed loops run in bulk (Monte-Carlo runs, tuning, robustness batteries) where
  * the throughput of whole loops counts, not the latency of a tick.  A loop of bmpc_stream_tick launches joins the grid once per tick, so it costs
  * the sum over the ticks of the slowest stream's solve; here every stream runs at its own pace and the launch lasts as long as the slowest
- * stream's sum.  The tick arrays and their argument test are those of bmpc_stream_tick.  One wave per stream ALWAYS: bmpc_set_team_waves does not
- * apply, workgroup w serves streams w, w + grid, w + 2 grid, ... (grid = min(B, bmpc_launch_info's grid)), so any B is served.
+ * stream's sum.  The tick arrays and their argument test are those of bmpc_stream_tick.  Waves per stream: bmpc_set_rollout_waves (below;
+ * bmpc_set_team_waves does not apply) -- one wave per stream by default, or a team of BMPC_TEAM_NW cooperating waves.  Workgroup w serves streams
+ * w, w + grid, w + 2 grid, ... (grid = min(B, bmpc_launch_info's grid), on teams min(B, resident teams)), so any B is served.
  * Per stream, tick after tick:
  *   lost plan  error count >= N at the start of a tick: what a fused tick writes for a skipped stream (status 3, iters 0, kkt 0) is written
  *              once, everything else keeps its last value, the stream stops;
  *   goal       goal_tol > 0: the stream stops behind the post that leaves phi_max - phi <= goal_tol (the rule of the node's loop); 0 = never.
  * With goal_tol = 0 every tick array (sstate, robot, p, x0, dual_state, x, g, iters, status, kkt, traj) holds afterwards what `ticks` successive
- * bmpc_stream_tick launches on one wave per stream (bmpc_set_team_waves(h, 1)) leave, bit for bit.
+ * bmpc_stream_tick launches on one wave per stream (bmpc_set_team_waves(h, 1)) leave, bit for bit -- on teams what the fused ticks of the teams
+ * (bmpc_set_team_waves(h, BMPC_TEAM_NW)) leave; the same holds for the loops of the entries with events, audit and log below.
  *   hist [ticks][B][BMPC_ROLL_LEN] (may be NULL): row [t][b] describes stream b BEHIND tick t: the robot record, phi, the error count, the
  *     solve's iters / status / kkt (NaN where that array is NULL) and the four trailer words of the tick's trajectory record;
  *   traj_hist [ticks][B][traj] (may be NULL): the whole trajectory record of that tick;
@@ -296,6 +298,15 @@ int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const double *path, in
                         double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
                         double goal_tol, double *hist /* [ticks][B][52] or NULL */, double *traj_hist /* [ticks][B][traj] or NULL */,
                         int *ticks_run /* [B] or NULL */, void *hip_stream);
+/* Waves per stream of the four rollout entries (bmpc_stream_rollout, _events, _audit, _log), read at launch time:
+ *   1 (default)   one wave per stream, on the resident waves of the device;
+ *   BMPC_TEAM_NW  a team of cooperating waves per stream whatever B is, striding over the resident teams (256 on an MI355X: a team owns a CU);
+ *                 BMPC_ERR_ARG on a handle without team kernels (N > 10 or S > 4), as bmpc_set_team_waves;
+ *   0             automatic: teams when the handle has them and B <= the resident teams, else one wave.
+ * Anything else: BMPC_ERR_ARG, the setting stays.  Teams pay where one wave per stream leaves SIMDs idle (B up to the resident teams); their
+ * results agree with the one-wave rollout's as the team ticks agree with the one-wave ticks.  bmpc_get_rollout_waves: the setting; -1: no handle. */
+int bmpc_set_rollout_waves(bmpc_handle *h, int waves);
+int bmpc_get_rollout_waves(const bmpc_handle *h);
 /* The logging records of step() (ref_data / err_data, BoundMPC.py:614-752) of the plan a tick left behind, one row per stream:
  *   log [B][bmpc_stream_log_len] = [N][88] | n_valid | error_count | 2 pad,  a stage being
  *     ref (55): p 6, dp 6, ddp 6, dp_normed 3, r_par_bound 1, bound_lower 4, bound_upper 4, e_p_off 2, e_r_off 2, bp1, bp2, br1, br2, v1, v2, v3 (3 each)
@@ -474,8 +485,8 @@ int bmpc_set_latency_buffer(bmpc_handle *h, double *latency_us);
  * else one wave per problem; (h, 1): always one wave; (h, 2): pairs whatever the batch; (h, 4): teams whatever the batch (an error where the
  * instantiation does not exist).  Results agree with the one-wave kernels up to the order of a few sums (same iterates unless a filter
  * decision sits on a rounding error).  bmpc_team_info: waves per problem a batch of B would get, resident teams / pairs of that kind, LDS
- * bytes of its workgroup.  The fused closed-loop ticks run on teams or on one wave per stream; a rollout (bmpc_stream_rollout) always runs one
- * wave per stream, whatever is set here. */
+ * bytes of its workgroup.  The fused closed-loop ticks run on teams or on one wave per stream; a rollout (bmpc_stream_rollout) has a setting
+ * of its own, bmpc_set_rollout_waves, whatever is set here. */
 int bmpc_set_team_waves(bmpc_handle *h, int waves);
 int bmpc_team_info(const bmpc_handle *h, int B, int *waves, int *resident_teams, int *lds_bytes);
 
