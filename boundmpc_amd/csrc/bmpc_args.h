@@ -1,5 +1,5 @@
 // bmpc_args.h -- the kernel argument records and what every kernel entry does with them: the wave of a workgroup from the argument head, and
-// problem b of a batch as the wave program's Problem.  Nothing of HIP in here: bmpc_gpu_common.h includes it for the kernels, and the CPU
+// problem b of a batch as the wave program's Problem; at the end the argument rule of the rollout entries (host only).  Nothing of HIP in here: bmpc_gpu_common.h includes it for the kernels, and the CPU
 // emulators of the kernel text (tests/emu) include it to run these very lines.  The macros name BMPC_NAMESPACE::Wave / Problem / make_gptr of the
 // wave program (bmpc_wave.inl) and are expanded behind it.
 #pragma once
@@ -108,3 +108,25 @@ struct RArgs {
     int log_stages;                  // 1..N: the stages of the plan a row keeps
     double *track;                   // [B][bmpcs::TRACK_LEN], initialised by the kernel
 };
+
+// ---- host only: what the rollout entries of the C ABI refuse and which kernel they run, once (bmpc_hip.hip rollout_launch; the CPU build of the
+// rollout, tests/emu/bmpc_emu_rollout.cpp, asks the same function) ----
+// the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice (needs the robot records), bit 2 poor bounds (with bit 1 only)
+inline bool bmpc_update_flags_ok(int flags, const void *robot) { return !(flags & ~7) && !((flags & 4) && !(flags & 2)) && !((flags & 2) && !robot); }
+// entry: the entry point the caller used -- 0 bmpc_stream_rollout, 1 _events, 2 _audit, 3 _log; r: its arguments (what an entry has no argument for is
+// 0 / NULL); N: the handle's horizon; flags, robot: the tick flags and the robot records.  Returns the level of the kernel text to run -- 0 plain, 1 EV,
+// 2 EV + AU, 3 EV + AU + LG -- or BMPC_ROLLOUT_REFUSED (the C ABI's BMPC_ERR_ARG).  An entry without the arrays of its own feature IS the entry below it.
+enum { BMPC_ROLLOUT_REFUSED = -1 };
+#define BMPC_TOL_MAX 1.7976931348623157e308      // the largest finite tolerance (plain comparisons: the flop-counting hosts of tests/emu read this file with their own number type)
+inline int bmpc_rollout_level(int entry, const RArgs &r, int N, int flags, const void *robot) {
+    if (r.ticks < 1 || !(r.goal_tol >= 0.0 && r.goal_tol <= BMPC_TOL_MAX)) return BMPC_ROLLOUT_REFUSED;      // (negative, NaN or infinite)
+    if (!(flags & 1)) return BMPC_ROLLOUT_REFUSED;                    // without the plant in the loop a second tick repeats the first
+    if (entry == 0) return 0;
+    if ((r.replan && !r.replan_tick) || !bmpc_update_flags_ok(r.update_flags, robot)) return BMPC_ROLLOUT_REFUSED;
+    if (entry >= 3 && (r.log_hist || r.track)) {
+        if (r.log_stages < 1 || r.log_stages > N) return BMPC_ROLLOUT_REFUSED;
+    } else if (entry >= 3) entry = 2;
+    if (entry >= 2 && !(r.audit_tol >= 0.0 && r.audit_tol <= BMPC_TOL_MAX)) return BMPC_ROLLOUT_REFUSED;
+    if (entry == 2 && !r.tube_hist && !r.audit) entry = 1;
+    return entry;
+}

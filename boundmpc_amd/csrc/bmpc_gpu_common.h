@@ -1,13 +1,13 @@
 // bmpc_gpu_common.h -- what the translation units of libboundmpc_hip.so share: the device math macros the wave program
 // (bmpc_wave.inl) is written in, its lane and phase macros (one set per BMPC_NW: one wave, or a workgroup of cooperating waves), the phase
 // stamps, the prologue of a one-wave kernel and the entry words (BMPCK_*) of the kernel entries the CPU tests compile whole (bmpc_tick_kernel.inl,
-// bmpc_rollout_kernel.inl); bmpc_args.h holds the kernel argument records and the per-problem / per-stream slicing of a batch.  The kernel entry texts shared between
+// bmpc_rollout_kernel.inl); bmpc_args.h holds the kernel argument records, the per-problem / per-stream slicing of a batch and the argument rule of the rollout entries.  The kernel entry texts shared between
 // units are bmpc_multi_batch.inl (team and pair batch kernel) and bmpc_tick_kernel.inl (one-wave and team fused tick).  bmpc_hip.hip holds the one-wave-per-problem batch kernel, the service kernel (one entry
 // over the jobs of bmpc_dual.inl, bmpc_kkt.inl and bmpc_sens.inl, each of which slices its own batch) and the C ABI, bmpc_team.hip the team
 // kernels (NW cooperating waves per problem), bmpc_pair.hip the pair kernel, bmpc_resto.hip the restoration kernels, bmpc_tick.hip the
 // one-wave fused ticks, bmpc_rollout.hip the rollouts (many ticks per stream in one launch; kernel text bmpc_rollout_kernel.inl), bmpc_rollout_events.hip the rollouts with events,
 // bmpc_rollout_audit.hip the rollouts with events and the tube audit, bmpc_rollout_log.hip those with the logging records on top, bmpc_team_rollout.hip
-// the rollouts on teams (the same kernel text with BMPC_NW waves per stream).
+// the rollouts on teams (the same kernel text with BMPC_NW waves per stream); all five launch through bmpc_rollout_run (bmpc_rollout_kernel.inl).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -48,6 +48,7 @@
 #define BMPCK_UNIFORM(i) __builtin_amdgcn_readfirstlane(i)      // a wave-uniform decision as a scalar: the barriers behind it sit in uniform control flow
 #define BMPCK_SYNC() __syncthreads()      // WORKGROUP barrier for every BMPC_NW (BMPCS_SYNC is a wave fence in a team unit)
 #define BMPCK_WAVE_HOOK(W)          // behind BMPC_WAVE_INIT; a host build gives the wave its lane and wave order here
+#define BMPCK_LAUNCH(kernel, grid, st, ...) hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * BMPC_NW), 0, st, __VA_ARGS__)      // a host build calls the function
 
 #if BMPC_NW > 1
 // ---- a workgroup of BMPC_NW cooperating waves per problem (bmpc_team.hip, bmpc_pair.hip) ----

@@ -856,15 +856,13 @@ extern "C" int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int p
 
 // ---- rollout: `ticks` ticks of every stream in one launch (bmpc_rollout.hip), a direct launch on the caller's stream ----
 extern "C" int bmpc_stream_rollout_len(void) { return BMPC_ROLL_LEN; }
-// the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice (needs the robot records), bit 2 poor bounds (with bit 1 only)
-static bool update_flags_ok(int flags, const void *robot) { return !(flags & ~7) && !((flags & 4) && !(flags & 2)) && !((flags & 2) && !robot); }
-// the rollout entries: the argument test, then the launch of the kernels without the event code (events = 0: r holds no event), with it (1), or with
-// the event and the audit code (2), or with the log code on top of both (3)
-static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, const RArgs &r, int events, hipStream_t st) {
-    const int ticks = r.ticks, flags = t.flags; const double goal_tol = r.goal_tol;
-    if (!tick_args_ok(h, B, io, t) || ticks < 1) return BMPC_ERR_ARG;
-    if (!(flags & 1)) return BMPC_ERR_ARG;                            // without the plant in the loop a second tick repeats the first
-    if (!(goal_tol >= 0.0) || !std::isfinite(goal_tol)) return BMPC_ERR_ARG;
+// The rollout entries: each fills the solve, stream and rollout records from its arguments and names itself (entry: 0 bmpc_stream_rollout, 1 _events,
+// 2 _audit, 3 _log); the argument test and the level of the kernel text that runs -- without the event code (0), with it (1), with the event and the audit
+// code (2), with the log code on top of both (3) -- are bmpc_rollout_level's (bmpc_args.h).
+static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, const RArgs &r, int entry, hipStream_t st) {
+    if (!tick_args_ok(h, B, io, t)) return BMPC_ERR_ARG;
+    const int level = bmpc_rollout_level(entry, r, h->N, t.flags, t.robot);
+    if (level == BMPC_ROLLOUT_REFUSED) return BMPC_ERR_ARG;
     if (h->rt_budget_us > 0.0) return BMPC_ERR_ARG;                   // a rollout is not real time, and budgeted results depend on the clock
     if (h->closed || caller_is_capturing(st)) return BMPC_ERR_ARG;    // (a direct launch: the workspace may grow, and the ordering events are recorded)
     if (B == 0) return BMPC_OK;
@@ -880,10 +878,11 @@ static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const Stream
     const SArgs s = stream_sargs(h, t);
     hipEvent_t *pair = nullptr;
     if (h->timing) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
-    if (team) HIPCHK(bmpc_team_rollout_launch(BMPC_TEAM_NW, resto, events != 0, &a, &s, &r, grid, st));      // (one kernel with everything serves the three entries with events)
-    else if (events == 3) HIPCHK(bmpc_rollout_log_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
-    else if (events == 2) HIPCHK(bmpc_rollout_audit_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
-    else if (events) HIPCHK(bmpc_rollout_events_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    // (teams at levels 1 and 2 hand the LG text the caller's log_stages UNCHECKED, with log_hist and track NULL: the kernel reads it behind r.log_hist only)
+    if (team) HIPCHK(bmpc_team_rollout_launch(BMPC_TEAM_NW, resto, level != 0, &a, &s, &r, grid, st));      // (one kernel with everything serves every level above 0)
+    else if (level == 3) HIPCHK(bmpc_rollout_log_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    else if (level == 2) HIPCHK(bmpc_rollout_audit_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
+    else if (level == 1) HIPCHK(bmpc_rollout_events_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else HIPCHK(bmpc_rollout_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     if (h->timing) { HIPCHK(hipEventRecord(pair[1], st)); h->n_timed++; }
     return order_after(h, st);
@@ -897,14 +896,13 @@ extern "C" int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const doubl
     return rollout_launch(h, B, io, t, r, 0, (hipStream_t)hip_stream);
 }
 // with events behind every tick's post (bmpc_rollout_events.hip): disturbances of the plant and one scheduled re-plan per stream
+// (the table is written by a re-plan: the caller's `path` is not const where a record may be consumed)
 extern "C" int bmpc_stream_rollout_events(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
                                           double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
                                           double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan, const int *replan_tick, int *replan_info,
                                           int update_flags, const double *disturb, void *hip_stream) {
     const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
     const StreamIO t{path, path_entries, sstate, robot, traj, flags};
-    if ((replan && !replan_tick) || !update_flags_ok(update_flags, robot)) return BMPC_ERR_ARG;
-    // (the table is written by a re-plan: the caller's `path` is not const where a record may be consumed)
     const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb};
     return rollout_launch(h, B, io, t, r, 1, (hipStream_t)hip_stream);
 }
@@ -913,13 +911,8 @@ extern "C" int bmpc_stream_rollout_audit(bmpc_handle *h, int B, int ticks, const
                                          double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
                                          double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan, const int *replan_tick, int *replan_info,
                                          int update_flags, const double *disturb, double *tube_hist, double *audit, double audit_tol, void *hip_stream) {
-    if (!(audit_tol >= 0.0) || !std::isfinite(audit_tol)) return BMPC_ERR_ARG;
-    if (!tube_hist && !audit)
-        return bmpc_stream_rollout_events(h, B, ticks, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, goal_tol, hist,
-                                          traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb, hip_stream);
     const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
     const StreamIO t{path, path_entries, sstate, robot, traj, flags};
-    if ((replan && !replan_tick) || !update_flags_ok(update_flags, robot)) return BMPC_ERR_ARG;
     const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb, tube_hist, audit, audit_tol};
     return rollout_launch(h, B, io, t, r, 2, (hipStream_t)hip_stream);
 }
@@ -931,14 +924,8 @@ extern "C" int bmpc_stream_rollout_log(bmpc_handle *h, int B, int ticks, const d
                                        double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan, const int *replan_tick, int *replan_info,
                                        int update_flags, const double *disturb, double *tube_hist, double *audit, double audit_tol, double *log_hist, int log_stages,
                                        double *track, void *hip_stream) {
-    if (!log_hist && !track)
-        return bmpc_stream_rollout_audit(h, B, ticks, path, path_entries, sstate, robot, p, x0, dual_state, max_iter, x, g, iters, status, kkt, traj, flags, goal_tol, hist,
-                                         traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb, tube_hist, audit, audit_tol, hip_stream);
-    if (!h || log_stages < 1 || log_stages > h->N) return BMPC_ERR_ARG;
-    if (!(audit_tol >= 0.0) || !std::isfinite(audit_tol)) return BMPC_ERR_ARG;
     const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
     const StreamIO t{path, path_entries, sstate, robot, traj, flags};
-    if ((replan && !replan_tick) || !update_flags_ok(update_flags, robot)) return BMPC_ERR_ARG;
     const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb, tube_hist, audit, audit_tol, log_hist, log_stages, track};
     return rollout_launch(h, B, io, t, r, 3, (hipStream_t)hip_stream);
 }
@@ -1007,7 +994,7 @@ extern "C" int bmpc_stream_replan_len(const bmpc_handle *h, int path_entries) { 
 // (like the log: no workspace of the handle, no ordering event, and the launch may sit inside a capture of the caller's stream)
 extern "C" int bmpc_stream_update(bmpc_handle *h, int B, double *replan, double *path, int path_entries, double *sstate, double *robot, int *info, int flags,
                                   void *hip_stream) {
-    if (B < 1 || !stream_args_ok(h, B, 0, path_entries, {replan, path, sstate}) || !update_flags_ok(flags, robot)) return BMPC_ERR_ARG;
+    if (B < 1 || !stream_args_ok(h, B, 0, path_entries, {replan, path, sstate}) || !bmpc_update_flags_ok(flags, robot)) return BMPC_ERR_ARG;
     if (flags & 2) hipLaunchKernelGGL(bmpc_stream_update_splice_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, h->h, replan, path,
                                       path_entries * bmpcs::PT_LEN, sstate, robot, info, flags);
     else hipLaunchKernelGGL(bmpc_stream_update_kernel, dim3(B), dim3(64), 0, (hipStream_t)hip_stream, h->N, h->S, B, replan, path, path_entries * bmpcs::PT_LEN, sstate, robot,

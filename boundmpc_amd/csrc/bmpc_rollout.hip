@@ -23,10 +23,6 @@ static_assert(bmpcs::RH_ROBOT == BMPC_ROLL_ROBOT && bmpcs::RH_PHI == BMPC_ROLL_P
               && bmpcs::RH_LEN == BMPC_ROLL_LEN, "history slots of the header and of the kernel text");
 
 hipError_t bmpc_rollout_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st) {
-    KArgs a; memcpy(&a, kargs, sizeof(a));
-    if (zlds && resto) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<true, true>), dim3(grid), dim3(64), 0, st, a, *s, *r);
-    else if (zlds) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<true, false>), dim3(grid), dim3(64), 0, st, a, *s, *r);
-    else if (resto) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<false, true>), dim3(grid), dim3(64), 0, st, a, *s, *r);
-    else hipLaunchKernelGGL((bmpc_stream_rollout_kernel<false, false>), dim3(grid), dim3(64), 0, st, a, *s, *r);
+    bmpc_rollout_run<false, false, false>(zlds, resto, kargs, *s, *r, grid, st);
     return hipGetLastError();
 }

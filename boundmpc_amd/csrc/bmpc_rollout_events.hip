@@ -20,10 +20,6 @@ typedef KArgsT<bmpc::Opts> KArgs;
 static_assert(bmpcs::DIST_LEN == BMPC_DIST_LEN, "disturbance row of the header and of the kernel text");
 
 hipError_t bmpc_rollout_events_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st) {
-    KArgs a; memcpy(&a, kargs, sizeof(a));
-    if (zlds && resto) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<true, true, true>), dim3(grid), dim3(64), 0, st, a, *s, *r);
-    else if (zlds) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<true, false, true>), dim3(grid), dim3(64), 0, st, a, *s, *r);
-    else if (resto) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<false, true, true>), dim3(grid), dim3(64), 0, st, a, *s, *r);
-    else hipLaunchKernelGGL((bmpc_stream_rollout_kernel<false, false, true>), dim3(grid), dim3(64), 0, st, a, *s, *r);
+    bmpc_rollout_run<true, false, false>(zlds, resto, kargs, *s, *r, grid, st);
     return hipGetLastError();
 }

@@ -39,8 +39,9 @@
 // ss[SS_PHI], ss[SS_PHIMAX] (written by wave 0 in stream_post and stream_update, each followed by a barrier; the only word of ss the next pack writes
 // is SS_SECTOR, and the post behind it sits behind the solve's barriers, which need every wave), r.replan_tick (never written) and the kernel
 // arguments.  No decision is taken from a value that only wave 0 holds.
-// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp,
-// bmpc_emu_rollout_events.cpp, bmpc_emu_rollout_audit.cpp, bmpc_emu_rollout_log.cpp; the team's: bmpc_emu_team_rollout.cpp).
+// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp, once per
+// BMPC_NW).  The five units (bmpc_rollout.hip, bmpc_rollout_events.hip, bmpc_rollout_audit.hip, bmpc_rollout_log.hip, bmpc_team_rollout.hip) and that
+// build launch through bmpc_rollout_run at the end of this file, the one place that picks <ZLDS, RESTO>.
 #pragma once
 
 #include "bmpc_stream_events.inl"
@@ -171,6 +172,21 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
             if (a.latency_us) a.latency_us[b] = (double)busy * 0.01;
         }
         BMPCK_SYNC();      // the next stream's pack reuses the LDS words this stream's last phase read
+    }
+}
+
+// Host: the one place that picks the instantiation <ZLDS, RESTO> of a unit's <EV, AU, LG> and launches it on `grid` workgroups (BMPCK_LAUNCH: the GPU
+// launch on stream `st`, or the host build's call).  kargs points at a KArgsT<...> record (the layouts are identical across instantiations).  A team
+// keeps the iterate in LDS: its units hold no instantiation without ZLDS.  `static`: every unit has its own -- the name says nothing of the unit's KArgs
+// and BMPC_NW, and the linker would fold the one-wave units' and the team unit's into one.
+template <bool EV, bool AU, bool LG, class STREAM>
+static void bmpc_rollout_run(bool zlds, bool resto, const void *kargs, const SArgs &s, const RArgs &r, int grid, STREAM st) {
+    KArgs a; memcpy(&a, kargs, sizeof(a));
+    if (zlds && resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, true, EV, AU, LG>), grid, st, a, s, r);
+    else if (zlds) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, false, EV, AU, LG>), grid, st, a, s, r);
+    else if constexpr (BMPC_NW == 1) {
+        if (resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<false, true, EV, AU, LG>), grid, st, a, s, r);
+        else BMPCK_LAUNCH((bmpc_stream_rollout_kernel<false, false, EV, AU, LG>), grid, st, a, s, r);
     }
 }
 

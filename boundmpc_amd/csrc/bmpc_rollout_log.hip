@@ -26,10 +26,6 @@ static_assert(bmpcs::TRACK_SAMPLES == BMPC_TRACK_SAMPLES && bmpcs::TRACK_MAX_EP_
               "tracking slots of the header and of the kernel text");
 
 hipError_t bmpc_rollout_log_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st) {
-    KArgs a; memcpy(&a, kargs, sizeof(a));
-    if (zlds && resto) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<true, true, true, true, true>), dim3(grid), dim3(64), 0, st, a, *s, *r);
-    else if (zlds) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<true, false, true, true, true>), dim3(grid), dim3(64), 0, st, a, *s, *r);
-    else if (resto) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<false, true, true, true, true>), dim3(grid), dim3(64), 0, st, a, *s, *r);
-    else hipLaunchKernelGGL((bmpc_stream_rollout_kernel<false, false, true, true, true>), dim3(grid), dim3(64), 0, st, a, *s, *r);
+    bmpc_rollout_run<true, true, true>(zlds, resto, kargs, *s, *r, grid, st);
     return hipGetLastError();
 }

@@ -20,7 +20,7 @@
 //   audit [AUDIT_LEN = 12] = samples | max_pos, tick_pos | max_rot, tick_rot | max_q | max_dq | n_pos | n_rot | n_joint | first_out | pad
 // (BMPC_AUDIT_*).  Both are the work of ONE lane (lane 0: the lane that wrote the excess slots of the row, or saw them behind stream_tube's phase
 // boundary); the record lives in global memory between the ticks.
-// The same text is compiled by g++ for the CPU tests (tests/emu/bmpc_emu_stream_tube.cpp, bmpc_emu_rollout_audit.cpp).
+// The same text is compiled by g++ for the CPU tests (tests/emu/bmpc_emu_stream_tube.cpp, bmpc_emu_rollout.cpp).
 #pragma once
 
 namespace bmpcs {

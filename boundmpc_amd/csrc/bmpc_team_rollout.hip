@@ -25,10 +25,7 @@ static_assert(bmpct::NW == BMPC_NW, "team size");
 
 hipError_t bmpc_team_rollout_launch(int nw, bool resto, bool full, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st) {
     if (nw != BMPC_NW) return hipErrorInvalidValue;
-    KArgs a; memcpy(&a, kargs, sizeof(a));
-    if (full && resto) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<true, true, true, true, true>), dim3(grid), dim3(64 * BMPC_NW), 0, st, a, *s, *r);
-    else if (full) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<true, false, true, true, true>), dim3(grid), dim3(64 * BMPC_NW), 0, st, a, *s, *r);
-    else if (resto) hipLaunchKernelGGL((bmpc_stream_rollout_kernel<true, true>), dim3(grid), dim3(64 * BMPC_NW), 0, st, a, *s, *r);
-    else hipLaunchKernelGGL((bmpc_stream_rollout_kernel<true, false>), dim3(grid), dim3(64 * BMPC_NW), 0, st, a, *s, *r);
+    if (full) bmpc_rollout_run<true, true, true>(true, resto, kargs, *s, *r, grid, st);
+    else bmpc_rollout_run<false, false, false>(true, resto, kargs, *s, *r, grid, st);
     return hipGetLastError();
 }

@@ -63,6 +63,7 @@ inline thread_local EmuLaunch emu_launch;
 #define BMPCK_SYNC()
 #define BMPCS_SYNC()
 #define BMPCK_WAVE_HOOK(W) BMPC_NAMESPACE::emu_order(W, emu_launch.lane_order, emu_launch.wave_order)
+#define BMPCK_LAUNCH(kernel, grid, st, ...) kernel(__VA_ARGS__)      // (the caller has set emu_launch)
 #define BMPC_NOW() 0LL
 
 #include "../../boundmpc_amd/csrc/bmpc_args.h"

@@ -1,5 +1,6 @@
 """TEST-ONLY: ctypes bindings of the CPU lane emulators of the wave program (tests/emu/*.cpp) and the one place that builds them: solves, the stream
-functions one by one, and the fused tick as its kernel entry text (stream_tick, one wave or a team).  Modes of a solve (poison, in_kernel) are
+functions one by one, and the fused tick as its kernel entry text (stream_tick, one wave or a team).  Beside it: emu_rollout.py (the rollout text in
+all its variants, bmpc_emu_rollout.cpp per BMPC_NW, and the contract's loop), emu_stream_update.py (re-plan, splice, disturb), emu_stream_log.py, emu_stream_tube.py.  Modes of a solve (poison, in_kernel) are
 arguments, nothing is read from the environment.  Not part of the product; see the header of bmpc_emu.cpp."""
 import ctypes
 import functools

@@ -1,5 +1,5 @@
-"""TEST-ONLY: the CPU build of the stream re-planning (boundmpc_amd/csrc/bmpc_stream_update.inl through tests/emu/bmpc_emu_stream_update.cpp) and
-what the CPU and the GPU tests of it share: random paths with the degenerate branches, and the comparison of a table / state pair."""
+"""TEST-ONLY: the CPU build of the stream re-planning and of the two event functions (boundmpc_amd/csrc/bmpc_stream_update.inl, bmpc_stream_events.inl
+through tests/emu/bmpc_emu_stream_update.cpp) and what the CPU and the GPU tests of them share: random paths with the degenerate branches, and the comparison of a table / state pair."""
 import ctypes
 
 import numpy as np
@@ -8,11 +8,13 @@ from scipy.spatial.transform import Rotation as R
 from boundmpc_amd import stream as bstream
 from tests.emu import emu
 
-PT, SS = bstream.PT, bstream.SS
+PT, SS, RP, RV = bstream.PT, bstream.SS, bstream.RP, bstream.RV
 
 
 def lib():
-    return emu._build("libbmpc_emu_stream_update.so", "bmpc_emu_stream_update.cpp", (), ("bmpc_stream.inl", "bmpc_stream_update.inl"))
+    L = emu._build("libbmpc_emu_stream_update.so", "bmpc_emu_stream_update.cpp", (), ("bmpc_stream.inl", "bmpc_stream_update.inl", "bmpc_stream_events.inl"))
+    assert L.bmpc_emu_stream_disturb_len() == bstream.DIST_LEN
+    return L
 
 
 def stream_update(N, S, rec, path, ss, rb=None, set_goal=True):
@@ -25,6 +27,31 @@ def stream_update(N, S, rec, path, ss, rb=None, set_goal=True):
     assert path.shape[1] == PT["LEN"] and ss.shape == (bstream.ss_len(N),) and cap >= S + 1
     assert L.bmpc_emu_stream_replan_len(ctypes.c_int(S), ctypes.c_int(cap)) == bstream.replan_len(S, cap) == rec.shape[0]
     info = L.bmpc_emu_stream_update(ctypes.c_int(N), ctypes.c_int(S), emu._p(rec), emu._p(path), ctypes.c_int(cap), emu._p(ss), emu._p(rb), ctypes.c_int(int(bool(set_goal))))
+    return info, rec, path, ss, rb
+
+
+def stream_splice(h, S, rec, rb, poor_bounds=False, flags=None):
+    """the CPU build of stream_splice on a copy of the record -> the record after it"""
+    rec, rb = np.array(rec, dtype=np.float64, order="C"), np.array(rb, dtype=np.float64, order="C")
+    cap = (rec.shape[0] - RP["HEAD"]) // RV["LEN"] + S - 1
+    lib().bmpc_emu_stream_splice(ctypes.c_double(h), ctypes.c_int(S), ctypes.c_int(cap), emu._p(rec), emu._p(rb), ctypes.c_int(2 | (4 if poor_bounds else 0) if flags is None else flags))
+    return rec
+
+
+def stream_disturb(rb, d):
+    """the CPU build of stream_disturb on a copy of the robot record -> the record after it"""
+    rb, d = np.array(rb, dtype=np.float64, order="C"), np.array(d, dtype=np.float64, order="C")
+    assert d.shape == (bstream.DIST_LEN,)
+    lib().bmpc_emu_stream_disturb(emu._p(rb), emu._p(d))
+    return rb
+
+
+def stream_update_flags(N, S, h, rec, path, ss, rb, flags):
+    """what bmpc_stream_update(flags) does with one stream, on copies -> (info, rec, path, ss, rb); info -2: the C ABI's BMPC_ERR_ARG"""
+    rec, path, ss = (np.array(a, dtype=np.float64, order="C") for a in (rec, path, ss))
+    rb = None if rb is None else np.array(rb, dtype=np.float64, order="C")
+    info = lib().bmpc_emu_stream_update_flags(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), emu._p(rec), emu._p(path), ctypes.c_int(path.shape[0]), emu._p(ss), emu._p(rb),
+                                              ctypes.c_int(int(flags)))
     return info, rec, path, ss, rb
 
 

@@ -5,61 +5,9 @@ ordered against a graph replay on another stream of the same handle, and the arg
 import numpy as np
 import pytest
 
+from tests.rollout_contract import ARRAYS, assert_equal as _assert_equal, batch as _batch, close as _close, per_tick as _per_tick, small_streams as _small_streams, snapshot as _snapshot
+
 pytestmark = pytest.mark.gpu
-ARRAYS = ("state", "robot", "p", "x0", "dual", "x", "g", "iters", "status", "kkt", "traj")
-HELD = dict(tol=1e-3, max_iter=30, fixed_barrier="auto", bound_margin=2e-3)      # the held-barrier real-time mode bench.py reports for configs[4]
-
-
-def _small_streams(N, S, n=3):
-    from tests.emu import emu_rollout as er
-    made = [er.small_stream(N, S, which=i) for i in range(n)]
-    return [m[0] for m in made], np.stack([m[1] for m in made])
-
-
-def _batch(N, S, mpcs, recs, one_wave=False, held=False, **kw):
-    from boundmpc_amd import BatchedOCPSolver, stream as bstream
-    solver = BatchedOCPSolver(N, S, 0.1, **(HELD if held else {}), **kw)
-    if held:
-        solver.set_rt_feasibility_tol(1e-2); solver.set_rt_position_row_cap(1e-5)
-    if one_wave:
-        solver.set_team_waves(1)
-    sb = bstream.StreamBatch(solver, mpcs)
-    sb.set_robot(recs)
-    return solver, sb
-
-
-def _snapshot(sb):
-    return {k: getattr(sb, k).cpu().numpy().copy() for k in ARRAYS}
-
-
-def _per_tick(sb, ticks, **kw):
-    """`ticks` direct launches of the fused tick, read back after each: (hist rows [ticks][B][52], traj rows, snapshots); a stream the tick skipped
-    (it had lost its plan before the tick) gets NaN rows"""
-    import torch
-    from boundmpc_amd import stream as bstream
-    SS, rows, trajs, snaps = bstream.SS, [], [], []
-    for _ in range(ticks):
-        lost = sb.state[:, SS["ERRCNT"]].cpu().numpy() >= sb.N
-        sb.tick(simulate=True, **kw)
-        torch.cuda.synchronize()
-        s = _snapshot(sb)
-        row = np.concatenate([s["robot"], s["state"][:, [SS["PHI"], SS["ERRCNT"]]], s["iters"][:, None].astype(float), s["status"][:, None].astype(float), s["kkt"][:, None],
-                              s["traj"][:, -4:]], axis=1)
-        tr = s["traj"].copy()
-        row[lost] = np.nan; tr[lost] = np.nan
-        rows.append(row); trajs.append(tr); snaps.append(s)
-    return np.array(rows), np.array(trajs), snaps
-
-
-def _assert_equal(a, b, what, rows=None):
-    for k in ARRAYS:
-        x, y = (a[k], b[k]) if rows is None else (a[k][rows], b[k][rows])
-        assert np.array_equal(x, y, equal_nan=True), f"{what}: {k} differs"
-
-
-def _close(*pairs):
-    for solver, sb in pairs:
-        sb.close(); solver.close()
 
 
 @pytest.mark.parametrize("mode", ["converged", "held"])

@@ -5,17 +5,11 @@ streams than resident workgroups; the splice alone against its numpy mirror; the
 import numpy as np
 import pytest
 
-from tests.test_gpu_stream_rollout import ARRAYS, HELD, _assert_equal, _batch, _close, _small_streams, _snapshot
+from tests.rollout_contract import ARRAYS, assert_equal as _assert_equal, batch as _batch, close as _close, contract_loop, records as _records, small_streams as _small_streams, snapshot as _snapshot
 
 pytestmark = pytest.mark.gpu
 N, S, T = 2, 2, 6
 ATOL = 1e-11                     # tests/test_stream_rollout_events.py's bound of the splice (measured there: profiles/stream_splice.txt)
-
-
-def _records(mpcs, recs, entries, **leg):
-    from boundmpc_amd import stream as bstream
-    from tests.emu import emu_rollout_events as ee
-    return np.stack([bstream.replan_record(S, entries, *ee.leg_back(m, r, np.zeros((entries, 48)), S, **leg)) for m, r in zip(mpcs, recs)])
 
 
 def _raw_events(solver, t, B, ticks, flags, goal_tol, hist, th, run, replan, tick_of, info, uflags, dist, entries, max_iter=0):
@@ -28,41 +22,6 @@ def _raw_events(solver, t, B, ticks, flags, goal_tol, hist, th, run, replan, tic
 
 def _tensors(sb):
     return {k: getattr(sb, k) for k in ARRAYS + ("path",)}
-
-
-def _loop_with_events(sb, ticks, records, tick_of, dist, **kw):
-    """The contract's loop on the batch `sb`: per tick one fused tick on one wave per stream, bmpc_stream_disturb with the rows of the tick,
-    bmpc_stream_update(set_goal, splice) with exactly the flags of the streams whose tick it is raised -- events for the streams that still run only.
-    -> (hist rows, traj rows, ticks_run, replan_info)"""
-    import torch
-    from boundmpc_amd import stream as bstream
-    SS, B = bstream.SS, sb.B
-    rows, trajs = np.full((ticks, B, 52), np.nan), np.full((ticks, B, sb.tr_len), np.nan)
-    run, info = np.zeros(B, dtype=int), np.full(B, -1)
-    sb._replan_buffer(records, None)
-    stopped = np.zeros(B, dtype=bool)
-    for t in range(ticks):
-        stopped |= sb.state[:, SS["ERRCNT"]].cpu().numpy() >= sb.N
-        sb.tick(simulate=True, **kw)
-        torch.cuda.synchronize()
-        s = _snapshot(sb)
-        row = np.concatenate([s["robot"], s["state"][:, [SS["PHI"], SS["ERRCNT"]]], s["iters"][:, None].astype(float), s["status"][:, None].astype(float), s["kkt"][:, None],
-                              s["traj"][:, -4:]], axis=1)
-        live = ~stopped
-        rows[t, live], trajs[t, live] = row[live], s["traj"][live]
-        run[live] = t + 1
-        d = dist[t].copy(); d[stopped] = 0.0
-        sb.disturb(d)
-        due = live & (tick_of == t)
-        if due.any():
-            flags = sb.replan[:, 0].clone()
-            sb.replan[:, 0] = torch.where(torch.as_tensor(due, device=flags.device), flags, torch.zeros_like(flags))
-            i = sb.update_device(sb.replan, set_goal=True, splice=True)
-            torch.cuda.synchronize()
-            info[due] = i.cpu().numpy()[due]
-            sb.replan[:, 0] = torch.where(torch.as_tensor(due, device=flags.device), sb.replan[:, 0], flags)
-    torch.cuda.synchronize()
-    return rows, trajs, run, info
 
 
 def test_the_events_entry_without_events_equals_the_rollout():
@@ -90,7 +49,7 @@ def test_events_equal_the_per_tick_loop_bit_for_bit(mode):
     """Tick 0 solved out, then T = 6 with re-plans (splice) behind tick 2 of stream 0 and the last tick of stream 2, none for stream 1, disturbances on
     ticks 1 and 4: the rollout with events on one batch, the loop of one-wave ticks + bmpc_stream_disturb + bmpc_stream_update(splice) on its twin."""
     import torch
-    from tests.emu import emu_rollout_events as ee
+    from tests.emu import emu_rollout as ee
     mpcs, recs = _small_streams(N, S)
     held = mode == "held"
     kw = dict(max_iter=5, warm_dual=True, accept_capped=True) if held else dict(max_iter=0, warm_dual=True)
@@ -98,7 +57,8 @@ def test_events_equal_the_per_tick_loop_bit_for_bit(mode):
     for _, sb in (a, b):
         sb.tick(max_iter=100, warm_dual=True)
     records, tick_of, dist = _records(mpcs, recs, a[1].entries), np.array([2, -1, T - 1]), ee.disturbances(T, 3, on=(1, 4))
-    rows, trajs, run, info = _loop_with_events(a[1], T, records, tick_of, dist, **kw)
+    loop = contract_loop(a[1], T, records, tick_of, dist, **kw)
+    rows, trajs, run, info = loop["hist"], loop["traj_hist"], loop["ticks_run"], loop["replan_info"]
     out = b[1].rollout(T, want_traj=True, replan=records, replan_tick=tick_of, disturb=dist, **kw)
     torch.cuda.synchronize()
     _assert_equal(_snapshot(a[1]), _snapshot(b[1]), mode)
@@ -122,7 +82,7 @@ def test_events_on_the_gpu_equal_the_cpu_build_of_the_same_text():
     """From the cold start, converged with the dual state, the same events: the device arrays against tests/emu's g++ build of the kernel text, 1e-11
     with the two exclusions (iterations, kkt) of test_rollout_on_the_gpu_equals_the_cpu_build_of_the_same_text."""
     import torch
-    from tests.emu import emu, emu_rollout as er, emu_rollout_events as ee
+    from tests.emu import emu, emu_rollout as ee
     mpcs, recs = _small_streams(N, S)
     g = _batch(N, S, mpcs, recs)
     records, tick_of, dist = _records(mpcs, recs, g[1].entries), np.array([2, -1, T - 1]), ee.disturbances(T, 3, on=(1, 4))
@@ -131,7 +91,7 @@ def test_events_on_the_gpu_equal_the_cpu_build_of_the_same_text():
     got, hist, th = _snapshot(g[1]), out["hist"].cpu().numpy(), out["traj_hist"].cpu().numpy()
     _, A, Tab, R = ee.small_batch(N, S)
     assert np.array_equal(R, records)
-    r = ee.rollout_events(N, S, 0.1, Tab, A, T, replan=R, replan_tick=tick_of, disturb=dist, opts=emu.opts_for(N, start_rollout=0))
+    r = ee.rollout(N, S, 0.1, Tab, A, T, entry=1, replan=R, replan_tick=tick_of, disturb=dist, opts=emu.opts_for(N, start_rollout=0))
     assert out["ticks_run"].tolist() == r["ticks_run"].tolist() == [T] * 3 and out["replan_info"].tolist() == r["replan_info"].tolist() == [0, -1, 0]
     pairs = [(got["state"], A["ss"]), (got["robot"], A["rb"]), (got["p"], A["p"]), (got["x0"], A["x0"]), (got["x"], A["x"]), (got["g"], A["g"]), (got["traj"], A["traj"]),
              (np.delete(hist, [45, 47], axis=2), np.delete(r["hist"], [45, 47], axis=2)), (th, r["traj_hist"]), (g[1].path.cpu().numpy(), Tab), (g[1].replan.cpu().numpy(), R)]
@@ -145,7 +105,7 @@ def test_the_stride_serves_events_of_more_streams_than_resident_workgroups():
     """The arrays of the 3-stream batch tiled to B = grid + 2 rows, T = 2, a re-plan behind tick 0 and a disturbance on tick 0: every replica of
     stream i bit-equal to the 3-stream run."""
     import torch
-    from tests.emu import emu_rollout_events as ee
+    from tests.emu import emu_rollout as ee
     Ts = 2
     mpcs, recs = _small_streams(N, S)
     small, big = _batch(N, S, mpcs, recs), _batch(N, S, mpcs, recs)
@@ -178,7 +138,7 @@ def test_the_splice_of_update_device_equals_the_numpy_mirror():
     import torch
     from boundmpc_amd import stream as bstream
     from tests.emu import emu_stream_update as eup
-    from tests.test_stream_rollout_events import _args_of_record
+    from tests.emu.emu_rollout import args_of_record as _args_of_record
     RP, SS = bstream.RP, bstream.SS
     mpcs, recs = _small_streams(N, S)
     g = _batch(N, S, mpcs, recs)

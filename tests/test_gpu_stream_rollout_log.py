@@ -9,23 +9,13 @@ that is asserted on top: the rollout's log lines and the stand-alone kernel comp
 import numpy as np
 import pytest
 
-from tests.test_gpu_stream_rollout import ARRAYS, _assert_equal, _batch, _close, _small_streams, _snapshot
-from tests.test_gpu_stream_rollout_events import _records
+from tests.rollout_contract import assert_equal as _assert_equal, batch as _batch, close as _close, assert_track, contract_loop, cut, push, records as _records, small_streams as _small_streams, snapshot as _snapshot
 
 pytestmark = pytest.mark.gpu
 N, S, T = 2, 2, 6
 ATOL = 1e-11
 TOL = 1e-6
 TICK_OF = np.array([-1, -1, 3])
-INT_SLOTS = [0, 2, 5, 8, 10, 11]
-FLOAT_SLOTS = [1, 3, 4, 6, 7, 9]
-
-
-def _disturbance():
-    """behind tick 2 of stream 1, 0.01 rad in every joint with alternating signs: tests/test_stream_tube.py's"""
-    d = np.zeros((T, 3, 21))
-    d[2, 1, :7] = 0.01 * np.array([1.0, -1.0, 1.0, -1.0, 1.0, -1.0, 1.0])
-    return d
 
 
 def _assert_rows(got, want, what, exact=False):
@@ -39,45 +29,6 @@ def _assert_rows(got, want, what, exact=False):
     return dev
 
 
-def _assert_track(got, want, rtol=1e-12, atol=0.0):
-    assert np.array_equal(got[:, INT_SLOTS], want[:, INT_SLOTS]), (got, want)
-    np.testing.assert_allclose(got[:, FLOAT_SLOTS], want[:, FLOAT_SLOTS], rtol=rtol, atol=atol)
-
-
-def _cut(rows, stages):
-    return np.concatenate([rows[..., :88 * stages], rows[..., -4:]], axis=-1)
-
-
-def _loop_with_log(sb, ticks, records, tick_of, dist, **kw):
-    """The contract's loop on the batch `sb`: per tick one fused tick on one wave per stream, bmpc_stream_log, bmpc_stream_disturb with the rows of the
-    tick, bmpc_stream_update(set_goal, splice) with exactly the flags of the streams whose tick it is raised -- for the streams that still run only.
-    -> whole log rows [ticks][B][88 N + 4], NaN for the ticks a stream did not run"""
-    import torch
-    from boundmpc_amd import stream as bstream
-    SS, B = bstream.SS, sb.B
-    rows = np.full((ticks, B, bstream.log_len(sb.N)), np.nan)
-    sb._replan_buffer(records, None)
-    stopped = np.zeros(B, dtype=bool)
-    for t in range(ticks):
-        stopped |= sb.state[:, SS["ERRCNT"]].cpu().numpy() >= sb.N
-        sb.tick(simulate=True, **kw)
-        log = sb.log()
-        torch.cuda.synchronize()
-        row = log.cpu().numpy()
-        rows[t, ~stopped] = row[~stopped]
-        d = dist[t].copy(); d[stopped] = 0.0
-        sb.disturb(d)
-        due = ~stopped & (tick_of == t)
-        if due.any():
-            flags = sb.replan[:, 0].clone()
-            sb.replan[:, 0] = torch.where(torch.as_tensor(due, device=flags.device), flags, torch.zeros_like(flags))
-            sb.update_device(sb.replan, set_goal=True, splice=True)
-            torch.cuda.synchronize()
-            sb.replan[:, 0] = torch.where(torch.as_tensor(due, device=flags.device), sb.replan[:, 0], flags)
-    torch.cuda.synchronize()
-    return rows
-
-
 def test_rollout_log_equals_the_tick_loop_and_changes_nothing_else():
     """the disturbance behind tick 2 of stream 1, a spliced re-plan behind tick 3 of stream 2: rollout(want_log, track) with rows of N stages and of one
     stage on two batches, the loop with log() on a one-wave twin, a fourth batch through rollout() without the log"""
@@ -88,11 +39,11 @@ def test_rollout_log_equals_the_tick_loop_and_changes_nothing_else():
     a, b, b1, c = (_batch(N, S, mpcs, recs, one_wave=True) for _ in range(4))
     for _, sb in (a, b, b1, c):
         sb.tick(max_iter=100, warm_dual=True)
-    records, d = _records(mpcs, recs, a[1].entries), _disturbance()
+    records, d = _records(mpcs, recs, a[1].entries), push(T, 3)
     kw = dict(max_iter=0, warm_dual=True)
     ev = dict(replan=records, replan_tick=TICK_OF, disturb=d)
     table0 = a[1].path.clone()
-    rows = _loop_with_log(a[1], T, records, TICK_OF, d, **kw)
+    rows = contract_loop(a[1], T, records, TICK_OF, d, want_log=True, **kw)["log_hist"]
     full = b[1].rollout(T, want_traj=True, audit=True, want_tube=True, audit_tol=TOL, want_log=True, log_stages=N, track=True, **ev, **kw)
     one = b1[1].rollout(T, want_traj=True, audit=True, want_tube=True, audit_tol=TOL, want_log=True, log_stages=1, track=True, **ev, **kw)
     plain = c[1].rollout(T, want_traj=True, audit=True, want_tube=True, audit_tol=TOL, **ev, **kw)
@@ -100,8 +51,8 @@ def test_rollout_log_equals_the_tick_loop_and_changes_nothing_else():
     lf, l1 = full["log_hist"].cpu().numpy(), one["log_hist"].cpu().numpy()
     assert lf.shape == (T, 3, 88 * N + 4) and l1.shape == (T, 3, 92) and full["ticks_run"].tolist() == [T] * 3 and full["replan_info"].tolist() == [-1, -1, 0]
     _assert_rows(lf, rows, "log_stages = N against the twin's log()", exact=True)
-    _assert_rows(l1, _cut(rows, 1), "log_stages = 1 against the twin's log()", exact=True)
-    assert np.array_equal(l1, _cut(lf, 1), equal_nan=True)         # the same lines of the same kernel: the prefix and the trailer, bit for bit
+    _assert_rows(l1, cut(rows, N, 1), "log_stages = 1 against the twin's log()", exact=True)
+    assert np.array_equal(l1, cut(lf, N, 1), equal_nan=True)         # the same lines of the same kernel: the prefix and the trailer, bit for bit
     assert (lf[:, [0, 2], -4] == N).all() and (lf[:4, 1, -4] == N).all() and not torch.equal(table0[2], b[1].path[2])
     # nothing else moves: the tick arrays, the tables, the record buffer, every returned tensor
     for got, sb in ((full, b[1]), (one, b1[1])):
@@ -114,8 +65,8 @@ def test_rollout_log_equals_the_tick_loop_and_changes_nothing_else():
     # the record: numpy on the GPU's own rows; it does not depend on the row length
     hist = full["hist"].cpu().numpy()
     trk = full["track"].cpu().numpy()
-    _assert_track(trk, bstream.track_of_rows(lf, hist))
-    _assert_track(one["track"].cpu().numpy(), bstream.track_of_rows(l1, hist))
+    assert_track(trk, bstream.track_of_rows(lf, hist))
+    assert_track(one["track"].cpu().numpy(), bstream.track_of_rows(l1, hist))
     assert np.array_equal(trk, one["track"].cpu().numpy())
     print("stream 1:", bstream.unpack_track(trk[1]), "\nstream 0:", bstream.unpack_track(trk[0]))
     assert trk[0, TRACK["SAMPLES"]] == T and trk[1, TRACK["SAMPLES"]] == (lf[:, 1, -4] >= 1).sum() and trk[1, TRACK["TICK_EP_ORTH"]] >= 3
@@ -136,7 +87,7 @@ def test_rollout_log_equals_the_tick_loop_and_changes_nothing_else():
 
 def test_rollout_log_on_the_gpu_equals_the_cpu_build_of_the_same_text():
     """From the cold start, converged with the dual state, the spliced re-plan behind tick 3 of stream 2 and pushes of every stream behind ticks 1 and 4
-    (tests/emu/emu_rollout_events.py disturbances at a quarter of their scale: with this re-plan schedule the full ones leave stream 0 unconverged at
+    (tests/emu/emu_rollout.py disturbances at a quarter of their scale: with this re-plan schedule the full ones leave stream 0 unconverged at
     the last tick): rows and record against tests/emu's g++ build of the kernel text, 1e-11.
     Why not the 0.01 rad push of the test above: across two BUILDS only converged solves are comparable.  Behind that push stream 1 is outside its tube
     and its solves end unconverged (status 2, KKT 1e-3 .. 0.2); the two builds then stop at iterates 1.9e-6 apart in the robot record of `hist` itself,
@@ -145,7 +96,7 @@ def test_rollout_log_on_the_gpu_equals_the_cpu_build_of_the_same_text():
     asserted."""
     import torch
     from boundmpc_amd import stream as bstream
-    from tests.emu import emu, emu_rollout_events as ee, emu_rollout_log as elg
+    from tests.emu import emu, emu_rollout as ee
     mpcs, recs = _small_streams(N, S)
     g = _batch(N, S, mpcs, recs)
     records, d = _records(mpcs, recs, g[1].entries), ee.disturbances(T, 3, on=(1, 4), scale=(5e-4, 1.25e-3, 2.5e-3))
@@ -153,16 +104,16 @@ def test_rollout_log_on_the_gpu_equals_the_cpu_build_of_the_same_text():
     torch.cuda.synchronize()
     _, A, Tab, R = ee.small_batch(N, S)
     assert np.array_equal(R, records)
-    r = elg.rollout_log(N, S, 0.1, Tab, A, T, replan=R, replan_tick=TICK_OF, disturb=d, opts=emu.opts_for(N, start_rollout=0), log_stages=N)
+    r = ee.rollout(N, S, 0.1, Tab, A, T, entry=3, replan=R, replan_tick=TICK_OF, disturb=d, opts=emu.opts_for(N, start_rollout=0), log_stages=N)
     assert out["ticks_run"].tolist() == r["ticks_run"].tolist() == [T] * 3 and out["replan_info"].tolist() == r["replan_info"].tolist() == [-1, -1, 0]
     assert (out["hist"].cpu().numpy()[:, :, bstream.ROLL["STATUS"]] == 0).all() and (r["hist"][:, :, bstream.ROLL["STATUS"]] == 0).all()
     log = out["log_hist"].cpu().numpy()
     _assert_rows(log, r["log_hist"], "GPU against the g++ build")
     # the record: against the g++ build's, and against the specification on the g++ build's rows
     trk = out["track"].cpu().numpy()
-    _assert_track(trk, r["track"], rtol=ATOL, atol=ATOL)
-    _assert_track(trk, bstream.track_of_rows(_cut(r["log_hist"], 1), r["hist"]), rtol=ATOL, atol=ATOL)
-    _assert_track(trk, bstream.track_of_rows(log, out["hist"].cpu().numpy()))
+    assert_track(trk, r["track"], rtol=ATOL, atol=ATOL)
+    assert_track(trk, bstream.track_of_rows(cut(r["log_hist"], N, 1), r["hist"]), rtol=ATOL, atol=ATOL)
+    assert_track(trk, bstream.track_of_rows(log, out["hist"].cpu().numpy()))
     _close(g)
 
 
@@ -188,7 +139,7 @@ def test_stopped_streams_in_the_log():
     for i in range(3):
         assert np.isfinite(log[:run[i], i]).all() and np.isnan(log[run[i]:, i]).all() and trk[i, TRACK["SAMPLES"]] == run[i]
     assert (trk[2, [1, 4, 7]] == -np.inf).all() and (trk[2, [2, 5, 8]] == -1).all() and (trk[2, [0, 3, 6, 9, 10, 11]] == 0).all()
-    _assert_track(trk, bstream.track_of_rows(log, out["hist"].cpu().numpy()))
+    assert_track(trk, bstream.track_of_rows(log, out["hist"].cpu().numpy()))
     _close(a, b)
     # exhausted mid-run
     c = _batch(N, S, mpcs, recs, one_wave=True)
@@ -202,7 +153,7 @@ def test_stopped_streams_in_the_log():
     assert (log[1, :, -4] == 0).all() and (log[1, :, -3] == N).all() and (log[1, :, -2:] == 0).all() and np.isnan(log[1, :, :-4]).all()      # ran, and no sample
     assert (log[0, :, -4] == 1).all() and np.isfinite(log[0, :, :88]).all() and np.isnan(log[0, :, 88:-4]).all() and np.isnan(log[2:]).all()
     assert (trk[:, TRACK["SAMPLES"]] == 1).all() and (trk[:, [2, 5, 8]] == 0).all()
-    _assert_track(trk, bstream.track_of_rows(log, hist))
+    assert_track(trk, bstream.track_of_rows(log, hist))
     assert bstream.unpack_log(log[1, 0], N, stages=N) == (None, None) and bstream.unpack_log(log[3, 0], N, stages=N) == (None, None)
     _close(c)
 

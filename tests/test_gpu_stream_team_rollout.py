@@ -10,7 +10,7 @@ accepted under the real-time rule -- five orders below the bounds used here."""
 import numpy as np
 import pytest
 
-from tests.test_gpu_stream_rollout import ARRAYS, _assert_equal, _batch, _close, _per_tick, _small_streams, _snapshot
+from tests.rollout_contract import ARRAYS, assert_equal as _assert_equal, assert_track, cut, push, batch as _batch, close as _close, contract_loop, per_tick as _per_tick, records as _records, small_streams as _small_streams, snapshot as _snapshot
 
 pytestmark = pytest.mark.gpu
 N, S = 10, 4
@@ -97,47 +97,6 @@ def test_the_stride_serves_more_streams_than_resident_teams():
     _close(small, big)
 
 
-def _records(mpcs, recs, entries):
-    from boundmpc_amd import stream as bstream
-    from tests.emu import emu_rollout_events as ee
-    return np.stack([bstream.replan_record(S, entries, *ee.leg_back(m, r, np.zeros((entries, 48)), S)) for m, r in zip(mpcs, recs)])
-
-
-def _team_loop(sb, ticks, records, tick_of, dist, stages, **kw):
-    """The contract's loop on the batch `sb` (ticks on teams): per tick tick(), tube(), log(), disturb() with the rows of the tick, update_device(splice=True)
-    with exactly the flags of the streams whose tick it is raised -- for the streams that still run only.
-    -> (hist rows, tube rows, log rows cut to `stages`), NaN for the ticks a stream did not run"""
-    import torch
-    from boundmpc_amd import stream as bstream
-    SS, B = bstream.SS, sb.B
-    rows, tubes, logs = np.full((ticks, B, 52), np.nan), np.full((ticks, B, 16), np.nan), np.full((ticks, B, 88 * stages + 4), np.nan)
-    sb._replan_buffer(records, None)
-    stopped = np.zeros(B, dtype=bool)
-    for t in range(ticks):
-        stopped |= sb.state[:, SS["ERRCNT"]].cpu().numpy() >= sb.N
-        sb.tick(simulate=True, **kw)
-        tube, log = sb.tube(), sb.log()
-        torch.cuda.synchronize()
-        s = _snapshot(sb)
-        row = np.concatenate([s["robot"], s["state"][:, [SS["PHI"], SS["ERRCNT"]]], s["iters"][:, None].astype(float), s["status"][:, None].astype(float), s["kkt"][:, None],
-                              s["traj"][:, -4:]], axis=1)
-        live = ~stopped
-        lg = log.cpu().numpy()
-        rows[t, live], tubes[t, live] = row[live], tube.cpu().numpy()[live]
-        logs[t, live] = np.concatenate([lg[..., :88 * stages], lg[..., -4:]], axis=-1)[live]
-        d = dist[t].copy(); d[stopped] = 0.0
-        sb.disturb(d)
-        due = live & (tick_of == t)
-        if due.any():
-            flags = sb.replan[:, 0].clone()
-            sb.replan[:, 0] = torch.where(torch.as_tensor(due, device=flags.device), flags, torch.zeros_like(flags))
-            sb.update_device(sb.replan, set_goal=True, splice=True)
-            torch.cuda.synchronize()
-            sb.replan[:, 0] = torch.where(torch.as_tensor(due, device=flags.device), sb.replan[:, 0], flags)
-    torch.cuda.synchronize()
-    return rows, tubes, logs
-
-
 def test_the_full_kernel_equals_the_team_loop_and_the_plain_kernel():
     """B = 3, T = 6, a disturbance behind tick 2 of stream 1, a re-plan with splice behind tick 3 of stream 2, audit, tube rows, log rows of two stages
     and the tracking record, waves = 4: the arrays, hist, tube_hist and log_hist of the loop {team tick(), tube(), log(), disturb(),
@@ -148,14 +107,15 @@ def test_the_full_kernel_equals_the_team_loop_and_the_plain_kernel():
     from tests.emu import emu_stream_tube as et
     T, B, TOL = 6, 3, 1e-6
     tick_of = np.array([-1, -1, 3])
-    d = np.zeros((T, B, 21)); d[2, 1, :7] = 0.01 * np.array([1.0, -1.0, 1.0, -1.0, 1.0, -1.0, 1.0])
+    d = push(T, B)
     mpcs, recs = _small_streams(N, S, n=B)
     a, b, c, e = (_team_batch(mpcs, recs) for _ in range(4))
     for _, sb in (a, b, c, e):
         sb.tick(max_iter=100, warm_dual=True)
     records = _records(mpcs, recs, a[1].entries)
     table0 = a[1].path.clone()
-    rows, tubes, logs = _team_loop(a[1], T, records, tick_of, d, 2, **CONV_KW)
+    loop = contract_loop(a[1], T, records, tick_of, d, want_tube=True, want_log=True, **CONV_KW)      # (the twin ticks on teams)
+    rows, tubes, logs = loop["hist"], loop["tube_hist"], cut(loop["log_hist"], N, 2)
     full = b[1].rollout(T, replan=records, replan_tick=tick_of, disturb=d, audit=True, want_tube=True, audit_tol=TOL, want_log=True, log_stages=2, track=True, waves=NW, **CONV_KW)
     torch.cuda.synchronize()
     _assert_equal(_snapshot(a[1]), _snapshot(b[1]), "team loop against the full team rollout")
@@ -165,9 +125,7 @@ def test_the_full_kernel_equals_the_team_loop_and_the_plain_kernel():
     assert np.array_equal(hist, rows, equal_nan=True) and np.array_equal(th, tubes, equal_nan=True) and np.array_equal(lh, logs, equal_nan=True)
     np.testing.assert_allclose(full["audit"].cpu().numpy(), et.audit_of_batch(th, TOL), rtol=0.0, atol=1e-11)
     trk, want = full["track"].cpu().numpy(), bstream.track_of_rows(lh, hist)
-    ints, floats = [0, 2, 5, 8, 10, 11], [1, 3, 4, 6, 7, 9]
-    assert np.array_equal(trk[:, ints], want[:, ints])
-    np.testing.assert_allclose(trk[:, floats], want[:, floats], rtol=0.0, atol=1e-11)
+    assert_track(trk, want, rtol=0.0, atol=1e-11)
     assert (full["audit"].cpu().numpy()[:, bstream.AUDIT["SAMPLES"]] == T).all() and (trk[[0, 2], bstream.TRACK["SAMPLES"]] == T).all()
     # no event raised: the fully-featured kernel (audit and log arrays given) leaves what the plain team rollout leaves
     plain = c[1].rollout(T, waves=NW, **CONV_KW)

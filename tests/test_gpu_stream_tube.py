@@ -5,7 +5,7 @@ argument errors.  (2, 2), B = 3 streams; the rows of the recorded experiments ne
 import numpy as np
 import pytest
 
-from tests.test_gpu_stream_rollout import _assert_equal, _batch, _close, _small_streams, _snapshot
+from tests.rollout_contract import assert_equal as _assert_equal, batch as _batch, close as _close, push, small_streams as _small_streams, snapshot as _snapshot
 
 pytestmark = pytest.mark.gpu
 N, S = 2, 2
@@ -16,13 +16,6 @@ TOL = 1e-6
 def _raw_tube(solver, B, p, state, out):
     from boundmpc_amd.solver import _ptr
     return solver._lib.bmpc_stream_tube(solver._h, B, _ptr(p), _ptr(state), _ptr(out), None)
-
-
-def _disturbance(T):
-    """behind tick 2 of stream 1, 0.01 rad in every joint with alternating signs: tests/test_stream_tube.py's, 5 mm outside the position tube"""
-    d = np.zeros((T, 3, 21))
-    d[2, 1, :7] = 0.01 * np.array([1.0, -1.0, 1.0, -1.0, 1.0, -1.0, 1.0])
-    return d
 
 
 def test_service_launch_equals_the_cpu_build():
@@ -65,7 +58,7 @@ def test_rollout_audit_equals_the_tick_loop_and_changes_nothing_else():
     a, b, c = (_batch(N, S, mpcs, recs, one_wave=True) for _ in range(3))
     for _, sb in (a, b, c):
         sb.tick(max_iter=100, warm_dual=True)
-    d = _disturbance(T)
+    d = push(T, 3)
     kw = dict(max_iter=0, warm_dual=True)
     # the loop on the twin
     sb = a[1]

@@ -1,6 +1,6 @@
 """The rollout -- many closed-loop ticks of a stream in one launch -- as device code (csrc/bmpc_rollout_kernel.inl compiled for the CPU, tests/emu)
 against its exact checker: a loop of the fused tick's own kernel text (csrc/bmpc_tick_kernel.inl compiled for the CPU, emu.stream_tick), one tick at
-a time (tests/emu/emu_rollout.py per_tick_loop; tests/test_stream_tick.py holds that text to the separate pack, solve and post).  Bit for bit on every tick array, `hist` and `traj_hist` against the per-tick values,
+a time (tests/emu/emu_rollout.py contract_loop; tests/test_stream_tick.py holds that text to the separate pack, solve and post).  Bit for bit on every tick array, `hist` and `traj_hist` against the per-tick values,
 and the stop rules: a lost plan, the goal.  Every case asserts that each stream ran at least one tick."""
 import numpy as np
 import pytest
@@ -12,10 +12,16 @@ SS, ROLL = bstream.SS, bstream.ROLL
 H = 0.1
 
 
+def _loop(N, S, T, A, ticks, **kw):
+    """`ticks` fused ticks, one after the other -> (rows [ticks][52] with NaN rows for skipped ticks, traj rows, snapshots of the arrays behind every tick)"""
+    loop = er.contract_loop(N, S, H, T, A, ticks, **kw)
+    return loop["hist"], loop["traj_hist"], loop["snaps"]
+
+
 def _compare(N, S, T, A0, ticks, what, goal_tol=0.0, **kw):
     """rollout(ticks) on a copy of the arrays A0 against `ticks` single ticks on another; returns (rollout result, its arrays, per-tick rows, snapshots)"""
     A, B = er.copy_arrays(A0), er.copy_arrays(A0)
-    rows, trajs, snaps = er.per_tick_loop(N, S, H, T, A, ticks, **kw)
+    rows, trajs, snaps = _loop(N, S, T, A, ticks, **kw)
     r = er.rollout(N, S, H, T, B, ticks, goal_tol=goal_tol, **kw)
     assert r["ticks_run"] >= 1, what
     if goal_tol == 0.0:
@@ -98,7 +104,7 @@ def test_a_stream_stops_at_its_goal():
     _, rec, T, ss = er.small_stream(N, S)
     A0 = er.fresh_arrays(N, S, ss, rec)
     A = er.copy_arrays(A0)
-    rows, trajs, snaps = er.per_tick_loop(N, S, H, T, A, ticks, warm_dual=True)
+    rows, trajs, snaps = _loop(N, S, T, A, ticks, warm_dual=True)
     gap = A0["ss"][SS["PHIMAX"]] - rows[:, ROLL["PHI"]]
     assert (np.diff(gap) < 0).all()
     goal_tol = float(gap[1])                                               # reached behind tick 1, not behind tick 0
@@ -135,3 +141,34 @@ def test_history_slots_and_unpack():
     assert d["q"].tolist() == list(range(7)) and d["p"].tolist() == list(range(21, 27)) and d["x_phi_d"].tolist() == [33, 34, 35] and d["jerk"].tolist() == list(range(36, 43))
     assert (d["phi"], d["error_count"], d["iters"], d["status"], d["kkt"], d["n_valid"], d["g_viol"]) == (43.0, 44, 45, 46, 47.0, 48, 51.0)
     assert bstream.unpack_rollout(np.full(52, np.nan)) is None
+
+
+def test_the_entry_rule_of_the_library():
+    """The rule of csrc/bmpc_args.h bmpc_rollout_level -- which the C ABI's four entries and the CPU build both ask -- walked through the CPU build's entry
+    at (2, 2), B = 1, one tick: entry x arrays given x fault -> the level that runs, or a refusal ("R").  An entry is handed only what it has an argument
+    for.  The table is written out from the rule: entry 0 runs level 0 whatever else; entry 1 runs level 1; entry 2 runs 2 with an audit array, else 1, and
+    refuses a bad audit_tol either way; entry 3 runs 3 with a log array (and only then looks at log_stages), else it is entry 2; every entry above 0
+    refuses a record buffer without its ticks."""
+    R = "R"
+    table = {  # arrays: (good, audit_tol = -1, log_stages = 0, replan without replan_tick)
+        0: {"none": (0, 0, 0, 0), "audit": (0, 0, 0, 0), "log": (0, 0, 0, 0)},
+        1: {"none": (1, 1, 1, R), "audit": (1, 1, 1, R), "log": (1, 1, 1, R)},
+        2: {"none": (1, R, 1, R), "audit": (2, R, 2, R), "log": (1, R, 1, R)},
+        3: {"none": (1, R, 1, R), "audit": (2, R, 2, R), "log": (3, R, R, R)},
+    }
+    N, S = 2, 2
+    _, A0, Tab, recs = er.small_batch(N, S, B=1)
+    for entry, rows in table.items():
+        for arrays, want in rows.items():
+            for fault, level in zip(("good", "audit_tol", "log_stages", "replan"), want):
+                kw = dict(audit=arrays == "audit" and entry >= 2, want_tube=arrays == "audit" and entry >= 2, want_log=arrays == "log" and entry >= 3,
+                          track=arrays == "log" and entry >= 3, audit_tol=-1.0 if fault == "audit_tol" else 1e-6, log_stages=0 if fault == "log_stages" else 1,
+                          replan=recs.copy() if fault == "replan" and entry >= 1 else None)
+                A = er.copy_arrays(A0)
+                if level == R:
+                    assert er.rollout(N, S, H, Tab.copy(), A, 1, entry=entry, want_rc=True, **kw) == 1, (entry, arrays, fault)
+                    for k in A:
+                        assert np.array_equal(A[k], A0[k], equal_nan=True), (entry, arrays, fault, k)
+                else:
+                    r = er.rollout(N, S, H, Tab.copy(), A, 1, entry=entry, **kw)
+                    assert r["ran"] == level and r["ticks_run"].tolist() == [1], (entry, arrays, fault)

@@ -1,5 +1,5 @@
 """Events inside a rollout -- plant disturbances and one scheduled re-plan per stream with the measured state spliced in on the device -- as device code
-compiled for the CPU (csrc/bmpc_rollout_kernel.inl with EV, csrc/bmpc_stream_events.inl; tests/emu/bmpc_emu_rollout_events.cpp): without events the
+compiled for the CPU (csrc/bmpc_rollout_kernel.inl with EV, csrc/bmpc_stream_events.inl; tests/emu/bmpc_emu_rollout.cpp, bmpc_emu_stream_update.cpp): without events the
 rollout's own bits; with events the bits of the per-tick loop {fused tick's text, disturb text, splice + update text at the scheduled tick}; the splice
 and the disturbance against their numpy mirrors (stream.splice_record, stream.disturb_robot) and NodeLoop.update; the rescue of a stream whose plan
 ran out, the second leg behind a reached goal, and the argument errors.  B = 3 streams of emu_rollout.small_stream, T = 6."""
@@ -9,27 +9,27 @@ import pytest
 from boundmpc_amd import stream as bstream, workload
 from boundmpc_amd.bound_mpc import integrate_joint
 from boundmpc_amd.robot_model import RobotModel
-from tests.emu import emu_rollout as er, emu_rollout_events as ee, emu_stream_update as eup
+from tests.emu import emu_rollout as er, emu_stream_update as eup
 
 SS, RB, RP, RV, ROLL = bstream.SS, bstream.RB, bstream.RP, bstream.RV, bstream.ROLL
-H, T = ee.H, 6
+H, T = er.H, 6
 ATOL = 1e-11                     # tests/test_stream_update.py's; the header words a and jerk hold it too (measured: profiles/stream_splice.txt)
 
 
-def _copy(A):
-    return {k: v.copy() for k, v in A.items()}
+_copy = er.copy_arrays
 
 
 def _against_the_loop(N, S, A0, Tab, recs, ticks, replan_tick, disturb, what, update_flags=3, goal_tol=0.0, **kw):
     """the events text on copies of (A0, Tab, recs) against the per-tick loop, stream by stream, on other copies: every tick array, the path table, the
     record buffer, hist, traj_hist, ticks_run and replan_info, bit for bit.  -> (result, arrays, tables, records) of the events text"""
     A, Tb, R = _copy(A0), Tab.copy(), recs.copy()
-    r = ee.rollout_events(N, S, H, Tb, A, ticks, replan=R, replan_tick=replan_tick, update_flags=update_flags, disturb=disturb, goal_tol=goal_tol, **kw)
+    r = er.rollout(N, S, H, Tb, A, ticks, entry=1, replan=R, replan_tick=replan_tick, update_flags=update_flags, disturb=disturb, goal_tol=goal_tol, **kw)
     for b in range(Tab.shape[0]):
-        Ab, Tl, Rl = ee.unstack(A0, b), Tab[b].copy(), recs[b].copy()
-        rows, trajs, run, info = ee.per_tick_loop_events(N, S, H, Tl, Ab, ticks, replan=Rl, replan_tick=int(replan_tick[b]), update_flags=update_flags,
-                                                        disturb=None if disturb is None else disturb[:, b], goal_tol=goal_tol, **kw)
-        er.assert_arrays_equal(Ab, ee.unstack(A, b), f"{what}, stream {b}")
+        Ab, Tl, Rl = er.unstack(A0, b), Tab[b].copy(), recs[b].copy()
+        loop = er.contract_loop(N, S, H, Tl, Ab, ticks, replan=Rl, replan_tick=int(replan_tick[b]), update_flags=update_flags,
+                                disturb=None if disturb is None else disturb[:, b], goal_tol=goal_tol, **kw)
+        rows, trajs, run, info = loop["hist"], loop["traj_hist"], loop["ticks_run"], loop["replan_info"]
+        er.assert_arrays_equal(Ab, er.unstack(A, b), f"{what}, stream {b}")
         assert np.array_equal(Tl, Tb[b], equal_nan=True) and np.array_equal(Rl, R[b], equal_nan=True), f"{what}, stream {b}: table / record"
         assert np.array_equal(rows, r["hist"][:, b], equal_nan=True) and np.array_equal(trajs, r["traj_hist"][:, b], equal_nan=True), f"{what}, stream {b}: history"
         assert (run, info) == (r["ticks_run"][b], r["replan_info"][b]), f"{what}, stream {b}: ticks_run / replan_info"
@@ -39,17 +39,17 @@ def _against_the_loop(N, S, A0, Tab, recs, ticks, replan_tick, disturb, what, up
 @pytest.mark.parametrize("N,S", [(2, 2), (1, 2)])
 def test_without_events_the_events_text_equals_the_rollout_text(N, S):
     """every event pointer NULL: all tick arrays, hist, traj_hist and ticks_run of the rollout's own CPU build, bit for bit; the table stays"""
-    _, A0, Tab, _ = ee.small_batch(N, S)
+    _, A0, Tab, _ = er.small_batch(N, S)
     A, Tb = _copy(A0), Tab.copy()
-    r = ee.rollout_events(N, S, H, Tb, A, T)
+    r = er.rollout(N, S, H, Tb, A, T, entry=1)
     plain = _copy(A0)
-    r0 = ee.rollout_events(N, S, H, Tab.copy(), plain, T, events=False)      # (the instantiation without the event code, B = 3 on one workgroup)
+    r0 = er.rollout(N, S, H, Tab.copy(), plain, T, entry=1, level=0)      # (the instantiation without the event code, B = 3 on one workgroup)
     assert np.array_equal(Tb, Tab) and r["replan_info"].tolist() == [-1] * 3
     for b in range(3):
-        Ab = ee.unstack(A0, b)
+        Ab = er.unstack(A0, b)
         want = er.rollout(N, S, H, Tab[b], Ab, T, warm_dual=True)
-        er.assert_arrays_equal(Ab, ee.unstack(A, b), f"stream {b}")
-        er.assert_arrays_equal(Ab, ee.unstack(plain, b), f"stream {b}, EV = false")
+        er.assert_arrays_equal(Ab, er.unstack(A, b), f"stream {b}")
+        er.assert_arrays_equal(Ab, er.unstack(plain, b), f"stream {b}, EV = false")
         assert np.array_equal(r["hist"][:, b], want["hist"]) and np.array_equal(r["traj_hist"][:, b], want["traj_hist"]) and r["ticks_run"][b] == want["ticks_run"] == T
         assert np.array_equal(r0["hist"][:, b], want["hist"]) and r0["ticks_run"][b] == T
 
@@ -59,9 +59,9 @@ def test_events_equal_the_per_tick_loop_bit_for_bit(N, S):
     """Re-plans (splice, set_goal) behind tick 2 of stream 0 and behind the last tick of stream 2, none for stream 1 (replan_tick -1); disturbances on
     ticks 1 and 4.  The new path -- a leg back over the stream's own via points from the spliced pose -- is a good input: every tick behind the re-plan
     converges and its plan is applied."""
-    _, A0, Tab, recs = ee.small_batch(N, S)
+    _, A0, Tab, recs = er.small_batch(N, S)
     tick_of = np.array([2, -1, T - 1])
-    dist = ee.disturbances(T, 3, on=(1, 4))
+    dist = er.disturbances(T, 3, on=(1, 4))
     r, A, Tb, R = _against_the_loop(N, S, A0, Tab, recs, T, tick_of, dist, f"N {N} S {S}")
     assert r["ticks_run"].tolist() == [T] * 3 and r["replan_info"].tolist() == [0, -1, 0]
     assert R[:, RP["FLAG"]].tolist() == [0.0, 1.0, 0.0] and np.array_equal(R[1], recs[1]) and np.array_equal(Tb[1], Tab[1])
@@ -76,12 +76,12 @@ def test_events_equal_the_per_tick_loop_bit_for_bit(N, S):
     row = r["hist"][2, 0]
     assert np.array_equal(R[0, RP["P0"]:RP["P0"] + 3], row[RB["P"]:RB["P"] + 3]) and np.array_equal(R[0, RP["V"]:RP["V"] + 3], row[RB["V"]:RB["V"] + 3])
     # hist shows the UNDISTURBED plant behind a tick: without the disturbances ticks 0 and 1 have the same rows, tick 2 differs
-    r1 = ee.rollout_events(N, S, H, Tab.copy(), _copy(A0), T, replan=recs.copy(), replan_tick=tick_of)
+    r1 = er.rollout(N, S, H, Tab.copy(), _copy(A0), T, entry=1, replan=recs.copy(), replan_tick=tick_of)
     assert np.array_equal(r1["hist"][:2], r["hist"][:2]) and not np.array_equal(r1["hist"][2], r["hist"][2])
     # in any lane order of the solver's phases
     for order in (1, 2):
         C, Tc, Rc = _copy(A0), Tab.copy(), recs.copy()
-        rc = ee.rollout_events(N, S, H, Tc, C, T, replan=Rc, replan_tick=tick_of, disturb=dist, lane_order=order)
+        rc = er.rollout(N, S, H, Tc, C, T, entry=1, replan=Rc, replan_tick=tick_of, disturb=dist, lane_order=order)
         assert np.array_equal(rc["hist"], r["hist"]) and np.array_equal(C["ss"], A["ss"]) and np.array_equal(Tc, Tb)
 
 
@@ -92,18 +92,6 @@ def _random_robot(rng, which):
     dq, ddq, u = rng.normal(size=7) * 0.3, rng.normal(size=7) * 0.8, rng.normal(size=7) * 3.0
     p, J, _ = model.forward_kinematics(q, dq)
     return bstream.robot_record(q, dq, ddq, p, J @ dq, np.array([3.0, 0.0, 0.0]), u)
-
-
-def _args_of_record(rec, S):
-    """the arguments of apply_update after (ss, N, S) that a (spliced) record stands for"""
-    n, nb = int(rec[RP["N"]]), int(rec[RP["NB"]])
-    via = rec[RP["HEAD"]:RP["HEAD"] + n * RV["LEN"]].reshape(n, RV["LEN"])
-    col = lambda k, w: [via[j, RV[k]:RV[k] + w].copy() for j in range(n)]
-    sc = lambda k: [float(via[j, RV[k]]) for j in range(n)]
-    six = lambda k: np.concatenate([rec[RP[k]:RP[k] + 3], np.zeros(3)])
-    return [col("P", 3), [via[j, RV["R"]:RV["R"] + 9].reshape(3, 3).copy() for j in range(n)], [col("PLO", 2), col("PUP", 2)], [col("RLO", 2), col("RUP", 2)],
-            col("BP1", 3)[:nb], col("BR1", 3)[:nb], sc("S"), sc("EPMIN"), sc("ERMIN"), sc("EPMAX"), sc("ERMAX"), six("P0"), six("V"), six("A"), six("JERK"), six("P0"),
-            rec[RP["W"]:RP["W"] + 15].copy()]
 
 
 _SPLICE_WORST = {}
@@ -124,7 +112,7 @@ def test_splice_equals_the_numpy_mirror(case):
     rb[RB["V"] + 2] = -abs(rb[RB["V"] + 2]) - 0.01 if v2_neg else abs(rb[RB["V"] + 2]) + 0.01
     path["pos_points"][1][1] = (-1.0 if y_opposed else 1.0) * np.sign(rb[RB["P"] + 1]) * (abs(path["pos_points"][1][1]) + 0.05)
     rec0 = bstream.replan_record(S, entries, *eup.args_of(path))
-    got, want = ee.stream_splice(H, S, rec0, rb, poor_bounds=poor), bstream.splice_record(rec0, rb, H, S, poor_bounds=poor)
+    got, want = eup.stream_splice(H, S, rec0, rb, poor_bounds=poor), bstream.splice_record(rec0, rb, H, S, poor_bounds=poor)
     # what the splice writes, and nothing else
     words = np.r_[RP["P0"]:RP["P0"] + 12, RP["HEAD"] + RV["P"]:RP["HEAD"] + RV["R"] + 9]
     rest = np.setdiff1d(np.arange(rec0.shape[0]), words)
@@ -140,10 +128,10 @@ def test_splice_equals_the_numpy_mirror(case):
     assert abs(got[RP["HEAD"] + RV["P"] + 2] - z) < 1e-15 and np.array_equal(got[RP["P0"]:RP["P0"] + 3], rb[RB["P"]:RB["P"] + 3])
     # ... and through the update: table and state against apply_update on the mirror's numbers
     ss0 = eup.random_state(rng, N, has_prev=True)
-    info, rec1, Tn, ss, rb1 = ee.stream_update_flags(N, S, H, rec0, np.random.default_rng(9).normal(size=(entries, bstream.PT["LEN"])), ss0, rb, 3 | (4 if poor else 0))
+    info, rec1, Tn, ss, rb1 = eup.stream_update_flags(N, S, H, rec0, np.random.default_rng(9).normal(size=(entries, bstream.PT["LEN"])), ss0, rb, 3 | (4 if poor else 0))
     assert info == 0 and rec1[RP["FLAG"]] == 0.0 and np.array_equal(rec1[1:], got[1:])      # the spliced words stay, only the flag is cleared
     ss_ref = ss0.copy()
-    T_ref, M = bstream.apply_update(ss_ref, N, S, *_args_of_record(want, S), entries=entries)
+    T_ref, M = bstream.apply_update(ss_ref, N, S, *er.args_of_record(want, S), entries=entries)
     eup.assert_close(Tn, ss, T_ref, ss_ref, ATOL, f"case {case}: update behind the splice")
     assert rb1[RB["XPHID"]] == ss[SS["PHIMAX"]] and np.array_equal(np.delete(rb1, np.r_[RB["XPHID"]:RB["XPHID"] + 3]), np.delete(rb, np.r_[RB["XPHID"]:RB["XPHID"] + 3]))
 
@@ -154,36 +142,36 @@ def test_splice_leaves_a_lowered_flag_and_an_invalid_record_alone():
     rec0, rb = bstream.replan_record(S, entries, *eup.args_of(eup.random_path(rng, 4))), _random_robot(rng, 0)
     Tg, ss0 = rng.normal(size=(entries, bstream.PT["LEN"])), eup.random_state(rng, N)
     low = rec0.copy(); low[RP["FLAG"]] = 0.0
-    assert np.array_equal(ee.stream_splice(H, S, low, rb), low) and np.array_equal(bstream.splice_record(low, rb, H, S), low)
-    info, rec1, T1, ss1, rb1 = ee.stream_update_flags(N, S, H, low, Tg, ss0, rb, 7)
+    assert np.array_equal(eup.stream_splice(H, S, low, rb), low) and np.array_equal(bstream.splice_record(low, rb, H, S), low)
+    info, rec1, T1, ss1, rb1 = eup.stream_update_flags(N, S, H, low, Tg, ss0, rb, 7)
     assert info == 0 and np.array_equal(rec1, low) and np.array_equal(T1, Tg) and np.array_equal(ss1, ss0) and np.array_equal(rb1, rb)
     for n, nb in ((1, 1), (6, 2), (4, 0), (4, 5), (np.nan, 1), (4, np.inf)):      # n_max = 5
         bad = rec0.copy(); bad[RP["N"]], bad[RP["NB"]] = n, nb
-        assert np.array_equal(ee.stream_splice(H, S, bad, rb, poor_bounds=True), bad, equal_nan=True) and np.array_equal(bstream.splice_record(bad, rb, H, S, True), bad, equal_nan=True)
-        info, rec1, T1, ss1, rb1 = ee.stream_update_flags(N, S, H, bad, Tg, ss0, rb, 3)
+        assert np.array_equal(eup.stream_splice(H, S, bad, rb, poor_bounds=True), bad, equal_nan=True) and np.array_equal(bstream.splice_record(bad, rb, H, S, True), bad, equal_nan=True)
+        info, rec1, T1, ss1, rb1 = eup.stream_update_flags(N, S, H, bad, Tg, ss0, rb, 3)
         assert info == 1 and rec1[RP["FLAG"]] == 0.0 and np.array_equal(rec1[1:], bad[1:], equal_nan=True) and np.array_equal(T1, Tg) and np.array_equal(ss1, ss0)
     # the flags bmpc_stream_update refuses: an unknown bit, poor bounds without the splice, the splice without robot records
     for flags, robot in ((8, rb), (4, rb), (5, rb), (2, None), (3, None)):
-        assert ee.stream_update_flags(N, S, H, rec0, Tg, ss0, robot, flags)[0] == -2, flags
+        assert eup.stream_update_flags(N, S, H, rec0, Tg, ss0, robot, flags)[0] == -2, flags
     # flags 0 and 1 are the update text alone
     for flags in (0, 1):
-        a, b = ee.stream_update_flags(N, S, H, rec0, Tg, ss0, rb, flags), eup.stream_update(N, S, rec0, Tg, ss0, rb, set_goal=bool(flags))
+        a, b = eup.stream_update_flags(N, S, H, rec0, Tg, ss0, rb, flags), eup.stream_update(N, S, rec0, Tg, ss0, rb, set_goal=bool(flags))
         assert a[0] == b[0] == 0 and all(np.array_equal(x, y) for x, y in zip(a[1:], b[1:]))
 
 
 def test_disturbance_equals_the_numpy_mirror():
     rng = np.random.default_rng(31)
     rb = _random_robot(rng, 1)
-    assert np.array_equal(ee.stream_disturb(rb, np.zeros(21)), rb) and np.array_equal(bstream.disturb_robot(rb, np.zeros(21)), rb)
-    assert np.array_equal(ee.stream_disturb(rb, np.full(21, np.nan)), rb) and np.array_equal(ee.stream_disturb(rb, -np.zeros(21)), rb)
+    assert np.array_equal(eup.stream_disturb(rb, np.zeros(21)), rb) and np.array_equal(bstream.disturb_robot(rb, np.zeros(21)), rb)
+    assert np.array_equal(eup.stream_disturb(rb, np.full(21, np.nan)), rb) and np.array_equal(eup.stream_disturb(rb, -np.zeros(21)), rb)
     d = rng.normal(size=21) * 0.05
-    got, want = ee.stream_disturb(rb, d), bstream.disturb_robot(rb, d)
+    got, want = eup.stream_disturb(rb, d), bstream.disturb_robot(rb, d)
     assert np.array_equal(got[:21], rb[:21] + d) and np.array_equal(got[RB["XPHID"]:], rb[RB["XPHID"]:])
     np.testing.assert_allclose(got, want, atol=ATOL, rtol=0)
     assert np.abs(got[RB["P"]:RB["P"] + 6] - rb[RB["P"]:RB["P"] + 6]).max() > 1e-3
     d2 = d.copy(); d2[[0, 9, 20]] = [np.nan, np.inf, -np.inf]      # non-finite entries count as 0
     d3 = d.copy(); d3[[0, 9, 20]] = 0.0
-    assert np.array_equal(ee.stream_disturb(rb, d2), ee.stream_disturb(rb, d3)) and np.array_equal(bstream.disturb_robot(rb, d2), bstream.disturb_robot(rb, d3))
+    assert np.array_equal(eup.stream_disturb(rb, d2), eup.stream_disturb(rb, d3)) and np.array_equal(bstream.disturb_robot(rb, d2), bstream.disturb_robot(rb, d3))
 
 
 def test_node_loop_update_passes_what_the_splice_writes_but_for_the_jerk():
@@ -232,12 +220,12 @@ def test_a_replan_behind_the_post_that_exhausted_the_plan_rescues_the_stream():
     runs 2 ticks and is lost; re-planned behind tick 1 (error count N -> N - 1) it runs a third.  A stream lost on entry never consumes a record
     scheduled for tick 0.  Solved to tolerance, the spliced re-plan is a rescue in earnest: the new path starts where the plant is, and the stream runs on."""
     N, S = 2, 2
-    _, A0, Tab, recs = ee.small_batch(N, S)
+    _, A0, Tab, recs = er.small_batch(N, S)
     push = np.zeros(21); push[:4] = [0.1, -0.1, 0.1, 0.1]
     for b in range(3):
-        Ab = ee.unstack(A0, b)
+        Ab = er.unstack(A0, b)
         er.tick(N, S, H, Tab[b], Ab, max_iter=100, warm_dual=True)
-        Ab["rb"] = ee.stream_disturb(Ab["rb"], push)
+        Ab["rb"] = eup.stream_disturb(Ab["rb"], push)
         for k in A0:
             A0[k][b] = Ab[k]
     assert (A0["status"] == 0).all() and (A0["ss"][:, SS["ERRCNT"]] == 0).all() and (A0["ss"][:, SS["HASPREV"]] == 1).all()
@@ -250,8 +238,8 @@ def test_a_replan_behind_the_post_that_exhausted_the_plan_rescues_the_stream():
     assert (h[:3, 0, ROLL["SUCCESS"]] == 0).all() and (h[:2, 1, ROLL["SUCCESS"]] == 0).all() and (h[:3, 0, ROLL["STATUS"]] == 1).all() and (h[:3, 0, ROLL["GVIOL"]] > 1e-4).all()
     assert np.isfinite(h[:3, 0]).all() and np.isnan(h[3:, 0]).all() and np.isnan(h[2:, 1]).all() and np.isnan(h[:, 2]).all() and np.isnan(r["traj_hist"][3:, 0]).all()
     assert A["status"].ravel().tolist() == [3, 3, 3] and np.array_equal(Tb[2], Tab[2]) and np.array_equal(R[2], recs[2])
-    keep = ee.unstack(lost, 2); keep["status"][0], keep["iters"][0], keep["kkt"][0] = 3, 0, 0.0
-    er.assert_arrays_equal(keep, ee.unstack(A, 2), "lost on entry: nothing but the three words of a skipped stream")
+    keep = er.unstack(lost, 2); keep["status"][0], keep["iters"][0], keep["kkt"][0] = 3, 0, 0.0
+    er.assert_arrays_equal(keep, er.unstack(A, 2), "lost on entry: nothing but the three words of a skipped stream")
     full, _, _, _ = _against_the_loop(N, S, A0, Tab, recs, T, np.array([1, -1, 1]), None, "rescue, solved to tolerance")
     assert full["ticks_run"].tolist() == [T, 2, T] and (full["hist"][2:, [0, 2], ROLL["SUCCESS"]] == 1).all() and (full["hist"][2:, [0, 2], ROLL["ERRCNT"]] == 0).all()
 
@@ -261,18 +249,18 @@ def test_a_replan_behind_the_tick_that_reaches_the_goal_starts_a_second_leg():
     stop there -- the goal test sees the new phi_max -- and runs every tick, on the new path, as the per-tick loop under the same rule does.  (The goal
     tolerance of this construction is nearly the whole path, so the second leg is 0.1 m longer than the first: its goal stays out of reach for T ticks.)"""
     N, S = 2, 2
-    _, A0, Tab, recs = ee.small_batch(N, S, B=1, detour=0.05)
-    free = ee.rollout_events(N, S, H, Tab.copy(), _copy(A0), T)
+    _, A0, Tab, recs = er.small_batch(N, S, B=1, detour=0.05)
+    free = er.rollout(N, S, H, Tab.copy(), _copy(A0), T, entry=1)
     gap = A0["ss"][0, SS["PHIMAX"]] - free["hist"][:, 0, ROLL["PHI"]]
     goal_tol = float(gap[1])
-    stop = ee.rollout_events(N, S, H, Tab.copy(), _copy(A0), T, goal_tol=goal_tol)
+    stop = er.rollout(N, S, H, Tab.copy(), _copy(A0), T, entry=1, goal_tol=goal_tol)
     tg = int(stop["ticks_run"][0])
     assert tg == 2 < T and np.isnan(stop["hist"][tg:]).all()
     r, A, Tb, R = _against_the_loop(N, S, A0, Tab, recs, T, np.array([tg - 1]), None, "second leg", goal_tol=goal_tol)
     assert r["ticks_run"].tolist() == [T] and r["replan_info"].tolist() == [0] and np.isfinite(r["hist"]).all()
     ss_ref = A0["ss"][0].copy()
     want = bstream.splice_record(recs[0], r["hist"][tg - 1, 0, :RB["LEN"]], H, S)
-    T_ref, _ = bstream.apply_update(ss_ref, N, S, *_args_of_record(want, S), entries=Tab.shape[1])
+    T_ref, _ = bstream.apply_update(ss_ref, N, S, *er.args_of_record(want, S), entries=Tab.shape[1])
     assert abs(A["ss"][0, SS["PHIMAX"]] - ss_ref[SS["PHIMAX"]]) < ATOL and A["rb"][0, RB["XPHID"]] == A["ss"][0, SS["PHIMAX"]] != A0["ss"][0, SS["PHIMAX"]]
     assert np.abs(Tb[0] - T_ref).max() < ATOL
     late = _against_the_loop(N, S, A0, Tab, recs, T, np.array([tg]), None, "a re-plan one tick late", goal_tol=goal_tol)[0]      # stops win over events
@@ -282,23 +270,23 @@ def test_a_replan_behind_the_tick_that_reaches_the_goal_starts_a_second_leg():
 def test_argument_errors_of_the_entry():
     """what the C ABI refuses beside the rollout's own errors: a record buffer without its ticks, the update flags bmpc_stream_update refuses"""
     N, S = 2, 2
-    _, A0, Tab, recs = ee.small_batch(N, S)
+    _, A0, Tab, recs = er.small_batch(N, S)
     ok = dict(replan=recs, replan_tick=[1, 1, 1], update_flags=3)
     bad = [dict(ok, replan_tick=None), dict(ok, update_flags=8), dict(ok, update_flags=4), dict(ok, update_flags=5), dict(ok, update_flags=-1), dict(update_flags=16),
            dict(ok, ticks=0), dict(ok, simulate=False), dict(ok, goal_tol=-1.0), dict(ok, goal_tol=np.nan)]
     for kw in bad:
         A, Tb = _copy(A0), Tab.copy()
         kw = dict(kw); kw["replan"] = None if kw.get("replan") is None else recs.copy()
-        assert ee.rollout_events(N, S, H, Tb, A, kw.pop("ticks", 2), want_rc=True, **kw) == 1, kw
+        assert er.rollout(N, S, H, Tb, A, kw.pop("ticks", 2), entry=1, want_rc=True, **kw) == 1, kw
         for b in range(3):
-            er.assert_arrays_equal(ee.unstack(A0, b), ee.unstack(A, b), "nothing runs")
+            er.assert_arrays_equal(er.unstack(A0, b), er.unstack(A, b), "nothing runs")
         assert np.array_equal(Tb, Tab) and (kw["replan"] is None or np.array_equal(kw["replan"], recs))
-    assert ee.rollout_events(N, S, H, Tab.copy(), _copy(A0), 2, update_flags=2, want_rc=True) == 0      # the splice bit without records: allowed, ignored
-    assert ee.rollout_events(N, S, H, Tab.copy(), _copy(A0), 2, want_rc=True, **dict(ok, replan=recs.copy())) == 0
+    assert er.rollout(N, S, H, Tab.copy(), _copy(A0), 2, entry=1, update_flags=2, want_rc=True) == 0      # the splice bit without records: allowed, ignored
+    assert er.rollout(N, S, H, Tab.copy(), _copy(A0), 2, entry=1, want_rc=True, **dict(ok, replan=recs.copy())) == 0
 
 
 def test_lengths_and_the_python_surface():
-    assert bstream.DIST_LEN == 21 and ee.lib().bmpc_emu_stream_disturb_len() == 21
+    assert bstream.DIST_LEN == 21 and eup.lib().bmpc_emu_stream_disturb_len() == 21
     import inspect
     for fn, names in ((bstream.StreamBatch.update_device, ("splice", "poor_bounds")), (bstream.StreamBatch.rollout, ("replan", "replan_tick", "splice", "poor_bounds", "set_goal", "disturb")),
                       (bstream.StreamBatch.disturb, ("d", "stream"))):

@@ -10,51 +10,24 @@ import numpy as np
 import pytest
 
 from boundmpc_amd import stream as bstream
-from tests.emu import emu, emu_rollout as er, emu_rollout_audit as ea, emu_rollout_events as ee, emu_rollout_log as elg, emu_stream_log as el
+from tests.emu import emu, emu_rollout as er, emu_stream_log as el, emu_stream_update as eup
 
 ROLL, SS, TRACK, LS = bstream.ROLL, bstream.SS, bstream.TRACK, bstream.LOG_STAGE
 N, S, T, H = 2, 2, 6, 0.1
 TOL = 1e-6
-INT_SLOTS = [TRACK[k] for k in ("SAMPLES", "TICK_EP_ORTH", "TICK_EP_PAR", "TICK_ER", "REPLAYED")] + [11]
-FLOAT_SLOTS = [i for i in range(12) if i not in INT_SLOTS]
 REPLAN_TICK = np.array([-1, -1, 3])
 OUTPUTS = ("hist", "traj_hist", "ticks_run", "replan_info", "tube_hist", "audit")
 
 
-def _copy(A):
-    return {k: v.copy() for k, v in A.items()}
+_copy = er.copy_arrays
 
 
-def _disturbance():
-    """behind tick 2 of stream 1: the push of tests/test_stream_tube.py, 0.01 rad in every joint with alternating signs"""
-    d = np.zeros((T, 3, bstream.DIST_LEN))
-    d[2, 1, :7] = 0.01 * np.array([1.0, -1.0, 1.0, -1.0, 1.0, -1.0, 1.0])
-    return d
-
-
-def _opts():
-    return emu.opts_for(N, start_rollout=0)
-
-
-@functools.lru_cache(maxsize=None)
-def _start():
-    """(2, 2), B = 3, tick 0 of every stream solved out: (tick arrays, path tables, re-plan records)"""
-    _, A0, Tab, recs = ee.small_batch(N, S)
-    for b in range(3):
-        Ab = ee.unstack(A0, b)
-        er.tick(N, S, H, Tab[b], Ab, max_iter=100, warm_dual=True, opts=_opts())
-        for k in A0:
-            A0[k][b] = Ab[k]
-    assert (A0["status"] == 0).all() and (A0["ss"][:, SS["ERRCNT"]] == 0).all()
-    return A0, Tab, recs
-
-
-def _run(entry=elg.rollout_log, A0=None, disturb=True, replan=True, **kw):
+def _run(entry=3, A0=None, disturb=True, replan=True, **kw):
     """one emulated rollout of T ticks on copies of the start -> (result, tick arrays, tables, records)"""
-    A0_, Tab, recs = _start()
+    A0_, Tab, recs = er.start(N, S)
     A, Tb, R = _copy(A0_ if A0 is None else A0), Tab.copy(), recs.copy()
     ev = dict(replan=R, replan_tick=REPLAN_TICK, update_flags=3) if replan else {}
-    r = entry(N, S, H, Tb, A, T, disturb=_disturbance() if disturb else None, opts=_opts(), audit_tol=TOL, **ev, **kw)
+    r = er.rollout(N, S, H, Tb, A, T, entry=entry, disturb=er.push(T, 3) if disturb else None, opts=er.opts(N), audit_tol=TOL, **ev, **kw)
     return r, A, Tb, R
 
 
@@ -62,20 +35,20 @@ def _run(entry=elg.rollout_log, A0=None, disturb=True, replan=True, **kw):
 def _rollouts():
     """the disturbance behind tick 2 of stream 1, a spliced re-plan behind tick 3 of stream 2: the rollout with rows of N stages, with rows of one stage,
     the rollout with the audit alone, and per stream the per-tick loop for both row lengths -- computed once"""
-    full, one, off = _run(log_stages=N), _run(log_stages=1), _run(ea.rollout_audit)
-    A0, Tab, recs = _start()
-    d = _disturbance()
+    full, one, off = _run(log_stages=N), _run(log_stages=1), _run(2)
+    A0, Tab, recs = er.start(N, S)
+    d = er.push(T, 3)
     loops = {}
     for stages in (1, N):
-        per = [elg.per_tick_log_rows(N, S, H, Tab[b].copy(), ee.unstack(A0, b), T, stages, replan=recs[b].copy(), replan_tick=int(REPLAN_TICK[b]), update_flags=3,
-                                     disturb=d[:, b], opts=_opts()) for b in range(3)]
-        loops[stages] = (np.stack([p[0] for p in per], axis=1), np.stack([p[1] for p in per], axis=1))
+        per = [er.contract_loop(N, S, H, Tab[b].copy(), er.unstack(A0, b), T, stages, replan=recs[b].copy(), replan_tick=int(REPLAN_TICK[b]), update_flags=3,
+                                disturb=d[:, b], opts=er.opts(N)) for b in range(3)]
+        loops[stages] = (np.stack([p["log_hist"] for p in per], axis=1), np.stack([p["hist"] for p in per], axis=1))
     return full, one, off, loops
 
 
 def test_slot_maps_and_lengths():
     assert bstream.track_len() == TRACK["LEN"] == 12 and sorted(v for k, v in TRACK.items() if k != "LEN") == list(range(11))
-    assert [elg.rollout_log_len(N, k) for k in (1, N)] == [bstream.rollout_log_len(1), bstream.rollout_log_len(N)] == [92, 88 * N + 4] and bstream.rollout_log_len(N) == bstream.log_len(N)
+    assert [er.rollout_log_len(N, k) for k in (1, N)] == [bstream.rollout_log_len(1), bstream.rollout_log_len(N)] == [92, 88 * N + 4] and bstream.rollout_log_len(N) == bstream.log_len(N)
     row = np.zeros(12); row[[0, 1, 2, 3, 5, 8, 10]] = [4.0, 0.5, 2.0, 1.0, -1.0, -1.0, 3.0]
     u = bstream.unpack_track(row)
     assert u["samples"] == 4 and u["max_e_p_orth"] == 0.5 and u["tick_e_p_orth"] == 2 and u["rms_e_p_orth"] == 0.5 and u["tick_e_p_par"] is None and u["tick_e_r"] is None and u["replayed"] == 3
@@ -97,11 +70,11 @@ def test_log_rows_equal_the_per_tick_loop():
     assert len(err["e_p_orth"]) == 1 and np.array_equal(err["e_p_orth"][0], full["log_hist"][4, 0, 55 + 9:55 + 12]) and len(bstream.unpack_log(full["log_hist"][4, 0], N)[0]["p"]) == N
     # the row of the re-plan tick is the one taken BEFORE the table was rewritten: the loop stopped behind that tick holds the rewritten table, and the log
     # text on it gives another row
-    A0, Tab, recs = _start()
-    A2, T2 = ee.unstack(A0, 2), Tab[2].copy()
-    rows, _ = elg.per_tick_log_rows(N, S, H, T2, A2, 4, N, replan=recs[2].copy(), replan_tick=3, update_flags=3, opts=_opts())
+    A0, Tab, recs = er.start(N, S)
+    A2, T2 = er.unstack(A0, 2), Tab[2].copy()
+    rows = er.contract_loop(N, S, H, T2, A2, 4, N, replan=recs[2].copy(), replan_tick=3, update_flags=3, opts=er.opts(N))["log_hist"]
     assert np.array_equal(T2, Tb[2]) and not np.array_equal(T2, Tab[2])
-    behind = elg.cut(el.stream_log(N, S, H, T2, A2["ss"], A2["p"], A2["traj"]), N, N)
+    behind = er.cut(el.stream_log(N, S, H, T2, A2["ss"], A2["p"], A2["traj"]), N, N)
     assert np.array_equal(rows[3], full["log_hist"][3, 2]) and not np.array_equal(behind, full["log_hist"][3, 2], equal_nan=True)
 
 
@@ -132,15 +105,10 @@ def test_either_array_alone_and_neither():
     assert np.array_equal(one["track"], full["track"])      # the record does not depend on the row length, nor on where the row lives
 
 
-def _assert_track(got, want):
-    assert np.array_equal(got[:, INT_SLOTS], want[:, INT_SLOTS]), (got, want)
-    np.testing.assert_allclose(got[:, FLOAT_SLOTS], want[:, FLOAT_SLOTS], rtol=1e-12, atol=0.0)
-
-
 def test_track_equals_the_numpy_specification():
     (full, _, _, _), (one, _, _, _), _, _ = _rollouts()
     for r in (full, one):
-        _assert_track(r["track"], bstream.track_of_rows(r["log_hist"], r["hist"]))
+        er.assert_track(r["track"], bstream.track_of_rows(r["log_hist"], r["hist"]))
     trk = full["track"]
     assert (trk[[0, 2], TRACK["SAMPLES"]] == T).all() and (trk[:, 11] == 0).all() and (trk[[0, 2], TRACK["REPLAYED"]] == 0).all()
     sample = full["log_hist"][:, 1, -4] >= 1                       # (the last tick of the pushed stream exhausts its plan: a replay that is no sample)
@@ -165,10 +133,10 @@ def test_stopped_streams():
     """a stream lost on entry, a stream that stops at its goal inside the launch (the cold start and the tolerance of tests/test_stream_tube.py), and a
     stream whose plan a post exhausts mid-run (the forced failures of tests/test_stream_rollout_events.py: plants pushed 16 cm off their paths, one
     iteration a tick)"""
-    _, A0, Tab, _ = ee.small_batch(N, S)
+    _, A0, Tab, _ = er.small_batch(N, S)
     A = _copy(A0)
     A["ss"][2, SS["ERRCNT"]] = float(N)
-    r = elg.rollout_log(N, S, H, Tab.copy(), A, T, opts=_opts(), goal_tol=6.9242, log_stages=N)
+    r = er.rollout(N, S, H, Tab.copy(), A, T, entry=3, opts=er.opts(N), goal_tol=6.9242, log_stages=N)
     run = r["ticks_run"].tolist()
     assert 0 < run[0] < T and run[2] == 0
     for b in range(3):
@@ -176,29 +144,29 @@ def test_stopped_streams():
         assert r["track"][b, TRACK["SAMPLES"]] == run[b]
     lost = r["track"][2]
     assert lost[TRACK["SAMPLES"]] == 0 and (lost[[1, 4, 7]] == -np.inf).all() and (lost[[2, 5, 8]] == -1).all() and (lost[[3, 6, 9, 10, 11]] == 0).all()
-    _assert_track(r["track"], bstream.track_of_rows(r["log_hist"], r["hist"]))
+    er.assert_track(r["track"], bstream.track_of_rows(r["log_hist"], r["hist"]))
     # exhausted mid-run
-    A0, Tab, _ = _start()
+    A0, Tab, _ = er.start(N, S)
     A = _copy(A0)
     push = np.zeros(21); push[:4] = [0.1, -0.1, 0.1, 0.1]
     for b in range(3):
-        A["rb"][b] = ee.stream_disturb(A["rb"][b], push)
-    loop = elg.per_tick_log_rows(N, S, H, Tab[0].copy(), ee.unstack(A, 0), T, N, max_iter=1, opts=_opts())[0]
-    r = elg.rollout_log(N, S, H, Tab.copy(), A, T, opts=_opts(), max_iter=1, log_stages=N)
+        A["rb"][b] = eup.stream_disturb(A["rb"][b], push)
+    loop = er.contract_loop(N, S, H, Tab[0].copy(), er.unstack(A, 0), T, N, max_iter=1, opts=er.opts(N))["log_hist"]
+    r = er.rollout(N, S, H, Tab.copy(), A, T, entry=3, opts=er.opts(N), max_iter=1, log_stages=N)
     assert r["ticks_run"].tolist() == [2, 2, 2] and r["hist"][:2, 0, ROLL["ERRCNT"]].tolist() == [1, 2]
     assert np.array_equal(r["log_hist"][:, 0], loop, equal_nan=True)
     row = r["log_hist"][1, 0]                                      # a tick that RAN, and whose post exhausted the plan
     assert row[-4:].tolist() == [0.0, float(N), 0.0, 0.0] and np.isnan(row[:-4]).all() and bstream.unpack_log(row, N, stages=N) == (None, None)
     assert r["log_hist"][0, 0, -4] == 1 and np.isfinite(r["log_hist"][0, 0, :LS]).all() and np.isnan(r["log_hist"][0, 0, LS:-4]).all()
     assert (r["track"][:, TRACK["SAMPLES"]] == 1).all() and (r["track"][:, [2, 5, 8]] == 0).all() and np.isnan(r["log_hist"][2:]).all()
-    _assert_track(r["track"], bstream.track_of_rows(r["log_hist"], r["hist"]))
+    er.assert_track(r["track"], bstream.track_of_rows(r["log_hist"], r["hist"]))
     assert bstream.unpack_log(r["log_hist"][3, 0], N, stages=N) == (None, None)      # a tick the stream did not run
 
 
 def test_argument_refusals_mirror_the_entry():
-    A0, Tab, _ = _start()
+    A0, Tab, _ = er.start(N, S)
     A = _copy(A0)
-    call = lambda **kw: elg.rollout_log(N, S, H, Tab.copy(), A, kw.pop("ticks", T), opts=_opts(), want_rc=True, **kw)
+    call = lambda **kw: er.rollout(N, S, H, Tab.copy(), A, kw.pop("ticks", T), entry=3, opts=er.opts(N), want_rc=True, **kw)
     for stages in (0, N + 1, -1):
         for kw in (dict(), dict(want_log=False), dict(track=False)):
             assert call(log_stages=stages, **kw) == 1, (stages, kw)
@@ -207,7 +175,7 @@ def test_argument_refusals_mirror_the_entry():
         assert call(**kw) == 1, kw
     for k in A:
         assert np.array_equal(A[k], A0[k], equal_nan=True), k      # nothing ran
-    assert [elg.rollout_log_len(N, k) for k in (0, N + 1, -3)] == [-1, -1, -1]
+    assert [er.rollout_log_len(N, k) for k in (0, N + 1, -3)] == [-1, -1, -1]
     with pytest.raises(AssertionError):
         bstream.unpack_log(np.zeros(92), N)                       # the default keeps the whole-row assertion
     with pytest.raises(AssertionError):
@@ -216,7 +184,7 @@ def test_argument_refusals_mirror_the_entry():
 
 def test_sanitized_stand_alone_program():
     """the stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer on the four cases of the rollout with the audit, exact-size buffers"""
-    out = elg.run_sanitized()
+    out = er.run_sanitized(1, only=(3,))      # (the one program of the one-wave texts: its cases with the log, at that level)
     print("\n".join(out))
     assert len(out) == 4 and all("rc 0 ran 3" in line and "| rc 0 ran 3" in line for line in out)
 
@@ -228,9 +196,10 @@ def test_the_reference_shape_equals_the_per_tick_loop():
     _, rec, Tab, ss = er.small_stream(Nn, Sn)
     A0 = er.fresh_arrays(Nn, Sn, ss, rec)
     opts = emu.opts_for(Nn, start_rollout=0)
-    A = ee.stack([A0])
-    r = elg.rollout_log(Nn, Sn, H, np.ascontiguousarray(Tab[None]), A, ticks, opts=opts, log_stages=Nn)
-    rows, hist = elg.per_tick_log_rows(Nn, Sn, H, Tab.copy(), er.copy_arrays(A0), ticks, Nn, opts=opts)
+    A = er.stack([A0])
+    r = er.rollout(Nn, Sn, H, np.ascontiguousarray(Tab[None]), A, ticks, entry=3, opts=opts, log_stages=Nn)
+    loop = er.contract_loop(Nn, Sn, H, Tab.copy(), er.copy_arrays(A0), ticks, Nn, opts=opts)
+    rows, hist = loop["log_hist"], loop["hist"]
     assert r["ticks_run"].tolist() == [ticks] and np.array_equal(r["hist"][:, 0], hist, equal_nan=True)
     assert np.array_equal(r["log_hist"][:, 0], rows, equal_nan=True) and np.isfinite(rows).all() and (rows[:, -4] == Nn).all()
-    _assert_track(r["track"], bstream.track_of_rows(r["log_hist"], r["hist"]))
+    er.assert_track(r["track"], bstream.track_of_rows(r["log_hist"], r["hist"]))

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from boundmpc_amd import stream as bstream
-from tests.emu import emu, emu_rollout_audit as ea, emu_rollout_events as ee, emu_stream_tube as et
+from tests.emu import emu, emu_rollout as er, emu_stream_tube as et
 
 TUBE, AUDIT, SS = bstream.TUBE, bstream.AUDIT, bstream.SS
 ATOL = 1e-13
@@ -104,28 +104,21 @@ def test_the_numpy_reduction_handles_every_rule():
     assert np.array_equal(got, a, equal_nan=True)
 
 
-def _disturbance():
-    """behind tick 2 of stream 1: a push of 0.01 rad in every joint, alternating signs -- 5 mm outside the position tube (numpy says so below)"""
-    d = np.zeros((T, 3, bstream.DIST_LEN))
-    d[2, 1, :7] = 0.01 * np.array([1.0, -1.0, 1.0, -1.0, 1.0, -1.0, 1.0])
-    return d
-
-
 @functools.lru_cache(maxsize=None)
 def _rollouts():
     """(2, 2), B = 3 on one workgroup, T = 6, the disturbance: the rollout with the audit, the rollout with events without it, and per stream the
     per-tick loop with the tube text on every p -- computed once"""
-    opts = emu.opts_for(N, start_rollout=0)
-    _, A0, Tab, _ = ee.small_batch(N, S)
-    d = _disturbance()
+    opts = er.opts(N)
+    _, A0, Tab, _ = er.small_batch(N, S)
+    d = er.push(T, 3)
     A, B_ = {k: v.copy() for k, v in A0.items()}, {k: v.copy() for k, v in A0.items()}
-    with_audit = ea.rollout_audit(N, S, H, Tab.copy(), A, T, disturb=d, opts=opts, audit_tol=TOL)
-    without = ee.rollout_events(N, S, H, Tab.copy(), B_, T, disturb=d, opts=opts)
+    with_audit = er.rollout(N, S, H, Tab.copy(), A, T, entry=2, disturb=d, opts=opts, audit_tol=TOL)
+    without = er.rollout(N, S, H, Tab.copy(), B_, T, entry=1, disturb=d, opts=opts)
     loops = []
     for b in range(3):
-        Ab = ee.unstack(A0, b)
-        loops.append(ea.per_tick_tube_rows(N, S, H, Tab[b].copy(), Ab, T, disturb=d[:, b], opts=opts))
-    return with_audit, A, without, B_, np.stack([l[0] for l in loops], axis=1), A0, Tab, np.stack([l[1] for l in loops], axis=1)
+        Ab = er.unstack(A0, b)
+        loops.append(er.contract_loop(N, S, H, Tab[b].copy(), Ab, T, disturb=d[:, b], opts=opts))
+    return with_audit, A, without, B_, np.stack([l["tube_hist"] for l in loops], axis=1), A0, Tab, np.stack([l["p_hist"] for l in loops], axis=1)
 
 
 def test_rollout_audit_equals_the_per_tick_loop_and_the_numpy_reduction():
@@ -156,10 +149,10 @@ def test_the_audit_changes_nothing_else():
 def test_either_array_alone_and_neither():
     _, _, r0, A_plain, _, A0, Tab, _ = _rollouts()
     full = _rollouts()[0]
-    opts, d = emu.opts_for(N, start_rollout=0), _disturbance()
+    opts, d = er.opts(N), er.push(T, 3)
     for kw in (dict(audit=False), dict(want_tube=False), dict(audit=False, want_tube=False)):
         A = {k: v.copy() for k, v in A0.items()}
-        r = ea.rollout_audit(N, S, H, Tab.copy(), A, T, disturb=d, opts=opts, audit_tol=TOL, **kw)
+        r = er.rollout(N, S, H, Tab.copy(), A, T, entry=2, disturb=d, opts=opts, audit_tol=TOL, **kw)
         for k in A:
             assert np.array_equal(A[k], A_plain[k], equal_nan=True), (kw, k)
         assert np.array_equal(r["hist"], r0["hist"], equal_nan=True)
@@ -174,7 +167,7 @@ def test_stopped_streams_have_nan_rows_and_their_samples():
     A0, Tab = _rollouts()[5:7]
     A = {k: v.copy() for k, v in A0.items()}
     A["ss"][2, SS["ERRCNT"]] = float(N)
-    r = ea.rollout_audit(N, S, H, Tab.copy(), A, T, opts=emu.opts_for(N, start_rollout=0), goal_tol=6.9242, audit_tol=TOL)
+    r = er.rollout(N, S, H, Tab.copy(), A, T, entry=2, opts=er.opts(N), goal_tol=6.9242, audit_tol=TOL)
     run = r["ticks_run"].tolist()
     assert 0 < run[0] < T and run[2] == 0
     for b in range(3):
@@ -188,7 +181,7 @@ def test_stopped_streams_have_nan_rows_and_their_samples():
 def test_argument_refusals_mirror_the_entry():
     A0, Tab = _rollouts()[5:7]
     A = {k: v.copy() for k, v in A0.items()}
-    call = lambda **kw: ea.rollout_audit(N, S, H, Tab.copy(), A, kw.pop("ticks", T), opts=emu.opts_for(N, start_rollout=0), want_rc=True, **kw)
+    call = lambda **kw: er.rollout(N, S, H, Tab.copy(), A, kw.pop("ticks", T), entry=2, opts=er.opts(N), want_rc=True, **kw)
     for kw in (dict(audit_tol=-1e-9), dict(audit_tol=float("nan")), dict(audit_tol=float("inf")), dict(ticks=0), dict(simulate=False), dict(goal_tol=-1.0), dict(update_flags=8),
                dict(replan=np.zeros((3, bstream.replan_len(S, Tab.shape[1])))), dict(audit_tol=-1.0, audit=False, want_tube=False)):
         assert call(**kw) == 1, kw
