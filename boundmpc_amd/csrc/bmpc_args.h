@@ -107,22 +107,36 @@ struct RArgs {
     double *log_hist;                // [ticks][B][bmpcs::LOG_STAGE * log_stages + 4]
     int log_stages;                  // 1..N: the stages of the plan a row keeps
     double *track;                   // [B][bmpcs::TRACK_LEN], initialised by the kernel
+    // a queue of re-plan records per stream in the place of the one scheduled record (the QU instantiations, bmpc_stream_rollout_legs): replan is
+    // [B][legs][replan_len], replan_info [B][legs], replan_tick is not looked at; 0 / NULL = what an initialiser of the members above leaves
+    int legs;                        // records per stream, >= 1 with replan
+    const int *leg_tick, *leg_on;    // [B][legs]: the tick at or after which record k is due (negative: no tick condition); bit 0 at its goal, bit 1 on a lost plan
+    const double *leg_tol;           // [B][legs] or NULL (goal_tol for every record): the goal tolerance of record k
+    int *legs_done;                  // [B], initialised by the kernel: the head of the queue = the records consumed; required with replan
+    int *leg_fired, *leg_why;        // [B][legs] or NULL: the tick behind which record k was consumed (-1: never), the conditions that held (0: never)
 };
 
 // ---- host only: what the rollout entries of the C ABI refuse and which kernel they run, once (bmpc_hip.hip rollout_launch; the CPU build of the
 // rollout, tests/emu/bmpc_emu_rollout.cpp, asks the same function) ----
 // the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice (needs the robot records), bit 2 poor bounds (with bit 1 only)
 inline bool bmpc_update_flags_ok(int flags, const void *robot) { return !(flags & ~7) && !((flags & 4) && !(flags & 2)) && !((flags & 2) && !robot); }
-// entry: the entry point the caller used -- 0 bmpc_stream_rollout, 1 _events, 2 _audit, 3 _log; r: its arguments (what an entry has no argument for is
+// entry: the entry point the caller used -- 0 bmpc_stream_rollout, 1 _events, 2 _audit, 3 _log, 4 _legs; r: its arguments (what an entry has no argument for is
 // 0 / NULL); N: the handle's horizon; flags, robot: the tick flags and the robot records.  Returns the level of the kernel text to run -- 0 plain, 1 EV,
-// 2 EV + AU, 3 EV + AU + LG -- or BMPC_ROLLOUT_REFUSED (the C ABI's BMPC_ERR_ARG).  An entry without the arrays of its own feature IS the entry below it.
+// 2 EV + AU, 3 EV + AU + LG, 4 all of them with the queue (QU: the one text that reads a queue, whatever else is on) -- or BMPC_ROLLOUT_REFUSED (the C
+// ABI's BMPC_ERR_ARG).  An entry without the arrays of its own feature IS the entry below it.
 enum { BMPC_ROLLOUT_REFUSED = -1 };
 #define BMPC_TOL_MAX 1.7976931348623157e308      // the largest finite tolerance (plain comparisons: the flop-counting hosts of tests/emu read this file with their own number type)
 inline int bmpc_rollout_level(int entry, const RArgs &r, int N, int flags, const void *robot) {
     if (r.ticks < 1 || !(r.goal_tol >= 0.0 && r.goal_tol <= BMPC_TOL_MAX)) return BMPC_ROLLOUT_REFUSED;      // (negative, NaN or infinite)
     if (!(flags & 1)) return BMPC_ROLLOUT_REFUSED;                    // without the plant in the loop a second tick repeats the first
     if (entry == 0) return 0;
-    if ((r.replan && !r.replan_tick) || !bmpc_update_flags_ok(r.update_flags, robot)) return BMPC_ROLLOUT_REFUSED;
+    if (entry == 4) {      // the queue: without records the log entry without a re-plan, and no queue argument is looked at
+        if (r.replan && (!r.leg_tick || !r.leg_on || !r.legs_done || r.legs < 1)) return BMPC_ROLLOUT_REFUSED;
+        if (!r.replan) entry = 3;
+    } else if (r.replan && !r.replan_tick) return BMPC_ROLLOUT_REFUSED;
+    if (!bmpc_update_flags_ok(r.update_flags, robot)) return BMPC_ROLLOUT_REFUSED;
+    if (entry == 4) return (r.log_hist || r.track) && (r.log_stages < 1 || r.log_stages > N) ? BMPC_ROLLOUT_REFUSED
+                           : (r.audit_tol >= 0.0 && r.audit_tol <= BMPC_TOL_MAX) ? 4 : BMPC_ROLLOUT_REFUSED;
     if (entry >= 3 && (r.log_hist || r.track)) {
         if (r.log_stages < 1 || r.log_stages > N) return BMPC_ROLLOUT_REFUSED;
     } else if (entry >= 3) entry = 2;

@@ -857,8 +857,8 @@ extern "C" int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int p
 // ---- rollout: `ticks` ticks of every stream in one launch (bmpc_rollout.hip), a direct launch on the caller's stream ----
 extern "C" int bmpc_stream_rollout_len(void) { return BMPC_ROLL_LEN; }
 // The rollout entries: each fills the solve, stream and rollout records from its arguments and names itself (entry: 0 bmpc_stream_rollout, 1 _events,
-// 2 _audit, 3 _log); the argument test and the level of the kernel text that runs -- without the event code (0), with it (1), with the event and the audit
-// code (2), with the log code on top of both (3) -- are bmpc_rollout_level's (bmpc_args.h).
+// 2 _audit, 3 _log, 4 _legs); the argument test and the level of the kernel text that runs -- without the event code (0), with it (1), with the event and
+// the audit code (2), with the log code on top of both (3), with the queue of re-plan records on top of all (4) -- are bmpc_rollout_level's (bmpc_args.h).
 static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, const RArgs &r, int entry, hipStream_t st) {
     if (!tick_args_ok(h, B, io, t)) return BMPC_ERR_ARG;
     const int level = bmpc_rollout_level(entry, r, h->N, t.flags, t.robot);
@@ -879,7 +879,9 @@ static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const Stream
     hipEvent_t *pair = nullptr;
     if (h->timing) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
     // (teams at levels 1 and 2 hand the LG text the caller's log_stages UNCHECKED, with log_hist and track NULL: the kernel reads it behind r.log_hist only)
-    if (team) HIPCHK(bmpc_team_rollout_launch(BMPC_TEAM_NW, resto, level != 0, &a, &s, &r, grid, st));      // (one kernel with everything serves every level above 0)
+    if (team && level == 4) HIPCHK(bmpc_team_rollout_legs_launch(BMPC_TEAM_NW, resto, &a, &s, &r, grid, st));
+    else if (team) HIPCHK(bmpc_team_rollout_launch(BMPC_TEAM_NW, resto, level != 0, &a, &s, &r, grid, st));      // (one kernel with everything serves every level from 1 to 3)
+    else if (level == 4) HIPCHK(bmpc_rollout_legs_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else if (level == 3) HIPCHK(bmpc_rollout_log_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else if (level == 2) HIPCHK(bmpc_rollout_audit_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else if (level == 1) HIPCHK(bmpc_rollout_events_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
@@ -928,6 +930,20 @@ extern "C" int bmpc_stream_rollout_log(bmpc_handle *h, int B, int ticks, const d
     const StreamIO t{path, path_entries, sstate, robot, traj, flags};
     const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, replan_tick, replan_info, update_flags, disturb, tube_hist, audit, audit_tol, log_hist, log_stages, track};
     return rollout_launch(h, B, io, t, r, 3, (hipStream_t)hip_stream);
+}
+// with a queue of re-plan records per stream in the place of the one scheduled record (bmpc_rollout_legs.hip, bmpc_team_rollout_legs.hip); without
+// records it IS the entry above without a re-plan
+extern "C" int bmpc_stream_rollout_legs(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                                        double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                                        double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan, int *replan_info, int update_flags,
+                                        const double *disturb, double *tube_hist, double *audit, double audit_tol, double *log_hist, int log_stages, double *track,
+                                        int legs, const int *leg_tick, const int *leg_on, const double *leg_tol, int *legs_done, int *leg_fired, int *leg_why,
+                                        void *hip_stream) {
+    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
+    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
+    const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, nullptr, replan_info, update_flags, disturb, tube_hist, audit, audit_tol, log_hist, log_stages, track,
+                  legs, leg_tick, leg_on, leg_tol, legs_done, leg_fired, leg_why};
+    return rollout_launch(h, B, io, t, r, 4, (hipStream_t)hip_stream);
 }
 
 extern "C" int bmpc_stream_set_rt_feasibility_tol(bmpc_handle *h, double tol) {

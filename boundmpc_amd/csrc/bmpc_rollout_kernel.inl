@@ -37,11 +37,21 @@
 // leaves through data-dependent exits (lost plan, goal, replan_tick[b] == t), so all waves must take every exit together: each wave reads every
 // such decision itself from memory that does not change between the last barrier ahead of the read and the first barrier behind it -- ss[SS_ERRCNT],
 // ss[SS_PHI], ss[SS_PHIMAX] (written by wave 0 in stream_post and stream_update, each followed by a barrier; the only word of ss the next pack writes
-// is SS_SECTOR, and the post behind it sits behind the solve's barriers, which need every wave), r.replan_tick (never written) and the kernel
+// is SS_SECTOR, and the post behind it sits behind the solve's barriers, which need every wave), r.replan_tick (never written), under QU the trigger
+// arrays (never written) and r.legs_done[b] (written by wave 0 at the start of the stream and ahead of the barrier behind stream_update), and the kernel
 // arguments.  No decision is taken from a value that only wave 0 holds.
-// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp, once per
-// BMPC_NW).  The five units (bmpc_rollout.hip, bmpc_rollout_events.hip, bmpc_rollout_audit.hip, bmpc_rollout_log.hip, bmpc_team_rollout.hip) and that
-// build launch through bmpc_rollout_run at the end of this file, the one place that picks <ZLDS, RESTO>.
+// MISSIONS (the instantiations with QU, bmpc_stream_rollout_legs; bmpc_rollout_legs.hip, bmpc_team_rollout_legs.hip): in the place of the one scheduled
+// re-plan a QUEUE of r.legs records per stream, r.replan[b][k], each with a trigger -- a tick number (at or after it), the goal of the leg the stream
+// is on (phi_max - phi <= its own tolerance), the lost plan (the post of this tick exhausted it) --, facts of the stream's own state that only the
+// device knows and that every stream meets on another tick.  Only the head of the queue, record r.legs_done[b], can fire, at most one record per tick,
+// where the single re-plan sits: behind the tick's rows and disturbance, ahead of the goal test and of the next tick's lost-plan test, so a
+// goal-triggered record gives the stream its next phi_max before the goal test sees the old one, and an on-lost record rescues the stream.  The head
+// lives in memory (it IS the output legs_done), not in a register: nothing of the queue is carried across the solve, and on a team every wave reads the
+// same word behind a barrier.  Without QU no queue line is compiled and the kernels are the ones from before.
+// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp and
+// bmpc_emu_rollout_legs.cpp, once per BMPC_NW).  The seven units (bmpc_rollout.hip, bmpc_rollout_events.hip, bmpc_rollout_audit.hip, bmpc_rollout_log.hip,
+// bmpc_rollout_legs.hip, bmpc_team_rollout.hip, bmpc_team_rollout_legs.hip) and those builds launch through bmpc_rollout_run at the end of this file, the
+// one place that picks <ZLDS, RESTO>.
 #pragma once
 
 #include "bmpc_stream_events.inl"
@@ -49,6 +59,8 @@
 #include "bmpc_stream_log.inl"
 
 namespace bmpcs {
+// trigger word of a queued re-plan record (BMPC_LEG_* of include/boundmpc_hip.h) and the conditions that held when it fired (BMPC_LEG_WHY_*)
+enum { LEG_AT_GOAL = 1, LEG_ON_LOST = 2, LEG_WHY_GOAL = 1, LEG_WHY_LOST = 2, LEG_WHY_TICK = 4 };
 // history row of one tick of one stream (BMPC_ROLL_* of include/boundmpc_hip.h): the robot record behind the post, then the named scalars, then the
 // four trailer words of the tick's trajectory record
 enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH_NVALID, RH_USINGPREV, RH_SUCCESS, RH_GVIOL, RH_LEN };
@@ -64,7 +76,7 @@ enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH
 #endif
 // (the body of a tick in the kernel itself, as in bmpc_tick_kernel.inl: behind a function that takes `a` the argument loads lose their no-clobber
 // property -- bmpc_args.h, BMPC_PROBLEM)
-template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false, bool LG = false>
+template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false, bool LG = false, bool QU = false>
 BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
     static_assert(BMPC_NW == 1 || ZLDS, "a team keeps the iterate in LDS");
     BMPCK_LDS double lds[BMPC_NAMESPACE::L_SIZE];
@@ -81,7 +93,20 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
         BMPC_STREAM_SLICES(a, s, b);
         long long busy = 0;      // counts of the 100 MHz clock spent in the stream's solves
         int t = 0;
-        if (EV) { if (r.replan_info && BMPCK_LANE == 0) r.replan_info[b] = -1; }
+        if (EV && !QU) { if (r.replan_info && BMPCK_LANE == 0) r.replan_info[b] = -1; }
+        if (QU) {
+            // (the head of the queue lives in memory, legs_done[b]: wave 0 writes it here and behind a consumed record, every wave reads it behind the
+            // barrier of a tick's post; the per-record outputs start as "never")
+            if (r.replan && w0 && BMPCK_LANE == 0) {
+                r.legs_done[b] = 0;
+                for (int k = 0; k < r.legs; k++) {
+                    const long long q = (long long)b * r.legs + k;
+                    if (r.replan_info) r.replan_info[q] = -1;
+                    if (r.leg_fired) r.leg_fired[q] = -1;
+                    if (r.leg_why) r.leg_why[q] = 0;
+                }
+            }
+        }
         if (AU) { if (r.audit && BMPCK_LANE == 0) bmpcs::stream_audit_init(r.audit + (long long)b * bmpcs::AUDIT_LEN); }
         if (LG) { if (r.track && BMPCK_LANE == 0) bmpcs::stream_track_init(r.track + (long long)b * bmpcs::TRACK_LEN); }
         for (; t < r.ticks; t++) {
@@ -146,12 +171,51 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
                     if (w0) bmpcs::stream_disturb(rb, r.disturb + ((long long)t_ * a.B + b_) * bmpcs::DIST_LEN, BMPCK_LANE, BMPCK_NL);
                     BMPCK_SYNC();
                 }
-                if (r.replan && BMPCK_UNIFORM((int)(r.replan_tick[b_] == t_))) {
-                    double *rec = r.replan + (long long)b_ * bmpcs::replan_len(S_, cap_);
-                    if (r.update_flags & 2) { if (w0) bmpcs::stream_splice(a.h, S_, cap_, rec, rb, r.update_flags, BMPCK_LANE, BMPCK_NL); BMPCK_SYNC(); }
-                    if (w0) bmpcs::stream_update(N_, S_, rec, const_cast<double *>(path), cap_, ss, rb, r.replan_info ? r.replan_info + b_ : nullptr, r.update_flags & 1,
-                                         BMPCK_LANE, BMPCK_NL);
-                    BMPCK_SYNC();      // the goal test, the lost-plan test and the next pack read what the re-plan stored
+                if (!QU) {
+                    if (r.replan && BMPCK_UNIFORM((int)(r.replan_tick[b_] == t_))) {
+                        double *rec = r.replan + (long long)b_ * bmpcs::replan_len(S_, cap_);
+                        if (r.update_flags & 2) { if (w0) bmpcs::stream_splice(a.h, S_, cap_, rec, rb, r.update_flags, BMPCK_LANE, BMPCK_NL); BMPCK_SYNC(); }
+                        if (w0) bmpcs::stream_update(N_, S_, rec, const_cast<double *>(path), cap_, ss, rb, r.replan_info ? r.replan_info + b_ : nullptr, r.update_flags & 1,
+                                             BMPCK_LANE, BMPCK_NL);
+                        BMPCK_SYNC();      // the goal test, the lost-plan test and the next pack read what the re-plan stored
+                    }
+                } else if (r.replan) {
+                    // The head record of the stream's queue, legs_done[b], and whether it is due behind this tick: EVERY wave decides for itself, from words
+                    // that do not change between the barrier ahead (the post's, the log's or the disturbance's) and the first barrier behind the decision --
+                    // the three ss words the stops read, the read-only trigger arrays, and legs_done[b], which wave 0 writes at the start of the stream and
+                    // ahead of the last barrier of a consumed record.  Bit 0 of `why`: the record's goal, bit 1: the post of this tick exhausted the plan,
+                    // bit 2: at or after its tick.  A word with an unknown bit, or without any condition, is never due: it ends the queue.
+                    int L_ = r.legs;
+                    BMPCR_OPAQUE("+s"(L_));
+                    const int k_ = BMPCK_UNIFORM(r.legs_done[b_]);
+                    int why_ = 0;
+                    if (k_ < L_) {
+                        const long long q_ = (long long)b_ * L_ + k_;
+                        const int on_ = r.leg_on[q_], tk_ = r.leg_tick[q_];
+                        const double tol_ = r.leg_tol ? r.leg_tol[q_] : r.goal_tol;
+                        if (!(on_ & ~(bmpcs::LEG_AT_GOAL | bmpcs::LEG_ON_LOST))) {
+                            if ((on_ & bmpcs::LEG_AT_GOAL) && ss[bmpcs::SS_PHIMAX] - ss[bmpcs::SS_PHI] <= tol_) why_ |= bmpcs::LEG_WHY_GOAL;
+                            if ((on_ & bmpcs::LEG_ON_LOST) && ss[bmpcs::SS_ERRCNT] >= (double)a.N) why_ |= bmpcs::LEG_WHY_LOST;
+                            if (tk_ >= 0 && t_ >= tk_) why_ |= bmpcs::LEG_WHY_TICK;
+                        }
+                    }
+                    why_ = BMPCK_UNIFORM(why_);
+                    if (why_) {
+                        const long long q_ = (long long)b_ * L_ + k_;
+                        double *rec = r.replan + q_ * bmpcs::replan_len(S_, cap_);
+                        // (a barrier between the decision, which reads ss, and stream_update, which writes it: the splice's, or one of its own)
+                        if (r.update_flags & 2) { if (w0) bmpcs::stream_splice(a.h, S_, cap_, rec, rb, r.update_flags, BMPCK_LANE, BMPCK_NL); }
+                        BMPCK_SYNC();
+                        // (every wave has read the head ahead of that barrier: it advances here, ahead of the barrier behind stream_update)
+                        if (w0 && BMPCK_LANE == 0) {
+                            if (r.leg_fired) r.leg_fired[q_] = t_;
+                            if (r.leg_why) r.leg_why[q_] = why_;
+                            r.legs_done[b_] = k_ + 1;
+                        }
+                        if (w0) bmpcs::stream_update(N_, S_, rec, const_cast<double *>(path), cap_, ss, rb, r.replan_info ? r.replan_info + q_ : nullptr, r.update_flags & 1,
+                                             BMPCK_LANE, BMPCK_NL);
+                        BMPCK_SYNC();      // the goal test, the lost-plan test, the next tick's head and the next pack read what the re-plan stored
+                    }
                 }
             }
             if (BMPCK_UNIFORM((int)(r.goal_tol > 0.0 && ss[bmpcs::SS_PHIMAX] - ss[bmpcs::SS_PHI] <= r.goal_tol))) { t++; break; }
@@ -175,18 +239,18 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
     }
 }
 
-// Host: the one place that picks the instantiation <ZLDS, RESTO> of a unit's <EV, AU, LG> and launches it on `grid` workgroups (BMPCK_LAUNCH: the GPU
+// Host: the one place that picks the instantiation <ZLDS, RESTO> of a unit's <EV, AU, LG, QU> and launches it on `grid` workgroups (BMPCK_LAUNCH: the GPU
 // launch on stream `st`, or the host build's call).  kargs points at a KArgsT<...> record (the layouts are identical across instantiations).  A team
 // keeps the iterate in LDS: its units hold no instantiation without ZLDS.  `static`: every unit has its own -- the name says nothing of the unit's KArgs
 // and BMPC_NW, and the linker would fold the one-wave units' and the team unit's into one.
-template <bool EV, bool AU, bool LG, class STREAM>
+template <bool EV, bool AU, bool LG, bool QU = false, class STREAM>
 static void bmpc_rollout_run(bool zlds, bool resto, const void *kargs, const SArgs &s, const RArgs &r, int grid, STREAM st) {
     KArgs a; memcpy(&a, kargs, sizeof(a));
-    if (zlds && resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, true, EV, AU, LG>), grid, st, a, s, r);
-    else if (zlds) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, false, EV, AU, LG>), grid, st, a, s, r);
+    if (zlds && resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, true, EV, AU, LG, QU>), grid, st, a, s, r);
+    else if (zlds) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, false, EV, AU, LG, QU>), grid, st, a, s, r);
     else if constexpr (BMPC_NW == 1) {
-        if (resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<false, true, EV, AU, LG>), grid, st, a, s, r);
-        else BMPCK_LAUNCH((bmpc_stream_rollout_kernel<false, false, EV, AU, LG>), grid, st, a, s, r);
+        if (resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<false, true, EV, AU, LG, QU>), grid, st, a, s, r);
+        else BMPCK_LAUNCH((bmpc_stream_rollout_kernel<false, false, EV, AU, LG, QU>), grid, st, a, s, r);
     }
 }
 

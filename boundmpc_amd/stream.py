@@ -376,6 +376,9 @@ def track_of_rows(log_hist, hist):
 
 # csrc/bmpc_rollout_kernel.inl: the history row of one tick of one stream (BMPC_ROLL_* of include/boundmpc_hip.h)
 ROLL = dict(ROBOT=0, PHI=43, ERRCNT=44, ITERS=45, STATUS=46, KKT=47, NVALID=48, USINGPREV=49, SUCCESS=50, GVIOL=51, LEN=52)
+# a mission (bmpc_stream_rollout_legs, BMPC_LEG_* of include/boundmpc_hip.h): the bits of a record's trigger word leg_on, and of leg_why, the conditions
+# that held when the record fired
+LEG = dict(AT_GOAL=1, ON_LOST=2, WHY_GOAL=1, WHY_LOST=2, WHY_TICK=4)
 
 
 def rollout_len():
@@ -529,6 +532,7 @@ class StreamBatch:
         self._log = None         # log(): allocated on first use
         self._tube = None        # tube(): allocated on first use
         self.replan = self.replan_info = None      # update_device(): record buffer [B][replan_len] and info [B], allocated on first use
+        self.legs = None         # rollout(legs=...): queue buffer [B][K][replan_len], allocated on first use
         self.tick_ms = None      # closed_loop(timed=True): HIP-event time of the tick just run
         solver._children.add(self)
 
@@ -559,6 +563,24 @@ class StreamBatch:
             with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.path.device)):      # the copy ahead of the launch, same stream
                 self.replan.copy_(records)
         return self.replan
+
+    def _legs_buffer(self, records, stream):
+        """the device queue buffer `self.legs` [B][K][replan_len] (allocated on first use and whenever K changes) holding `records`: a tensor or an array
+        of that shape, or B lists of K `replan_record` rows; `self.legs` itself is taken as it is.  -> K"""
+        import torch
+        if records is self.legs and records is not None:
+            return int(self.legs.shape[1])
+        if not torch.is_tensor(records):
+            records = torch.as_tensor(np.ascontiguousarray(records, dtype=np.float64))
+        n = self.solver._lib.bmpc_stream_replan_len(self.solver._h, self.entries)
+        assert n == replan_len(self.S, self.entries)
+        if records.ndim != 3 or records.shape[0] != self.B or records.shape[1] < 1 or records.shape[2] != n:
+            raise ValueError(f"legs must be [{self.B}][K >= 1][{n}] (replan_len(S, entries)), got {list(records.shape)}")
+        if self.legs is None or tuple(self.legs.shape) != tuple(records.shape):
+            self.legs = torch.zeros(tuple(records.shape), dtype=torch.float64, device=self.path.device)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.path.device)):      # the copy ahead of the launch, same stream
+            self.legs.copy_(records)
+        return int(self.legs.shape[1])
 
     @staticmethod
     def _update_flags(set_goal, splice, poor_bounds):
@@ -711,7 +733,7 @@ class StreamBatch:
 
     def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None,
                 replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None, audit=False, audit_tol=1e-6, want_tube=False,
-                want_log=False, log_stages=1, track=False, waves=None):
+                want_log=False, log_stages=1, track=False, waves=None, legs=None, leg_tick=None, leg_on=None, leg_tol=None):
         """`ticks` closed-loop ticks (plant simulation on) of every stream in ONE launch (bmpc_stream_rollout): each stream runs at its own pace, so
         the launch lasts as long as the slowest stream's SUM of solves, where a loop of tick() / tick_graph() pays the slowest stream of every tick.
         For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, a time
@@ -746,14 +768,27 @@ class StreamBatch:
                                            behind tick t -- path reference, tube bounds, errors in the path frame (unpack_log(row, N, log_stages)) --
                                            with the n_valid of the whole plan; NaN likewise
           track: track [B][12]             the stream's tracking record over stage 0 of its rows, the state the plant is in behind every tick (slots
-                                           TRACK, unpack_track): largest ||e_p_orth||, ||e_p_par||, ||e_r|| with their ticks, sums of squares, replays."""
+                                           TRACK, unpack_track): largest ||e_p_orth||, ||e_p_par||, ||e_r|| with their ticks, sums of squares, replays.
+        MISSIONS (bmpc_stream_rollout_legs; exclusive with replan / replan_tick; without `legs` nothing changes): a QUEUE of K re-plan records per stream
+        in the place of the one scheduled record -- task sequences and recovery policies in one launch, every stream at its own pace.
+          legs [B][K][replan_len]          records (tensor or array), or B lists of K `replan_record`s; copied into a device buffer kept in `self.legs`
+                                           (passing `self.legs` itself copies nothing); consumed as replan is: set_goal, splice, poor_bounds
+          leg_tick [B][K] int              record k is due at or after this tick; negative (the default for all): no tick condition
+          leg_on [B][K] int                LEG["AT_GOAL"]: due once phi_max - phi <= its tolerance; LEG["ON_LOST"]: due when the post of a tick
+                                           exhausted the plan; default 0.  A record without any condition (or with an unknown bit) ends the queue.
+          leg_tol [B][K]                   the goal tolerance of record k; None: goal_tol for every record
+        Only the head of a stream's queue can fire, one record per tick, where the single re-plan sits: a goal-triggered record gives the stream its next
+        phi_max before the goal test sees the old one (with goal_tol > 0 a stream stops only at the goal of its last leg), an on-lost record rescues it.
+        Then the result also holds  legs_done [B] int32: records consumed;  leg_fired [B][K]: the tick behind which record k was consumed, -1 never;
+        leg_why [B][K]: LEG["WHY_GOAL"] | LEG["WHY_LOST"] | LEG["WHY_TICK"], 0 never;  replan_info [B][K]: -1 not consumed, 0 consumed, 1 invalid.
+        The audit and the tracking record run over the whole mission; per-leg spans follow from leg_fired."""
         import torch
         if waves is not None:
             former = self.solver.rollout_waves
             self.solver.set_rollout_waves(waves)      # (a refused value raises here, the setting intact)
             try:
                 return self.rollout(ticks, max_iter, warm_dual, accept_capped, goal_tol, want_traj, stream, replan, replan_tick, splice, poor_bounds, set_goal,
-                                    disturb, audit, audit_tol, want_tube, want_log, log_stages, track)
+                                    disturb, audit, audit_tol, want_tube, want_log, log_stages, track, None, legs, leg_tick, leg_on, leg_tol)
             finally:
                 self.solver.set_rollout_waves(former)
         if max_iter and not warm_dual:
@@ -778,6 +813,30 @@ class StreamBatch:
         if track:
             assert self.solver._lib.bmpc_stream_track_len() == TRACK["LEN"]
             out["track"] = torch.empty((self.B, TRACK["LEN"]), dtype=torch.float64, device=dev)
+        if legs is not None:
+            if replan is not None or replan_tick is not None:
+                raise ValueError("legs is the queue of re-plan records: it does not go with replan / replan_tick")
+            flags = self._update_flags(set_goal, splice, poor_bounds)
+            K = self._legs_buffer(legs, stream)
+            i32 = lambda a, fill, name: torch.full((self.B, K), fill, dtype=torch.int32, device=dev) if a is None else self._dev64(a, (self.B, K), name, stream, dtype=torch.int32)
+            leg_tick, leg_on = i32(leg_tick, -1, "leg_tick"), i32(leg_on, 0, "leg_on")
+            if leg_tol is not None:
+                leg_tol = self._dev64(leg_tol, (self.B, K), "leg_tol", stream)
+            if disturb is not None:
+                disturb = self._dev64(disturb, (n, self.B, DIST_LEN), "disturb", stream)
+            out["legs_done"] = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+            out["leg_fired"], out["replan_info"] = (torch.full((self.B, K), -1, dtype=torch.int32, device=dev) for _ in range(2))
+            out["leg_why"] = torch.zeros((self.B, K), dtype=torch.int32, device=dev)
+            _lib.check(self.solver._lib.bmpc_stream_rollout_legs(
+                self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]), _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]),
+                _ptr(self.legs), _ptr(out["replan_info"]), flags, _ptr(disturb) if disturb is not None else None, _ptr(out["tube_hist"]) if want_tube else None,
+                _ptr(out["audit"]) if audit else None, float(audit_tol), _ptr(out["log_hist"]) if want_log else None, int(log_stages), _ptr(out["track"]) if track else None,
+                K, _ptr(leg_tick), _ptr(leg_on), _ptr(leg_tol) if leg_tol is not None else None, _ptr(out["legs_done"]), _ptr(out["leg_fired"]), _ptr(out["leg_why"]),
+                self._stream(stream)), "bmpc_stream_rollout_legs")
+            self._event_inputs = (leg_tick, leg_on, leg_tol, disturb)      # the launch is asynchronous: its inputs live until the next one replaces them
+            return out
+        if leg_tick is not None or leg_on is not None or leg_tol is not None:
+            raise ValueError("leg_tick, leg_on and leg_tol describe the records of legs")
         if replan is None and replan_tick is None and disturb is None and not audited and not logged:
             _lib.check(self.solver._lib.bmpc_stream_rollout(self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]),
                                                             _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]), self._stream(stream)),

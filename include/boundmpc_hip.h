@@ -298,7 +298,7 @@ int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const double *path, in
                         double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
                         double goal_tol, double *hist /* [ticks][B][52] or NULL */, double *traj_hist /* [ticks][B][traj] or NULL */,
                         int *ticks_run /* [B] or NULL */, void *hip_stream);
-/* Waves per stream of the four rollout entries (bmpc_stream_rollout, _events, _audit, _log), read at launch time:
+/* Waves per stream of the five rollout entries (bmpc_stream_rollout, _events, _audit, _log, _legs), read at launch time:
  *   1 (default)   one wave per stream, on the resident waves of the device;
  *   BMPC_TEAM_NW  a team of cooperating waves per stream whatever B is, striding over the resident teams (256 on an MI355X: a team owns a CU);
  *                 BMPC_ERR_ARG on a handle without team kernels (N > 10 or S > 4), as bmpc_set_team_waves;
@@ -369,8 +369,9 @@ int bmpc_stream_disturb(bmpc_handle *h, int B, double *robot, const double *d /*
  *   disturb [ticks][B][BMPC_DIST_LEN] or NULL: row [t][b] disturbs the plant of stream b behind tick t, as bmpc_stream_disturb does;
  *   replan [B][bmpc_stream_replan_len] or NULL, replan_tick [B] (required with replan): the record of stream b is consumed behind tick
  *     replan_tick[b] as bmpc_stream_update(update_flags) consumes it -- with bit 1 the state behind that tick is spliced in on the device, where
- *     alone it is known.  One re-plan per stream and launch; several legs are several rollouts.  The path table is written then (the const of
- *     `path` is the plain rollout's).
+ *     alone it is known.  One re-plan per stream and launch here; a queue of them per stream, each fired by a tick, by the goal of its leg or by a
+ *     lost plan, is bmpc_stream_rollout_legs (below): several legs are one rollout.  The path table is written then (the const of `path` is the
+ *     plain rollout's).
  * Per stream and tick: pack, solve, post, the hist and traj_hist rows (as in the rollout: hist[t][b] shows the UNDISTURBED plant behind tick t),
  * the disturbance, the re-plan, the goal test, the next tick's lost-plan test.  So a re-plan behind the tick that reaches the old goal gives the
  * stream a new phi_max and it goes on (a second leg), and a re-plan behind the post that exhausted the plan (error count back to N - 1) rescues the
@@ -459,6 +460,49 @@ int bmpc_stream_rollout_log(bmpc_handle *h, int B, int ticks, const double *path
                             const double *disturb /* [ticks][B][21] or NULL */, double *tube_hist /* [ticks][B][16] or NULL */,
                             double *audit /* [B][12] or NULL */, double audit_tol, double *log_hist /* [ticks][B][88 log_stages + 4] or NULL */,
                             int log_stages, double *track /* [B][12] or NULL */, void *hip_stream);
+/* Rollout with a MISSION: bmpc_stream_rollout_log (its arguments in their order up to and including track, their meaning, tests and contract; NULL
+ * event, audit and log pointers switch those off) with a QUEUE of re-plan records per stream in the place of the one scheduled record -- task
+ * sequences ("follow leg A; once there, take leg B; once there, leg C") and recovery policies ("if the plan is lost, re-plan from where the plant
+ * is") in ONE launch.  Both triggers are facts of the stream's own state, known on the device only, and every stream meets them on another tick; a
+ * chain of rollouts with goal_tol, each followed by bmpc_stream_update, waits for the slowest stream of the batch once per leg.  replan_tick is gone,
+ * replan and replan_info grow an axis:
+ *   legs       >= 1: records per stream
+ *   replan     [B][legs][bmpc_stream_replan_len] or NULL: record k of stream b, in the layout of bmpc_stream_update with its flag protocol
+ *   leg_tick   [B][legs]: a tick number >= 0, or negative for "no tick condition"
+ *   leg_on     [B][legs]: bit 0 BMPC_LEG_AT_GOAL, bit 1 BMPC_LEG_ON_LOST
+ *   leg_tol    [B][legs] or NULL: the goal tolerance of record k; NULL means goal_tol for every record
+ *   legs_done  [B], required with replan, initialised by the kernel: the number of records the stream consumed
+ *   leg_fired  [B][legs] or NULL: the tick behind which record k was consumed; -1 if never
+ *   leg_why    [B][legs] or NULL: the conditions that held when it fired -- BMPC_LEG_WHY_GOAL | _LOST | _TICK; 0 if never
+ *   replan_info [B][legs] or NULL: what bmpc_stream_update writes for that record; -1 if never consumed
+ * Only the HEAD of the queue can fire: record k = legs_done[b] while k < legs.  It is due behind tick t when any of its enabled conditions holds:
+ *   leg_tick >= 0 and t >= leg_tick (AT OR AFTER its tick: a record queued behind a late one still fires);
+ *   bit 0 and phi_max - phi <= leg_tol (the state row behind the tick's post: the goal of the leg the stream is on);
+ *   bit 1 and error count >= N (the post of this tick exhausted the plan).
+ * A record with no tick condition and neither bit, or with any higher bit set, ENDS the queue: it and everything behind it are never consumed (the
+ * trigger words live on the device and are not validated on the host).  At most one record is consumed per stream and tick.
+ * The due record is consumed where the single re-plan of bmpc_stream_rollout_events sits: behind the tick's history and log rows and its disturbance,
+ * ahead of the goal test and of the next tick's lost-plan test -- with update_flags bit 1 spliced from the robot record of that moment, then updated.
+ * A due record whose flag is 0 or which is invalid is consumed as bmpc_stream_update consumes it (info 0 or 1, stream untouched) and the head still
+ * advances.  So a goal-triggered record gives the stream a new phi_max before the goal test sees the old one -- with goal_tol > 0 a stream stops only
+ * at the goal of its LAST leg --, and an on-lost record rescues the stream before the lost-plan stop.  Stops still win over records that are not yet
+ * due: their flags stay raised.  The audit and the tracking record keep accumulating over the whole mission; per-leg spans follow from leg_fired.
+ * With goal_tol = 0 every array the contract of bmpc_stream_rollout_log names, the record buffer and the path tables hold what this loop leaves, bit
+ * for bit:
+ *   for t in 0..ticks-1: bmpc_stream_tick on one wave per stream; bmpc_stream_log; bmpc_stream_disturb(rows of tick t);
+ *                        bmpc_stream_update(update_flags) with exactly the flags of the streams whose head record is due raised
+ * legs = 1, leg_on = 0, leg_tick = replan_tick in 0..ticks-1 IS bmpc_stream_rollout_log, bit for bit.  With replan == NULL the call is
+ * bmpc_stream_rollout_log without a re-plan, and the queue arguments are not looked at.  Waves per stream: bmpc_set_rollout_waves, as for the others.
+ * BMPC_ERR_ARG, nothing launched: what bmpc_stream_rollout_log refuses, replan without leg_tick, leg_on or legs_done, legs < 1 with replan. */
+enum { BMPC_LEG_AT_GOAL = 1, BMPC_LEG_ON_LOST = 2, BMPC_LEG_WHY_GOAL = 1, BMPC_LEG_WHY_LOST = 2, BMPC_LEG_WHY_TICK = 4 };
+int bmpc_stream_rollout_legs(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                             double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                             double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan /* [B][legs][len] or NULL */,
+                             int *replan_info /* [B][legs] or NULL */, int update_flags, const double *disturb /* [ticks][B][21] or NULL */,
+                             double *tube_hist /* [ticks][B][16] or NULL */, double *audit /* [B][12] or NULL */, double audit_tol,
+                             double *log_hist /* [ticks][B][88 log_stages + 4] or NULL */, int log_stages, double *track /* [B][12] or NULL */,
+                             int legs, const int *leg_tick /* [B][legs] */, const int *leg_on /* [B][legs] */, const double *leg_tol /* [B][legs] or NULL */,
+                             int *legs_done /* [B] */, int *leg_fired /* [B][legs] or NULL */, int *leg_why /* [B][legs] or NULL */, void *hip_stream);
 
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
