@@ -114,21 +114,127 @@ struct RArgs {
     const double *leg_tol;           // [B][legs] or NULL (goal_tol for every record): the goal tolerance of record k
     int *legs_done;                  // [B], initialised by the kernel: the head of the queue = the records consumed; required with replan
     int *leg_fired, *leg_why;        // [B][legs] or NULL: the tick behind which record k was consumed (-1: never), the conditions that held (0: never)
+    // controller settings per stream (the TU instantiations, bmpc_stream_rollout_tuned): NULL = off, what an initialiser of the members above leaves
+    const double *tune;              // [B][bmpctu::LEN]: row b replaces the launch's settings for every tick of stream b; a NaN slot keeps the launch's
+    int *tune_info;                  // [B] or NULL: the mask of the invalid slots of row b (bit CROSS: the level rule as resolved); 0 = the stream ran
+    double *tune_used;               // [B][bmpctu::LEN] or NULL: the row as resolved, pad words 0
 };
+
+// ---- host and device: a row of per-stream controller settings (BMPC_TUNE_* of include/boundmpc_hip.h), what it resolves to and what is refused ----
+// The slots of a row; a slot holds NaN ("the launch's value") or the value of the option, setter or argument named behind it.
+namespace bmpctu {
+enum { MAX_ITER = 0,      // Opts::max_iter                      (the launch's: the max_iter argument when > 0, else the handle's option)
+       TOL,               // Opts::tol
+       MU_INIT, MU_WARM, MU_MIN_FAC, SLACK_PUSH,      // the barrier start of Opts
+       BOUND_MARGIN,      // Opts::bound_margin
+       HOLD,              // Opts::hold_mu                       (bmpc_set_barrier_hold)
+       LVL_C, LVL_LO, LVL_HI,      // SArgs::lvl_*               (bmpc_stream_set_level_rule)
+       RT_TOL,            // SArgs::rt_tol                       (bmpc_stream_set_rt_feasibility_tol)
+       RT_ROW_CAP,        // SArgs::rt_row_cap                   (bmpc_stream_set_rt_position_row_cap)
+       STALL_WINDOW,      // Opts::stall_window
+       SLOTS,             // the slots that are looked at; the words behind them up to LEN are pad
+       LEN = 16, CROSS = 15 };      // CROSS: the bit of tune_info for the one test across slots
+}
+#define BMPC_TOL_MAX 1.7976931348623157e308      // the largest finite tolerance (plain comparisons: the flop-counting hosts of tests/emu read this file with their own number type)
+#if defined(__HIPCC__)
+#define BMPC_ARGS_HD __host__ __device__ inline
+#else
+#define BMPC_ARGS_HD inline
+#endif
+// the launch's own value of slot k: what a NaN slot resolves to
+template <class OPTS>
+BMPC_ARGS_HD double bmpc_tune_launch_value(int k, const OPTS &o, const SArgs &s) {
+    switch (k) {
+    case bmpctu::MAX_ITER: return (double)o.max_iter;
+    case bmpctu::TOL: return o.tol;
+    case bmpctu::MU_INIT: return o.mu_init;
+    case bmpctu::MU_WARM: return o.mu_warm;
+    case bmpctu::MU_MIN_FAC: return o.mu_min_fac;
+    case bmpctu::SLACK_PUSH: return o.slack_push;
+    case bmpctu::BOUND_MARGIN: return o.bound_margin;
+    case bmpctu::HOLD: return (double)o.hold_mu;
+    case bmpctu::LVL_C: return s.lvl_c;
+    case bmpctu::LVL_LO: return s.lvl_lo;
+    case bmpctu::LVL_HI: return s.lvl_hi;
+    case bmpctu::RT_TOL: return s.rt_tol;
+    case bmpctu::RT_ROW_CAP: return s.rt_row_cap;
+    case bmpctu::STALL_WINDOW: return (double)o.stall_window;
+    default: return 0.0;
+    }
+}
+// THE validity rule of a slot that is not NaN, once: the test of bmpc_create or of the setter that guards the same value (plain comparisons; a cast to
+// int only behind the range test that makes it defined).  NaN never gets here: it is "the launch's value".
+BMPC_ARGS_HD bool bmpc_tune_slot_ok(int k, double v) {
+    if (!(v >= -BMPC_TOL_MAX && v <= BMPC_TOL_MAX)) return false;      // (infinite)
+    switch (k) {
+    case bmpctu::MAX_ITER: return v >= 1.0 && v <= 100000.0 && (double)(int)v == v;
+    case bmpctu::TOL: case bmpctu::MU_INIT: case bmpctu::MU_WARM: case bmpctu::MU_MIN_FAC: case bmpctu::SLACK_PUSH: case bmpctu::RT_TOL: return v > 0.0;
+    case bmpctu::BOUND_MARGIN: return v >= 0.0 && v <= 0.5;
+    case bmpctu::HOLD: return v == 0.0 || v == 1.0;
+    case bmpctu::LVL_C: case bmpctu::LVL_LO: case bmpctu::LVL_HI: case bmpctu::RT_ROW_CAP: return v >= 0.0;
+    case bmpctu::STALL_WINDOW: return v >= 0.0 && v <= 2147483646.0 && (double)(int)v == v && !((int)v & 1);
+    default: return true;      // (pad words: never looked at)
+    }
+}
+// Row `row` against the launch's settings {o, s}: the mask of its invalid slots, bit CROSS for the level rule AS RESOLVED (hi > 0 needs 0 < lo <= hi,
+// the test of bmpc_stream_set_level_rule); 0 = the stream runs.  used (or NULL): the resolved row, a refused value as it was given, pad words 0.
+template <class OPTS>
+BMPC_ARGS_HD int bmpc_tune_check(const double *row, const OPTS &o, const SArgs &s, double *used) {
+    int bad = 0;
+    double lo = 0.0, hi = 0.0;
+    for (int k = 0; k < bmpctu::LEN; k++) {
+        double v = k < bmpctu::SLOTS ? row[k] : 0.0;
+        if (k < bmpctu::SLOTS) {
+            if (v != v) v = bmpc_tune_launch_value(k, o, s);
+            else if (!bmpc_tune_slot_ok(k, v)) bad |= 1 << k;
+        }
+        if (k == bmpctu::LVL_LO) lo = v;
+        if (k == bmpctu::LVL_HI) hi = v;
+        if (used) used[k] = v;
+    }
+    if (hi > 0.0 && !(lo > 0.0 && lo <= hi)) bad |= 1 << bmpctu::CROSS;
+    return bad;
+}
+// A VALID row onto the option record of a solve and onto (a copy of) the stream arguments: every slot that is not NaN replaces its value
+template <class OPTS>
+BMPC_ARGS_HD void bmpc_tune_opts(const double *row, OPTS &o) {
+    double v;
+    v = row[bmpctu::MAX_ITER]; if (v == v) o.max_iter = (int)v;
+    v = row[bmpctu::TOL]; if (v == v) o.tol = v;
+    v = row[bmpctu::MU_INIT]; if (v == v) o.mu_init = v;
+    v = row[bmpctu::MU_WARM]; if (v == v) o.mu_warm = v;
+    v = row[bmpctu::MU_MIN_FAC]; if (v == v) o.mu_min_fac = v;
+    v = row[bmpctu::SLACK_PUSH]; if (v == v) o.slack_push = v;
+    v = row[bmpctu::BOUND_MARGIN]; if (v == v) o.bound_margin = v;
+    v = row[bmpctu::HOLD]; if (v == v) o.hold_mu = (int)v;
+    v = row[bmpctu::STALL_WINDOW]; if (v == v) o.stall_window = (int)v;
+}
+BMPC_ARGS_HD void bmpc_tune_sargs(const double *row, SArgs &s) {
+    double v;
+    v = row[bmpctu::LVL_C]; if (v == v) s.lvl_c = v;
+    v = row[bmpctu::LVL_LO]; if (v == v) s.lvl_lo = v;
+    v = row[bmpctu::LVL_HI]; if (v == v) s.lvl_hi = v;
+    v = row[bmpctu::RT_TOL]; if (v == v) s.rt_tol = v;
+    v = row[bmpctu::RT_ROW_CAP]; if (v == v) s.rt_row_cap = v;
+}
 
 // ---- host only: what the rollout entries of the C ABI refuse and which kernel they run, once (bmpc_hip.hip rollout_launch; the CPU build of the
 // rollout, tests/emu/bmpc_emu_rollout.cpp, asks the same function) ----
 // the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice (needs the robot records), bit 2 poor bounds (with bit 1 only)
 inline bool bmpc_update_flags_ok(int flags, const void *robot) { return !(flags & ~7) && !((flags & 4) && !(flags & 2)) && !((flags & 2) && !robot); }
-// entry: the entry point the caller used -- 0 bmpc_stream_rollout, 1 _events, 2 _audit, 3 _log, 4 _legs; r: its arguments (what an entry has no argument for is
+// entry: the entry point the caller used -- 0 bmpc_stream_rollout, 1 _events, 2 _audit, 3 _log, 4 _legs, 5 _tuned; r: its arguments (what an entry has no argument for is
 // 0 / NULL); N: the handle's horizon; flags, robot: the tick flags and the robot records.  Returns the level of the kernel text to run -- 0 plain, 1 EV,
-// 2 EV + AU, 3 EV + AU + LG, 4 all of them with the queue (QU: the one text that reads a queue, whatever else is on) -- or BMPC_ROLLOUT_REFUSED (the C
-// ABI's BMPC_ERR_ARG).  An entry without the arrays of its own feature IS the entry below it.
+// 2 EV + AU, 3 EV + AU + LG, 4 all of them with the queue (QU: the one text that reads a queue, whatever else is on), 5 all of them with the table of
+// per-stream settings (TU: with or without a queue or any of the other arrays; the table's rows are validated on the device, where they live) -- or
+// BMPC_ROLLOUT_REFUSED (the C ABI's BMPC_ERR_ARG).  An entry without the arrays of its own feature IS the entry below it.
 enum { BMPC_ROLLOUT_REFUSED = -1 };
-#define BMPC_TOL_MAX 1.7976931348623157e308      // the largest finite tolerance (plain comparisons: the flop-counting hosts of tests/emu read this file with their own number type)
 inline int bmpc_rollout_level(int entry, const RArgs &r, int N, int flags, const void *robot) {
     if (r.ticks < 1 || !(r.goal_tol >= 0.0 && r.goal_tol <= BMPC_TOL_MAX)) return BMPC_ROLLOUT_REFUSED;      // (negative, NaN or infinite)
     if (!(flags & 1)) return BMPC_ROLLOUT_REFUSED;                    // without the plant in the loop a second tick repeats the first
+    if (entry == 5) {      // the table: whatever the queue entry refuses; without a table that entry, and no table argument is looked at
+        const int below = bmpc_rollout_level(4, r, N, flags, robot);
+        return (below == BMPC_ROLLOUT_REFUSED || !r.tune) ? below : 5;
+    }
     if (entry == 0) return 0;
     if (entry == 4) {      // the queue: without records the log entry without a re-plan, and no queue argument is looked at
         if (r.replan && (!r.leg_tick || !r.leg_on || !r.legs_done || r.legs < 1)) return BMPC_ROLLOUT_REFUSED;

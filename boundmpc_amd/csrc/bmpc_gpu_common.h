@@ -7,8 +7,9 @@
 // kernels (NW cooperating waves per problem), bmpc_pair.hip the pair kernel, bmpc_resto.hip the restoration kernels, bmpc_tick.hip the
 // one-wave fused ticks, bmpc_rollout.hip the rollouts (many ticks per stream in one launch; kernel text bmpc_rollout_kernel.inl), bmpc_rollout_events.hip the rollouts with events,
 // bmpc_rollout_audit.hip the rollouts with events and the tube audit, bmpc_rollout_log.hip those with the logging records on top, bmpc_rollout_legs.hip
-// those with a queue of re-plan records per stream, bmpc_team_rollout.hip and bmpc_team_rollout_legs.hip the rollouts on teams (the same kernel text
-// with BMPC_NW waves per stream); all seven launch through bmpc_rollout_run (bmpc_rollout_kernel.inl).
+// those with a queue of re-plan records per stream, bmpc_rollout_tune.hip those with a table of controller settings per stream, bmpc_team_rollout.hip,
+// bmpc_team_rollout_legs.hip and bmpc_team_rollout_tune.hip the rollouts on teams (the same kernel text with BMPC_NW waves per stream); all nine launch
+// through bmpc_rollout_run (bmpc_rollout_kernel.inl).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -122,6 +123,8 @@ hipError_t bmpc_rollout_audit_launch(bool zlds, bool resto, const void *kargs, c
 hipError_t bmpc_rollout_log_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // ---- the same with a queue of re-plan records per stream, fired by tick, goal or lost plan (bmpc_rollout_legs.hip; EV, AU, LG and QU) ----
 hipError_t bmpc_rollout_legs_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
+// ---- the same with a table of controller settings per stream, validated and resolved on the device (bmpc_rollout_tune.hip; EV, AU, LG, QU and TU) ----
+hipError_t bmpc_rollout_tune_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // ---- the measurement on its own, one wave per stream of the batch (bmpc_rollout_audit.hip; bmpc_stream_tube.inl) ----
 hipError_t bmpc_stream_tube_launch(int N, int S, int B, const double *p, const double *ss, double *tube, hipStream_t st);
 
@@ -135,6 +138,8 @@ hipError_t bmpc_team_launch_tick(int nw, bool resto, const void *kargs, const SA
 hipError_t bmpc_team_rollout_launch(int nw, bool resto, bool full, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // the same with the queue of re-plan records (bmpc_team_rollout_legs.hip): the fully-featured kernel with QU
 hipError_t bmpc_team_rollout_legs_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
+// the same with the table of controller settings per stream (bmpc_team_rollout_tune.hip): the fully-featured kernel with QU and TU
+hipError_t bmpc_team_rollout_tune_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 int bmpc_team_lds_bytes(int nw);
 int bmpc_team_nmax(int nw);      // longest horizon the team kernels take (their LDS holds most of the workspace)
 

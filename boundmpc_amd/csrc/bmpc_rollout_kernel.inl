@@ -48,9 +48,21 @@
 // goal-triggered record gives the stream its next phi_max before the goal test sees the old one, and an on-lost record rescues the stream.  The head
 // lives in memory (it IS the output legs_done), not in a register: nothing of the queue is carried across the solve, and on a team every wave reads the
 // same word behind a barrier.  Without QU no queue line is compiled and the kernels are the ones from before.
-// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp and
-// bmpc_emu_rollout_legs.cpp, once per BMPC_NW).  The seven units (bmpc_rollout.hip, bmpc_rollout_events.hip, bmpc_rollout_audit.hip, bmpc_rollout_log.hip,
-// bmpc_rollout_legs.hip, bmpc_team_rollout.hip, bmpc_team_rollout_legs.hip) and those builds launch through bmpc_rollout_run at the end of this file, the
+// SWEEPS (the instantiations with TU, bmpc_stream_rollout_tuned; bmpc_rollout_tune.hip, bmpc_team_rollout_tune.hip): a table r.tune[b][bmpctu::LEN] of
+// controller settings per stream -- iteration cap, tolerance, barrier start and hold, level rule, acceptance threshold and position-row cap, joint-limit
+// margin, stall window --, every slot NaN ("the launch's value") or a value that replaces, for every tick of stream b and nothing else, what `a.o` and `s`
+// carry for the whole launch: a grid over settings is one launch of as many streams, not as many handles.  The table lives on the device, so a row is
+// validated here, once per stream ahead of its tick loop, by the rule the host states (bmpc_tune_check, bmpc_args.h): a row with an invalid slot does
+// not run -- no tick, no status word, NaN history rows, its mask in r.tune_info[b] -- and no stream ever runs on a default it did not ask for.  EVERY
+// wave of a team takes that decision itself, from the read-only table and the kernel arguments.  A valid row is resolved AT EVERY TICK, three times, each
+// where its words are consumed: the level rule onto a copy of the stream arguments ahead of the pack, the solver's words onto W.o behind BMPC_WAVE_INIT
+// (which has just rebuilt it from a.o), the acceptance words onto a copy of the stream arguments ahead of the post.  Each is a handful of loads of a
+// wave-uniform row made scalar (BMPCR_UNIFORM_F64), behind an opaque stream index: nothing of the table is carried in a register across the solve but
+// what the solve itself reads, W.o, which it holds in any instantiation.  Without TU no tune line is compiled.
+// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp,
+// bmpc_emu_rollout_legs.cpp and bmpc_emu_rollout_tune.cpp, once per BMPC_NW).  The nine units (bmpc_rollout.hip, bmpc_rollout_events.hip,
+// bmpc_rollout_audit.hip, bmpc_rollout_log.hip, bmpc_rollout_legs.hip, bmpc_rollout_tune.hip, bmpc_team_rollout.hip, bmpc_team_rollout_legs.hip,
+// bmpc_team_rollout_tune.hip) and those builds launch through bmpc_rollout_run at the end of this file, the
 // one place that picks <ZLDS, RESTO>.
 #pragma once
 
@@ -71,13 +83,25 @@ enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH
 // LANES_BEGIN guards against per phase).  Opaque per tick, the body allocates like the fused tick's.  Code generation of this kernel on the GPU only.
 #ifndef BMPC_EMU
 #define BMPCR_OPAQUE(...) asm volatile("" : __VA_ARGS__)
+#define BMPCR_UNIFORM_F64(x) __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(x)), __builtin_amdgcn_readfirstlane(__double2loint(x)))
 #else
 #define BMPCR_OPAQUE(...)
+#define BMPCR_UNIFORM_F64(x) (x)
 #endif
+// (TU) the row of stream b_ as wave-uniform scalars: every lane loads the same words of the read-only table, the first lane's go to scalar registers.
+// Expanded where the words are consumed; the slots a site does not read are dead loads.
+#define BMPCR_TUNE_ROW(tr_, b_) \
+    double tr_[bmpctu::SLOTS]; \
+    { const double *g_ = r.tune + (long long)(b_) * bmpctu::LEN; \
+      _Pragma("unroll") for (int k_ = 0; k_ < bmpctu::SLOTS; k_++) tr_[k_] = BMPCR_UNIFORM_F64(g_[k_]); }
 // (the body of a tick in the kernel itself, as in bmpc_tick_kernel.inl: behind a function that takes `a` the argument loads lose their no-clobber
 // property -- bmpc_args.h, BMPC_PROBLEM)
-template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false, bool LG = false, bool QU = false>
+// (QT: the sixth argument counts what sits on top of the log -- 0 nothing, 1 the queue QU, 2 the queue and the table TU, which is only ever compiled with
+// everything below it on.  One argument for both keeps the kernels' mangled names at the length they had: tests/kernel_resources.py tells a team kernel
+// from a one-wave kernel by the namespace inside the first 70 characters.)
+template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false, bool LG = false, int QT = 0>
 BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
+    constexpr bool QU = QT >= 1, TU = QT == 2;
     static_assert(BMPC_NW == 1 || ZLDS, "a team keeps the iterate in LDS");
     BMPCK_LDS double lds[BMPC_NAMESPACE::L_SIZE];
     BMPC_STRIDES(a);
@@ -109,7 +133,16 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
         }
         if (AU) { if (r.audit && BMPCK_LANE == 0) bmpcs::stream_audit_init(r.audit + (long long)b * bmpcs::AUDIT_LEN); }
         if (LG) { if (r.track && BMPCK_LANE == 0) bmpcs::stream_track_init(r.track + (long long)b * bmpcs::TRACK_LEN); }
-        for (; t < r.ticks; t++) {
+        int bad = 0;      // (TU) the invalid slots of the stream's row: such a stream runs no tick
+        if constexpr (TU) {
+            // (every wave reads the row and the kernel arguments itself; lane 0 of wave 0 stores the mask and the row as resolved)
+            if (r.tune) {
+                const bool out_ = w0 && BMPCK_LANE == 0;
+                bad = BMPCK_UNIFORM(bmpc_tune_check(r.tune + (long long)b * bmpctu::LEN, a.o, s, out_ && r.tune_used ? r.tune_used + (long long)b * bmpctu::LEN : nullptr));
+                if (out_ && r.tune_info) r.tune_info[b] = bad;
+            }
+        }
+        if (!TU || !bad) for (; t < r.ticks; t++) {
             // (the lost-plan test of the fused tick: BoundMPC.step() returns five Nones there and the reference node stops)
             if (BMPCK_UNIFORM((int)(ss[bmpcs::SS_ERRCNT] >= (double)a.N))) {
                 if (BMPCK_LANE == 0) { a.status[b] = 3; if (a.iters) a.iters[b] = 0; if (a.kkt) a.kkt[b] = 0.0; }
@@ -117,7 +150,13 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
             }
             int N_ = a.N, S_ = a.S;
             BMPCR_OPAQUE("+s"(N_), "+s"(S_));      // (what the stream functions are given)
-            if (w0) bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCK_LANE, BMPCK_NL, s.lvl_c, s.lvl_lo, s.lvl_hi);
+            if constexpr (!TU) {
+                if (w0) bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCK_LANE, BMPCK_NL, s.lvl_c, s.lvl_lo, s.lvl_hi);
+            } else {
+                SArgs sp = s;      // (what the pack is given: the launch's level rule, or the stream's)
+                if (r.tune) { int b_ = b; BMPCR_OPAQUE("+s"(b_)); BMPCR_TUNE_ROW(tr_, b_); bmpc_tune_sargs(tr_, sp); }
+                if (w0) bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCK_LANE, BMPCK_NL, sp.lvl_c, sp.lvl_lo, sp.lvl_hi);
+            }
             BMPCK_SYNC();
             if (AU) {
                 // (the stream and the tick opaque, as for the events: what the audit addresses is computed here and dead before the solve)
@@ -129,6 +168,7 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
                 BMPCK_SYNC();      // the solver's reductions reuse the LDS words of the row
             }
             BMPC_WAVE_INIT(W, a, lds, a.scratch + (long long)BMPCK_BLOCK * a.scr_stride, wv); BMPCK_WAVE_HOOK(W);
+            if constexpr (TU) { if (r.tune) { int b_ = b; BMPCR_OPAQUE("+s"(b_)); BMPCR_TUNE_ROW(tr_, b_); bmpc_tune_opts(tr_, W.o); } }      // (W.o has just been rebuilt from a.o)
             BMPC_TICK_PROBLEM(pr, a, b, p, x0, dual);
             BMPCR_OPAQUE("+s"(W.N), "+s"(W.S), "+s"(W.h), "+s"(W.G.b), "+s"(pr.p), "+s"(pr.x0), "+s"(pr.x), "+s"(pr.g), "+s"(pr.state));
             const long long t0_ = a.latency_us ? BMPC_NOW() : 0;
@@ -136,7 +176,13 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
             BMPCK_SYNC();
             if (a.latency_us) busy += BMPC_NOW() - t0_;
             BMPCR_OPAQUE("+s"(N_), "+s"(S_));
-            if (w0) bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, s.rt_tol, sh, BMPCK_LANE, BMPCK_NL, s.rt_row_cap);
+            if constexpr (!TU) {
+                if (w0) bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, s.rt_tol, sh, BMPCK_LANE, BMPCK_NL, s.rt_row_cap);
+            } else {
+                SArgs sq = s;      // (what the post is given: the launch's acceptance words, or the stream's, loaded here, behind the solve)
+                if (r.tune) { int b_ = b; BMPCR_OPAQUE("+s"(b_)); BMPCR_TUNE_ROW(tr_, b_); bmpc_tune_sargs(tr_, sq); }
+                if (w0) bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, sq.rt_tol, sh, BMPCK_LANE, BMPCK_NL, sq.rt_row_cap);
+            }
             BMPCK_SYNC();      // the history and the next pack read ss, rb, x, traj and the dual state that other lanes have just stored
             const long long row = (long long)t * a.B + b;
             if (r.hist && w0) {
@@ -239,18 +285,20 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
     }
 }
 
-// Host: the one place that picks the instantiation <ZLDS, RESTO> of a unit's <EV, AU, LG, QU> and launches it on `grid` workgroups (BMPCK_LAUNCH: the GPU
+// Host: the one place that picks the instantiation <ZLDS, RESTO> of a unit's <EV, AU, LG, QU, TU> (the kernel's sixth argument counts QU and TU) and launches it on `grid` workgroups (BMPCK_LAUNCH: the GPU
 // launch on stream `st`, or the host build's call).  kargs points at a KArgsT<...> record (the layouts are identical across instantiations).  A team
 // keeps the iterate in LDS: its units hold no instantiation without ZLDS.  `static`: every unit has its own -- the name says nothing of the unit's KArgs
 // and BMPC_NW, and the linker would fold the one-wave units' and the team unit's into one.
-template <bool EV, bool AU, bool LG, bool QU = false, class STREAM>
+template <bool EV, bool AU, bool LG, bool QU = false, bool TU = false, class STREAM>
 static void bmpc_rollout_run(bool zlds, bool resto, const void *kargs, const SArgs &s, const RArgs &r, int grid, STREAM st) {
+    static_assert(QU || !TU, "the table sits on top of the queue");
+    constexpr int QT = TU ? 2 : QU ? 1 : 0;
     KArgs a; memcpy(&a, kargs, sizeof(a));
-    if (zlds && resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, true, EV, AU, LG, QU>), grid, st, a, s, r);
-    else if (zlds) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, false, EV, AU, LG, QU>), grid, st, a, s, r);
+    if (zlds && resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, true, EV, AU, LG, QT>), grid, st, a, s, r);
+    else if (zlds) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, false, EV, AU, LG, QT>), grid, st, a, s, r);
     else if constexpr (BMPC_NW == 1) {
-        if (resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<false, true, EV, AU, LG, QU>), grid, st, a, s, r);
-        else BMPCK_LAUNCH((bmpc_stream_rollout_kernel<false, false, EV, AU, LG, QU>), grid, st, a, s, r);
+        if (resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<false, true, EV, AU, LG, QT>), grid, st, a, s, r);
+        else BMPCK_LAUNCH((bmpc_stream_rollout_kernel<false, false, EV, AU, LG, QT>), grid, st, a, s, r);
     }
 }
 

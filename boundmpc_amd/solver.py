@@ -233,6 +233,13 @@ class BatchedOCPSolver:
         _lib.check(self._lib.bmpc_team_info(self._h, int(B), ctypes.byref(w), ctypes.byref(r), ctypes.byref(l)), "bmpc_team_info")
         return dict(waves=w.value, resident_teams=r.value, lds_bytes=l.value)
 
+    def tune_defaults(self, max_iter=0):
+        """The row of controller settings (stream.TUNE, stream.unpack_tune) a rollout launched now with this max_iter argument reads from the handle:
+        what an all-NaN row of StreamBatch.rollout(tune=...) resolves to (bmpc_stream_tune_defaults).  numpy [stream.TUNE["LEN"]], pad words 0."""
+        row = np.zeros(int(self._lib.bmpc_stream_tune_len()))
+        _lib.check(self._lib.bmpc_stream_tune_defaults(self._h, int(max_iter), _ptr(row)), "bmpc_stream_tune_defaults")
+        return row
+
     def set_rt_position_row_cap(self, cap_m2):
         """Real-time stream ticks: a position tube row (l^2 - w^2 of any stage, m^2) above the cap vetoes the iterate (include/boundmpc_hip.h
         bmpc_stream_set_rt_position_row_cap; 0 = off, the default).  Set it before the tick graph is captured."""

@@ -379,6 +379,105 @@ ROLL = dict(ROBOT=0, PHI=43, ERRCNT=44, ITERS=45, STATUS=46, KKT=47, NVALID=48, 
 # a mission (bmpc_stream_rollout_legs, BMPC_LEG_* of include/boundmpc_hip.h): the bits of a record's trigger word leg_on, and of leg_why, the conditions
 # that held when the record fired
 LEG = dict(AT_GOAL=1, ON_LOST=2, WHY_GOAL=1, WHY_LOST=2, WHY_TICK=4)
+# a sweep (bmpc_stream_rollout_tuned, BMPC_TUNE_* of include/boundmpc_hip.h): the slots of a stream's row of controller settings; NaN = the handle's value
+TUNE = dict(MAX_ITER=0, TOL=1, MU_INIT=2, MU_WARM=3, MU_MIN_FAC=4, SLACK_PUSH=5, BOUND_MARGIN=6, HOLD=7, LVL_C=8, LVL_LO=9, LVL_HI=10, RT_TOL=11, RT_ROW_CAP=12,
+            STALL_WINDOW=13, LEN=16)
+TUNE_CROSS = 15      # the bit of tune_info for the one test across slots: the level rule as resolved
+
+
+def tune_len():
+    return TUNE["LEN"]
+
+
+def tune_slot_ok(name, v):
+    """The validity rule of one slot that is not NaN (csrc/bmpc_args.h bmpc_tune_slot_ok, restated): the test of bmpc_create or of the setter that
+    guards the same value."""
+    v = float(v)
+    if not (-np.finfo(np.float64).max <= v <= np.finfo(np.float64).max):
+        return False
+    if name == "MAX_ITER":
+        return 1.0 <= v <= 100000.0 and float(int(v)) == v
+    if name in ("TOL", "MU_INIT", "MU_WARM", "MU_MIN_FAC", "SLACK_PUSH", "RT_TOL"):
+        return v > 0.0
+    if name == "BOUND_MARGIN":
+        return 0.0 <= v <= 0.5
+    if name == "HOLD":
+        return v == 0.0 or v == 1.0
+    if name in ("LVL_C", "LVL_LO", "LVL_HI", "RT_ROW_CAP"):
+        return v >= 0.0
+    if name == "STALL_WINDOW":
+        return 0.0 <= v <= 2147483646.0 and float(int(v)) == v and not int(v) & 1
+    raise KeyError(name)
+
+
+def tune_check(row, defaults=None):
+    """What the device answers for `row` [TUNE_LEN] in tune_info: the bit mask of its invalid slots, bit TUNE_CROSS where the level rule as resolved fails
+    (LVL_HI > 0 needs 0 < LVL_LO <= LVL_HI).  defaults: the row NaN slots resolve to (BatchedOCPSolver.tune_defaults); None: the cross-slot test runs on
+    the slots that are given, a NaN level counting as fine."""
+    row = np.asarray(row, dtype=np.float64)
+    assert row.shape == (TUNE["LEN"],)
+    bad = 0
+    for name, k in TUNE.items():
+        if name != "LEN" and not np.isnan(row[k]) and not tune_slot_ok(name, row[k]):
+            bad |= 1 << k
+    lo, hi = (row[TUNE[n]] if not np.isnan(row[TUNE[n]]) else (defaults[TUNE[n]] if defaults is not None else np.nan) for n in ("LVL_LO", "LVL_HI"))
+    if not np.isnan(lo) and not np.isnan(hi) and hi > 0.0 and not (lo > 0.0 and lo <= hi):      # (a level only the handle knows: the device decides)
+        bad |= 1 << TUNE_CROSS
+    return bad
+
+
+def tune_table(B, fixed_barrier=None, level_c=0.02, **columns):
+    """The table of a sweep, [B][TUNE_LEN] float64 for StreamBatch.rollout(tune=...): per slot name (any case: max_iter=, tol=, mu_init=, mu_warm=,
+    mu_min_fac=, slack_push=, bound_margin=, hold=, lvl_c=, lvl_lo=, lvl_hi=, rt_tol=, rt_row_cap=, stall_window=) a scalar or a length-B array; NaN
+    (a slot not named, or an entry of an array) keeps the handle's value for that stream.
+    fixed_barrier: one setting for every stream, or a LIST of B settings (None: nothing for that stream), each of which expands exactly as BatchedOCPSolver(fixed_barrier=...) does -- None: nothing; "auto": the pair
+    (0.01, 0.1); a pair (lo, hi): HOLD 1, the level rule (level_c, lo, hi), MU_INIT hi, MU_WARM lo, MU_MIN_FAC lo / tol; a float f: one fixed level,
+    HOLD 0, no level rule, MU_INIT = MU_WARM = f, MU_MIN_FAC f / tol.  It needs the stream's `tol` column (the constructor's own tol), and the slots
+    it sets must not be named as well.
+    Raises ValueError on what the device would refuse (tune_check without defaults)."""
+    B = int(B)
+    T = np.full((B, TUNE["LEN"]), np.nan)
+    for name, col in columns.items():
+        k = TUNE.get(name.upper())
+        if k is None or name.upper() == "LEN":
+            raise ValueError(f"no slot {name!r}: {', '.join(n.lower() for n in TUNE if n != 'LEN')}")
+        col = np.asarray(col, dtype=np.float64)
+        if col.ndim and col.shape != (B,):
+            raise ValueError(f"{name} must be a scalar or [{B}], got {list(col.shape)}")
+        T[:, k] = col
+    if fixed_barrier is not None:
+        per = fixed_barrier if isinstance(fixed_barrier, list) else [fixed_barrier] * B
+        if len(per) != B:
+            raise ValueError(f"fixed_barrier must be one setting or a list of {B}")
+        sets = ("HOLD", "LVL_C", "LVL_LO", "LVL_HI", "MU_INIT", "MU_WARM", "MU_MIN_FAC")
+        for b, fb in enumerate(per):
+            if fb is None:
+                continue
+            if any(not np.isnan(T[b, TUNE[n]]) for n in sets):
+                raise ValueError("fixed_barrier sets hold, lvl_*, mu_init, mu_warm and mu_min_fac itself")
+            if np.isnan(T[b, TUNE["TOL"]]):
+                raise ValueError("fixed_barrier needs the tol column: the final level is tol * mu_min_fac")
+            auto = isinstance(fb, (str, tuple, list))
+            if isinstance(fb, str) and fb != "auto":
+                raise ValueError(f"fixed_barrier {fb!r}: 'auto', a pair (lo, hi) or a float")
+            lo, hi = (0.01, 0.1) if isinstance(fb, str) else ((float(fb[0]), float(fb[1])) if auto else (float(fb),) * 2)
+            rule = (float(level_c), lo, hi) if auto else (0.0, 0.0, 0.0)
+            T[b, [TUNE[n] for n in sets]] = [1.0 if auto else 0.0, *rule, hi, lo, lo / T[b, TUNE["TOL"]]]
+    for b in range(B):
+        bad = tune_check(T[b])
+        if bad:
+            names = [n.lower() for n, k in TUNE.items() if n != "LEN" and bad >> k & 1] + (["the level rule (lvl_hi > 0 needs 0 < lvl_lo <= lvl_hi)"] if bad >> TUNE_CROSS & 1 else [])
+            raise ValueError(f"tune row {b}: invalid {', '.join(names)}")
+    return T
+
+
+def unpack_tune(row):
+    """A row of a sweep's table (tune_table(...)[b], rollout()["tune_used"][b], BatchedOCPSolver.tune_defaults(); numpy) -> dict of its slots by lower-case
+    name: max_iter, hold and stall_window as int, the rest float; None for a slot that holds NaN."""
+    row = np.asarray(row, dtype=np.float64)
+    assert row.shape == (TUNE["LEN"],)
+    ints = ("MAX_ITER", "HOLD", "STALL_WINDOW")
+    return {n.lower(): (None if np.isnan(row[k]) else (int(row[k]) if n in ints and np.isfinite(row[k]) else float(row[k]))) for n, k in TUNE.items() if n != "LEN"}
 
 
 def rollout_len():
@@ -733,7 +832,7 @@ class StreamBatch:
 
     def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None,
                 replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None, audit=False, audit_tol=1e-6, want_tube=False,
-                want_log=False, log_stages=1, track=False, waves=None, legs=None, leg_tick=None, leg_on=None, leg_tol=None):
+                want_log=False, log_stages=1, track=False, waves=None, legs=None, leg_tick=None, leg_on=None, leg_tol=None, tune=None, want_tune_used=False):
         """`ticks` closed-loop ticks (plant simulation on) of every stream in ONE launch (bmpc_stream_rollout): each stream runs at its own pace, so
         the launch lasts as long as the slowest stream's SUM of solves, where a loop of tick() / tick_graph() pays the slowest stream of every tick.
         For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, a time
@@ -781,14 +880,25 @@ class StreamBatch:
         phi_max before the goal test sees the old one (with goal_tol > 0 a stream stops only at the goal of its last leg), an on-lost record rescues it.
         Then the result also holds  legs_done [B] int32: records consumed;  leg_fired [B][K]: the tick behind which record k was consumed, -1 never;
         leg_why [B][K]: LEG["WHY_GOAL"] | LEG["WHY_LOST"] | LEG["WHY_TICK"], 0 never;  replan_info [B][K]: -1 not consumed, 0 consumed, 1 invalid.
-        The audit and the tracking record run over the whole mission; per-leg spans follow from leg_fired."""
+        The audit and the tracking record run over the whole mission; per-leg spans follow from leg_fired.
+        SWEEPS (bmpc_stream_rollout_tuned; with or without `legs`, not with replan / replan_tick; without `tune` nothing changes): controller settings
+        per stream in the place of the one set the handle carries -- a grid over settings is one launch of as many streams, not as many handles.
+          tune [B][TUNE_LEN]               `tune_table(B, ...)`, an array or a device tensor (taken as it is): row b, slots TUNE, replaces for every
+                                           tick of stream b the iteration cap, tol, the barrier start and hold, the level rule, the acceptance threshold
+                                           and position-row cap, bound_margin and the stall window; a NaN slot keeps the handle's value as this launch
+                                           reads it (MAX_ITER: the max_iter argument when > 0).  An iteration cap in the table needs warm_dual as well.
+        The rows are validated on the device.  A row with an invalid slot does not run: ticks_run 0, NaN rows, untouched tick arrays, and
+          tune_info [B] int32              0: the row was valid and the stream ran; else the bit mask of its invalid slots (bit TUNE_CROSS: the level
+                                           rule as resolved) -- READ IT: the other streams are served as if the row were not there
+          tune_used [B][TUNE_LEN]          want_tune_used: the rows as resolved (unpack_tune), what the streams ran with or were refused for.
+        Every array of stream b holds what the same call without a table leaves for the one-stream batch {b} on a solver set up from tune_used[b]."""
         import torch
         if waves is not None:
             former = self.solver.rollout_waves
             self.solver.set_rollout_waves(waves)      # (a refused value raises here, the setting intact)
             try:
                 return self.rollout(ticks, max_iter, warm_dual, accept_capped, goal_tol, want_traj, stream, replan, replan_tick, splice, poor_bounds, set_goal,
-                                    disturb, audit, audit_tol, want_tube, want_log, log_stages, track, None, legs, leg_tick, leg_on, leg_tol)
+                                    disturb, audit, audit_tol, want_tube, want_log, log_stages, track, None, legs, leg_tick, leg_on, leg_tol, tune, want_tune_used)
             finally:
                 self.solver.set_rollout_waves(former)
         if max_iter and not warm_dual:
@@ -813,6 +923,29 @@ class StreamBatch:
         if track:
             assert self.solver._lib.bmpc_stream_track_len() == TRACK["LEN"]
             out["track"] = torch.empty((self.B, TRACK["LEN"]), dtype=torch.float64, device=dev)
+        if tune is not None:
+            if replan is not None or replan_tick is not None:
+                raise ValueError("tune goes with legs, the queue of re-plan records: it does not go with replan / replan_tick")
+            assert self.solver._lib.bmpc_stream_tune_len() == TUNE["LEN"]
+            tune = self._dev64(tune, (self.B, TUNE["LEN"]), "tune", stream)
+            out["tune_info"] = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
+            if want_tune_used:
+                out["tune_used"] = torch.empty((self.B, TUNE["LEN"]), dtype=torch.float64, device=dev)
+            tuned = (_ptr(tune), _ptr(out["tune_info"]), _ptr(out["tune_used"]) if want_tune_used else None)
+        elif want_tune_used:
+            raise ValueError("want_tune_used goes with tune")
+        if tune is not None and legs is None:      # a sweep without a queue: replan = NULL, and no queue argument is looked at
+            if leg_tick is not None or leg_on is not None or leg_tol is not None:
+                raise ValueError("leg_tick, leg_on and leg_tol describe the records of legs")
+            if disturb is not None:
+                disturb = self._dev64(disturb, (n, self.B, DIST_LEN), "disturb", stream)
+            _lib.check(self.solver._lib.bmpc_stream_rollout_tuned(
+                self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]), _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]),
+                None, None, self._update_flags(set_goal, splice, poor_bounds), _ptr(disturb) if disturb is not None else None, _ptr(out["tube_hist"]) if want_tube else None,
+                _ptr(out["audit"]) if audit else None, float(audit_tol), _ptr(out["log_hist"]) if want_log else None, int(log_stages), _ptr(out["track"]) if track else None,
+                0, None, None, None, None, None, None, *tuned, self._stream(stream)), "bmpc_stream_rollout_tuned")
+            self._event_inputs = (tune, disturb)      # the launch is asynchronous: its inputs live until the next one replaces them
+            return out
         if legs is not None:
             if replan is not None or replan_tick is not None:
                 raise ValueError("legs is the queue of re-plan records: it does not go with replan / replan_tick")
@@ -827,13 +960,14 @@ class StreamBatch:
             out["legs_done"] = torch.zeros((self.B,), dtype=torch.int32, device=dev)
             out["leg_fired"], out["replan_info"] = (torch.full((self.B, K), -1, dtype=torch.int32, device=dev) for _ in range(2))
             out["leg_why"] = torch.zeros((self.B, K), dtype=torch.int32, device=dev)
-            _lib.check(self.solver._lib.bmpc_stream_rollout_legs(
+            entry, name = (self.solver._lib.bmpc_stream_rollout_legs, "bmpc_stream_rollout_legs") if tune is None else (self.solver._lib.bmpc_stream_rollout_tuned, "bmpc_stream_rollout_tuned")
+            _lib.check(entry(
                 self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]), _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]),
                 _ptr(self.legs), _ptr(out["replan_info"]), flags, _ptr(disturb) if disturb is not None else None, _ptr(out["tube_hist"]) if want_tube else None,
                 _ptr(out["audit"]) if audit else None, float(audit_tol), _ptr(out["log_hist"]) if want_log else None, int(log_stages), _ptr(out["track"]) if track else None,
                 K, _ptr(leg_tick), _ptr(leg_on), _ptr(leg_tol) if leg_tol is not None else None, _ptr(out["legs_done"]), _ptr(out["leg_fired"]), _ptr(out["leg_why"]),
-                self._stream(stream)), "bmpc_stream_rollout_legs")
-            self._event_inputs = (leg_tick, leg_on, leg_tol, disturb)      # the launch is asynchronous: its inputs live until the next one replaces them
+                *(tuned if tune is not None else ()), self._stream(stream)), name)
+            self._event_inputs = (leg_tick, leg_on, leg_tol, disturb, tune)      # the launch is asynchronous: its inputs live until the next one replaces them
             return out
         if leg_tick is not None or leg_on is not None or leg_tol is not None:
             raise ValueError("leg_tick, leg_on and leg_tol describe the records of legs")

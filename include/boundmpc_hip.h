@@ -298,7 +298,7 @@ int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const double *path, in
                         double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
                         double goal_tol, double *hist /* [ticks][B][52] or NULL */, double *traj_hist /* [ticks][B][traj] or NULL */,
                         int *ticks_run /* [B] or NULL */, void *hip_stream);
-/* Waves per stream of the five rollout entries (bmpc_stream_rollout, _events, _audit, _log, _legs), read at launch time:
+/* Waves per stream of the six rollout entries (bmpc_stream_rollout, _events, _audit, _log, _legs, _tuned), read at launch time:
  *   1 (default)   one wave per stream, on the resident waves of the device;
  *   BMPC_TEAM_NW  a team of cooperating waves per stream whatever B is, striding over the resident teams (256 on an MI355X: a team owns a CU);
  *                 BMPC_ERR_ARG on a handle without team kernels (N > 10 or S > 4), as bmpc_set_team_waves;
@@ -503,6 +503,49 @@ int bmpc_stream_rollout_legs(bmpc_handle *h, int B, int ticks, const double *pat
                              double *log_hist /* [ticks][B][88 log_stages + 4] or NULL */, int log_stages, double *track /* [B][12] or NULL */,
                              int legs, const int *leg_tick /* [B][legs] */, const int *leg_on /* [B][legs] */, const double *leg_tol /* [B][legs] or NULL */,
                              int *legs_done /* [B] */, int *leg_fired /* [B][legs] or NULL */, int *leg_why /* [B][legs] or NULL */, void *hip_stream);
+/* Rollout for SWEEPS: bmpc_stream_rollout_legs (its arguments in their order up to and including leg_why, their meaning, tests and contract; NULL
+ * event, audit, log and queue pointers switch those off) with a TABLE of controller settings per stream in the place of the one set the handle carries
+ * for a whole launch -- a grid over (level rule, cap, margin, acceptance), or a robustness battery with its own joint-limit margin per stream, is ONE
+ * launch of as many streams, not as many handles with as many workspaces:
+ *   tune       [B][BMPC_TUNE_LEN] or NULL, DEVICE: row b, slots BMPC_TUNE_*; the two words behind BMPC_TUNE_STALL_WINDOW are pad and never looked at
+ *   tune_info  [B] or NULL: 0 = row b was valid and the stream ran; else the bit mask of its invalid slots (bit k = slot k, bit 15 = the level rule
+ *              as resolved, below)
+ *   tune_used  [B][BMPC_TUNE_LEN] or NULL: the row as resolved, pad words 0; for an invalid row the row as resolved too, the refused values as given
+ * A slot that holds NaN takes the handle's value AS THE LAUNCH READS IT (for BMPC_TUNE_MAX_ITER the max_iter argument when it is > 0, else
+ * options.max_iter).  Any other value replaces it for every tick of stream b and for nothing else:
+ *   MAX_ITER, TOL, MU_INIT, MU_WARM, MU_MIN_FAC, SLACK_PUSH, BOUND_MARGIN, STALL_WINDOW   the options of bmpc_create of the same names, in every solve
+ *   HOLD                                bmpc_set_barrier_hold, in every solve
+ *   LVL_C, LVL_LO, LVL_HI               bmpc_stream_set_level_rule, in every pack
+ *   RT_TOL, RT_ROW_CAP                  bmpc_stream_set_rt_feasibility_tol, bmpc_stream_set_rt_position_row_cap, in every post
+ * The restoration mode, its short-step count and cap, the Hessian choice, the tick flags and the waves per stream stay the handle's.
+ * A slot that is not NaN is valid when it passes the test that guards the same value in bmpc_create or in its setter: finite; MAX_ITER an integer in
+ * 1..100000; TOL, MU_INIT, MU_WARM, MU_MIN_FAC, SLACK_PUSH, RT_TOL > 0; BOUND_MARGIN in [0, 0.5]; HOLD 0 or 1; LVL_C, LVL_LO, LVL_HI, RT_ROW_CAP >= 0;
+ * STALL_WINDOW an even integer >= 0.  One test runs across slots, on the row as resolved: LVL_HI > 0 needs 0 < LVL_LO <= LVL_HI.
+ * The table lives on the device, so it is validated there, as the trigger words of a mission are.  A row with an invalid slot DOES NOT RUN -- a sweep
+ * never runs silently on a default: ticks_run[b] = 0, the rows of stream b in every history array are NaN, its audit and tracking records are those of
+ * a stream lost on entry, legs_done[b] = 0 and its records keep their flags, and its tick arrays -- status, iters and kkt included -- keep every bit.
+ * Every other stream is served as if the row were not there.
+ * With tune == NULL the call IS bmpc_stream_rollout_legs, and tune_info and tune_used are not looked at.  With a table of NaN it leaves what that
+ * entry leaves, bit for bit.  Otherwise every array of stream b holds what the same call without a table leaves for the one-stream batch {b} on a
+ * handle whose options and setters carry tune_used[b], bit for bit, on one wave per stream or on teams (bmpc_set_rollout_waves, as for the others): a
+ * stream's result does not depend on the batch it is in nor on the workgroup that serves it.
+ * bmpc_stream_tune_defaults writes the row an all-NaN row resolves to on this handle with this max_iter argument (HOST, BMPC_TUNE_LEN doubles).
+ * BMPC_ERR_ARG, nothing launched: what bmpc_stream_rollout_legs refuses; bmpc_stream_tune_defaults: no handle, max_iter < 0, no row. */
+enum { BMPC_TUNE_MAX_ITER = 0, BMPC_TUNE_TOL, BMPC_TUNE_MU_INIT, BMPC_TUNE_MU_WARM, BMPC_TUNE_MU_MIN_FAC, BMPC_TUNE_SLACK_PUSH, BMPC_TUNE_BOUND_MARGIN,
+       BMPC_TUNE_HOLD, BMPC_TUNE_LVL_C, BMPC_TUNE_LVL_LO, BMPC_TUNE_LVL_HI, BMPC_TUNE_RT_TOL, BMPC_TUNE_RT_ROW_CAP, BMPC_TUNE_STALL_WINDOW,
+       BMPC_TUNE_LEN = 16 };      /* two pad words, never looked at */
+int bmpc_stream_tune_len(void);
+int bmpc_stream_tune_defaults(const bmpc_handle *h, int max_iter, double *row /* HOST [BMPC_TUNE_LEN] */);
+int bmpc_stream_rollout_tuned(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                              double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                              double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan /* [B][legs][len] or NULL */,
+                              int *replan_info /* [B][legs] or NULL */, int update_flags, const double *disturb /* [ticks][B][21] or NULL */,
+                              double *tube_hist /* [ticks][B][16] or NULL */, double *audit /* [B][12] or NULL */, double audit_tol,
+                              double *log_hist /* [ticks][B][88 log_stages + 4] or NULL */, int log_stages, double *track /* [B][12] or NULL */,
+                              int legs, const int *leg_tick /* [B][legs] */, const int *leg_on /* [B][legs] */, const double *leg_tol /* [B][legs] or NULL */,
+                              int *legs_done /* [B] */, int *leg_fired /* [B][legs] or NULL */, int *leg_why /* [B][legs] or NULL */,
+                              const double *tune /* [B][BMPC_TUNE_LEN] or NULL */, int *tune_info /* [B] or NULL */,
+                              double *tune_used /* [B][BMPC_TUNE_LEN] or NULL */, void *hip_stream);
 
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
