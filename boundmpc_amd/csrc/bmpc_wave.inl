@@ -711,6 +711,11 @@ BMPC_D inline void wave_init_tables(Wave &W, const POff &po) {
     LANES_END
     LANES_BEGIN
         if (lane < 20) L[L_CFT + lane] = chain_cf(W.h, lane / 5, lane % 5);
+#if BMPC_NW == 1
+        // t6 of the Riccati sweep: stage 0 reads it behind a 0/1 factor and only the stages k >= 1 write it -- at N = 1 nobody does, and what
+        // LDS held before (a NaN of an earlier kernel) would pass the factor (0 x NaN)
+        if (lane < 6) L[L_T6 + lane] = 0.0;
+#endif
         if (lane < NS) {
             const int r = lane;
             const int z = r < 7 ? ZQ + r : (r < 14 ? ZDQ + r - 7 : (r < SJ ? ZDDQ + r - SDDQ : (r < SPHI ? ZJ + r - SJ : (r == SPHI ? ZPHI : (r == SDPHI ? ZDPHI :

@@ -94,6 +94,17 @@ def newton_dir(p, x, t, nu, mu, N, S, h, exact=1, delta=0.0):
     return rc, dZ
 
 
+def debug_qp(p, x, t, nu, mu, N, S, h, exact=1, delta=0.0):
+    """The reduced QP of one Newton system at (x, t, nu, mu) and its Riccati solution (bmpc_oracle_debug_qp): dict with rc (0, or 3 where a
+    stage block is not positive definite), Qt, qt, Xt, A, rdyn, T, rloc, Kg [N][8][35], kff [N][8], dZ [44 N]."""
+    arrs = [np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (p, x, t, nu)]
+    o = dict(Qt=np.zeros((N, 35, 35)), qt=np.zeros((N, 35)), Xt=np.zeros((N, 35, 35)), A=np.zeros((N, 35, 43)), rdyn=np.zeros((N, 35)),
+             T=np.zeros((N, NZ, 35)), rloc=np.zeros((N, NZ)), Kg=np.zeros((N, 8, 35)), kff=np.zeros((N, 8)), dZ=np.zeros(N * NZ))
+    o["rc"] = lib().bmpc_oracle_debug_qp(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), *[_p(v) for v in arrs], ctypes.c_double(mu), ctypes.c_int(exact),
+                                         ctypes.c_double(delta), *[_p(o[k]) for k in ("Qt", "qt", "Xt", "A", "rdyn", "T", "rloc", "Kg", "kff", "dZ")])
+    return o
+
+
 def state_len(N):
     return N * 57 + 2
 

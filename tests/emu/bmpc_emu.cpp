@@ -131,6 +131,56 @@ extern "C" int EMU_STREAM_TICK(int N, int S, double h, const ns::Opts *opts, int
 }
 #endif
 
+// debug: ONE Newton direction at (x, t, nu, mu) with the regularisation delta, through the calls of wave_solve's Newton system in its order
+// (evaluation, adjoint, row data, QP gradient, stage data, team_backward, wave_forward on wave 0, teams: wave_dz_wide) on the instantiation the
+// solve entries choose.  Every wave program: one wave (any shape), teams and pairs (N <= TEAM_NMAX, S <= 4: their kernels' shapes).  Out: the gains
+// kt [N][8][35], the feed-forward kf [N][8], the direction dz [N][44].  Returns 0, 3 (a stage block is not positive definite) or 1 (shape).
+#if BMPC_NW > 1
+#define EMU_NEWTON bmpc_emu_team_newton
+#else
+#define EMU_NEWTON bmpc_emu_newton
+#endif
+extern "C" int EMU_NEWTON(int N, int S, double h, const ns::Opts *opts, const double *p, const double *x, const double *t, const double *nu, double mu, double delta,
+                          double *kt, double *kf, double *dz, int lane_order, int wave_order) {
+    using namespace ns;
+    if (!emu_shape_ok(N, S)) return 1;
+    const bool zl = emu_zlds(N, S);
+#if BMPC_NW > 1
+    if (N > TEAM_NMAX || !zl) return 1;
+#endif
+    const Scr sc = make_scr(N); const POff po = make_poff_lds(S, L_ZL);
+    std::vector<double> lds(L_SIZE, 0.0), scr(sc.size, 0.0);
+    Wave W = emu_wave(emu_args(N, S, 1, h, *opts), lds, scr, lane_order, wave_order, true);      // (poisoned: the entry reads only what it wrote)
+    double *L = W.L; const GPtr G = W.G; const LPtr WL = BMPC_WL(W);
+    for (int i = 0; i < po.size; i++) L[L_PAR + (zl ? i : lds_index_of_p(S, i, L_ZL))] = p[i];
+    wave_init_tables(W, po);
+    W.Zc = zl ? L + L_ZL : (G + sc.Z).ptr(); W.Zt = zl ? L + L_PB : (G + sc.ZT).ptr(); W.Dz = zl ? L + L_PB + 512 : (G + sc.DZ).ptr();
+    for (int i = 0; i < N * NZ; i++) W.Zc[i] = x[i];
+    wave_eval(W, po, sc, W.Zc, sc.G, sc.HIN, false);
+    BMPC_LANE_REGS(LRs);
+    for (int i = 0; i < N * NI; i++) {      // row pass A of wave_solve on the caller's slacks and multipliers
+        const double tt = t[i], nn = nu[i], ti = 1.0 / tt;
+        WL[sc.T + i] = tt; WL[sc.NUm + i] = nn; WL[sc.SG + i] = nn * ti; WL[sc.TI + i] = ti; WL[sc.SR + i] = nn * ti * (WL[sc.HIN + i] + tt);
+    }
+    wave_adjoint(W, po, sc, sc.NUm, false, 0.0, LRs);
+    wave_adjoint(W, po, sc, sc.NUm, true, mu, LRs);
+    wave_stage_data_wide(W, po, sc);
+    const bool ok = team_backward(W, po, sc, mu, delta, LRs);
+    if (ok) {
+        SOLO_BEGIN(0)
+        wave_forward(W, sc, LRs);
+        SOLO_END
+        TEAM_SYNC();
+#if BMPC_NW > 1
+        wave_dz_wide(W, sc, LRs);
+#endif
+        for (int i = 0; i < N * NS * NU; i++) kt[i] = G[sc.KT + i];
+        for (int i = 0; i < N * NU; i++) kf[i] = G[sc.KF + i];
+        for (int i = 0; i < N * NZ; i++) dz[i] = W.Dz[i];
+    }
+    return ok ? 0 : 3;
+}
+
 #if BMPC_NW == 1
 // CPU build of the stream functions (same text as the device kernels), one call per stream
 extern "C" void bmpc_emu_stream_lengths(int N, int *out) { out[0] = bmpcs::PT_LEN; out[1] = bmpcs::ss_len(N); out[2] = bmpcs::RB_LEN; out[3] = bmpcs::tr_len(N); }
@@ -152,36 +202,6 @@ extern "C" void bmpc_emu_fk_motion(const double *q, const double *dq, const doub
     for (int c = 0; c < 3; c++) out[18 + c] = M.jk[c];
 }
 
-// debug: one Newton direction at (x, t, nu, mu); dumps the scratch slab
-extern "C" int bmpc_emu_newton(int N, int S, double h, const bmpc::Opts *opts, const double *p, const double *x, const double *t, const double *nu,
-                               double mu, double delta, double *scratch_out, double *lds_out) {
-    using namespace bmpc;
-    const Scr sc = make_scr(N); const POff po = make_poff_lds(S, L_ZL);
-    std::vector<double> lds(L_SIZE, 0.0), scr(sc.size, 0.0);
-    Wave W = emu_wave(emu_args(N, S, 1, h, *opts), lds, scr, 0);
-    for (int i = 0; i < po.size; i++) W.L[L_PAR + lds_index_of_p(S, i, L_ZL)] = p[i];
-    wave_init_tables(W, po);
-    const bool zl = emu_zlds(N, S); W.Zc = zl ? W.L + L_ZL : (W.G + sc.Z).ptr(); W.Zt = zl ? W.L + L_PB : (W.G + sc.ZT).ptr(); W.Dz = zl ? W.L + L_PB + 512 : (W.G + sc.DZ).ptr();
-    for (int i = 0; i < N * NZ; i++) W.Zc[i] = x[i];
-    for (int i = 0; i < N * NI; i++) { W.G[sc.T + i] = t[i]; W.G[sc.NUm + i] = nu[i]; }
-    wave_eval(W, po, sc, W.Zc, sc.G, sc.HIN, false);
-    LaneRegs LRs[64];
-    wave_adjoint(W, po, sc, sc.NUm, false, 0.0, LRs);
-    for (int i = 0; i < N * NI; i++) { const double tt = W.G[sc.T + i], nn = W.G[sc.NUm + i]; W.G[sc.SG + i] = nn / tt; W.G[sc.TI + i] = 1.0 / tt; W.G[sc.SR + i] = nn / tt * (W.G[sc.HIN + i] + tt); }
-    wave_adjoint(W, po, sc, sc.NUm, true, mu, LRs);
-    wave_stage_data_wide(W, po, sc);
-    bool ok = wave_backward_blk(W, po, sc, mu, delta, LRs);
-    if (ok) wave_forward(W, sc, LRs);
-    if (ok) for (int i = 0; i < N * NZ; i++) W.G[sc.DZ + i] = W.Dz[i];
-    memcpy(scratch_out, scr.data(), sizeof(double) * sc.size);
-    memcpy(lds_out, lds.data(), sizeof(double) * L_SIZE);
-    return ok ? 0 : 3;
-}
-extern "C" void bmpc_emu_scr_offsets(int N, int *out) {
-    const bmpc::Scr s = bmpc::make_scr(N);
-    int v[] = {s.Z, s.ZT, s.T, s.TT, s.NUm, s.LAM, s.G, s.GT, s.HIN, s.HT, s.DZ, s.DT, s.DNU, s.GH, s.GVP, s.RJ, s.KIN, s.REF, s.KT, s.KF, s.RDY, s.AES, s.RLV, s.SG, s.TI, s.SR, s.size};
-    for (unsigned i = 0; i < sizeof(v) / sizeof(int); i++) out[i] = v[i];
-}
 extern "C" void bmpc_emu_sincos(int n, const double *x, double *s, double *c) { for (int i = 0; i < n; i++) bmpc::bmpc_sincos(x[i], s + i, c + i); }
 // the library's horizon rule (csrc/bmpc_args.h): the option record of a handle of horizon N, its size, the longest short horizon
 extern "C" void bmpc_emu_opts_for(int N, bmpc::Opts *o) { bmpc_opts_for(N, *o); }

@@ -105,6 +105,20 @@ def solve_team(p, x0, N, S, h, nw=4, opts=None, lane_order=0, wave_order=0, nthr
     return _solve(team_lib(nw).bmpc_emu_team_solve, p, x0, N, S, h, opts, lane_order, wave_order, nthreads, state, poison)
 
 
+def newton(p, x, t, nu, mu, delta, N, S, h, nw=1, opts=None, lane_order=0, wave_order=0):
+    """ONE Newton direction of the wave program at the interior point (x, t, nu) on the barrier level mu with the regularisation delta, through the
+    calls of wave_solve's Newton system (bmpc_emu.cpp EMU_NEWTON); nw = 1, 4, 2 or "pair".  Returns (rc, KT [N][8][35], KF [N][8], dZ [44 N]);
+    rc 0, or 3 where a stage block is not positive definite (the arrays are zero then)."""
+    a = [np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (p, x, t, nu)]
+    assert a[0].size == 141 + 91 * S and a[1].size == 44 * N and a[2].size == 57 * N and a[3].size == 57 * N
+    kt, kf, dz = np.zeros((N, 8, 35)), np.zeros((N, 8)), np.zeros(44 * N)
+    entry = lib().bmpc_emu_newton if nw == 1 else team_lib(nw).bmpc_emu_team_newton
+    rc = entry(ctypes.c_int(N), ctypes.c_int(S), ctypes.c_double(h), ctypes.byref(opts if opts is not None else default_opts()), *[_p(v) for v in a],
+               ctypes.c_double(mu), ctypes.c_double(delta), _p(kt), _p(kf), _p(dz), ctypes.c_int(lane_order), ctypes.c_int(wave_order))
+    assert rc in (0, 3), rc
+    return rc, kt, kf, dz
+
+
 # ---- CPU build of the stream functions (boundmpc_amd/csrc/bmpc_stream.inl) ----
 def stream_lengths(N):
     out = (ctypes.c_int * 4)()

@@ -127,32 +127,59 @@ def test_emu_other_window_sizes_and_horizons(S, N):
 def test_emu_newton_direction_equals_oracle_dense_solve(N):
     """One Newton direction at a random interior point: the wave program's block-Riccati (gains, feed-forward, dZ) against the
     oracle's dense per-stage Riccati on the same QP -- isolates the linear algebra from the globalisation."""
-    import ctypes
     from oracle import nlp
-    L, CO = emu.lib(), c_oracle.lib()
     d = np.load(os.path.join(G, "g6_pack_exp1_tick0.npz"))
     p, x0f = d["p_f64"], d["x0_f64"]
-    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)
-    names = "Z ZT T TT NUm LAM G GT HIN HT DZ DT DNU GH GVP RJ KIN REF KT KF RDY AES RLV SG TI SR size".split()
     rng = np.random.default_rng(3 + N)
     S, h = 4, 0.1
-    offs = (ctypes.c_int * len(names))(); L.bmpc_emu_scr_offsets(N, offs); off = dict(zip(names, list(offs)))
     x = x0f[:44 * N] + rng.normal(size=44 * N) * 0.02
     x.reshape(N, 44)[:, 41] = np.linspace(0.3, 1.0, N)
     hin = nlp.internal_ineq(x, p, N, S)
     t = np.maximum(-hin, 1e-2); mu = 0.1; nu = mu / t * rng.uniform(0.5, 2, t.shape); delta = 10.0 if N < 10 else 1000.0
-    scr = np.zeros(off["size"]); lds = np.zeros(L.bmpc_emu_lds_doubles())
-    o = emu.default_opts()
-    rc = L.bmpc_emu_newton(N, S, ctypes.c_double(h), ctypes.byref(o), P(p), P(x), P(t), P(nu), ctypes.c_double(mu), ctypes.c_double(delta), P(scr), P(lds))
-    Qt = np.zeros((N, 35, 35)); qt = np.zeros((N, 35)); Xt = np.zeros((N, 35, 35)); A = np.zeros((N, 35, 43)); rd = np.zeros((N, 35))
-    T = np.zeros((N, 44, 35)); rl = np.zeros((N, 44)); Kg = np.zeros((N, 8, 35)); kff = np.zeros((N, 8)); dZ = np.zeros(N * 44)
-    rc2 = CO.bmpc_oracle_debug_qp(N, S, ctypes.c_double(h), P(p), P(x), P(t), P(nu), ctypes.c_double(mu), 1, ctypes.c_double(delta), P(Qt), P(qt),
-                                  P(Xt), P(A), P(rd), P(T), P(rl), P(Kg), P(kff), P(dZ))
-    assert rc == 0 and rc2 == 0
-    KT = scr[off["KT"]:off["KT"] + N * 35 * 8].reshape(N, 8, 35)      # control-major since round 3
-    np.testing.assert_allclose(KT, Kg, atol=1e-12)
-    np.testing.assert_allclose(scr[off["KF"]:off["KF"] + 8 * N], kff.ravel(), atol=1e-12)
-    np.testing.assert_allclose(scr[off["DZ"]:off["DZ"] + 44 * N], dZ, atol=1e-12)
+    rc, KT, KF, DZ = emu.newton(p, x, t, nu, mu, delta, N, S, h)
+    o = c_oracle.debug_qp(p, x, t, nu, mu, N, S, h, 1, delta)
+    assert rc == 0 and o["rc"] == 0
+    np.testing.assert_allclose(KT, o["Kg"], atol=1e-12)      # control-major since round 3
+    np.testing.assert_allclose(KF, o["kff"], atol=1e-12)
+    np.testing.assert_allclose(DZ, o["dZ"], atol=1e-12)
+
+
+def _direction_against_oracle(N, S, nw, orders):
+    """One Newton direction of a wave program (tests/emu bmpc_emu_newton: the calls of wave_solve's Newton system -- team_backward, wave_forward,
+    wave_dz_wide) at the interior point of tests/newton_points.py, seed N, with delta = 1 and with the exact Hessian and the
+    Gauss-Newton matrix: dZ, gains and feed-forward against the oracle at 1e-12, and bit for bit the same under every (lane order, wave order)."""
+    from tests import newton_points as pts
+    p, x, t, nu, mu = pts.interior_point(N, S, seed=N)
+    assert pts.sigma_spread(t, nu) >= 6.0
+    delta = 1.0      # (the smallest of 1, 10, 100 at which the oracle factorises every one of these points; less damping than the 10 / 1000 above)
+    for exact in (1, 0):
+        o = c_oracle.debug_qp(p, x, t, nu, mu, N, S, 0.1, exact, delta)
+        assert o["rc"] == 0
+        first = None
+        for lo, wo in orders:
+            rc, KT, KF, DZ = emu.newton(p, x, t, nu, mu, delta, N, S, 0.1, nw=nw, opts=emu.default_opts(exact_hessian=exact), lane_order=lo, wave_order=wo)
+            assert rc == 0
+            if first is None:
+                first = (KT, KF, DZ)
+                np.testing.assert_allclose(KT, o["Kg"], atol=1e-12)
+                np.testing.assert_allclose(KF, o["kff"], atol=1e-12)
+                np.testing.assert_allclose(DZ, o["dZ"], atol=1e-12)
+            else:
+                assert all(np.array_equal(a, b) for a, b in zip(first, (KT, KF, DZ))), (exact, lo, wo)
+
+
+@pytest.mark.parametrize("N,S", [(12, 4), (6, 5)])
+def test_emu_newton_direction_with_the_iterate_in_the_slab(N, S):
+    """N > 11 and S > 4 take the instantiation whose iterate, trial iterate and direction live in the workspace slab (S > 4: the tail of p in the
+    free iterate area of LDS)."""
+    _direction_against_oracle(N, S, 1, ((0, 0), (1, 0), (2, 0)))
+
+
+@pytest.mark.parametrize("nw,N", [(nw, N) for nw in (4, 2, "pair") for N in (1, 2, 3, 10)] + [("pair", 11)])
+def test_team_newton_direction_equals_oracle_and_is_order_invariant(nw, N):
+    """The team, two-wave and pair texts of the sweep (helper wave's staging and hand-over, wide dZ pass); horizons 1 and 2 are the ends of the
+    helper / sweep barrier pairing; N = 11 exists for pairs only.  Forward, reverse and scrambled orders of lanes and waves."""
+    _direction_against_oracle(N, 4, nw, ((0, 0), (1, 1), (2, 2), (0, 2)))
 
 
 def test_infeasible_problem_ends_as_status_2_in_oracle_and_emulator():
@@ -198,6 +225,18 @@ def test_no_solve_reads_what_it_has_not_written():
     for a, b in zip(plain, poisoned):
         for k in ("x", "g", "lam_g", "lam_x", "f", "kkt", "iters", "status"):
             assert np.array_equal(a[k], b[k], equal_nan=True), k
+
+
+@pytest.mark.parametrize("N", [1, 2])
+def test_shortest_horizons_read_nothing_they_have_not_written(N):
+    """N = 1 has no stage k >= 1: stage 0 of the one-wave sweep multiplies the t6 words by a 0 factor, and they are written by the stages k >= 1
+    only -- wave_init_tables zeroes them (a NaN left in LDS would pass the factor).  Poisoned and plain solves are bit-equal."""
+    from boundmpc_amd import workload
+    P, X, _ = workload.make_batch(4, seed=3, N=N, workers=1)
+    a, b = emu.solve(P, X, N, 4, 0.1), emu.solve(P, X, N, 4, 0.1, poison=True)
+    assert (a["status"] == 0).all()
+    for k in ("x", "g", "lam_g", "lam_x", "f", "kkt", "iters", "status"):
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
 
 
 def test_bounded_range_sincos_of_the_kinematics_against_libm():

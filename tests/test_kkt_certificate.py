@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 from oracle import c_oracle, nlp
+from tests.lagrangian import lagrangian_gradient
 from tests.multiplier_map import export_of, nu_of
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -72,19 +73,6 @@ def assert_record(got, rec, tol, what=""):
             assert got[i] == rec[k], (what, k, got[i])
         else:
             assert abs(got[i] - rec[k]) <= tol[k], (what, k, got[i], rec[k], tol[k])
-
-
-def lagrangian_gradient(p, x, lam_eq, nu, N, S, h=0.1):
-    """d/dx (f + lam_eq . g_eq + nu . h) by complex step, [N][44] -- independent of the C oracle's adjoint."""
-    lam_eq, nu = np.asarray(lam_eq).ravel(), np.asarray(nu).ravel()
-
-    def L(xc):
-        f, g = nlp.nlp_eval(xc, p, N, S, h)
-        return f + lam_eq @ g.reshape(N, NG)[:, :NE].reshape(-1) + nu @ nlp.internal_ineq(xc, p, N, S)
-    gl, xc = np.zeros(x.size), x.astype(complex)
-    for i in range(x.size):
-        xc[i] += 1e-30j; gl[i] = L(xc).imag / 1e-30; xc[i] = x[i]
-    return gl.reshape(N, NZ)
 
 
 # ---- the kernel text on the CPU lane emulator (tests/emu/bmpc_emu_kkt.cpp) ----

@@ -26,7 +26,8 @@ import pytest
 
 from oracle import c_oracle, nlp
 from tests.multiplier_map import nu_of
-from tests.test_kkt_certificate import lagrangian_gradient
+from tests import lagrangian as lg
+from tests.lagrangian import lagrangian_gradient
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NZ, NG, NE, NI, NU = 44, 43, 36, 57, 8
@@ -88,12 +89,10 @@ def active_rows(p, x, lam_g, lam_x, N, mu=MU):
 
 # ---- the checker --------------------------------------------------------------------------------------------------------------------------
 def _geq(xc, pc, N, S=S_):
-    return nlp.nlp_eval(xc, pc, N, S, H_)[1].reshape(N, NG)[:, :NE].reshape(-1)
+    return lg.g_eq(xc, pc, N, S, H_)
 
 
-def _FD5(fun, h=1e-3):
-    """five-point central difference of fun(t) at 0"""
-    return (8.0 * (fun(h) - fun(-h)) - (fun(2 * h) - fun(-2 * h))) / (12.0 * h)
+_FD5 = lg.fd5      # five-point central difference of fun(t) at 0, step 1e-3 (tests/lagrangian.py)
 
 
 class Checker:
@@ -104,39 +103,25 @@ class Checker:
         n = self.x.size
         nu, _, _, _, Hv = nu_of(p, x, lam_g, lam_x, N, S_)
         self.nu, self.h = nu.reshape(-1), Hv.reshape(-1)
-        gf, Jg = nlp.jac_g_complex_step(self.x, self.p, N, S_, H_)
-        self.Jg = Jg.reshape(N, NG, n)[:, :NE].reshape(N * NE, n)
-        Jh = np.zeros((N * NI, n)); xc = self.x.astype(complex)
-        for i in range(n):
-            xc[i] += 1e-30j; Jh[:, i] = nlp.internal_ineq(xc, self.p, N, S_).imag / 1e-30; xc[i] = self.x[i]
-        self.Jh = Jh
-        z = np.arange(n) % NZ
-        self.J, self.S = np.flatnonzero(z < 8), np.flatnonzero(z >= 8)
-        JgS, JgJ = self.Jg[:, self.S], self.Jg[:, self.J]
-        self.lam = np.linalg.solve(JgS.T, -(gf + Jh.T @ self.nu)[self.S])
+        gf, self.Jg, self.Jh = lg.jacobians(self.p, self.x, N, S_, H_)
+        self.J, self.S = lg.column_split(n)
+        self.lam = lg.lam_from_state_columns(gf, self.Jg, self.Jh, self.nu)
         self.s = np.maximum(-self.h, mu / np.maximum(self.nu, mu))
         self.Sigma = self.nu / self.s
-        self.JgS = JgS
-        Z = np.zeros((n, len(self.J)))
-        Z[self.J] = np.eye(len(self.J)); Z[self.S] = -np.linalg.solve(JgS, JgJ)
-        self.Z = Z
-        m = Z.shape[1]
+        self.Z, self.JgS = lg.null_space(self.Jg)
+        Z = self.Z
         # Z^T H Z: complex step along Z_a, five-point difference along Z_b (upper triangle)
-        Hzz = np.zeros((m, m))
-        for b in range(m):
-            col = _FD5(lambda t: self._grad_along(self.x + t * Z[:, b], self.p, Z[:, :b + 1]))
-            Hzz[:b + 1, b] = col; Hzz[b, :b + 1] = col
+        Hzz = lg.reduced_hessian(self.x, self.p, self.lam, self.nu, Z, N, S_, H_)
         JhZ = self.Jh @ Z
         self.K = Hzz + JhZ.T @ (self.Sigma[:, None] * JhZ)
         self.JhZ = JhZ
 
     def _L(self, xc, pc):
-        f, g = nlp.nlp_eval(xc, pc, self.N, S_, H_)
-        return f + self.lam @ g.reshape(self.N, NG)[:, :NE].reshape(-1) + self.nu @ nlp.internal_ineq(xc, pc, self.N, S_)
+        return lg.lagrangian(xc, pc, self.lam, self.nu, self.N, S_, H_)
 
     def _grad_along(self, x, p, U):
         """U^T grad_x L at (x, p) by complex step, one evaluation per column"""
-        return np.array([self._L(x + 1e-30j * U[:, a], p.astype(complex)).imag / 1e-30 for a in range(U.shape[1])])
+        return lg.grad_along(x, p, self.lam, self.nu, U, self.N, S_, H_)
 
     def tangent(self, dp, central=False):
         """dx (and dnu) along dp; central: the p-derivative terms by the central difference at the ABI's eps instead of the complex step"""
