@@ -8,3 +8,13 @@ from .solver import BatchedOCPSolver, NlpSolverShim  # noqa: F401
 from ._lib import BoundMPCHipError, LIB_PATH  # noqa: F401
 
 __all__ = ["BatchedOCPSolver", "NlpSolverShim", "BoundMPCHipError", "LIB_PATH"]
+
+# the plant model of a rollout (boundmpc_amd.stream), re-exported on first use: importing the package does not import the stream module
+_PLANT = ("PLANT", "PLANT_STATE", "PLANT_REC", "plant_table", "plant_check", "plant_state_of", "plant_robot", "unpack_plant_rec")
+
+
+def __getattr__(name):
+    if name in _PLANT:
+        from . import stream
+        return getattr(stream, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

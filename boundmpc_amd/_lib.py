@@ -42,6 +42,9 @@ SIGNATURES = {
     "bmpc_stream_rollout_log": (_ci, _TICK[:2] + [_ci] + _TICK[2:] + [_cd, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _cd, _vp, _ci, _vp, _vp]),      # ... audit_tol, log_hist, log_stages, track, stream
     "bmpc_stream_rollout_legs": (_ci, _TICK[:2] + [_ci] + _TICK[2:] + [_cd, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _cd, _vp, _ci, _vp] + [_ci] + [_vp] * 7),      # ... ticks_run, replan, replan_info, update_flags, disturb, tube_hist, audit, audit_tol, log_hist, log_stages, track, legs, leg_tick, leg_on, leg_tol, legs_done, leg_fired, leg_why, stream
     "bmpc_stream_rollout_tuned": (_ci, _TICK[:2] + [_ci] + _TICK[2:] + [_cd, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _cd, _vp, _ci, _vp] + [_ci] + [_vp] * 10),      # ... leg_why, tune, tune_info, tune_used, stream
+    "bmpc_stream_rollout_plant": (_ci, _TICK[:2] + [_ci] + _TICK[2:] + [_cd, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _cd, _vp, _ci, _vp] + [_ci] + [_vp] * 14),      # ... tune_used, plant, plant_state, plant_info, plant_rec, stream
+    "bmpc_stream_plant_len": (_ci, []), "bmpc_stream_plant_state_len": (_ci, []), "bmpc_stream_plant_rec_len": (_ci, []),
+    "bmpc_stream_plant": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp]),      # handle, B, robot, sstate, plant, plant_state, plant_info, plant_rec, tick, stream
     "bmpc_stream_tune_len": (_ci, []), "bmpc_stream_tune_defaults": (_ci, [_vp, _ci, _vp]),
     "bmpc_stream_track_len": (_ci, []), "bmpc_stream_rollout_log_len": (_ci, [_vp, _ci]),
     "bmpc_stream_tube_len": (_ci, []), "bmpc_stream_tube": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp]),

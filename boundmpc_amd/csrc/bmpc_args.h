@@ -118,6 +118,12 @@ struct RArgs {
     const double *tune;              // [B][bmpctu::LEN]: row b replaces the launch's settings for every tick of stream b; a NaN slot keeps the launch's
     int *tune_info;                  // [B] or NULL: the mask of the invalid slots of row b (bit CROSS: the level rule as resolved); 0 = the stream ran
     double *tune_used;               // [B][bmpctu::LEN] or NULL: the row as resolved, pad words 0
+    // an actuator model per stream between the command and the plant (the PL instantiations, bmpc_stream_rollout_plant): NULL = off, what an initialiser
+    // of the members above leaves
+    const double *plant;             // [B][bmpcpl::LEN]: row b stands between the first planned jerk of every tick of stream b and its plant; a NaN slot is the identity
+    double *plant_state;             // [B][bmpcpl::ST_LEN], in and out: the lag's state and the previous command; required with plant
+    int *plant_info;                 // [B] or NULL: the mask of the invalid slots of row b; 0 = the stream ran
+    double *plant_rec;               // [B][bmpcpl::REC_LEN] or NULL, initialised by the kernel: what the plant did to the commands
 };
 
 // ---- host and device: a row of per-stream controller settings (BMPC_TUNE_* of include/boundmpc_hip.h), what it resolves to and what is refused ----
@@ -218,19 +224,63 @@ BMPC_ARGS_HD void bmpc_tune_sargs(const double *row, SArgs &s) {
     v = row[bmpctu::RT_ROW_CAP]; if (v == v) s.rt_row_cap = v;
 }
 
+// ---- host and device: a row of a per-stream actuator model (BMPC_PLANT_* of include/boundmpc_hip.h), its state and its record; the rule of the step is
+// stream_plant (bmpc_stream_plant.inl) ----
+namespace bmpcpl {
+enum { GAIN = 0,          // [7] actuator gain of joint j                                    identity 1, valid when finite
+       BIAS = 7,          // [7] jerk offset, rad/s^3                                        identity 0, valid when finite
+       LAG = 14,          // first-order response per tick, u_act += LAG (a - u_act)        identity 1 (none), valid when 0 < LAG <= 1
+       SAT = 15,          // jerk magnitude the drive delivers                               identity +inf (none), valid when > 0 (+inf allowed)
+       DELAY = 16,        // 1: the command applied is the previous tick's                   identity 0, valid when 0 or 1
+       SLOTS = 17,        // the slots that are looked at; the words behind them up to LEN are pad
+       LEN = 20 };
+enum { ST_ACT = 0, ST_CMD = 7, ST_LEN = 16 };      // the state: the lag's state [7], the previous command [7], two pad words
+enum { REC_SAMPLES = 0, REC_N_SAT, REC_MAX_DU, REC_TICK_DU, REC_JOINT_DU, REC_SUMSQ_DU, REC_LEN = 8 };      // the record; two pad words
+}
+// what a NaN slot resolves to: the plant that IS the model
+BMPC_ARGS_HD double bmpc_plant_identity(int k) { return k < bmpcpl::BIAS ? 1.0 : k < bmpcpl::LAG ? 0.0 : k == bmpcpl::LAG ? 1.0 : k == bmpcpl::SAT ? __builtin_huge_val() : 0.0; }
+// THE validity rule of a slot that is not NaN, once (plain comparisons)
+BMPC_ARGS_HD bool bmpc_plant_slot_ok(int k, double v) {
+    if (k < bmpcpl::LAG) return v >= -BMPC_TOL_MAX && v <= BMPC_TOL_MAX;
+    if (k == bmpcpl::LAG) return v > 0.0 && v <= 1.0;
+    if (k == bmpcpl::SAT) return v > 0.0;
+    if (k == bmpcpl::DELAY) return v == 0.0 || v == 1.0;
+    return true;      // (pad words: never looked at)
+}
+// Row `row`: the mask of its invalid slots, bit k = slot k; 0 = the stream runs.  used (or NULL): the row as resolved -- a NaN slot its identity value, a
+// refused value as it was given, pad words 0.
+BMPC_ARGS_HD int bmpc_plant_check(const double *row, double *used) {
+    int bad = 0;
+    for (int k = 0; k < bmpcpl::LEN; k++) {
+        double v = k < bmpcpl::SLOTS ? row[k] : 0.0;
+        if (k < bmpcpl::SLOTS) {
+            if (v != v) v = bmpc_plant_identity(k);
+            else if (!bmpc_plant_slot_ok(k, v)) bad |= 1 << k;
+        }
+        if (used) used[k] = v;
+    }
+    return bad;
+}
+
 // ---- host only: what the rollout entries of the C ABI refuse and which kernel they run, once (bmpc_hip.hip rollout_launch; the CPU build of the
 // rollout, tests/emu/bmpc_emu_rollout.cpp, asks the same function) ----
 // the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice (needs the robot records), bit 2 poor bounds (with bit 1 only)
 inline bool bmpc_update_flags_ok(int flags, const void *robot) { return !(flags & ~7) && !((flags & 4) && !(flags & 2)) && !((flags & 2) && !robot); }
-// entry: the entry point the caller used -- 0 bmpc_stream_rollout, 1 _events, 2 _audit, 3 _log, 4 _legs, 5 _tuned; r: its arguments (what an entry has no argument for is
+// entry: the entry point the caller used -- 0 bmpc_stream_rollout, 1 _events, 2 _audit, 3 _log, 4 _legs, 5 _tuned, 6 _plant; r: its arguments (what an entry has no argument for is
 // 0 / NULL); N: the handle's horizon; flags, robot: the tick flags and the robot records.  Returns the level of the kernel text to run -- 0 plain, 1 EV,
 // 2 EV + AU, 3 EV + AU + LG, 4 all of them with the queue (QU: the one text that reads a queue, whatever else is on), 5 all of them with the table of
-// per-stream settings (TU: with or without a queue or any of the other arrays; the table's rows are validated on the device, where they live) -- or
+// per-stream settings (TU: with or without a queue or any of the other arrays; the table's rows are validated on the device, where they live), 6 all of
+// them with the plant table (PL: with or without a queue, a settings table or any of the other arrays; validated on the device too) -- or
 // BMPC_ROLLOUT_REFUSED (the C ABI's BMPC_ERR_ARG).  An entry without the arrays of its own feature IS the entry below it.
 enum { BMPC_ROLLOUT_REFUSED = -1 };
 inline int bmpc_rollout_level(int entry, const RArgs &r, int N, int flags, const void *robot) {
     if (r.ticks < 1 || !(r.goal_tol >= 0.0 && r.goal_tol <= BMPC_TOL_MAX)) return BMPC_ROLLOUT_REFUSED;      // (negative, NaN or infinite)
     if (!(flags & 1)) return BMPC_ROLLOUT_REFUSED;                    // without the plant in the loop a second tick repeats the first
+    if (entry == 6) {      // the plant: whatever the sweeps entry refuses, and a table without its state; without a table that entry, and no plant argument is looked at
+        const int below = bmpc_rollout_level(5, r, N, flags, robot);
+        if (below == BMPC_ROLLOUT_REFUSED || !r.plant) return below;
+        return r.plant_state ? 6 : BMPC_ROLLOUT_REFUSED;
+    }
     if (entry == 5) {      // the table: whatever the queue entry refuses; without a table that entry, and no table argument is looked at
         const int below = bmpc_rollout_level(4, r, N, flags, robot);
         return (below == BMPC_ROLLOUT_REFUSED || !r.tune) ? below : 5;

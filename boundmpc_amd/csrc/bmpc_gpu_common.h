@@ -125,6 +125,10 @@ hipError_t bmpc_rollout_log_launch(bool zlds, bool resto, const void *kargs, con
 hipError_t bmpc_rollout_legs_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // ---- the same with a table of controller settings per stream, validated and resolved on the device (bmpc_rollout_tune.hip; EV, AU, LG, QU and TU) ----
 hipError_t bmpc_rollout_tune_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
+// ---- the same with a table of actuator models per stream between the command and the plant (bmpc_rollout_plant.hip; EV, AU, LG, QU, TU and PL) ----
+hipError_t bmpc_rollout_plant_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
+// ---- the plant step on its own, one lane per stream of the batch (bmpc_rollout_plant.hip; bmpc_stream_plant.inl) ----
+hipError_t bmpc_stream_plant_launch(int N, int B, double h, double *rb, const double *ss, const double *plant, double *state, int *info, double *rec, int tick, hipStream_t st);
 // ---- the measurement on its own, one wave per stream of the batch (bmpc_rollout_audit.hip; bmpc_stream_tube.inl) ----
 hipError_t bmpc_stream_tube_launch(int N, int S, int B, const double *p, const double *ss, double *tube, hipStream_t st);
 
@@ -140,6 +144,8 @@ hipError_t bmpc_team_rollout_launch(int nw, bool resto, bool full, const void *k
 hipError_t bmpc_team_rollout_legs_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // the same with the table of controller settings per stream (bmpc_team_rollout_tune.hip): the fully-featured kernel with QU and TU
 hipError_t bmpc_team_rollout_tune_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
+// the same with the table of actuator models per stream (bmpc_team_rollout_plant.hip): the fully-featured kernel with QU, TU and PL
+hipError_t bmpc_team_rollout_plant_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 int bmpc_team_lds_bytes(int nw);
 int bmpc_team_nmax(int nw);      // longest horizon the team kernels take (their LDS holds most of the workspace)
 

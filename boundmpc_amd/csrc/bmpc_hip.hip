@@ -794,6 +794,8 @@ __global__ void __launch_bounds__(64) bmpc_stream_disturb_kernel(int B, double *
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b < B) bmpcs::stream_disturb(rb + (long long)b * bmpcs::RB_LEN, d + (long long)b * bmpcs::DIST_LEN, 0, 1);
 }
+// (the plant kernel, bmpc_stream_plant.inl, lives in bmpc_rollout_plant.hip, as the tube kernel lives in bmpc_rollout_audit.hip: this unit's device text is
+// not touched by it)
 // (the fused one-launch tick kernels of one wave per stream live in bmpc_tick.hip, those of the teams in bmpc_team.hip)
 // The argument test of the four stream entry points (max_iter: 0 where the entry point has none; need: the arrays it cannot do without, looked
 // at for B > 0 only).  False: BMPC_ERR_ARG.
@@ -857,9 +859,9 @@ extern "C" int bmpc_stream_tick(bmpc_handle *h, int B, const double *path, int p
 // ---- rollout: `ticks` ticks of every stream in one launch (bmpc_rollout.hip), a direct launch on the caller's stream ----
 extern "C" int bmpc_stream_rollout_len(void) { return BMPC_ROLL_LEN; }
 // The rollout entries: each fills the solve, stream and rollout records from its arguments and names itself (entry: 0 bmpc_stream_rollout, 1 _events,
-// 2 _audit, 3 _log, 4 _legs, 5 _tuned); the argument test and the level of the kernel text that runs -- without the event code (0), with it (1), with the
+// 2 _audit, 3 _log, 4 _legs, 5 _tuned, 6 _plant); the argument test and the level of the kernel text that runs -- without the event code (0), with it (1), with the
 // event and the audit code (2), with the log code on top of both (3), with the queue of re-plan records on top of all (4), with the table of per-stream
-// settings on top of that (5) -- are bmpc_rollout_level's (bmpc_args.h).
+// settings on top of that (5), with the table of per-stream actuator models on top of that (6) -- are bmpc_rollout_level's (bmpc_args.h).
 static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, const RArgs &r, int entry, hipStream_t st) {
     if (!tick_args_ok(h, B, io, t)) return BMPC_ERR_ARG;
     const int level = bmpc_rollout_level(entry, r, h->N, t.flags, t.robot);
@@ -880,9 +882,11 @@ static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const Stream
     hipEvent_t *pair = nullptr;
     if (h->timing) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
     // (teams at levels 1 and 2 hand the LG text the caller's log_stages UNCHECKED, with log_hist and track NULL: the kernel reads it behind r.log_hist only)
-    if (team && level == 5) HIPCHK(bmpc_team_rollout_tune_launch(BMPC_TEAM_NW, resto, &a, &s, &r, grid, st));
+    if (team && level == 6) HIPCHK(bmpc_team_rollout_plant_launch(BMPC_TEAM_NW, resto, &a, &s, &r, grid, st));
+    else if (team && level == 5) HIPCHK(bmpc_team_rollout_tune_launch(BMPC_TEAM_NW, resto, &a, &s, &r, grid, st));
     else if (team && level == 4) HIPCHK(bmpc_team_rollout_legs_launch(BMPC_TEAM_NW, resto, &a, &s, &r, grid, st));
     else if (team) HIPCHK(bmpc_team_rollout_launch(BMPC_TEAM_NW, resto, level != 0, &a, &s, &r, grid, st));      // (one kernel with everything serves every level from 1 to 3)
+    else if (level == 6) HIPCHK(bmpc_rollout_plant_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else if (level == 5) HIPCHK(bmpc_rollout_tune_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else if (level == 4) HIPCHK(bmpc_rollout_legs_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
     else if (level == 3) HIPCHK(bmpc_rollout_log_launch(handle_zlds(h), resto, &a, &s, &r, grid, st));
@@ -972,6 +976,31 @@ extern "C" int bmpc_stream_rollout_tuned(bmpc_handle *h, int B, int ticks, const
     const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, nullptr, replan_info, update_flags, disturb, tube_hist, audit, audit_tol, log_hist, log_stages, track,
                   legs, leg_tick, leg_on, leg_tol, legs_done, leg_fired, leg_why, tune, tune_info, tune_used};
     return rollout_launch(h, B, io, t, r, 5, (hipStream_t)hip_stream);
+}
+// with a table of actuator models per stream between the command and the plant on top (bmpc_rollout_plant.hip, bmpc_team_rollout_plant.hip): the rows live on
+// the device and are validated there, by the rule of bmpc_args.h; without a table it IS the entry above
+extern "C" int bmpc_stream_plant_len(void) { return BMPC_PLANT_LEN; }
+extern "C" int bmpc_stream_plant_state_len(void) { return BMPC_PLANT_STATE_LEN; }
+extern "C" int bmpc_stream_plant_rec_len(void) { return BMPC_PLANT_REC_LEN; }
+extern "C" int bmpc_stream_rollout_plant(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                                         double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                                         double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan, int *replan_info, int update_flags,
+                                         const double *disturb, double *tube_hist, double *audit, double audit_tol, double *log_hist, int log_stages, double *track,
+                                         int legs, const int *leg_tick, const int *leg_on, const double *leg_tol, int *legs_done, int *leg_fired, int *leg_why,
+                                         const double *tune, int *tune_info, double *tune_used, const double *plant, double *plant_state, int *plant_info,
+                                         double *plant_rec, void *hip_stream) {
+    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
+    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
+    const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, nullptr, replan_info, update_flags, disturb, tube_hist, audit, audit_tol, log_hist, log_stages, track,
+                  legs, leg_tick, leg_on, leg_tol, legs_done, leg_fired, leg_why, tune, tune_info, tune_used, plant, plant_state, plant_info, plant_rec};
+    return rollout_launch(h, B, io, t, r, 6, (hipStream_t)hip_stream);
+}
+// the step on its own, for per-tick loops (no workspace of the handle: may sit inside a capture)
+extern "C" int bmpc_stream_plant(bmpc_handle *h, int B, double *robot, const double *sstate, const double *plant, double *plant_state, int *plant_info, double *plant_rec,
+                                 int tick, void *hip_stream) {
+    if (!h || B < 1 || !robot || !sstate || !plant || !plant_state || h->N > bmpcs::STREAM_NMAX) return BMPC_ERR_ARG;
+    HIPCHK(bmpc_stream_plant_launch(h->N, B, h->h, robot, sstate, plant, plant_state, plant_info, plant_rec, tick, (hipStream_t)hip_stream));
+    return BMPC_OK;
 }
 
 extern "C" int bmpc_stream_set_rt_feasibility_tol(bmpc_handle *h, double tol) {

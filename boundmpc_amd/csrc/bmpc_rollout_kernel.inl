@@ -59,14 +59,27 @@
 // (which has just rebuilt it from a.o), the acceptance words onto a copy of the stream arguments ahead of the post.  Each is a handful of loads of a
 // wave-uniform row made scalar (BMPCR_UNIFORM_F64), behind an opaque stream index: nothing of the table is carried in a register across the solve but
 // what the solve itself reads, W.o, which it holds in any instantiation.  Without TU no tune line is compiled.
+// PLANTS (the instantiations with PL, bmpc_stream_rollout_plant; bmpc_rollout_plant.hip, bmpc_team_rollout_plant.hip; bmpc_stream_plant.inl): a table
+// r.plant[b][bmpcpl::LEN] of an actuator model per stream -- gain and offset per joint, a first-order lag, a clip, one tick of dead time -- between the
+// first planned jerk of a tick and the plant, which without it IS the model: stream_post moves the robot record with the model's own chain and the
+// planned jerk.  Such a plant responds to the command, and inside a rollout the command exists on the device only.  The step sits right behind the
+// barrier behind stream_post, AHEAD of the history, trajectory and log rows and of the tick's disturbance and re-plan, and only where the post stepped
+// the plant (ss[SS_ERRCNT] < N behind it, a word every wave reads there; the barrier behind the step is unconditional): hist[t][b] shows the TRUE plant
+// behind tick t, a disturbance acts on it, a spliced re-plan takes it, the next pack and the audit row of tick t + 1 measure it.  The log and the
+// tracking record keep describing the PLAN (stage 0 of traj is the plan's): the measurement of the plant is the audit.  The row is validated once per
+// stream ahead of its tick loop by the rule the host states (bmpc_plant_check, bmpc_args.h), by EVERY wave from the read-only row; an invalid row gets the
+// treatment of an invalid settings row -- no tick, NaN history rows, its mask in r.plant_info[b], plant_state untouched.  Row, state (r.plant_state[b],
+// in and out: rollouts chain) and record (r.plant_rec[b]) live in global memory, behind opaque stream and tick indices: nothing of the plant is carried
+// in a register across the solve.  Without PL no plant line is compiled.
 // Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp,
-// bmpc_emu_rollout_legs.cpp and bmpc_emu_rollout_tune.cpp, once per BMPC_NW).  The nine units (bmpc_rollout.hip, bmpc_rollout_events.hip,
-// bmpc_rollout_audit.hip, bmpc_rollout_log.hip, bmpc_rollout_legs.hip, bmpc_rollout_tune.hip, bmpc_team_rollout.hip, bmpc_team_rollout_legs.hip,
-// bmpc_team_rollout_tune.hip) and those builds launch through bmpc_rollout_run at the end of this file, the
+// bmpc_emu_rollout_legs.cpp, bmpc_emu_rollout_tune.cpp and bmpc_emu_rollout_plant.cpp, once per BMPC_NW).  The eleven units (bmpc_rollout.hip,
+// bmpc_rollout_events.hip, bmpc_rollout_audit.hip, bmpc_rollout_log.hip, bmpc_rollout_legs.hip, bmpc_rollout_tune.hip, bmpc_rollout_plant.hip,
+// bmpc_team_rollout.hip, bmpc_team_rollout_legs.hip, bmpc_team_rollout_tune.hip, bmpc_team_rollout_plant.hip) and those builds launch through bmpc_rollout_run at the end of this file, the
 // one place that picks <ZLDS, RESTO>.
 #pragma once
 
 #include "bmpc_stream_events.inl"
+#include "bmpc_stream_plant.inl"
 #include "bmpc_stream_tube.inl"
 #include "bmpc_stream_log.inl"
 
@@ -94,14 +107,27 @@ enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH
     double tr_[bmpctu::SLOTS]; \
     { const double *g_ = r.tune + (long long)(b_) * bmpctu::LEN; \
       _Pragma("unroll") for (int k_ = 0; k_ < bmpctu::SLOTS; k_++) tr_[k_] = BMPCR_UNIFORM_F64(g_[k_]); }
+// (PL) the four plant members of r, read where they are consumed THROUGH THE KERNEL-ARGUMENT SEGMENT behind an opaque pointer, not as r.plant: the compiler
+// loads every member of a by-value argument it names at the kernel's entry and keeps it -- eight more scalar registers spilled across the whole solve, which
+// on the team kernel with the restoration phase is one more spill register than the file holds.  So the plant lines never name those members, and what they
+// address is loaded behind the solve and dead before the next one, as the stream and tick indices are.  BMPCR_RARGS_AT: where r lies in the segment, the
+// arguments in their order at their natural alignment (tests/kernel_resources.py reads the same offset from the code object's metadata).
+#ifndef BMPC_EMU
+#define BMPCR_RARGS_AT ((((sizeof(KArgs) + alignof(SArgs) - 1) / alignof(SArgs) * alignof(SArgs) + sizeof(SArgs)) + alignof(RArgs) - 1) / alignof(RArgs) * alignof(RArgs))
+#define BMPCR_PLANT_ARGS(pa_) \
+    const RArgs *pa_; \
+    { const char *k_ = (const char *)__builtin_amdgcn_kernarg_segment_ptr(); BMPCR_OPAQUE("+s"(k_)); pa_ = (const RArgs *)(k_ + BMPCR_RARGS_AT); }
+#else
+#define BMPCR_PLANT_ARGS(pa_) const RArgs *pa_ = &r
+#endif
 // (the body of a tick in the kernel itself, as in bmpc_tick_kernel.inl: behind a function that takes `a` the argument loads lose their no-clobber
 // property -- bmpc_args.h, BMPC_PROBLEM)
-// (QT: the sixth argument counts what sits on top of the log -- 0 nothing, 1 the queue QU, 2 the queue and the table TU, which is only ever compiled with
-// everything below it on.  One argument for both keeps the kernels' mangled names at the length they had: tests/kernel_resources.py tells a team kernel
+// (QT: the sixth argument counts what sits on top of the log -- 0 nothing, 1 the queue QU, 2 the queue and the table TU, 3 the queue, the table and the
+// plant PL, each only ever compiled with everything below it on.  One argument for both keeps the kernels' mangled names at the length they had: tests/kernel_resources.py tells a team kernel
 // from a one-wave kernel by the namespace inside the first 70 characters.)
 template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false, bool LG = false, int QT = 0>
 BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
-    constexpr bool QU = QT >= 1, TU = QT == 2;
+    constexpr bool QU = QT >= 1, TU = QT >= 2, PL = QT == 3;
     static_assert(BMPC_NW == 1 || ZLDS, "a team keeps the iterate in LDS");
     BMPCK_LDS double lds[BMPC_NAMESPACE::L_SIZE];
     BMPC_STRIDES(a);
@@ -141,6 +167,18 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
                 bad = BMPCK_UNIFORM(bmpc_tune_check(r.tune + (long long)b * bmpctu::LEN, a.o, s, out_ && r.tune_used ? r.tune_used + (long long)b * bmpctu::LEN : nullptr));
                 if (out_ && r.tune_info) r.tune_info[b] = bad;
             }
+        }
+        if constexpr (PL) {
+            // (a PL kernel is launched with a table only -- bmpc_rollout_level --, so no line here asks whether there is one.  Every wave reads the row
+            // itself; lane 0 of wave 0 stores the mask and starts the record)
+            BMPCR_PLANT_ARGS(pl_);
+            int b_ = b; BMPCR_OPAQUE("+s"(b_));
+            const int pbad = BMPCK_UNIFORM(bmpc_plant_check(pl_->plant + (long long)b_ * bmpcpl::LEN, nullptr));
+            if (w0 && BMPCK_LANE == 0) {
+                if (pl_->plant_info) pl_->plant_info[b_] = pbad;
+                if (pl_->plant_rec) bmpcs::stream_plant_init(pl_->plant_rec + (long long)b_ * bmpcpl::REC_LEN);
+            }
+            bad |= pbad;      // (an invalid plant row keeps the stream from running as an invalid settings row does: one word decides)
         }
         if (!TU || !bad) for (; t < r.ticks; t++) {
             // (the lost-plan test of the fused tick: BoundMPC.step() returns five Nones there and the reference node stops)
@@ -184,6 +222,18 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
                 if (w0) bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, sq.rt_tol, sh, BMPCK_LANE, BMPCK_NL, sq.rt_row_cap);
             }
             BMPCK_SYNC();      // the history and the next pack read ss, rb, x, traj and the dual state that other lanes have just stored
+            if constexpr (PL) {
+                // The drive between the command the post has just stored and the plant it has just stepped: only where it did step it (every wave reads the
+                // error count behind the post's barrier; the pack of the next tick does not write it).  The stream and the tick opaque, as for the events.
+                BMPCR_PLANT_ARGS(pl_);
+                int b_ = b, t_ = t;
+                BMPCR_OPAQUE("+s"(b_), "+s"(t_));
+                if (BMPCK_UNIFORM((int)(ss[bmpcs::SS_ERRCNT] < (double)N_))) {
+                    if (w0) bmpcs::stream_plant(a.h, pl_->plant + (long long)b_ * bmpcpl::LEN, pl_->plant_state + (long long)b_ * bmpcpl::ST_LEN, rb,
+                                                pl_->plant_rec ? pl_->plant_rec + (long long)b_ * bmpcpl::REC_LEN : nullptr, t_, BMPCK_LANE, BMPCK_NL);
+                }
+                BMPCK_SYNC();      // the rows, the events and the next pack read the TRUE plant
+            }
             const long long row = (long long)t * a.B + b;
             if (r.hist && w0) {
                 double *hr = r.hist + row * bmpcs::RH_LEN;
@@ -285,14 +335,14 @@ BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
     }
 }
 
-// Host: the one place that picks the instantiation <ZLDS, RESTO> of a unit's <EV, AU, LG, QU, TU> (the kernel's sixth argument counts QU and TU) and launches it on `grid` workgroups (BMPCK_LAUNCH: the GPU
+// Host: the one place that picks the instantiation <ZLDS, RESTO> of a unit's <EV, AU, LG, QU, TU, PL> (the kernel's sixth argument counts QU, TU and PL) and launches it on `grid` workgroups (BMPCK_LAUNCH: the GPU
 // launch on stream `st`, or the host build's call).  kargs points at a KArgsT<...> record (the layouts are identical across instantiations).  A team
 // keeps the iterate in LDS: its units hold no instantiation without ZLDS.  `static`: every unit has its own -- the name says nothing of the unit's KArgs
 // and BMPC_NW, and the linker would fold the one-wave units' and the team unit's into one.
-template <bool EV, bool AU, bool LG, bool QU = false, bool TU = false, class STREAM>
+template <bool EV, bool AU, bool LG, bool QU = false, bool TU = false, bool PL = false, class STREAM>
 static void bmpc_rollout_run(bool zlds, bool resto, const void *kargs, const SArgs &s, const RArgs &r, int grid, STREAM st) {
-    static_assert(QU || !TU, "the table sits on top of the queue");
-    constexpr int QT = TU ? 2 : QU ? 1 : 0;
+    static_assert((QU || !TU) && (TU || !PL), "the table sits on top of the queue, the plant on top of the table");
+    constexpr int QT = PL ? 3 : TU ? 2 : QU ? 1 : 0;
     KArgs a; memcpy(&a, kargs, sizeof(a));
     if (zlds && resto) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, true, EV, AU, LG, QT>), grid, st, a, s, r);
     else if (zlds) BMPCK_LAUNCH((bmpc_stream_rollout_kernel<true, false, EV, AU, LG, QT>), grid, st, a, s, r);

@@ -480,6 +480,116 @@ def unpack_tune(row):
     return {n.lower(): (None if np.isnan(row[k]) else (int(row[k]) if n in ints and np.isfinite(row[k]) else float(row[k]))) for n, k in TUNE.items() if n != "LEN"}
 
 
+# a plant model (bmpc_stream_rollout_plant, bmpc_stream_plant; BMPC_PLANT_* of include/boundmpc_hip.h): the slots of a stream's row -- the drive between
+# the first planned jerk of a tick and the plant; NaN = the identity value --, of its state and of its record
+PLANT = dict(GAIN=0, BIAS=7, LAG=14, SAT=15, DELAY=16, LEN=20)
+PLANT_STATE = dict(ACT=0, CMD=7, LEN=16)
+PLANT_REC = dict(SAMPLES=0, N_SAT=1, MAX_DU=2, TICK_DU=3, JOINT_DU=4, SUMSQ_DU=5, LEN=8)
+_PLANT_SLOTS = 17      # the slots that are looked at: GAIN[7], BIAS[7], LAG, SAT, DELAY
+
+
+def plant_identity():
+    """the row every NaN slot resolves to: the plant that IS the model (pad words 0)"""
+    row = np.zeros(PLANT["LEN"])
+    row[PLANT["GAIN"]:PLANT["GAIN"] + 7], row[PLANT["LAG"]], row[PLANT["SAT"]] = 1.0, 1.0, np.inf
+    return row
+
+
+def plant_check(row):
+    """What the device answers for `row` [PLANT_LEN] in plant_info (csrc/bmpc_args.h bmpc_plant_check, restated): the bit mask of its invalid slots, bit k =
+    slot k.  A NaN slot is the identity and valid; GAIN and BIAS must be finite, 0 < LAG <= 1, SAT > 0 (+inf allowed), DELAY 0 or 1; the pad words are
+    never looked at."""
+    row = np.asarray(row, dtype=np.float64)
+    assert row.shape == (PLANT["LEN"],)
+    bad = 0
+    for k in range(_PLANT_SLOTS):
+        v = float(row[k])
+        if np.isnan(v):
+            continue
+        if k < PLANT["LAG"]:
+            ok = np.isfinite(v)
+        elif k == PLANT["LAG"]:
+            ok = 0.0 < v <= 1.0
+        elif k == PLANT["SAT"]:
+            ok = v > 0.0
+        else:
+            ok = v == 0.0 or v == 1.0
+        if not ok:
+            bad |= 1 << k
+    return bad
+
+
+def plant_table(B, gain=None, bias=None, lag=None, sat=None, delay=None):
+    """The table of plant models, [B][PLANT_LEN] float64 for StreamBatch.rollout(plant=...) and plant_step: gain and bias a scalar, [7] or [B][7], lag, sat
+    and delay a scalar or [B]; NaN (an argument not given, or an entry of an array) is the identity -- gain 1, bias 0, lag 1 (none), sat +inf (none),
+    delay 0.  Raises ValueError on what the device would refuse (plant_check)."""
+    B = int(B)
+    T = np.full((B, PLANT["LEN"]), np.nan)
+    for name, col, at, w in (("gain", gain, PLANT["GAIN"], 7), ("bias", bias, PLANT["BIAS"], 7), ("lag", lag, PLANT["LAG"], 1), ("sat", sat, PLANT["SAT"], 1),
+                             ("delay", delay, PLANT["DELAY"], 1)):
+        if col is None:
+            continue
+        col = np.asarray(col, dtype=np.float64)
+        ok = (col.ndim == 0 or col.shape in ((7,), (B, 7))) if w == 7 else (col.ndim == 0 or col.shape == (B,))
+        if not ok:
+            raise ValueError(f"{name} must be a scalar, " + (f"[7] or [{B}][7]" if w == 7 else f"or [{B}]") + f", got {list(col.shape)}")
+        T[:, at:at + w] = col if w == 7 or col.ndim == 0 else col[:, None]
+    for b in range(B):
+        bad = plant_check(T[b])
+        if bad:
+            raise ValueError(f"plant row {b}: invalid slots {[k for k in range(_PLANT_SLOTS) if bad >> k & 1]}")
+    return T
+
+
+def plant_state_of(robot):
+    """The plant state of streams whose drive has settled on the jerk of their robot records: robot [B][RB_LEN] (or one row) -> [B][PLANT_STATE_LEN] (or one
+    row) with ACT = CMD = that jerk, pad words 0.  What plant_step and rollout(plant=) start from."""
+    rb = np.asarray(robot, dtype=np.float64)
+    st = np.zeros(rb.shape[:-1] + (PLANT_STATE["LEN"],))
+    st[..., PLANT_STATE["ACT"]:PLANT_STATE["ACT"] + 7] = st[..., PLANT_STATE["CMD"]:PLANT_STATE["CMD"] + 7] = rb[..., RB["JERK"]:RB["JERK"] + 7]
+    return st
+
+
+def plant_robot(robot_row, plant_row, state_row, h):
+    """The device plant step (stream_plant; bmpc_stream_plant) as numpy over `RobotModel`, the specification of one step: robot_row is the record behind a
+    post that stepped the plant, c = its jerk the command.  Per joint c' = CMD if DELAY else c, CMD = c; a = GAIN c' + BIAS; f = a if LAG == 1 else
+    ACT + LAG (a - ACT), ACT = f; u = clip(f, -SAT, SAT) (a NaN passes); D = u - c; q += h^3/24 D, dq += h^2/6 D, ddq += h/2 D, jerk = u.  Where any
+    D != 0, p_lie and v are recomputed from the new joint state; where every D == 0 the record is returned unchanged.
+    -> (robot row, state row, D [7], clipped: some joint was) -- copies."""
+    from .robot_model import RobotModel
+    rb, st = np.array(robot_row, dtype=float), np.array(state_row, dtype=float)
+    w = np.asarray(plant_row, dtype=float)
+    assert w.shape == (PLANT["LEN"],) and st.shape == (PLANT_STATE["LEN"],) and plant_check(w) == 0
+    w = np.where(np.isnan(w), plant_identity(), w)
+    c = rb[RB["JERK"]:RB["JERK"] + 7].copy()
+    act, cmd = st[PLANT_STATE["ACT"]:PLANT_STATE["ACT"] + 7].copy(), st[PLANT_STATE["CMD"]:PLANT_STATE["CMD"] + 7].copy()
+    a = w[PLANT["GAIN"]:PLANT["GAIN"] + 7] * (cmd if w[PLANT["DELAY"]] == 1.0 else c) + w[PLANT["BIAS"]:PLANT["BIAS"] + 7]
+    lag, sat = w[PLANT["LAG"]], w[PLANT["SAT"]]
+    f = a if lag == 1.0 else act + lag * (a - act)
+    u = np.where(f > sat, sat, np.where(f < -sat, -sat, f))
+    st[PLANT_STATE["ACT"]:PLANT_STATE["ACT"] + 7], st[PLANT_STATE["CMD"]:PLANT_STATE["CMD"] + 7] = f, c
+    D = u - c
+    if (D != 0.0).any():
+        rb[RB["Q"]:RB["Q"] + 7] += h * h * h / 24 * D
+        rb[RB["DQ"]:RB["DQ"] + 7] += h * h / 6 * D
+        rb[RB["DDQ"]:RB["DDQ"] + 7] += h / 2 * D
+        rb[RB["JERK"]:RB["JERK"] + 7] = u
+        p, J, _ = RobotModel().forward_kinematics(rb[RB["Q"]:RB["Q"] + 7], rb[RB["DQ"]:RB["DQ"] + 7])
+        rb[RB["P"]:RB["P"] + 6], rb[RB["V"]:RB["V"] + 6] = p, J @ rb[RB["DQ"]:RB["DQ"] + 7]
+    return rb, st, D, bool(((f > sat) | (f < -sat)).any())
+
+
+def unpack_plant_rec(row):
+    """A plant record (rollout()["plant_rec"][b], numpy) -> dict: samples (the plant steps taken), n_sat (the ticks on which some joint clipped), max_du (the
+    largest |u - c|; None without a sample), tick_du and joint_du (its first tick and joint; None likewise), sumsq_du, rms_du (over samples x 7)."""
+    row = np.asarray(row, dtype=np.float64)
+    assert row.shape == (PLANT_REC["LEN"],)
+    n = int(row[PLANT_REC["SAMPLES"]])
+    return dict(samples=n, n_sat=int(row[PLANT_REC["N_SAT"]]), max_du=float(row[PLANT_REC["MAX_DU"]]) if n else None,
+                tick_du=int(row[PLANT_REC["TICK_DU"]]) if n else None, joint_du=int(row[PLANT_REC["JOINT_DU"]]) if n else None,
+                sumsq_du=float(row[PLANT_REC["SUMSQ_DU"]]), rms_du=float(np.sqrt(row[PLANT_REC["SUMSQ_DU"]] / (7 * n))) if n else None)
+
+
 def rollout_len():
     """[robot record 43 | phi | error count | iters | status | kkt | n_valid | using_previous | success | g_viol]"""
     return ROLL["LEN"]
@@ -633,6 +743,8 @@ class StreamBatch:
         self.replan = self.replan_info = None      # update_device(): record buffer [B][replan_len] and info [B], allocated on first use
         self.legs = None         # rollout(legs=...): queue buffer [B][K][replan_len], allocated on first use
         self.tick_ms = None      # closed_loop(timed=True): HIP-event time of the tick just run
+        self.plant_state = None  # plant_step(), rollout(plant=...): the drives' state [B][PLANT_STATE_LEN], created from the robot records on first use
+        self.plant_info = self.plant_rec = None      # plant_step(): masks [B] and accumulated records [B][PLANT_REC_LEN], allocated on first use
         solver._children.add(self)
 
     def update(self, b, *args, **kw):
@@ -709,6 +821,46 @@ class StreamBatch:
         assert self.solver._lib.bmpc_stream_disturb_len() == DIST_LEN
         d = self._dev64(d, (self.B, DIST_LEN), "d", stream)
         _lib.check(self.solver._lib.bmpc_stream_disturb(self.solver._h, self.B, _ptr(self.robot), _ptr(d), self._stream(stream)), "bmpc_stream_disturb")
+
+    def _plant_state(self, stream):
+        """the drives' state on the device; on first use ACT = CMD = the jerk of the robot records as they are now (plant_state_of, on `stream`)"""
+        import torch
+        if self.plant_state is None:
+            lib = self.solver._lib
+            assert (lib.bmpc_stream_plant_len(), lib.bmpc_stream_plant_state_len(), lib.bmpc_stream_plant_rec_len()) == (PLANT["LEN"], PLANT_STATE["LEN"], PLANT_REC["LEN"])
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.path.device)):
+                self.plant_state = torch.zeros((self.B, PLANT_STATE["LEN"]), dtype=torch.float64, device=self.path.device)
+                for at in (PLANT_STATE["ACT"], PLANT_STATE["CMD"]):
+                    self.plant_state[:, at:at + 7] = self.robot[:, RB["JERK"]:RB["JERK"] + 7]
+        return self.plant_state
+
+    def plant_reset(self, stream=None):
+        """Start the drives afresh: `self.plant_state` from the robot records as they are NOW (ACT = CMD = their jerk, plant_state_of) and an empty
+        `self.plant_rec`.  A per-tick loop that is to leave what rollout(plant=) leaves calls it where that launch would start: ahead of the first tick."""
+        self.plant_state = self.plant_rec = self.plant_info = None
+        return self._plant_state(stream)
+
+    def plant_step(self, plant, tick=0, stream=None):
+        """The drives between the commands and the plants, one step (bmpc_stream_plant): plant [B][PLANT_LEN] (`plant_table(B, ...)`, an array or a device
+        tensor, taken as it is), row b the actuator model of stream b.  Call it behind tick() (or post()) and AHEAD of log(), tube of the next tick, disturb()
+        and update_device(): it corrects the robot records from the plant the post stepped with the planned jerk to the plant under the jerk the drive
+        delivers (`plant_robot` is the mirror).  A stream without a plan is skipped; a stream with an invalid row is left alone, its mask in the result.
+        Keeps `self.plant_state` (created from the robot records as they are on first use -- behind the first tick of a loop, unless plant_reset() was called
+        ahead of it, which is where rollout(plant=) creates it) and accumulates `self.plant_rec`
+        [B][PLANT_REC_LEN] (slots PLANT_REC; `tick` is what its TICK_DU names), initialised on first use.  One launch, asynchronous on `stream`, capturable.
+        Returns the `plant_info` tensor [B] (int32), valid once `stream` has run the launch."""
+        import torch
+        plant = self._dev64(plant, (self.B, PLANT["LEN"]), "plant", stream)
+        state = self._plant_state(stream)
+        if self.plant_rec is None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.path.device)):
+                self.plant_info = torch.zeros((self.B,), dtype=torch.int32, device=self.path.device)
+                rec0 = np.zeros(PLANT_REC["LEN"]); rec0[PLANT_REC["MAX_DU"]], rec0[PLANT_REC["TICK_DU"]], rec0[PLANT_REC["JOINT_DU"]] = -np.inf, -1.0, -1.0
+                self.plant_rec = torch.as_tensor(rec0).to(self.path.device).repeat(self.B, 1).contiguous()
+        _lib.check(self.solver._lib.bmpc_stream_plant(self.solver._h, self.B, _ptr(self.robot), _ptr(self.state), _ptr(plant), _ptr(state), _ptr(self.plant_info),
+                                                      _ptr(self.plant_rec), int(tick), self._stream(stream)), "bmpc_stream_plant")
+        self._plant_input = plant      # the launch is asynchronous: its input lives until the next one replaces it
+        return self.plant_info
 
     def _dev64(self, a, shape, name, stream, dtype=None):
         """`a` as a contiguous device tensor of `shape` (float64 unless dtype), copied on `stream` when it is not one already"""
@@ -832,7 +984,8 @@ class StreamBatch:
 
     def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None,
                 replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None, audit=False, audit_tol=1e-6, want_tube=False,
-                want_log=False, log_stages=1, track=False, waves=None, legs=None, leg_tick=None, leg_on=None, leg_tol=None, tune=None, want_tune_used=False):
+                want_log=False, log_stages=1, track=False, waves=None, legs=None, leg_tick=None, leg_on=None, leg_tol=None, tune=None, want_tune_used=False,
+                plant=None, want_plant_rec=False):
         """`ticks` closed-loop ticks (plant simulation on) of every stream in ONE launch (bmpc_stream_rollout): each stream runs at its own pace, so
         the launch lasts as long as the slowest stream's SUM of solves, where a loop of tick() / tick_graph() pays the slowest stream of every tick.
         For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, a time
@@ -891,14 +1044,26 @@ class StreamBatch:
           tune_info [B] int32              0: the row was valid and the stream ran; else the bit mask of its invalid slots (bit TUNE_CROSS: the level
                                            rule as resolved) -- READ IT: the other streams are served as if the row were not there
           tune_used [B][TUNE_LEN]          want_tune_used: the rows as resolved (unpack_tune), what the streams ran with or were refused for.
-        Every array of stream b holds what the same call without a table leaves for the one-stream batch {b} on a solver set up from tune_used[b]."""
+        Every array of stream b holds what the same call without a table leaves for the one-stream batch {b} on a solver set up from tune_used[b].
+        PLANTS (bmpc_stream_rollout_plant; with or without `legs` and `tune`, not with replan / replan_tick; without `plant` nothing changes): an actuator
+        model per stream between the first planned jerk of every tick and the plant, which otherwise IS the model -- "gain error x lag x margin" is one
+        launch whose audit answers.
+          plant [B][PLANT_LEN]             `plant_table(B, gain=, bias=, lag=, sat=, delay=)`, an array or a device tensor (taken as it is): row b, slots
+                                           PLANT; a NaN slot is the identity.  The step (`plant_robot` is the mirror) sits behind the post of every tick that
+                                           stepped the plant, AHEAD of that tick's rows, disturbance and re-plan: hist[t][b] shows the TRUE plant, the next
+                                           pack and tube_hist[t + 1][b] / audit measure it.  log_hist and track keep describing the PLAN, not the plant.
+        The drives' state is `self.plant_state` [B][PLANT_STATE_LEN], created from the robot records on first use (plant_state_of) and carried from launch to
+        launch, so rollouts chain.  The rows are validated on the device; a row with an invalid slot does not run, as an invalid tune row.
+          plant_info [B] int32             0: the row was valid and the stream ran; else the bit mask of its invalid slots -- READ IT
+          plant_rec [B][PLANT_REC_LEN]     want_plant_rec: what the drives did to the commands (slots PLANT_REC, unpack_plant_rec)."""
         import torch
         if waves is not None:
             former = self.solver.rollout_waves
             self.solver.set_rollout_waves(waves)      # (a refused value raises here, the setting intact)
             try:
                 return self.rollout(ticks, max_iter, warm_dual, accept_capped, goal_tol, want_traj, stream, replan, replan_tick, splice, poor_bounds, set_goal,
-                                    disturb, audit, audit_tol, want_tube, want_log, log_stages, track, None, legs, leg_tick, leg_on, leg_tol, tune, want_tune_used)
+                                    disturb, audit, audit_tol, want_tube, want_log, log_stages, track, None, legs, leg_tick, leg_on, leg_tol, tune, want_tune_used,
+                                    plant, want_plant_rec)
             finally:
                 self.solver.set_rollout_waves(former)
         if max_iter and not warm_dual:
@@ -934,6 +1099,42 @@ class StreamBatch:
             tuned = (_ptr(tune), _ptr(out["tune_info"]), _ptr(out["tune_used"]) if want_tune_used else None)
         elif want_tune_used:
             raise ValueError("want_tune_used goes with tune")
+        if plant is None and want_plant_rec:
+            raise ValueError("want_plant_rec goes with plant")
+        if plant is not None:
+            # the plant entry: the arguments of the sweeps entry in their order, with or without a queue and a settings table, then the plant's
+            if replan is not None or replan_tick is not None:
+                raise ValueError("plant goes with legs, the queue of re-plan records: it does not go with replan / replan_tick")
+            plant = self._dev64(plant, (self.B, PLANT["LEN"]), "plant", stream)
+            state = self._plant_state(stream)
+            out["plant_info"] = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
+            if want_plant_rec:
+                out["plant_rec"] = torch.empty((self.B, PLANT_REC["LEN"]), dtype=torch.float64, device=dev)
+            if legs is None and (leg_tick is not None or leg_on is not None or leg_tol is not None):
+                raise ValueError("leg_tick, leg_on and leg_tol describe the records of legs")
+            if disturb is not None:
+                disturb = self._dev64(disturb, (n, self.B, DIST_LEN), "disturb", stream)
+            queue = (None, None, self._update_flags(set_goal, splice, poor_bounds))
+            legs_args = (0, None, None, None, None, None, None)
+            if legs is not None:
+                K = self._legs_buffer(legs, stream)
+                i32 = lambda a, fill, name: torch.full((self.B, K), fill, dtype=torch.int32, device=dev) if a is None else self._dev64(a, (self.B, K), name, stream, dtype=torch.int32)
+                leg_tick, leg_on = i32(leg_tick, -1, "leg_tick"), i32(leg_on, 0, "leg_on")
+                if leg_tol is not None:
+                    leg_tol = self._dev64(leg_tol, (self.B, K), "leg_tol", stream)
+                out["legs_done"] = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+                out["leg_fired"], out["replan_info"] = (torch.full((self.B, K), -1, dtype=torch.int32, device=dev) for _ in range(2))
+                out["leg_why"] = torch.zeros((self.B, K), dtype=torch.int32, device=dev)
+                queue = (_ptr(self.legs), _ptr(out["replan_info"]), queue[2])
+                legs_args = (K, _ptr(leg_tick), _ptr(leg_on), _ptr(leg_tol) if leg_tol is not None else None, _ptr(out["legs_done"]), _ptr(out["leg_fired"]), _ptr(out["leg_why"]))
+            _lib.check(self.solver._lib.bmpc_stream_rollout_plant(
+                self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]), _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]),
+                *queue, _ptr(disturb) if disturb is not None else None, _ptr(out["tube_hist"]) if want_tube else None,
+                _ptr(out["audit"]) if audit else None, float(audit_tol), _ptr(out["log_hist"]) if want_log else None, int(log_stages), _ptr(out["track"]) if track else None,
+                *legs_args, *(tuned if tune is not None else (None, None, None)), _ptr(plant), _ptr(state), _ptr(out["plant_info"]),
+                _ptr(out["plant_rec"]) if want_plant_rec else None, self._stream(stream)), "bmpc_stream_rollout_plant")
+            self._event_inputs = (leg_tick, leg_on, leg_tol, disturb, tune, plant)      # the launch is asynchronous: its inputs live until the next one replaces them
+            return out
         if tune is not None and legs is None:      # a sweep without a queue: replan = NULL, and no queue argument is looked at
             if leg_tick is not None or leg_on is not None or leg_tol is not None:
                 raise ValueError("leg_tick, leg_on and leg_tol describe the records of legs")

@@ -298,7 +298,7 @@ int bmpc_stream_rollout(bmpc_handle *h, int B, int ticks, const double *path, in
                         double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
                         double goal_tol, double *hist /* [ticks][B][52] or NULL */, double *traj_hist /* [ticks][B][traj] or NULL */,
                         int *ticks_run /* [B] or NULL */, void *hip_stream);
-/* Waves per stream of the six rollout entries (bmpc_stream_rollout, _events, _audit, _log, _legs, _tuned), read at launch time:
+/* Waves per stream of the seven rollout entries (bmpc_stream_rollout, _events, _audit, _log, _legs, _tuned, _plant), read at launch time:
  *   1 (default)   one wave per stream, on the resident waves of the device;
  *   BMPC_TEAM_NW  a team of cooperating waves per stream whatever B is, striding over the resident teams (256 on an MI355X: a team owns a CU);
  *                 BMPC_ERR_ARG on a handle without team kernels (N > 10 or S > 4), as bmpc_set_team_waves;
@@ -546,6 +546,70 @@ int bmpc_stream_rollout_tuned(bmpc_handle *h, int B, int ticks, const double *pa
                               int *legs_done /* [B] */, int *leg_fired /* [B][legs] or NULL */, int *leg_why /* [B][legs] or NULL */,
                               const double *tune /* [B][BMPC_TUNE_LEN] or NULL */, int *tune_info /* [B] or NULL */,
                               double *tune_used /* [B][BMPC_TUNE_LEN] or NULL */, void *hip_stream);
+/* Rollout with a PLANT MODEL: bmpc_stream_rollout_tuned (its arguments in their order up to and including tune_used, their meaning, tests and contract;
+ * NULL event, audit, log, queue and settings pointers switch those off) with a TABLE of actuator models per stream.  In every other rollout the plant IS
+ * the model: the post moves the robot record with the model's own integrator chain and the planned jerk, and the only deviation is the additive disturb
+ * table, which cannot depend on what the controller commands.  Here a drive stands between the first planned jerk c of every tick and the plant:
+ *   plant       [B][BMPC_PLANT_LEN] or NULL, DEVICE: row b, slots BMPC_PLANT_*; the three words behind BMPC_PLANT_DELAY are pad and never looked at
+ *                 GAIN[7]   actuator gain of joint j                                   identity 1       valid when finite
+ *                 BIAS[7]   jerk offset, rad/s^3                                       identity 0       valid when finite
+ *                 LAG       first-order response per tick, u_act += LAG (a - u_act)    identity 1       valid when 0 < LAG <= 1
+ *                 SAT       jerk magnitude the drive delivers                          identity +inf    valid when > 0 (+inf allowed)
+ *                 DELAY     1: the command applied is the previous tick's              identity 0       valid when 0 or 1
+ *               a NaN slot takes its identity value
+ *   plant_state [B][BMPC_PLANT_STATE_LEN], required with plant, IN AND OUT so that rollouts chain: ACT[7] the lag's state, CMD[7] the previous command,
+ *               two pad words; a stream at rest starts from ACT = CMD = the jerk of its robot record
+ *   plant_info  [B] or NULL: 0 = row b was valid and the stream ran; else the bit mask of its invalid slots (bit k = slot k)
+ *   plant_rec   [B][BMPC_PLANT_REC_LEN] or NULL, initialised by the call: SAMPLES the plant steps taken, N_SAT the ticks on which some joint clipped,
+ *               MAX_DU the largest |u - c| with TICK_DU and JOINT_DU its first tick and joint, SUMSQ_DU the sum of (u - c)^2 in tick order, joints
+ *               0..6 inside a tick, two pad words; a stream without a step: SAMPLES 0, MAX_DU -inf, TICK_DU and JOINT_DU -1, sums 0; a non-finite |u - c|
+ *               makes MAX_DU NaN for good
+ * The step, behind every post that stepped the plant (a tick whose post exhausted the plan takes none), per joint j with c_j the first planned jerk:
+ *   c' = DELAY ? CMD_j : c_j;  CMD_j = c_j;  a = GAIN_j c' + BIAS_j;  f = LAG == 1 ? a : ACT_j + LAG (a - ACT_j);  ACT_j = f;
+ *   u = f > SAT ? SAT : f < -SAT ? -SAT : f  (a NaN passes);  D = u - c_j;
+ *   q_j += h^3/24 D;  dq_j += h^2/6 D;  ddq_j += h/2 D;  the record's jerk_j = u
+ * -- the coefficients of the new jerk in the model's chain, which is linear: exactly the plant ramped from the old true jerk to u instead of to c.  Where
+ * any D != 0, p_lie and v of the robot record are recomputed from the new joint state, as bmpc_stream_disturb does; where every D == 0 the record
+ * keeps every bit.  Non-finite words give non-finite records.
+ * The step sits AHEAD of the history, trajectory and log rows of its tick and of the tick's disturbance and re-plan: hist[t][b] shows the TRUE plant
+ * behind tick t, a disturbance acts on the true plant, a spliced re-plan takes the true state, the next pack and the audit row of tick t + 1 measure it.
+ * THE LOG ROWS AND THE TRACKING RECORD KEEP DESCRIBING THE PLAN, NOT THE PLANT -- stage 0 of a trajectory record comes from the plan --: the measurement
+ * of the plant is the audit (tube_hist, audit).
+ * The table lives on the device, so it is validated there.  A row with an invalid slot DOES NOT RUN and gets the treatment of an invalid tune row:
+ * ticks_run[b] = 0, NaN history rows, the records of a stream lost on entry, untouched tick arrays and plant_state, its mask in plant_info[b]; every
+ * other stream is served as if the row were not there.
+ * With plant == NULL the call IS bmpc_stream_rollout_tuned, and no plant argument is looked at.  With a table of NaN or of identity values every array
+ * that entry names holds what it leaves, bit for bit, and plant_state holds the commands.  With goal_tol = 0 every array, plant_state and plant_rec hold
+ * what this loop leaves, bit for bit:
+ *   for t in 0..ticks-1: bmpc_stream_tick on one wave per stream; bmpc_stream_plant(tick t); bmpc_stream_log; bmpc_stream_disturb(rows of tick t);
+ *                        bmpc_stream_update of the head records due
+ * bmpc_stream_plant is that step on its own, one launch over the batch, for per-tick loops: between a tick (or post) and bmpc_stream_log.  It skips a
+ * stream whose sstate error count is >= N; for an invalid row it writes the mask and touches nothing; plant_rec (or NULL) is ACCUMULATED, not
+ * initialised.  It uses no workspace of the handle and may sit inside a capture of the caller's stream, like bmpc_stream_disturb.
+ * BMPC_ERR_ARG, nothing launched: what bmpc_stream_rollout_tuned refuses, and plant without plant_state; bmpc_stream_plant: no handle, B < 1, no robot,
+ * sstate, plant or plant_state. */
+enum { BMPC_PLANT_GAIN = 0, BMPC_PLANT_BIAS = 7, BMPC_PLANT_LAG = 14, BMPC_PLANT_SAT = 15, BMPC_PLANT_DELAY = 16, BMPC_PLANT_LEN = 20 };      /* three pad words */
+enum { BMPC_PLANT_STATE_ACT = 0, BMPC_PLANT_STATE_CMD = 7, BMPC_PLANT_STATE_LEN = 16 };                                                   /* two pad words */
+enum { BMPC_PLANT_REC_SAMPLES = 0, BMPC_PLANT_REC_N_SAT, BMPC_PLANT_REC_MAX_DU, BMPC_PLANT_REC_TICK_DU, BMPC_PLANT_REC_JOINT_DU, BMPC_PLANT_REC_SUMSQ_DU,
+       BMPC_PLANT_REC_LEN = 8 };                                                                                                            /* two pad words */
+int bmpc_stream_plant_len(void);
+int bmpc_stream_plant_state_len(void);
+int bmpc_stream_plant_rec_len(void);
+int bmpc_stream_rollout_plant(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                              double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                              double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan /* [B][legs][len] or NULL */,
+                              int *replan_info /* [B][legs] or NULL */, int update_flags, const double *disturb /* [ticks][B][21] or NULL */,
+                              double *tube_hist /* [ticks][B][16] or NULL */, double *audit /* [B][12] or NULL */, double audit_tol,
+                              double *log_hist /* [ticks][B][88 log_stages + 4] or NULL */, int log_stages, double *track /* [B][12] or NULL */,
+                              int legs, const int *leg_tick /* [B][legs] */, const int *leg_on /* [B][legs] */, const double *leg_tol /* [B][legs] or NULL */,
+                              int *legs_done /* [B] */, int *leg_fired /* [B][legs] or NULL */, int *leg_why /* [B][legs] or NULL */,
+                              const double *tune /* [B][BMPC_TUNE_LEN] or NULL */, int *tune_info /* [B] or NULL */,
+                              double *tune_used /* [B][BMPC_TUNE_LEN] or NULL */, const double *plant /* [B][BMPC_PLANT_LEN] or NULL */,
+                              double *plant_state /* [B][BMPC_PLANT_STATE_LEN] */, int *plant_info /* [B] or NULL */,
+                              double *plant_rec /* [B][BMPC_PLANT_REC_LEN] or NULL */, void *hip_stream);
+int bmpc_stream_plant(bmpc_handle *h, int B, double *robot, const double *sstate, const double *plant /* [B][BMPC_PLANT_LEN] */,
+                      double *plant_state /* [B][BMPC_PLANT_STATE_LEN] */, int *plant_info /* [B] or NULL */,
+                      double *plant_rec /* [B][BMPC_PLANT_REC_LEN] or NULL, accumulated, not initialised */, int tick, void *hip_stream);
 
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
