@@ -71,8 +71,8 @@
 // treatment of an invalid settings row -- no tick, NaN history rows, its mask in r.plant_info[b], plant_state untouched.  Row, state (r.plant_state[b],
 // in and out: rollouts chain) and record (r.plant_rec[b]) live in global memory, behind opaque stream and tick indices: nothing of the plant is carried
 // in a register across the solve.  Without PL no plant line is compiled.
-// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp,
-// bmpc_emu_rollout_legs.cpp, bmpc_emu_rollout_tune.cpp and bmpc_emu_rollout_plant.cpp, once per BMPC_NW).  The eleven units (bmpc_rollout.hip,
+// Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp:
+// one source and one entry for every variant, built once per BMPC_NW).  The eleven units (bmpc_rollout.hip,
 // bmpc_rollout_events.hip, bmpc_rollout_audit.hip, bmpc_rollout_log.hip, bmpc_rollout_legs.hip, bmpc_rollout_tune.hip, bmpc_rollout_plant.hip,
 // bmpc_team_rollout.hip, bmpc_team_rollout_legs.hip, bmpc_team_rollout_tune.hip, bmpc_team_rollout_plant.hip) and those builds launch through bmpc_rollout_run at the end of this file, the
 // one place that picks <ZLDS, RESTO>.

@@ -292,6 +292,25 @@ def log_len(N):
     return N * LOG_STAGE + 4
 
 
+ROLLOUT_ENTRIES = ("bmpc_stream_rollout", "bmpc_stream_rollout_events", "bmpc_stream_rollout_audit", "bmpc_stream_rollout_log", "bmpc_stream_rollout_legs",
+                   "bmpc_stream_rollout_tuned", "bmpc_stream_rollout_plant")      # by entry number (csrc/bmpc_args.h bmpc_rollout_level)
+
+
+def rollout_entry(replan=False, replan_tick=False, disturb=False, audit=False, want_tube=False, want_log=False, track=False, legs=False, tune=False, plant=False):
+    """The C ABI entry StreamBatch.rollout calls, from which of its argument groups are present (booleans; a combination its argument checks pass).  The
+    entry decides the kernel that runs: the highest feature present names it; without a queue, a table or a plant it is the lowest entry that has an
+    argument for everything asked."""
+    if plant:
+        return ROLLOUT_ENTRIES[6]
+    if tune:
+        return ROLLOUT_ENTRIES[5]
+    if legs:
+        return ROLLOUT_ENTRIES[4]
+    if not (replan or replan_tick or disturb or audit or want_tube or want_log or track):
+        return ROLLOUT_ENTRIES[0]
+    return ROLLOUT_ENTRIES[3 if want_log or track else 2 if audit or want_tube else 1]
+
+
 def rollout_log_len(stages):
     """a log row of a rollout, cut to the first `stages` stages of the plan: [stages][LOG_STAGE] | n_valid | error_count | 2 pad"""
     return int(stages) * LOG_STAGE + 4
@@ -1057,149 +1076,85 @@ class StreamBatch:
           plant_info [B] int32             0: the row was valid and the stream ran; else the bit mask of its invalid slots -- READ IT
           plant_rec [B][PLANT_REC_LEN]     want_plant_rec: what the drives did to the commands (slots PLANT_REC, unpack_plant_rec)."""
         import torch
+        former = self.solver.rollout_waves
         if waves is not None:
-            former = self.solver.rollout_waves
             self.solver.set_rollout_waves(waves)      # (a refused value raises here, the setting intact)
-            try:
-                return self.rollout(ticks, max_iter, warm_dual, accept_capped, goal_tol, want_traj, stream, replan, replan_tick, splice, poor_bounds, set_goal,
-                                    disturb, audit, audit_tol, want_tube, want_log, log_stages, track, None, legs, leg_tick, leg_on, leg_tol, tune, want_tune_used,
-                                    plant, want_plant_rec)
-            finally:
-                self.solver.set_rollout_waves(former)
-        if max_iter and not warm_dual:
-            raise ValueError("an iteration cap needs the dual state (warm_dual=True): the multipliers must be shifted with the plan")
-        assert self.solver._lib.bmpc_stream_rollout_len() == ROLL["LEN"]
-        n, dev = max(int(ticks), 0), self.path.device
-        out = {"hist": torch.empty((n, self.B, ROLL["LEN"]), dtype=torch.float64, device=dev), "ticks_run": torch.zeros((self.B,), dtype=torch.int32, device=dev)}
-        if want_traj:
-            out["traj_hist"] = torch.empty((n, self.B, self.tr_len), dtype=torch.float64, device=dev)
-        args = self._tick_args(max_iter, warm_dual, True, accept_capped)
-        audited = bool(audit) or bool(want_tube)
-        if audit:
-            out["audit"] = torch.empty((self.B, AUDIT["LEN"]), dtype=torch.float64, device=dev)
-        if want_tube:
-            out["tube_hist"] = torch.empty((n, self.B, TUBE["LEN"]), dtype=torch.float64, device=dev)
-        logged = bool(want_log) or bool(track)
-        if want_log:
-            if not 1 <= int(log_stages) <= self.N:
+        try:
+            # 1. the argument checks
+            scheduled = replan is not None or replan_tick is not None
+            if max_iter and not warm_dual:
+                raise ValueError("an iteration cap needs the dual state (warm_dual=True): the multipliers must be shifted with the plan")
+            if want_log and not 1 <= int(log_stages) <= self.N:
                 raise ValueError("log_stages must be in 1..N")
-            assert self.solver._lib.bmpc_stream_rollout_log_len(self.solver._h, int(log_stages)) == rollout_log_len(log_stages)
-            out["log_hist"] = torch.empty((n, self.B, rollout_log_len(log_stages)), dtype=torch.float64, device=dev)
-        if track:
-            assert self.solver._lib.bmpc_stream_track_len() == TRACK["LEN"]
-            out["track"] = torch.empty((self.B, TRACK["LEN"]), dtype=torch.float64, device=dev)
-        if tune is not None:
-            if replan is not None or replan_tick is not None:
+            if tune is not None and scheduled:
                 raise ValueError("tune goes with legs, the queue of re-plan records: it does not go with replan / replan_tick")
-            assert self.solver._lib.bmpc_stream_tune_len() == TUNE["LEN"]
-            tune = self._dev64(tune, (self.B, TUNE["LEN"]), "tune", stream)
-            out["tune_info"] = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
-            if want_tune_used:
-                out["tune_used"] = torch.empty((self.B, TUNE["LEN"]), dtype=torch.float64, device=dev)
-            tuned = (_ptr(tune), _ptr(out["tune_info"]), _ptr(out["tune_used"]) if want_tune_used else None)
-        elif want_tune_used:
-            raise ValueError("want_tune_used goes with tune")
-        if plant is None and want_plant_rec:
-            raise ValueError("want_plant_rec goes with plant")
-        if plant is not None:
-            # the plant entry: the arguments of the sweeps entry in their order, with or without a queue and a settings table, then the plant's
-            if replan is not None or replan_tick is not None:
+            if tune is None and want_tune_used:
+                raise ValueError("want_tune_used goes with tune")
+            if plant is None and want_plant_rec:
+                raise ValueError("want_plant_rec goes with plant")
+            if plant is not None and scheduled:
                 raise ValueError("plant goes with legs, the queue of re-plan records: it does not go with replan / replan_tick")
-            plant = self._dev64(plant, (self.B, PLANT["LEN"]), "plant", stream)
-            state = self._plant_state(stream)
-            out["plant_info"] = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
-            if want_plant_rec:
-                out["plant_rec"] = torch.empty((self.B, PLANT_REC["LEN"]), dtype=torch.float64, device=dev)
+            if legs is not None and scheduled:
+                raise ValueError("legs is the queue of re-plan records: it does not go with replan / replan_tick")
             if legs is None and (leg_tick is not None or leg_on is not None or leg_tol is not None):
                 raise ValueError("leg_tick, leg_on and leg_tol describe the records of legs")
-            if disturb is not None:
-                disturb = self._dev64(disturb, (n, self.B, DIST_LEN), "disturb", stream)
-            queue = (None, None, self._update_flags(set_goal, splice, poor_bounds))
-            legs_args = (0, None, None, None, None, None, None)
+            if (replan is None) != (replan_tick is None):
+                raise ValueError("replan and replan_tick go together")
+            name = rollout_entry(replan=replan is not None, replan_tick=replan_tick is not None, disturb=disturb is not None, audit=bool(audit), want_tube=bool(want_tube),
+                                 want_log=bool(want_log), track=bool(track), legs=legs is not None, tune=tune is not None, plant=plant is not None)
+            entry = ROLLOUT_ENTRIES.index(name)
+            flags = self._update_flags(set_goal, splice, poor_bounds) if entry else 0      # (the plain rollout has no events: their words are not looked at)
+            lib, B, n, dev = self.solver._lib, self.B, max(int(ticks), 0), self.path.device
+            assert lib.bmpc_stream_rollout_len() == ROLL["LEN"] and (not track or lib.bmpc_stream_track_len() == TRACK["LEN"]) and (tune is None or lib.bmpc_stream_tune_len() == TUNE["LEN"])
+            assert not want_log or lib.bmpc_stream_rollout_log_len(self.solver._h, int(log_stages)) == rollout_log_len(log_stages)
+            # 2. every input on the device, once
+            record = state = None
+            K = 0
+            if replan is not None:
+                record = self._replan_buffer(replan, stream)
+                replan_tick = self._dev64(replan_tick, (B,), "replan_tick", stream, dtype=torch.int32)
             if legs is not None:
                 K = self._legs_buffer(legs, stream)
-                i32 = lambda a, fill, name: torch.full((self.B, K), fill, dtype=torch.int32, device=dev) if a is None else self._dev64(a, (self.B, K), name, stream, dtype=torch.int32)
+                record = self.legs
+                i32 = lambda a, fill, what: torch.full((B, K), fill, dtype=torch.int32, device=dev) if a is None else self._dev64(a, (B, K), what, stream, dtype=torch.int32)
                 leg_tick, leg_on = i32(leg_tick, -1, "leg_tick"), i32(leg_on, 0, "leg_on")
                 if leg_tol is not None:
-                    leg_tol = self._dev64(leg_tol, (self.B, K), "leg_tol", stream)
-                out["legs_done"] = torch.zeros((self.B,), dtype=torch.int32, device=dev)
-                out["leg_fired"], out["replan_info"] = (torch.full((self.B, K), -1, dtype=torch.int32, device=dev) for _ in range(2))
-                out["leg_why"] = torch.zeros((self.B, K), dtype=torch.int32, device=dev)
-                queue = (_ptr(self.legs), _ptr(out["replan_info"]), queue[2])
-                legs_args = (K, _ptr(leg_tick), _ptr(leg_on), _ptr(leg_tol) if leg_tol is not None else None, _ptr(out["legs_done"]), _ptr(out["leg_fired"]), _ptr(out["leg_why"]))
-            _lib.check(self.solver._lib.bmpc_stream_rollout_plant(
-                self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]), _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]),
-                *queue, _ptr(disturb) if disturb is not None else None, _ptr(out["tube_hist"]) if want_tube else None,
-                _ptr(out["audit"]) if audit else None, float(audit_tol), _ptr(out["log_hist"]) if want_log else None, int(log_stages), _ptr(out["track"]) if track else None,
-                *legs_args, *(tuned if tune is not None else (None, None, None)), _ptr(plant), _ptr(state), _ptr(out["plant_info"]),
-                _ptr(out["plant_rec"]) if want_plant_rec else None, self._stream(stream)), "bmpc_stream_rollout_plant")
-            self._event_inputs = (leg_tick, leg_on, leg_tol, disturb, tune, plant)      # the launch is asynchronous: its inputs live until the next one replaces them
-            return out
-        if tune is not None and legs is None:      # a sweep without a queue: replan = NULL, and no queue argument is looked at
-            if leg_tick is not None or leg_on is not None or leg_tol is not None:
-                raise ValueError("leg_tick, leg_on and leg_tol describe the records of legs")
+                    leg_tol = self._dev64(leg_tol, (B, K), "leg_tol", stream)
             if disturb is not None:
-                disturb = self._dev64(disturb, (n, self.B, DIST_LEN), "disturb", stream)
-            _lib.check(self.solver._lib.bmpc_stream_rollout_tuned(
-                self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]), _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]),
-                None, None, self._update_flags(set_goal, splice, poor_bounds), _ptr(disturb) if disturb is not None else None, _ptr(out["tube_hist"]) if want_tube else None,
-                _ptr(out["audit"]) if audit else None, float(audit_tol), _ptr(out["log_hist"]) if want_log else None, int(log_stages), _ptr(out["track"]) if track else None,
-                0, None, None, None, None, None, None, *tuned, self._stream(stream)), "bmpc_stream_rollout_tuned")
-            self._event_inputs = (tune, disturb)      # the launch is asynchronous: its inputs live until the next one replaces them
+                disturb = self._dev64(disturb, (n, B, DIST_LEN), "disturb", stream)
+            if tune is not None:
+                tune = self._dev64(tune, (B, TUNE["LEN"]), "tune", stream)
+            if plant is not None:
+                plant, state = self._dev64(plant, (B, PLANT["LEN"]), "plant", stream), self._plant_state(stream)
+            # 3. every output, once
+            out = {"hist": torch.empty((n, B, ROLL["LEN"]), dtype=torch.float64, device=dev), "ticks_run": torch.zeros((B,), dtype=torch.int32, device=dev)}
+            for key, want, shape in (("traj_hist", want_traj, (n, B, self.tr_len)), ("audit", audit, (B, AUDIT["LEN"])), ("tube_hist", want_tube, (n, B, TUBE["LEN"])),
+                                     ("log_hist", want_log, (n, B, rollout_log_len(log_stages) if want_log else 0)), ("track", track, (B, TRACK["LEN"])),
+                                     ("tune_used", want_tune_used, (B, TUNE["LEN"])), ("plant_rec", want_plant_rec, (B, PLANT_REC["LEN"]))):
+                if want:
+                    out[key] = torch.empty(shape, dtype=torch.float64, device=dev)
+            for key, want, shape, fill in (("tune_info", tune is not None, (B,), -1), ("plant_info", plant is not None, (B,), -1), ("legs_done", K, (B,), 0), ("leg_fired", K, (B, K), -1),
+                                           ("leg_why", K, (B, K), 0), ("replan_info", K or 1 <= entry <= 3, (B, K) if K else (B,), -1)):
+                if want:
+                    out[key] = torch.full(shape, fill, dtype=torch.int32, device=dev)
+            # 4. the argument tuple of the entry: the common prefix, then the groups its signature states -- entry k takes the first k of them
+            at = lambda t: None if t is None else _ptr(t)
+            o = lambda key: at(out.get(key))
+            tick = self._tick_args(max_iter, warm_dual, True, accept_capped)
+            prefix = (self.solver._h, tick[0], int(ticks), *tick[1:], float(goal_tol), o("hist"), o("traj_hist"), o("ticks_run"))
+            groups = ((at(record),) + ((at(replan_tick),) if entry <= 3 else ()) + (o("replan_info"), flags, at(disturb)),      # events: the scheduled record (1 to 3) or the queue's
+                      (o("tube_hist"), o("audit"), float(audit_tol)),                                                          # audit
+                      (o("log_hist"), int(log_stages), o("track")),                                                            # log
+                      (K, at(leg_tick), at(leg_on), at(leg_tol), o("legs_done"), o("leg_fired"), o("leg_why")),                 # queue
+                      (at(tune), o("tune_info"), o("tune_used")),                                                              # table
+                      (at(plant), at(state), o("plant_info"), o("plant_rec")))                                                 # plant
+            _lib.check(getattr(lib, name)(*prefix, *(a for group in groups[:entry] for a in group), self._stream(stream)), name)
+            if entry:
+                self._event_inputs = (replan_tick, leg_tick, leg_on, leg_tol, disturb, tune, plant)      # the launch is asynchronous: its inputs live until the next one replaces them
             return out
-        if legs is not None:
-            if replan is not None or replan_tick is not None:
-                raise ValueError("legs is the queue of re-plan records: it does not go with replan / replan_tick")
-            flags = self._update_flags(set_goal, splice, poor_bounds)
-            K = self._legs_buffer(legs, stream)
-            i32 = lambda a, fill, name: torch.full((self.B, K), fill, dtype=torch.int32, device=dev) if a is None else self._dev64(a, (self.B, K), name, stream, dtype=torch.int32)
-            leg_tick, leg_on = i32(leg_tick, -1, "leg_tick"), i32(leg_on, 0, "leg_on")
-            if leg_tol is not None:
-                leg_tol = self._dev64(leg_tol, (self.B, K), "leg_tol", stream)
-            if disturb is not None:
-                disturb = self._dev64(disturb, (n, self.B, DIST_LEN), "disturb", stream)
-            out["legs_done"] = torch.zeros((self.B,), dtype=torch.int32, device=dev)
-            out["leg_fired"], out["replan_info"] = (torch.full((self.B, K), -1, dtype=torch.int32, device=dev) for _ in range(2))
-            out["leg_why"] = torch.zeros((self.B, K), dtype=torch.int32, device=dev)
-            entry, name = (self.solver._lib.bmpc_stream_rollout_legs, "bmpc_stream_rollout_legs") if tune is None else (self.solver._lib.bmpc_stream_rollout_tuned, "bmpc_stream_rollout_tuned")
-            _lib.check(entry(
-                self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]), _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]),
-                _ptr(self.legs), _ptr(out["replan_info"]), flags, _ptr(disturb) if disturb is not None else None, _ptr(out["tube_hist"]) if want_tube else None,
-                _ptr(out["audit"]) if audit else None, float(audit_tol), _ptr(out["log_hist"]) if want_log else None, int(log_stages), _ptr(out["track"]) if track else None,
-                K, _ptr(leg_tick), _ptr(leg_on), _ptr(leg_tol) if leg_tol is not None else None, _ptr(out["legs_done"]), _ptr(out["leg_fired"]), _ptr(out["leg_why"]),
-                *(tuned if tune is not None else ()), self._stream(stream)), name)
-            self._event_inputs = (leg_tick, leg_on, leg_tol, disturb, tune)      # the launch is asynchronous: its inputs live until the next one replaces them
-            return out
-        if leg_tick is not None or leg_on is not None or leg_tol is not None:
-            raise ValueError("leg_tick, leg_on and leg_tol describe the records of legs")
-        if replan is None and replan_tick is None and disturb is None and not audited and not logged:
-            _lib.check(self.solver._lib.bmpc_stream_rollout(self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]),
-                                                            _ptr(out["traj_hist"]) if want_traj else None, _ptr(out["ticks_run"]), self._stream(stream)),
-                       "bmpc_stream_rollout")
-            return out
-        if (replan is None) != (replan_tick is None):
-            raise ValueError("replan and replan_tick go together")
-        flags = self._update_flags(set_goal, splice, poor_bounds)
-        if replan is not None:
-            self._replan_buffer(replan, stream)
-            replan_tick = self._dev64(replan_tick, (self.B,), "replan_tick", stream, dtype=torch.int32)
-        if disturb is not None:
-            disturb = self._dev64(disturb, (n, self.B, DIST_LEN), "disturb", stream)
-        out["replan_info"] = torch.full((self.B,), -1, dtype=torch.int32, device=dev)
-        events = (self.solver._h, args[0], int(ticks), *args[1:], float(goal_tol), _ptr(out["hist"]), _ptr(out["traj_hist"]) if want_traj else None,
-                  _ptr(out["ticks_run"]), _ptr(self.replan) if replan is not None else None, _ptr(replan_tick) if replan is not None else None,
-                  _ptr(out["replan_info"]), flags, _ptr(disturb) if disturb is not None else None)
-        if logged:
-            _lib.check(self.solver._lib.bmpc_stream_rollout_log(*events, _ptr(out["tube_hist"]) if want_tube else None, _ptr(out["audit"]) if audit else None,
-                                                                float(audit_tol), _ptr(out["log_hist"]) if want_log else None, int(log_stages),
-                                                                _ptr(out["track"]) if track else None, self._stream(stream)), "bmpc_stream_rollout_log")
-        elif audited:
-            _lib.check(self.solver._lib.bmpc_stream_rollout_audit(*events, _ptr(out["tube_hist"]) if want_tube else None, _ptr(out["audit"]) if audit else None,
-                                                                  float(audit_tol), self._stream(stream)), "bmpc_stream_rollout_audit")
-        else:
-            _lib.check(self.solver._lib.bmpc_stream_rollout_events(*events, self._stream(stream)), "bmpc_stream_rollout_events")
-        self._event_inputs = (replan_tick, disturb)      # the launch is asynchronous: its inputs live until the next one replaces them
-        return out
+        finally:
+            if waves is not None:
+                self.solver.set_rollout_waves(former)
 
     def closed_loop(self, ticks, cap=0, warm=True, accept_capped=False, first_cap=100, budget_us=None, graph=True, fused=True, timed=False, tick=None):
         """THE closed loop of BASELINE configs[4], as a generator over the tick index: `for t in sb.closed_loop(ticks, ...)`.

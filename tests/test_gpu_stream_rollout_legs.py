@@ -7,7 +7,8 @@ against a graph replay on another stream.  (2, 2), B = 3 streams of tests/emu/em
 import numpy as np
 import pytest
 
-from tests.rollout_contract import ARRAYS, assert_equal as _assert_equal, batch as _batch, close as _close, cut, history_rows, records as _records, small_streams as _small_streams, snapshot as _snapshot
+from tests.rollout_contract import (ARRAYS, assert_equal as _assert_equal, batch as _batch, close as _close, contract_loop, cut, raw_rollout, records as _records,
+                                    small_streams as _small_streams, snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 N, S = 2, 2
@@ -34,55 +35,6 @@ def _mission(B, T):
     return lt, lo, c
 
 
-def _due(ss, t, tick_k, on_k, tol_k):
-    from tests.emu.emu_rollout_legs import due
-    return due(N, ss, t, tick_k, on_k, tol_k)
-
-
-def _mission_loop(sb, ticks, Q, lt, lo, tol, dist, want_tube=True, want_log=True, **kw):
-    """The contract's loop on the batch `sb` (on one wave per stream or on teams, as the batch's handle is set): per tick one fused tick, tube() and
-    log(), bmpc_stream_disturb with the rows of the tick, then -- the host reads the state rows -- bmpc_stream_update(set_goal, splice) on the head records
-    with exactly the flags of the streams whose head is due raised.  Q [B][K][len] is advanced as the device's queue buffer is.
-    -> dict(hist, traj_hist, tube_hist, log_hist: whole rows, ticks_run, legs_done, leg_fired, leg_why, replan_info [B][K], queue)"""
-    import torch
-    from boundmpc_amd import stream as bstream
-    SS, B, K = bstream.SS, sb.B, Q.shape[1]
-    Q = Q.copy()
-    r = dict(hist=np.full((ticks, B, 52), np.nan), traj_hist=np.full((ticks, B, sb.tr_len), np.nan), tube_hist=np.full((ticks, B, 16), np.nan),
-             log_hist=np.full((ticks, B, bstream.log_len(sb.N)), np.nan), ticks_run=np.zeros(B, dtype=int), legs_done=np.zeros(B, dtype=int),
-             leg_fired=np.full((B, K), -1), leg_why=np.zeros((B, K), dtype=int), replan_info=np.full((B, K), -1), queue=Q)
-    stopped = np.zeros(B, dtype=bool)
-    for t in range(ticks):
-        stopped |= sb.state[:, SS["ERRCNT"]].cpu().numpy() >= sb.N
-        sb.tick(simulate=True, **kw)
-        tube, log = sb.tube() if want_tube else None, sb.log() if want_log else None
-        torch.cuda.synchronize()
-        s = _snapshot(sb)
-        live = ~stopped
-        r["hist"][t, live], r["traj_hist"][t, live] = history_rows(s)[live], s["traj"][live]
-        r["ticks_run"][live] = t + 1
-        if want_tube:
-            r["tube_hist"][t, live] = tube.cpu().numpy()[live]
-        if want_log:
-            r["log_hist"][t, live] = log.cpu().numpy()[live]
-        d = dist[t].copy(); d[stopped] = 0.0
-        sb.disturb(d)
-        head = np.minimum(r["legs_done"], K - 1)
-        why = np.array([_due(s["state"][b], t, lt[b, head[b]], lo[b, head[b]], tol[b, head[b]]) if live[b] and r["legs_done"][b] < K else 0 for b in range(B)])
-        if why.any():
-            recs = Q[np.arange(B), head].copy()
-            recs[why == 0, 0] = 0.0
-            info = sb.update_device(recs, set_goal=True, splice=True)
-            torch.cuda.synchronize()
-            after = sb.replan.cpu().numpy()
-            for b in np.nonzero(why)[0]:
-                Q[b, head[b]] = after[b]
-                r["replan_info"][b, head[b]], r["leg_fired"][b, head[b]], r["leg_why"][b, head[b]] = int(info[b]), t, why[b]
-                r["legs_done"][b] += 1
-    torch.cuda.synchronize()
-    return r
-
-
 def _assert_mission(out, loop, sb, what):
     for k in ("ticks_run", "legs_done", "leg_fired", "leg_why", "replan_info"):
         assert out[k].cpu().numpy().tolist() == loop[k].tolist(), f"{what}: {k} {out[k].tolist()}, the loop's {loop[k].tolist()}"
@@ -103,7 +55,7 @@ def _run_against_the_loop(a, b, T, held, waves=None):
     lt, lo, c = _mission(B, T)
     tol = a[1].state[:, bstream.SS["PHIMAX"]].cpu().numpy()[:, None] - c
     dist = ee.disturbances(T, B, on=(1, 4))
-    loop = _mission_loop(a[1], T, Q, lt, lo, tol, dist, **kw)
+    loop = contract_loop(a[1], T, dist=dist, want_tube=True, want_log=True, queue=Q, leg_tick=lt, leg_on=lo, leg_tol=tol, **kw)
     out = b[1].rollout(T, want_traj=True, legs=Q, leg_tick=lt, leg_on=lo, leg_tol=tol, disturb=dist, audit=True, want_tube=True, want_log=True, log_stages=N, track=True,
                        waves=waves, **kw)
     torch.cuda.synchronize()
@@ -173,7 +125,7 @@ def test_a_mission_on_the_gpu_equals_the_cpu_build_of_the_same_text():
     (iterations, kkt) of the siblings."""
     import torch
     from boundmpc_amd.stream import LEG
-    from tests.emu import emu, emu_rollout as ee, emu_rollout_legs as eq
+    from tests.emu import emu, emu_rollout as ee
     T = 8
     (solver, sb, mpcs, recs), = _twins(1)
     _, A, Tab, _ = ee.small_batch(N, S)
@@ -184,14 +136,14 @@ def test_a_mission_on_the_gpu_equals_the_cpu_build_of_the_same_text():
     lo = np.array([[LEG["AT_GOAL"], 0]] * 3, dtype=np.int32)
     tol = np.zeros((3, 2))
     for b in range(3):
-        tr = eq.mission_loop(N, S, 0.1, Tab[b].copy(), ee.unstack(A, b), T, opts=o)
+        tr = ee.contract_loop(N, S, 0.1, Tab[b].copy(), ee.unstack(A, b), T, opts=o)
         tol[b, 0] = tr["phi_max"][at[b]] - 0.5 * (tr["phi"][at[b] - 1] + tr["phi"][at[b]])
         assert tr["phi"][at[b]] - tr["phi"][at[b] - 1] > 1e-6      # (the gap is far above what separates the two builds)
     out = sb.rollout(T, warm_dual=True, want_traj=True, legs=Q, leg_tick=lt, leg_on=lo, leg_tol=tol)
     torch.cuda.synchronize()
     got, hist, th = _snapshot(sb), out["hist"].cpu().numpy(), out["traj_hist"].cpu().numpy()
     R = Q.copy()
-    r = eq.rollout_legs(N, S, 0.1, Tab, A, T, replan=R, leg_tick=lt, leg_on=lo, leg_tol=tol, opts=o)
+    r = ee.rollout(N, S, 0.1, Tab, A, T, entry=4, replan=R, leg_tick=lt, leg_on=lo, leg_tol=tol, opts=o)
     for k in ("ticks_run", "legs_done", "leg_fired", "leg_why", "replan_info"):
         assert out[k].tolist() == r[k].tolist(), k
     assert r["leg_fired"].tolist() == [[2, 6], [3, 6], [4, 6]] and r["ticks_run"].tolist() == [T] * 3 and (r["hist"][:, :, 46] == 0).all()
@@ -224,17 +176,6 @@ def test_a_mission_on_teams_equals_the_team_tick_loop_and_one_wave_closely(mode)
     _close(a[:2], b[:2])
 
 
-def _raw_legs(solver, t, B, ticks, entries, queue, lt, lo, tol, done, fired, why, info, hist=None, run=None, flags=1, goal_tol=0.0, uflags=3, legs=None, audit_tol=1e-6,
-              log_stages=1, max_iter=0):
-    """bmpc_stream_rollout_legs on the tensors of `t` (ARRAYS + path); any of the outputs and queue arrays may be None"""
-    from boundmpc_amd.solver import _ptr
-    K = (queue.shape[1] if queue is not None else 1) if legs is None else legs
-    return solver._lib.bmpc_stream_rollout_legs(solver._h, B, ticks, _ptr(t["path"]), entries, _ptr(t["state"]), _ptr(t["robot"]), _ptr(t["p"]), _ptr(t["x0"]), _ptr(t["dual"]),
-                                                max_iter, _ptr(t["x"]), _ptr(t["g"]), _ptr(t["iters"]), _ptr(t["status"]), _ptr(t["kkt"]), _ptr(t["traj"]), flags, goal_tol,
-                                                _ptr(hist), None, _ptr(run), _ptr(queue), _ptr(info), uflags, None, None, None, audit_tol, None, log_stages, None, K,
-                                                _ptr(lt), _ptr(lo), _ptr(tol), _ptr(done), _ptr(fired), _ptr(why), None)
-
-
 def _tensors(sb):
     return {k: getattr(sb, k) for k in ARRAYS + ("path",)}
 
@@ -258,7 +199,8 @@ def test_the_stride_serves_missions_of_more_streams_than_resident_workgroups():
     hist, run = torch.empty((Ts, B, 52), dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.int32, device=dev)
     done = torch.full((B,), 7, dtype=torch.int32, device=dev)
     fired, why, info = (torch.full((B, 2), 7, dtype=torch.int32, device=dev) for _ in range(3))
-    assert _raw_legs(solver, t, B, Ts, sb.entries, q, tlt, tlo, ttol, done, fired, why, info, hist=hist, run=run) == 0
+    assert raw_rollout(solver, sb, 4, tensors=t, B=B, ticks=Ts, replan=q, leg_tick=tlt, leg_on=tlo, leg_tol=ttol, legs_done=done, leg_fired=fired, leg_why=why, replan_info=info,
+                       hist=hist, ticks_run=run)[0] == 0
     torch.cuda.synchronize()
     assert want["leg_fired"].tolist() == [[0, 2], [1, 2], [0, 3]] and want["leg_why"].tolist() == [[4, 4], [4, 4], [1, 4]]
     assert (run == Ts).all() and (done == 2).all() and (info == 0).all() and (q[:, :, 0] == 0.0).all()
@@ -280,12 +222,11 @@ def test_argument_errors_launch_nothing():
     lt, lo = torch.ones((3, 2), dtype=torch.int32, device=dev), torch.zeros((3, 2), dtype=torch.int32, device=dev)
     done = torch.full((3,), 7, dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
-    before, t = _snapshot(sb), _tensors(sb)
-    call = lambda ticks=2, queue=q, lt=lt, lo=lo, done=done, **kw: _raw_legs(solver, t, 3, ticks, sb.entries, queue, lt, lo, None, done, None, None, None, **kw)
-    for kw in (dict(lt=None), dict(lo=None), dict(done=None), dict(legs=0), dict(legs=-1), dict(uflags=8), dict(uflags=4), dict(ticks=0), dict(flags=0), dict(goal_tol=-1.0),
-               dict(goal_tol=float("nan")), dict(audit_tol=-1.0), dict(queue=None, audit_tol=float("nan"))):
+    before = _snapshot(sb)
+    call = lambda **kw: raw_rollout(solver, sb, 4, **{**dict(replan=q, leg_tick=lt, leg_on=lo, legs_done=done), **kw})[0]
+    for kw in (dict(leg_tick=None), dict(leg_on=None), dict(legs_done=None), dict(legs=0), dict(legs=-1), dict(update_flags=8), dict(update_flags=4), dict(ticks=0), dict(flags=0),
+               dict(goal_tol=-1.0), dict(goal_tol=float("nan")), dict(audit_tol=-1.0), dict(replan=None, audit_tol=float("nan")), dict(handle=None)):
         assert call(**kw) == 1, kw
-    assert _raw_legs(type("NoHandle", (), {"_lib": solver._lib, "_h": None}), t, 3, 2, sb.entries, q, lt, lo, None, done, None, None, None) == 1
     with pytest.raises(ValueError, match="does not go with"):
         sb.rollout(2, warm_dual=True, legs=Q, replan=Q[:, 0], replan_tick=[1, 1, 1])
     with pytest.raises(ValueError, match="records of legs"):
@@ -300,7 +241,7 @@ def test_argument_errors_launch_nothing():
     _assert_equal(before, _snapshot(sb), "nothing was launched")
     assert torch.equal(q, torch.as_tensor(Q, device=dev)) and done.tolist() == [7, 7, 7]
     # without records the queue arguments are not looked at: the call runs (as the log entry without a re-plan)
-    assert call(queue=None, lt=None, lo=None, done=None, legs=-3) == 0
+    assert call(replan=None, leg_tick=None, leg_on=None, legs_done=None, legs=-3) == 0
     torch.cuda.synchronize()
     _close((solver, sb))
 

@@ -7,7 +7,7 @@ tests/emu/emu_rollout.py, T = 6, the tables of tests/test_stream_rollout_plant.p
 import numpy as np
 import pytest
 
-from tests.rollout_contract import (ARRAYS, assert_equal as _assert_equal, batch as _batch, close as _close, cut, history_rows, records as _records,
+from tests.rollout_contract import (ARRAYS, assert_equal as _assert_equal, batch as _batch, close as _close, contract_loop, cut, raw_rollout, records as _records,
                                     small_streams as _small_streams, snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
@@ -60,51 +60,6 @@ def _fixed_table():
     return bstream.plant_table(B, gain=[[0.8] * 7, [NAN] * 7, [NAN] * 7, [NAN] * 7], lag=[NAN, 0.5, NAN, NAN], delay=[NAN, 1.0, NAN, NAN], sat=[NAN, NAN, 0.1, NAN])
 
 
-def _plant_loop(sb, ticks, Q, lt, plant, dist, **kw):
-    """The contract's loop on the batch `sb` (on one wave per stream or on teams, as the batch's handle is set): per tick one fused tick, plant_step(tick t),
-    tube() and log(), bmpc_stream_disturb with the rows of the tick, then -- the host reads the state rows -- bmpc_stream_update(set_goal, splice) on the head
-    records with exactly the flags of the streams whose head is due (a tick condition alone here) raised.  Q [B][K][len] is advanced as the device's queue is.
-    -> dict(hist, traj_hist, tube_hist, log_hist: whole rows, ticks_run, legs_done, leg_fired, replan_info [B][K], queue, plant_state, plant_rec)"""
-    import torch
-    from boundmpc_amd import stream as bstream
-    SS, Bn, K = bstream.SS, sb.B, Q.shape[1]
-    Q = Q.copy()
-    r = dict(hist=np.full((ticks, Bn, 52), np.nan), traj_hist=np.full((ticks, Bn, sb.tr_len), np.nan), tube_hist=np.full((ticks, Bn, 16), np.nan),
-             log_hist=np.full((ticks, Bn, bstream.log_len(sb.N)), np.nan), ticks_run=np.zeros(Bn, dtype=int), legs_done=np.zeros(Bn, dtype=int),
-             leg_fired=np.full((Bn, K), -1), replan_info=np.full((Bn, K), -1), queue=Q)
-    stopped = np.zeros(Bn, dtype=bool)
-    sb.plant_reset()      # (the drives start where the launch starts them: from the robot records ahead of the first tick)
-    for t in range(ticks):
-        stopped |= sb.state[:, SS["ERRCNT"]].cpu().numpy() >= sb.N
-        sb.tick(simulate=True, **kw)
-        info = sb.plant_step(plant, tick=t)
-        tube, log = sb.tube(), sb.log()
-        torch.cuda.synchronize()
-        assert not info.any()
-        s = _snapshot(sb)
-        live = ~stopped
-        r["hist"][t, live], r["traj_hist"][t, live] = history_rows(s)[live], s["traj"][live]
-        r["ticks_run"][live] = t + 1
-        r["tube_hist"][t, live], r["log_hist"][t, live] = tube.cpu().numpy()[live], log.cpu().numpy()[live]
-        d = dist[t].copy(); d[stopped] = 0.0
-        sb.disturb(d)
-        head = np.minimum(r["legs_done"], K - 1)
-        due = np.array([live[b] and r["legs_done"][b] < K and 0 <= lt[b, head[b]] <= t for b in range(Bn)])
-        if due.any():
-            recs = Q[np.arange(Bn), head].copy()
-            recs[~due, 0] = 0.0
-            inf = sb.update_device(recs, set_goal=True, splice=True)
-            torch.cuda.synchronize()
-            after = sb.replan.cpu().numpy()
-            for b in np.nonzero(due)[0]:
-                Q[b, head[b]] = after[b]
-                r["replan_info"][b, head[b]], r["leg_fired"][b, head[b]] = int(inf[b]), t
-                r["legs_done"][b] += 1
-    torch.cuda.synchronize()
-    r["plant_state"], r["plant_rec"] = sb.plant_state.cpu().numpy(), sb.plant_rec.cpu().numpy()
-    return r
-
-
 def _deviation(x, y):
     x, y = np.asarray(x, dtype=float), np.asarray(y, dtype=float)
     assert x.shape == y.shape and np.array_equal(np.isnan(x), np.isnan(y)), "shapes or NaN slots differ"
@@ -131,7 +86,7 @@ def _contract(held, team):
         a, b = _made(held, team), _made(held, team)
         for _, sb, _, _ in (a, b):
             sb.tick(max_iter=100, warm_dual=True)
-        loop = _plant_loop(a[1], T, Q, ev["leg_tick"], tab, ev["disturb"], **kw)
+        loop = contract_loop(a[1], T, dist=ev["disturb"], want_tube=True, want_log=True, queue=Q, leg_tick=ev["leg_tick"], plant=tab, **kw)
         out = b[1].rollout(T, legs=Q, plant=tab, want_plant_rec=True, waves=waves, **ev, **ON, **kw)
         torch.cuda.synchronize()
         got, want = _snapshot(b[1]), _snapshot(a[1])
@@ -171,38 +126,12 @@ def test_a_rollout_with_plants_on_teams_equals_the_per_tick_loop_of_team_ticks(m
     _contract(mode == "held", True)
 
 
-def _raw_plant(solver, sb, ticks, Q, ev, plant, state, tune=None, waves=None, t=None, Bn=None, **kw):
-    """bmpc_stream_rollout_plant on the tensors of the batch (or on `t`: ARRAYS + path of Bn streams) with every output on; plant: [B][20] array or None,
-    state: a device tensor or None -> dict of device tensors (the outputs, queue: the record buffer), rc with kw want_rc"""
-    import torch
-    from boundmpc_amd.solver import _ptr
-    dev = sb.path.device
-    t = t or {k: getattr(sb, k) for k in ARRAYS + ("path",)}
-    Bn = Bn or sb.B
-    dt = lambda a, d: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=dev).to(d).contiguous()
-    q, lt, dist, tn, pl = dt(Q, torch.float64), dt(ev.get("leg_tick"), torch.int32), dt(ev.get("disturb"), torch.float64), dt(tune, torch.float64), dt(plant, torch.float64)
-    K = q.shape[1] if q is not None else 1
-    lo = None if lt is None else torch.zeros_like(lt)
-    f64 = lambda *shape: torch.full(shape, -7.0, dtype=torch.float64, device=dev)
-    i32 = lambda *shape: torch.full(shape, -7, dtype=torch.int32, device=dev)
-    r = dict(hist=f64(ticks, Bn, 52), traj_hist=f64(ticks, Bn, sb.tr_len), tube_hist=f64(ticks, Bn, 16), log_hist=f64(ticks, Bn, 88 * N + 4), audit=f64(Bn, 12), track=f64(Bn, 12),
-             ticks_run=i32(Bn), legs_done=i32(Bn), leg_fired=i32(Bn, K), leg_why=i32(Bn, K), replan_info=i32(Bn, K), tune_info=i32(Bn), tune_used=f64(Bn, 16),
-             plant_info=i32(Bn), plant_rec=f64(Bn, 8), queue=q, plant_state=state)
-    former = solver.rollout_waves
-    if waves is not None:
-        solver.set_rollout_waves(waves)
-    rc = solver._lib.bmpc_stream_rollout_plant(
-        kw.get("handle", solver._h), Bn, ticks, _ptr(t["path"]), sb.entries, _ptr(t["state"]), _ptr(t["robot"]), _ptr(t["p"]), _ptr(t["x0"]), _ptr(t["dual"]), kw.get("max_iter", 0),
-        _ptr(t["x"]), _ptr(t["g"]), _ptr(t["iters"]), _ptr(t["status"]), _ptr(t["kkt"]), _ptr(t["traj"]), kw.get("flags", 3), kw.get("goal_tol", 0.0), _ptr(r["hist"]),
-        _ptr(r["traj_hist"]), _ptr(r["ticks_run"]), _ptr(q), _ptr(r["replan_info"]), kw.get("uflags", 3), _ptr(dist), _ptr(r["tube_hist"]), _ptr(r["audit"]), kw.get("audit_tol", 1e-6),
-        _ptr(r["log_hist"]), kw.get("log_stages", N), _ptr(r["track"]), K, _ptr(lt), _ptr(lo), None, _ptr(r["legs_done"]) if kw.get("done", True) else None, _ptr(r["leg_fired"]),
-        _ptr(r["leg_why"]), _ptr(tn), _ptr(r["tune_info"]), _ptr(r["tune_used"]), _ptr(pl), _ptr(state) if state is not None else None, _ptr(r["plant_info"]), _ptr(r["plant_rec"]), None)
-    solver.set_rollout_waves(former)
-    if kw.get("want_rc"):
-        return rc
-    assert rc == 0
-    r["inputs"] = (lt, lo, dist, tn, pl)
-    return r
+def _every_output_on(solver, sb, ticks, Q, ev, plant, state, **kw):
+    """bmpc_stream_rollout_plant on the tensors of the batch with every output on, the log rows of all N stages, the real-time rule and leg_on = 0;
+    plant: [B][20] array or None, state: a device tensor or None; kw: arguments of raw_rollout -> (rc, dict of what was passed)"""
+    lt = ev.get("leg_tick")
+    return raw_rollout(solver, sb, 6, outputs=True, **{**dict(ticks=ticks, flags=3, log_stages=N, replan=Q, leg_tick=lt, leg_on=None if lt is None else np.zeros_like(lt),
+                                                              disturb=ev.get("disturb"), plant=plant, plant_state=state), **kw})
 
 
 # ---- 2. no table, the table of NaN, the identity table ----
@@ -210,22 +139,23 @@ def _raw_plant(solver, sb, ticks, Q, ev, plant, state, tune=None, waves=None, t=
 def test_no_table_a_table_of_nan_and_the_identity_table_are_the_sweeps_entry(waves):
     import torch
     from boundmpc_amd import stream as bstream
-    from tests.emu import emu_rollout_tune as tu
+    from tests.emu import emu_rollout as ee
     made = [_made() for _ in range(4)]
     for _, sb, _, _ in made:
         sb.tick(max_iter=100, warm_dual=True)
-    Q, ev, tune = _queue(made[0][2], made[0][3], made[0][1].entries), _events(), tu.table()
+    Q, ev, tune = _queue(made[0][2], made[0][3], made[0][1].entries), _events(), ee.table()
     want = made[0][1].rollout(T, legs=Q, tune=tune, want_tune_used=True, waves=waves, **ev, **ON, **CONV_KW)
     nan = made[1][1].rollout(T, legs=Q, tune=tune, want_tune_used=True, plant=np.full((B, 20), NAN), want_plant_rec=True, waves=waves, **ev, **ON, **CONV_KW)
     ident = made[2][1].rollout(T, legs=Q, tune=tune, want_tune_used=True, plant=np.tile(bstream.plant_identity(), (B, 1)), want_plant_rec=True, waves=waves, **ev, **ON, **CONV_KW)
-    none = _raw_plant(made[3][0], made[3][1], T, Q, ev, None, None, tune=tune, waves=waves)
+    rc, none = _every_output_on(made[3][0], made[3][1], T, Q, ev, None, None, tune=tune, waves=waves)
     torch.cuda.synchronize()
+    assert rc == 0
     for r, sb, what in ((nan, made[1][1], "a table of NaN"), (ident, made[2][1], "the identity table"), (none, made[3][1], "no table")):
         _assert_equal(_snapshot(made[0][1]), _snapshot(sb), what)
         assert torch.equal(made[0][1].path, sb.path)
         for k in OUT + PER + ("tune_info", "tune_used"):
             assert np.array_equal(want[k].cpu().numpy(), r[k].cpu().numpy(), equal_nan=True), f"{what}: {k}"
-    assert torch.equal(made[0][1].legs, made[1][1].legs) and torch.equal(made[0][1].legs, made[2][1].legs) and torch.equal(made[0][1].legs, none["queue"])
+    assert torch.equal(made[0][1].legs, made[1][1].legs) and torch.equal(made[0][1].legs, made[2][1].legs) and torch.equal(made[0][1].legs, none["replan"])
     for r, sb in ((nan, made[1][1]), (ident, made[2][1])):      # the state holds the commands: the jerk the last post stored
         assert r["plant_info"].tolist() == [0] * B and r["plant_rec"].tolist() == [[T, 0, 0, 0, 0, 0, 0, 0]] * B
         st, last = sb.plant_state.cpu().numpy(), r["hist"][T - 1].cpu().numpy()[:, 36:43]
@@ -291,7 +221,7 @@ def test_a_rollout_with_plants_on_the_gpu_equals_the_cpu_build_of_the_same_text(
     tests/emu's g++ build of the kernel text -- the comparison of the sweeps' and the missions' tests: 1e-11 with its two exclusions (iterations, kkt)."""
     import torch
     from boundmpc_amd import stream as bstream
-    from tests.emu import emu, emu_rollout as ee, emu_rollout_plant as ep
+    from tests.emu import emu, emu_rollout as ee
     solver, sb, mpcs, recs = _made()
     _, A, Tab, _ = ee.small_batch(N, S, B)
     Q, ev, tab = _queue(mpcs, recs, sb.entries), _events(), _fixed_table()
@@ -299,7 +229,7 @@ def test_a_rollout_with_plants_on_the_gpu_equals_the_cpu_build_of_the_same_text(
     torch.cuda.synchronize()
     got, hist, th = _snapshot(sb), out["hist"].cpu().numpy(), out["traj_hist"].cpu().numpy()
     R, st = Q.copy(), bstream.plant_state_of(A["rb"])
-    r = ep.rollout_plant(N, S, 0.1, Tab, A, T, tab, st, replan=R, leg_on=np.zeros((B, 2)), accept_capped=True, opts=emu.opts_for(N, start_rollout=0), **ev)
+    r = ee.rollout(N, S, 0.1, Tab, A, T, entry=6, plant=tab, plant_state=st, replan=R, leg_on=np.zeros((B, 2)), accept_capped=True, opts=emu.opts_for(N, start_rollout=0), **ev)
     for k in ("ticks_run", "legs_done", "leg_fired", "leg_why", "replan_info", "plant_info"):
         assert out[k].tolist() == r[k].tolist(), k
     assert r["ticks_run"].tolist() == [T] * B and (hist[:, :, 46] == 0).all()
@@ -333,12 +263,13 @@ def test_the_stride_serves_more_streams_than_resident_workgroups():
     state = torch.zeros((Bn, 16), dtype=torch.float64, device=dev)
     state[:, :7] = state[:, 7:14] = t["robot"][:, 36:43]
     i = idx.cpu().numpy()
-    r = _raw_plant(solver, sb, Ts, Q[i], dict(leg_tick=ev["leg_tick"][i]), tab[i], state, t=t, Bn=Bn)
+    rc, r = _every_output_on(solver, sb, Ts, Q[i], dict(leg_tick=ev["leg_tick"][i]), tab[i], state, tensors=t, B=Bn)
     torch.cuda.synchronize()
+    assert rc == 0
     assert (r["ticks_run"] == Ts).all() and (r["plant_info"] == 0).all()
     for k in ARRAYS + ("path",):
         assert torch.equal(t[k], getattr(small[1], k)[idx]), k
-    assert torch.equal(r["queue"], small[1].legs[idx]) and torch.equal(r["hist"], want["hist"][:, idx]) and torch.equal(r["plant_rec"], want["plant_rec"][idx])
+    assert torch.equal(r["replan"], small[1].legs[idx]) and torch.equal(r["hist"], want["hist"][:, idx]) and torch.equal(r["plant_rec"], want["plant_rec"][idx])
     assert torch.equal(state, small[1].plant_state[idx]) and torch.equal(r["leg_fired"], want["leg_fired"][idx]) and torch.equal(r["legs_done"], want["legs_done"][idx])
     _close(small[:2], big[:2])
 
@@ -354,8 +285,8 @@ def test_argument_errors_launch_nothing():
     state = torch.zeros((B, 16), dtype=torch.float64, device=sb.path.device)
     torch.cuda.synchronize()
     before = _snapshot(sb)
-    call = lambda ticks=2, queue=Q, ev=ev, state=state, **kw: _raw_plant(solver, sb, ticks, queue, ev, tab, state, want_rc=True, **kw)
-    for kw in (dict(state=None), dict(queue=None, ev={}, state=None), dict(ev=dict(disturb=None)), dict(done=False), dict(uflags=8), dict(uflags=4), dict(ticks=0), dict(flags=0),
+    call = lambda ticks=2, queue=Q, ev=ev, state=state, **kw: _every_output_on(solver, sb, ticks, queue, ev, tab, state, **kw)[0]
+    for kw in (dict(state=None), dict(queue=None, ev={}, state=None), dict(ev=dict(disturb=None)), dict(legs_done=None), dict(update_flags=8), dict(update_flags=4), dict(ticks=0), dict(flags=0),
                dict(flags=2), dict(goal_tol=-1.0), dict(goal_tol=float("nan")), dict(audit_tol=-1.0), dict(queue=None, ev={}, audit_tol=float("nan")), dict(log_stages=0),
                dict(log_stages=N + 1), dict(max_iter=-1), dict(handle=None)):
         assert call(**kw) == 1, kw

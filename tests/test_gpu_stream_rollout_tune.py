@@ -3,11 +3,12 @@ csrc/bmpc_team_rollout_tune.hip: csrc/bmpc_rollout_kernel.inl with TU) -- agains
 table of the one-stream batch {b} on a handle of its own whose options and setters carry tune_used[b], bit for bit, on a converged and on a held launch,
 on one wave per stream and on teams; the table of NaN and no table against rollout(legs=...); invalid rows; tune_used and tune_defaults against the
 handle; the g++ build of the same text; the stride over more streams than resident workgroups; the refusals.  (2, 2), B = 4 streams of
-tests/emu/emu_rollout.py, T = 6, the table of tests/emu/emu_rollout_tune.py."""
+tests/emu/emu_rollout.py, T = 6, the table of tests/emu/emu_rollout.py."""
 import numpy as np
 import pytest
 
-from tests.rollout_contract import ARRAYS, HELD, assert_equal as _assert_equal, batch as _batch, close as _close, records as _records, small_streams as _small_streams, snapshot as _snapshot
+from tests.rollout_contract import (ARRAYS, HELD, assert_equal as _assert_equal, batch as _batch, close as _close, raw_rollout, records as _records, small_streams as _small_streams,
+                                    snapshot as _snapshot)
 
 pytestmark = pytest.mark.gpu
 N, S, T, B = 2, 2, 6, 4
@@ -20,8 +21,8 @@ PER = ("ticks_run", "audit", "track", "legs_done", "leg_fired", "leg_why", "repl
 
 
 def _table():
-    from tests.emu import emu_rollout_tune as tu
-    return tu.table()
+    from tests.emu import emu_rollout as ee
+    return ee.table()
 
 
 def _queue(mpcs, recs, entries, K=2):
@@ -138,50 +139,26 @@ def test_a_table_of_nan_and_no_table_are_the_queue_entry(waves):
     Q, ev = _queue(made[0][2], made[0][3], made[0][1].entries), _events()
     want = made[0][1].rollout(T, legs=Q, waves=waves, **ev, **ON, **CONV_KW)
     nan = made[1][1].rollout(T, legs=Q, tune=np.full((B, 16), np.nan), want_tune_used=True, waves=waves, **ev, **ON, **CONV_KW)
-    none = _raw_tuned(made[2][0], made[2][1], T, Q, ev, None, waves=waves)
+    rc, none = _every_output_on(made[2][0], made[2][1], T, Q, ev, None, waves=waves)
     torch.cuda.synchronize()
+    assert rc == 0
     for r, sb, what in ((nan, made[1][1], "a table of NaN"), (none, made[2][1], "no table")):
         _assert_equal(_snapshot(made[0][1]), _snapshot(sb), what)
         assert torch.equal(made[0][1].path, sb.path)
         for k in OUT + PER:
             assert np.array_equal(want[k].cpu().numpy(), r[k].cpu().numpy(), equal_nan=True), f"{what}: {k}"
-    assert torch.equal(made[0][1].legs, made[1][1].legs) and torch.equal(made[0][1].legs, none["queue"])
+    assert torch.equal(made[0][1].legs, made[1][1].legs) and torch.equal(made[0][1].legs, none["replan"])
     assert nan["tune_info"].tolist() == [0] * B and np.array_equal(nan["tune_used"].cpu().numpy(), np.tile(made[1][0].tune_defaults(), (B, 1)))
     assert none["tune_info"].tolist() == [-7] * B and (none["tune_used"] == -7.0).all()      # (not looked at)
     _close(*[m[:2] for m in made])
 
 
-def _raw_tuned(solver, sb, ticks, Q, ev, tune, waves=None, t=None, Bn=None, **kw):
-    """bmpc_stream_rollout_tuned on the tensors of the batch (or on `t`: ARRAYS + path of Bn streams) with every output on; tune: [B][16] array or None
-    -> dict of device tensors (the outputs, queue: the record buffer), rc with kw want_rc"""
-    import torch
-    from boundmpc_amd.solver import _ptr
-    dev = sb.path.device
-    t = t or {k: getattr(sb, k) for k in ARRAYS + ("path",)}
-    Bn = Bn or sb.B
-    dt = lambda a, d: None if a is None else torch.as_tensor(np.ascontiguousarray(a), device=dev).to(d).contiguous()
-    q, lt, dist, tn = dt(Q, torch.float64), dt(ev.get("leg_tick"), torch.int32), dt(ev.get("disturb"), torch.float64), dt(tune, torch.float64)
-    K = q.shape[1] if q is not None else kw.pop("legs", 1)
-    lo = None if lt is None else torch.zeros_like(lt)
-    f64 = lambda *shape: torch.full(shape, -7.0, dtype=torch.float64, device=dev)
-    i32 = lambda *shape: torch.full(shape, -7, dtype=torch.int32, device=dev)
-    r = dict(hist=f64(ticks, Bn, 52), traj_hist=f64(ticks, Bn, sb.tr_len), tube_hist=f64(ticks, Bn, 16), log_hist=f64(ticks, Bn, 88 * N + 4), audit=f64(Bn, 12), track=f64(Bn, 12),
-             ticks_run=i32(Bn), legs_done=i32(Bn), leg_fired=i32(Bn, K), leg_why=i32(Bn, K), replan_info=i32(Bn, K), tune_info=i32(Bn), tune_used=f64(Bn, 16), queue=q)
-    former = solver.rollout_waves
-    if waves is not None:
-        solver.set_rollout_waves(waves)
-    rc = solver._lib.bmpc_stream_rollout_tuned(
-        kw.get("handle", solver._h), Bn, ticks, _ptr(t["path"]), sb.entries, _ptr(t["state"]), _ptr(t["robot"]), _ptr(t["p"]), _ptr(t["x0"]), _ptr(t["dual"]), kw.get("max_iter", 0),
-        _ptr(t["x"]), _ptr(t["g"]), _ptr(t["iters"]), _ptr(t["status"]), _ptr(t["kkt"]), _ptr(t["traj"]), kw.get("flags", 3), kw.get("goal_tol", 0.0), _ptr(r["hist"]),
-        _ptr(r["traj_hist"]), _ptr(r["ticks_run"]), _ptr(q), _ptr(r["replan_info"]), kw.get("uflags", 3), _ptr(dist), _ptr(r["tube_hist"]), _ptr(r["audit"]), kw.get("audit_tol", 1e-6),
-        _ptr(r["log_hist"]), kw.get("log_stages", N), _ptr(r["track"]), K, _ptr(lt), _ptr(lo), None, _ptr(r["legs_done"]) if kw.get("done", True) else None, _ptr(r["leg_fired"]),
-        _ptr(r["leg_why"]), _ptr(tn), _ptr(r["tune_info"]), _ptr(r["tune_used"]), None)
-    solver.set_rollout_waves(former)
-    if kw.get("want_rc"):
-        return rc
-    assert rc == 0
-    r["inputs"] = (lt, lo, dist, tn)
-    return r
+def _every_output_on(solver, sb, ticks, Q, ev, tune, **kw):
+    """bmpc_stream_rollout_tuned on the tensors of the batch with every output on, the log rows of all N stages, the real-time rule and leg_on = 0; tune:
+    [B][16] array or None; kw: arguments of raw_rollout -> (rc, dict of what was passed)"""
+    lt = ev.get("leg_tick")
+    return raw_rollout(solver, sb, 5, outputs=True, **{**dict(ticks=ticks, flags=3, log_stages=N, replan=Q, leg_tick=lt, leg_on=None if lt is None else np.zeros_like(lt),
+                                                              disturb=ev.get("disturb"), tune=tune), **kw})
 
 
 # ---- 3. invalid rows ----
@@ -265,7 +242,7 @@ def test_a_sweep_on_the_gpu_equals_the_cpu_build_of_the_same_text():
     """From the cold start with the dual state, T = 6, the table of the tests and a two-record queue: the device arrays against tests/emu's g++ build of
     the kernel text -- the comparison of test_a_mission_on_the_gpu_equals_the_cpu_build_of_the_same_text: 1e-11 with its two exclusions (iterations, kkt)."""
     import torch
-    from tests.emu import emu, emu_rollout as ee, emu_rollout_tune as tu
+    from tests.emu import emu, emu_rollout as ee
     solver, sb, mpcs, recs = _made()
     _, A, Tab, _ = ee.small_batch(N, S, B)
     Q, ev, tab = _queue(mpcs, recs, sb.entries), _events(), _table()
@@ -273,7 +250,7 @@ def test_a_sweep_on_the_gpu_equals_the_cpu_build_of_the_same_text():
     torch.cuda.synchronize()
     got, hist, th = _snapshot(sb), out["hist"].cpu().numpy(), out["traj_hist"].cpu().numpy()
     R = Q.copy()
-    r = tu.rollout_tuned(N, S, 0.1, Tab, A, T, tab, replan=R, leg_on=np.zeros((B, 2)), accept_capped=True, opts=emu.opts_for(N, start_rollout=0), **ev)
+    r = ee.rollout(N, S, 0.1, Tab, A, T, entry=5, tune=tab, replan=R, leg_on=np.zeros((B, 2)), accept_capped=True, opts=emu.opts_for(N, start_rollout=0), **ev)
     for k in ("ticks_run", "legs_done", "leg_fired", "leg_why", "replan_info", "tune_info"):
         assert out[k].tolist() == r[k].tolist(), k
     assert np.array_equal(out["tune_used"].cpu().numpy(), r["tune_used"]) and r["ticks_run"].tolist() == [T] * B
@@ -302,12 +279,13 @@ def test_the_stride_serves_sweeps_of_more_streams_than_resident_workgroups():
     idx = torch.arange(Bn, device=dev) % B
     t = {k: getattr(sb, k)[idx].contiguous() for k in ARRAYS + ("path",)}
     i = idx.cpu().numpy()
-    r = _raw_tuned(solver, sb, Ts, Q[i], dict(leg_tick=ev["leg_tick"][i]), tab[i], t=t, Bn=Bn)
+    rc, r = _every_output_on(solver, sb, Ts, Q[i], dict(leg_tick=ev["leg_tick"][i]), tab[i], tensors=t, B=Bn)
     torch.cuda.synchronize()
+    assert rc == 0
     assert (r["ticks_run"] == Ts).all() and (r["tune_info"] == 0).all()
     for k in ARRAYS + ("path",):
         assert torch.equal(t[k], getattr(small[1], k)[idx]), k
-    assert torch.equal(r["queue"], small[1].legs[idx]) and torch.equal(r["hist"], want["hist"][:, idx]) and torch.equal(r["tune_used"], want["tune_used"][idx])
+    assert torch.equal(r["replan"], small[1].legs[idx]) and torch.equal(r["hist"], want["hist"][:, idx]) and torch.equal(r["tune_used"], want["tune_used"][idx])
     assert torch.equal(r["leg_fired"], want["leg_fired"][idx]) and torch.equal(r["legs_done"], want["legs_done"][idx])
     _close(small[:2], big[:2])
 
@@ -321,8 +299,8 @@ def test_argument_errors_launch_nothing():
     Q, ev, tab = _queue(mpcs, recs, sb.entries), _events(), _table()
     torch.cuda.synchronize()
     before = _snapshot(sb)
-    call = lambda ticks=2, queue=Q, ev=ev, **kw: _raw_tuned(solver, sb, ticks, queue, ev, tab, want_rc=True, **kw)
-    for kw in (dict(ev=dict(disturb=None)), dict(done=False), dict(uflags=8), dict(uflags=4), dict(ticks=0), dict(flags=0), dict(flags=2), dict(goal_tol=-1.0), dict(goal_tol=float("nan")),
+    call = lambda ticks=2, queue=Q, ev=ev, **kw: _every_output_on(solver, sb, ticks, queue, ev, tab, **kw)[0]
+    for kw in (dict(ev=dict(disturb=None)), dict(legs_done=None), dict(update_flags=8), dict(update_flags=4), dict(ticks=0), dict(flags=0), dict(flags=2), dict(goal_tol=-1.0), dict(goal_tol=float("nan")),
                dict(audit_tol=-1.0), dict(queue=None, ev={}, audit_tol=float("nan")), dict(log_stages=0), dict(log_stages=N + 1), dict(max_iter=-1), dict(handle=None)):
         assert call(**kw) == 1, kw
     with pytest.raises(ValueError, match="does not go with"):

@@ -172,3 +172,48 @@ def test_the_entry_rule_of_the_library():
                 else:
                     r = er.rollout(N, S, H, Tab.copy(), A, 1, entry=entry, **kw)
                     assert r["ran"] == level and r["ticks_run"].tolist() == [1], (entry, arrays, fault)
+
+
+def test_the_entry_choice_of_the_python_layer_is_the_table():
+    """stream.rollout_entry -- the one place StreamBatch.rollout picks its C ABI entry, which decides the kernel that runs -- against the table, first row
+    that holds, over every combination of the ten presence flags that the argument checks of rollout pass (replan and replan_tick together, and neither
+    with legs, tune or plant); and how many combinations each entry serves, counted by hand: of 256 without and 32 with a scheduled record."""
+    import itertools
+    from boundmpc_amd import _lib
+    table = [(lambda f: f["plant"], "bmpc_stream_rollout_plant"),
+             (lambda f: f["tune"], "bmpc_stream_rollout_tuned"),                                                    # with or without legs
+             (lambda f: f["legs"], "bmpc_stream_rollout_legs"),
+             (lambda f: not any(f[k] for k in ("replan", "replan_tick", "disturb", "audit", "want_tube", "want_log", "track")), "bmpc_stream_rollout"),
+             (lambda f: f["want_log"] or f["track"], "bmpc_stream_rollout_log"),
+             (lambda f: f["audit"] or f["want_tube"], "bmpc_stream_rollout_audit"),
+             (lambda f: True, "bmpc_stream_rollout_events")]
+    names = ("replan", "replan_tick", "disturb", "audit", "want_tube", "want_log", "track", "legs", "tune", "plant")
+    served = {}
+    for bits in itertools.product((False, True), repeat=len(names)):
+        f = dict(zip(names, bits))
+        if f["replan"] != f["replan_tick"] or (f["replan"] and (f["legs"] or f["tune"] or f["plant"])):
+            continue
+        want = next(entry for holds, entry in table if holds(f))
+        assert bstream.rollout_entry(**f) == want, f
+        served[want] = served.get(want, 0) + 1
+    assert served == {"bmpc_stream_rollout_plant": 128, "bmpc_stream_rollout_tuned": 64, "bmpc_stream_rollout_legs": 32, "bmpc_stream_rollout": 1,
+                      "bmpc_stream_rollout_log": 48, "bmpc_stream_rollout_audit": 12, "bmpc_stream_rollout_events": 3}
+    assert bstream.ROLLOUT_ENTRIES == tuple(sorted(served, key=lambda e: len(_lib.SIGNATURES[e][1]))) and bstream.rollout_entry() == bstream.ROLLOUT_ENTRIES[0]
+
+
+@pytest.mark.parametrize("nw", [1, 4])
+def test_the_rargs_mirror_is_the_librarys_record(nw):
+    """emu_rollout.RArgs, the ctypes record the one entry of the CPU build takes, against csrc/bmpc_args.h RArgs: the members the header declares, in its
+    order, and the size and every offset as the build lays the record out -- a new member is one field there and one here, and no argument position"""
+    import ctypes
+    import os
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "boundmpc_amd", "csrc", "bmpc_args.h")).read()
+    body = re.sub(r"//[^\n]*", "", re.search(r"struct RArgs \{(.*?)\n\};", text, re.S).group(1))
+    declared = [name.strip(" *\n") for decl in body.split(";") if decl.strip() for name in re.sub(r"^\s*(const\s+)?\w+\s", "", decl.strip()).split(",")]
+    names = [n for n, _ in er.RArgs._fields_]
+    assert names == declared and len(names) == 30
+    L = er.lib(nw)
+    assert L.bmpc_emu_rargs_size() == ctypes.sizeof(er.RArgs)
+    assert [L.bmpc_emu_rargs_offset(n.encode()) for n in names] == [getattr(er.RArgs, n).offset for n in names]
+    assert L.bmpc_emu_rargs_offset(b"no_such_member") == -1

@@ -1,6 +1,6 @@
 """Missions inside a rollout -- a queue of re-plan records per stream, each fired by a tick number, by the goal of the leg the stream is on or by a lost
-plan -- as device code compiled for the CPU (csrc/bmpc_rollout_kernel.inl with QU; tests/emu/bmpc_emu_rollout_legs.cpp, once for one wave per stream and
-once for teams of four under wave orders 0 and 1).  Everything is bit for bit against the contract's loop for one stream, emu_rollout_legs.mission_loop:
+plan -- as device code compiled for the CPU (csrc/bmpc_rollout_kernel.inl with QU; tests/emu/bmpc_emu_rollout.cpp, once for one wave per stream and
+once for teams of four under wave orders 0 and 1).  Everything is bit for bit against the contract's loop for one stream, emu_rollout.contract_loop with a queue:
 {fused tick's text, tube text, log text, disturb text, splice + update text of the head record when it is due}.  B = 3 streams of emu_rollout.small_stream
 behind a solved-out tick 0, T <= 10; one case at (1, 2), one at (10, 4) with T = 3."""
 import inspect
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from boundmpc_amd import stream as bstream
-from tests.emu import emu_rollout as er, emu_rollout_legs as eq, emu_stream_update as eup
+from tests.emu import emu_rollout as er, emu_stream_update as eup
 
 SS, RP, ROLL = bstream.SS, bstream.RP, bstream.ROLL
 H = er.H
@@ -57,7 +57,7 @@ def test_one_tick_triggered_record_is_the_log_entry(nw, wave_order):
     A, Tb, R = _copy(A0), Tab.copy(), recs.copy()
     want = er.rollout(N, S, H, Tb, A, T, nw=nw, wave_order=wave_order, entry=3, replan=R, replan_tick=tick_of, disturb=dist, log_stages=N)
     C, Tc, Rc = _copy(A0), Tab.copy(), recs[:, None].copy()
-    r = eq.rollout_legs(N, S, H, Tc, C, T, nw=nw, wave_order=wave_order, replan=Rc, leg_tick=tick_of[:, None], leg_on=np.zeros((3, 1)), disturb=dist, log_stages=N)
+    r = er.rollout(N, S, H, Tc, C, T, entry=4, nw=nw, wave_order=wave_order, replan=Rc, leg_tick=tick_of[:, None], leg_on=np.zeros((3, 1)), disturb=dist, log_stages=N)
     assert want["ran"] == 3 and r["ran"] == 4
     for k in er.TICK_ARRAYS:
         assert np.array_equal(A[k], C[k], equal_nan=True), k
@@ -65,12 +65,12 @@ def test_one_tick_triggered_record_is_the_log_entry(nw, wave_order):
     for k in ("hist", "traj_hist", "ticks_run", "tube_hist", "audit", "log_hist", "track"):
         assert np.array_equal(want[k], r[k], equal_nan=True), k
     assert np.array_equal(want["replan_info"], r["replan_info"][:, 0]) and r["replan_info"][:, 0].tolist() == [0, -1, 0]
-    assert r["legs_done"].tolist() == [1, 0, 1] and r["leg_fired"][:, 0].tolist() == [2, -1, T - 1] and r["leg_why"][:, 0].tolist() == [eq.WHY_TICK, 0, eq.WHY_TICK]
+    assert r["legs_done"].tolist() == [1, 0, 1] and r["leg_fired"][:, 0].tolist() == [2, -1, T - 1] and r["leg_why"][:, 0].tolist() == [er.WHY_TICK, 0, er.WHY_TICK]
     # without records: the log entry without a re-plan, and the queue arguments are not looked at (legs = 0 among them)
     A, Tb = _copy(A0), Tab.copy()
     want = er.rollout(N, S, H, Tb, A, T, nw=nw, wave_order=wave_order, entry=3, disturb=dist, log_stages=N)
     C, Tc = _copy(A0), Tab.copy()
-    r = eq.rollout_legs(N, S, H, Tc, C, T, nw=nw, wave_order=wave_order, legs=0, want_done=False, want_fired=False, disturb=dist, log_stages=N)
+    r = er.rollout(N, S, H, Tc, C, T, entry=4, nw=nw, wave_order=wave_order, legs=0, want_done=False, want_fired=False, disturb=dist, log_stages=N)
     assert r["ran"] == want["ran"] == 3 and np.array_equal(Tc, Tab)
     for k in er.TICK_ARRAYS:
         assert np.array_equal(A[k], C[k], equal_nan=True), k
@@ -94,7 +94,7 @@ def test_records_scheduled_by_tick_fire_in_queue_order(nw, wave_order):
     N, S, T = 2, 2, 8
     A0, Tab, Q, lt, lo = _tick_case(N, S, nw)
     dist = er.disturbances(T, 3, on=(1, 4))
-    r, A, Tb, R = eq.assert_equals_the_loop(N, S, A0, Tab, Q, T, lt, lo, None, f"ticks, nw {nw} order {wave_order}", nw=nw, wave_order=wave_order, stages=N, disturb=dist)
+    r, A, Tb, R, _ = er.assert_equals_the_loop(N, S, A0, Tab, Q, T, f"ticks, nw {nw} order {wave_order}", leg_tick=lt, leg_on=lo, leg_tol=None, nw=nw, wave_order=wave_order, stages=N, disturb=dist)
     assert r["ticks_run"].tolist() == [T] * 3 and r["legs_done"].tolist() == [3, 3, 0]
     assert r["leg_fired"].tolist() == [[1, 3, 5], [2, 3, 4], [-1, -1, -1]] and r["leg_why"].tolist() == [[4, 4, 4], [4, 4, 4], [0, 0, 0]]
     assert r["replan_info"].tolist() == [[0, 0, 0], [0, 0, 0], [-1, -1, -1]]
@@ -113,11 +113,11 @@ def test_other_shapes(N, S, T):
     A0, Tab, _ = er.start(N, S)
     Q = _queue(N, S, 2)
     lt = np.array([[0, 1], [-1, T - 1], [-1, -1]], dtype=np.int32)
-    lo = np.array([[0, 0], [eq.AT_GOAL, 0], [0, 0]], dtype=np.int32)
+    lo = np.array([[0, 0], [er.AT_GOAL, 0], [0, 0]], dtype=np.int32)
     tol = np.full((3, 2), 100.0)
-    r, _, _, R = eq.assert_equals_the_loop(N, S, A0, Tab, Q, T, lt, lo, tol, f"N {N} S {S}", stages=N)
+    r, _, _, R, _ = er.assert_equals_the_loop(N, S, A0, Tab, Q, T, f"N {N} S {S}", leg_tick=lt, leg_on=lo, leg_tol=tol, stages=N)
     assert r["legs_done"].tolist() == [2, 2, 0] and r["leg_fired"].tolist() == [[0, 1], [0, T - 1], [-1, -1]]
-    assert r["leg_why"].tolist() == [[4, 4], [eq.WHY_GOAL, eq.WHY_TICK], [0, 0]] and np.array_equal(R[2], Q[2])
+    assert r["leg_why"].tolist() == [[4, 4], [er.WHY_GOAL, er.WHY_TICK], [0, 0]] and np.array_equal(R[2], Q[2])
 
 
 # ---- (c) goals ----
@@ -128,10 +128,10 @@ def _goal_case(N, S, T, nw=1):
     -> (A0, Tab, Q, leg_tick, leg_on, leg_tol, goal_tol, the ticks chosen [B][2], the stop tick chosen for stream 1)"""
     A0, Tab, _ = er.start(N, S, nw)
     Q = _queue(N, S, 2)
-    lt, lo = _words(3, 2, on=eq.AT_GOAL)
+    lt, lo = _words(3, 2, on=er.AT_GOAL)
     tol = np.zeros((3, 2))
     at = np.array([[1, 4], [2, 4], [3, 6]])      # the ticks behind which the records shall fire
-    probe = lambda b, K, goal_tol=0.0: eq.mission_loop(N, S, H, Tab[b].copy(), er.unstack(A0, b), T, replan=Q[b, :K].copy(), leg_tick=lt[b], leg_on=lo[b], leg_tol=tol[b],
+    probe = lambda b, K, goal_tol=0.0: er.contract_loop(N, S, H, Tab[b].copy(), er.unstack(A0, b), T, replan=Q[b, :K].copy(), leg_tick=lt[b], leg_on=lo[b], leg_tol=tol[b],
                                                        goal_tol=goal_tol, nw=nw)
     for b in range(3):
         for k in range(2):
@@ -151,11 +151,11 @@ def _goal_case(N, S, T, nw=1):
 def test_goal_triggered_legs_follow_each_other_at_every_streams_own_pace(nw, wave_order):
     N, S, T = 2, 2, 9
     A0, Tab, Q, lt, lo, tol, goal_tol, at, stop = _goal_case(N, S, T, nw)
-    r, A, Tb, R = eq.assert_equals_the_loop(N, S, A0, Tab, Q, T, lt, lo, tol, f"goals, nw {nw} order {wave_order}", nw=nw, wave_order=wave_order, goal_tol=goal_tol)
+    r, A, Tb, R, _ = er.assert_equals_the_loop(N, S, A0, Tab, Q, T, f"goals, nw {nw} order {wave_order}", leg_tick=lt, leg_on=lo, leg_tol=tol, nw=nw, wave_order=wave_order, goal_tol=goal_tol)
     print("fired", r["leg_fired"].tolist(), "why", r["leg_why"].tolist(), "ticks_run", r["ticks_run"].tolist(), "leg_tol", tol.tolist(), "goal_tol", goal_tol)
     two = [b for b in range(3) if r["legs_done"][b] == 2]
     assert len(two) >= 2                                                                   # at least two streams consumed two records each
-    assert all(r["leg_why"][b].tolist() == [eq.WHY_GOAL, eq.WHY_GOAL] for b in two)        # by the goal alone
+    assert all(r["leg_why"][b].tolist() == [er.WHY_GOAL, er.WHY_GOAL] for b in two)        # by the goal alone
     assert len({tuple(r["leg_fired"][b]) for b in two}) >= 2                               # each at its own ticks
     short = [b for b in range(3) if r["ticks_run"][b] < T]
     assert short and all(np.isnan(r["hist"][r["ticks_run"][b]:, b]).all() and np.isfinite(r["hist"][:r["ticks_run"][b], b]).all() for b in short)
@@ -178,7 +178,7 @@ def _rescue_case(N, S, nw=1):
     A0["ss"][2, SS["ERRCNT"]] = N
     Q = _queue(N, S, 2)
     lt, lo = _words(3, 2)
-    lo[0, 0] = lo[2, 0] = eq.ON_LOST
+    lo[0, 0] = lo[2, 0] = er.ON_LOST
     return A0, Tab, Q, lt, lo
 
 
@@ -186,15 +186,15 @@ def _rescue_case(N, S, nw=1):
 def test_an_on_lost_record_rescues_the_stream(nw, wave_order):
     N, S, T = 2, 2, 6
     A0, Tab, Q, lt, lo = _rescue_case(N, S, nw)
-    r, A, Tb, R = eq.assert_equals_the_loop(N, S, A0, Tab, Q, T, lt, lo, None, f"rescue, nw {nw} order {wave_order}", nw=nw, wave_order=wave_order, max_iter=1)
-    off = eq.rollout_legs(N, S, H, Tab.copy(), _copy(A0), T, nw=nw, wave_order=wave_order, replan=Q.copy(), leg_tick=lt, leg_on=np.zeros_like(lo), max_iter=1)
+    r, A, Tb, R, _ = er.assert_equals_the_loop(N, S, A0, Tab, Q, T, f"rescue, nw {nw} order {wave_order}", leg_tick=lt, leg_on=lo, leg_tol=None, nw=nw, wave_order=wave_order, max_iter=1)
+    off = er.rollout(N, S, H, Tab.copy(), _copy(A0), T, entry=4, nw=nw, wave_order=wave_order, replan=Q.copy(), leg_tick=lt, leg_on=np.zeros_like(lo), max_iter=1)
     assert off["ticks_run"].tolist() == [2, 2, 0] and off["legs_done"].tolist() == [0, 0, 0]
     # the record fires behind the post that exhausted the plan, with WHY lost, and the stream runs on where the launch without it stops
-    assert r["leg_fired"].tolist() == [[1, -1], [-1, -1], [-1, -1]] and r["leg_why"].tolist() == [[eq.WHY_LOST, 0], [0, 0], [0, 0]] and r["legs_done"].tolist() == [1, 0, 0]
+    assert r["leg_fired"].tolist() == [[1, -1], [-1, -1], [-1, -1]] and r["leg_why"].tolist() == [[er.WHY_LOST, 0], [0, 0], [0, 0]] and r["legs_done"].tolist() == [1, 0, 0]
     assert r["ticks_run"][0] > 2 and r["ticks_run"].tolist()[1:] == [2, 0] and r["hist"][1, 0, ROLL["ERRCNT"]] == N
     assert R[:, :, RP["FLAG"]].tolist() == [[0.0, 1.0], [1.0, 1.0], [1.0, 1.0]] and np.array_equal(Tb[1:], Tab[1:])
     # solved to tolerance the rescue is one in earnest: the new path starts where the plant is, and the stream runs every tick
-    full = eq.assert_equals_the_loop(N, S, A0, Tab, Q, T, lt, lo, None, "rescue, solved to tolerance", nw=nw, wave_order=wave_order)[0]
+    full = er.assert_equals_the_loop(N, S, A0, Tab, Q, T, "rescue, solved to tolerance", leg_tick=lt, leg_on=lo, leg_tol=None, nw=nw, wave_order=wave_order)[0]
     assert full["ticks_run"].tolist() == [T, 2, 0] and full["leg_fired"][0, 0] == 1 and (full["hist"][2:, 0, ROLL["SUCCESS"]] == 1).all()
 
 
@@ -213,16 +213,16 @@ def test_mixed_conditions_and_records_that_are_consumed_without_effect(nw, wave_
     lo = np.array([[1, 0, 0], [1, 0, 0], [1, 0, 0]], dtype=np.int32)
     tol = np.zeros((3, 3))
     for b, t in ((0, 1), (2, 3)):
-        tr = eq.mission_loop(N, S, H, Tab[b].copy(), er.unstack(A0, b), T, nw=nw)
+        tr = er.contract_loop(N, S, H, Tab[b].copy(), er.unstack(A0, b), T, nw=nw)
         tol[b, 0] = tr["phi_max"][t] - 0.5 * (tr["phi"][t - 1] + tr["phi"][t])
-    r, A, Tb, R = eq.assert_equals_the_loop(N, S, A0, Tab, Q, T, lt, lo, tol, f"mixed, nw {nw} order {wave_order}", nw=nw, wave_order=wave_order)
+    r, A, Tb, R, _ = er.assert_equals_the_loop(N, S, A0, Tab, Q, T, f"mixed, nw {nw} order {wave_order}", leg_tick=lt, leg_on=lo, leg_tol=tol, nw=nw, wave_order=wave_order)
     assert r["leg_fired"].tolist() == [[1, 4, 5], [3, 4, 5], [3, 4, -1]] and r["legs_done"].tolist() == [3, 3, 2]
-    assert r["leg_why"].tolist() == [[eq.WHY_GOAL, 4, 4], [eq.WHY_TICK, 4, 4], [eq.WHY_GOAL | eq.WHY_TICK, 4, 0]]
+    assert r["leg_why"].tolist() == [[er.WHY_GOAL, 4, 4], [er.WHY_TICK, 4, 4], [er.WHY_GOAL | er.WHY_TICK, 4, 0]]
     assert r["replan_info"].tolist() == [[0, 0, 0], [0, 1, 0], [0, 0, -1]]
     # the lowered record is untouched, the invalid one has only its flag cleared, the record never reached keeps its flag
     assert np.array_equal(R[0, 1], Q[0, 1]) and R[1, 1, RP["FLAG"]] == 0.0 and np.array_equal(R[1, 1, 1:], Q[1, 1, 1:]) and np.array_equal(R[2, 2], Q[2, 2])
     # ... and neither touched its stream: the rows behind tick 4 are those of the mission without that record's turn
-    S0 = eq.rollout_legs(N, S, H, Tab.copy(), _copy(A0), T, nw=nw, wave_order=wave_order, replan=Q[:, [0, 2]].copy(), leg_tick=lt[:, [0, 2]], leg_on=lo[:, [0, 2]],
+    S0 = er.rollout(N, S, H, Tab.copy(), _copy(A0), T, entry=4, nw=nw, wave_order=wave_order, replan=Q[:, [0, 2]].copy(), leg_tick=lt[:, [0, 2]], leg_on=lo[:, [0, 2]],
                          leg_tol=tol[:, [0, 2]])
     assert np.array_equal(S0["hist"][:, :2], r["hist"][:, :2])
 
@@ -240,23 +240,23 @@ def test_argument_errors_of_the_entry():
     for kw in bad:
         A, Tb = _copy(A0), Tab.copy()
         kw = dict(kw); kw["replan"] = None if kw.get("replan") is None else Q.copy()
-        assert eq.rollout_legs(N, S, H, Tb, A, kw.pop("ticks", 2), want_rc=True, **kw) == 1, {k: v for k, v in kw.items() if k != "replan"}
+        assert er.rollout(N, S, H, Tb, A, kw.pop("ticks", 2), entry=4, want_rc=True, **kw) == 1, {k: v for k, v in kw.items() if k != "replan"}
         for b in range(3):
             er.assert_arrays_equal(er.unstack(A0, b), er.unstack(A, b), "nothing runs")
         assert np.array_equal(Tb, Tab) and (kw["replan"] is None or np.array_equal(kw["replan"], Q))
     # allowed: the per-record outputs and tolerances NULL, no records with any queue argument, log_stages not looked at without the log's arrays
     for kw in (dict(ok, want_fired=False), dict(legs=-5, want_done=False), dict(ok, log_stages=0, want_log=False, track=False)):
         kw = dict(kw); kw["replan"] = None if kw.get("replan") is None else Q.copy()
-        assert eq.rollout_legs(N, S, H, Tab.copy(), _copy(A0), 2, want_rc=True, **kw) == 0
+        assert er.rollout(N, S, H, Tab.copy(), _copy(A0), 2, entry=4, want_rc=True, **kw) == 0
     # the trigger words are not validated: negative words, huge ticks and unknown bits run and end the queue
     lo2 = np.array([[-1, 0], [8, 0], [1 << 30, 0]], dtype=np.int32)
-    r = eq.rollout_legs(N, S, H, Tab.copy(), _copy(A0), 2, replan=Q.copy(), leg_tick=np.zeros((3, 2)), leg_on=lo2)
+    r = er.rollout(N, S, H, Tab.copy(), _copy(A0), 2, entry=4, replan=Q.copy(), leg_tick=np.zeros((3, 2)), leg_on=lo2)
     assert r["legs_done"].tolist() == [0, 0, 0] and (r["leg_fired"] == -1).all()
 
 
 def test_the_python_surface():
     L = bstream.LEG
-    assert (L["AT_GOAL"], L["ON_LOST"], L["WHY_GOAL"], L["WHY_LOST"], L["WHY_TICK"]) == (eq.AT_GOAL, eq.ON_LOST, eq.WHY_GOAL, eq.WHY_LOST, eq.WHY_TICK) == (1, 2, 1, 2, 4)
+    assert (L["AT_GOAL"], L["ON_LOST"], L["WHY_GOAL"], L["WHY_LOST"], L["WHY_TICK"]) == (er.AT_GOAL, er.ON_LOST, er.WHY_GOAL, er.WHY_LOST, er.WHY_TICK) == (1, 2, 1, 2, 4)
     assert {"legs", "leg_tick", "leg_on", "leg_tol"} <= set(inspect.signature(bstream.StreamBatch.rollout).parameters)
     from boundmpc_amd import _lib
     assert len(_lib.SIGNATURES["bmpc_stream_rollout_legs"][1]) == len(_lib.SIGNATURES["bmpc_stream_rollout_log"][1]) - 1 + 7
@@ -279,7 +279,7 @@ def sanitizer_cases(nw):
 def test_the_queue_text_is_clean_under_the_sanitizers(nw):
     """the host program with its own main, built with -fsanitize=address,undefined on exact-size buffers and run as a child process (nothing is loaded
     into this interpreter): cases (b) to (d), on teams under both wave orders; what it prints agrees with this module's expectations"""
-    out = eq.run_sanitized(sanitizer_cases(nw), nw)
+    out = er.run_sanitized(sanitizer_cases(nw), nw)
     print("\n".join(out))
     assert len(out) == 3 and all("rc 0 ran 4" in line and "DIFFERS" not in line for line in out)
     assert "[stream 0 ticks_run 8 legs_done 3 fired 1 3 5 why 4 4 4 info 0 0 0]" in out[0] and "[stream 1 ticks_run 8 legs_done 3 fired 2 3 4" in out[0]

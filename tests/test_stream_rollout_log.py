@@ -184,7 +184,7 @@ def test_argument_refusals_mirror_the_entry():
 
 def test_sanitized_stand_alone_program():
     """the stand-alone program under AddressSanitizer and UndefinedBehaviorSanitizer on the four cases of the rollout with the audit, exact-size buffers"""
-    out = er.run_sanitized(1, only=(3,))      # (the one program of the one-wave texts: its cases with the log, at that level)
+    out = er.run_sanitized(er.plain_cases(1, only=(3,)), 1)      # (the one program of the one-wave texts: its cases with the log, at that level)
     print("\n".join(out))
     assert len(out) == 4 and all("rc 0 ran 3" in line and "| rc 0 ran 3" in line for line in out)
 

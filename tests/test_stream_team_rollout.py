@@ -131,9 +131,9 @@ def test_full_kernel_with_everything_raised_equals_the_assembled_loop(wave_order
 
 
 def test_sanitized_stand_alone_program():
-    """the stand-alone program of the team rollout text under AddressSanitizer and UndefinedBehaviorSanitizer on the cases of emu_rollout.run_sanitized,
+    """the stand-alone program of the team rollout text under AddressSanitizer and UndefinedBehaviorSanitizer on the cases of emu_rollout.plain_cases,
     exact-size heap buffers: per case the plain and the fully-featured kernel under both wave orders, equal checksums"""
-    out = er.run_sanitized(NW)
+    out = er.run_sanitized(er.plain_cases(NW), NW)
     print("\n".join(out))
     assert len(out) == 5 and all(line.count("rc 0") == 4 and "DIFFERS" not in line for line in out)
     assert "ticks_run 6 of 6" in out[0] and "status 3" in out[1] and "ticks_run 4 of 4" in out[4]
