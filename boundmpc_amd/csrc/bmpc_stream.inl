@@ -46,10 +46,13 @@ enum { RB_Q = 0, RB_DQ = 7, RB_DDQ = 14, RB_P = 21, RB_V = 27, RB_XPHID = 33, RB
 // trajectory record: [q dq ddq dddq](7 x N each) [p v a](6 x N each) [phi dphi ddphi dddphi](N each) n_valid
 BMPC_HD inline int tr_len(int N) { return 4 * 7 * N + 3 * 6 * N + 4 * N + 4; }
 // after the previous solution: Cartesian [pos | vel | acc | jerk] (linear parts, 3 x N each, [c][i]) of the previous plan, then the
-// `updated` flag of the reference object
+// `updated` flag of the reference object, the real-time continuation word (stream_post writes it, stream_pack reads it), dphi_max -- the
+// bound of the hard row dphi <= dphi_max, fixed when the stream is created (BoundMPC.py:77-79: weights[4] of the CONSTRUCTOR; update()
+// replaces the weights, :194, and leaves it) -- and one pad word
 BMPC_HD inline int ss_pc(int N) { return SS_PREV + 44 * N; }
 BMPC_HD inline int ss_updated(int N) { return SS_PREV + 56 * N; }
-BMPC_HD inline int ss_len(int N) { return SS_PREV + 56 * N + 2; }
+BMPC_HD inline int ss_dphimax(int N) { return SS_PREV + 56 * N + 2; }
+BMPC_HD inline int ss_len(int N) { return SS_PREV + 56 * N + 4; }
 
 BMPC_HD inline double norm3(const double *a) { return BMPC_SQRT(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]); }
 BMPC_HD inline double dot3(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -434,7 +437,10 @@ BMPC_HD inline void stream_pack(int N, int S, const double *path, int cap, doubl
     if (lane == 0) {
         p[o_xphid] = BMPC_FMIN(phi_cur + 5.0, rb[RB_XPHID]); p[o_xphid + 1] = rb[RB_XPHID + 1]; p[o_xphid + 2] = rb[RB_XPHID + 2];
         p[o_jerk + 7] = ss[SS_DDDPHI];
-        p[o_pm] = phimax_p; p[o_pm + 1] = ss[SS_W + 4];                                     // phi_max (clipped), dphi_max = weights[4]
+        // phi_max (clipped); dphi_max = weights[4] as the stream was CREATED with (a re-plan replaces the weights, not this bound).  A row whose
+        // word is 0 -- built by hand, not by initial_state -- has never been told: the current weights[4], which is that value up to the first re-plan
+        const double dpm = ss[ss_dphimax(N)];
+        p[o_pm] = phimax_p; p[o_pm + 1] = dpm != 0.0 ? dpm : ss[SS_W + 4];
     }
     // ---- warm-start vector: cold start :316-321, or previous plan with omega unwrap :326-333 and shift :372-375 ----
     if (!has_prev) {

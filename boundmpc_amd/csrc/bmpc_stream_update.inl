@@ -12,7 +12,7 @@
 //   path  [cap][PT_LEN]: every row is written: slots 0..M-1, M = n + S - 1, as path_table lays them out, rows M..cap-1 copy row M-1
 //   ss    SS_SECTOR = 0, the path-parameter state projected onto the first segment, SS_PRREF, SS_IWREF, SS_PHIMAX, the weights, SS_NENT = M, the
 //         `updated` flag; an error count >= N goes back to N - 1 (apply_update: a stream that lost its plan gets a new attempt).  The previous
-//         solution and its Cartesian arrays stay.
+//         solution, its Cartesian arrays and dphi_max (ss_dphimax: the constructor's weights[4], which update() leaves, BoundMPC.py:77-79,194) stay.
 //   rb    (may be null) with flag bit 0 (set_goal): RB_XPHID = (phi_max, 0, 0), what the node does right after update() (bound_mpc_node.py:164)
 // Flag protocol: flag == 0 leaves the stream alone (table block and state row untouched, info 0).  Otherwise the record is consumed: the flag
 // is cleared at the end, so a captured graph that holds this launch re-plans only when someone raises a flag again.  n < 2, n > n_max,

@@ -32,12 +32,19 @@ RB = dict(Q=0, DQ=7, DDQ=14, P=21, V=27, XPHID=33, JERK=36, LEN=43)
 
 
 def ss_len(N):
-    """[header 32 | previous solution 44 N | Cartesian pos, vel, acc, jerk of the previous plan 4 x 3 x N | updated flag, pad]"""
-    return SS["PREV"] + 56 * N + 2
+    """[header 32 | previous solution 44 N | Cartesian pos, vel, acc, jerk of the previous plan 4 x 3 x N | updated flag | real-time continuation word |
+    dphi_max | pad]"""
+    return SS["PREV"] + 56 * N + 4
 
 
 def ss_updated(N):
     return SS["PREV"] + 56 * N
+
+
+def ss_dphimax(N):
+    """dphi_max, the bound of the hard row dphi <= dphi_max: weights[4] of the CONSTRUCTOR (BoundMPC.py:77-79).  A re-plan replaces the weights and
+    leaves this word, as the reference's update() does.  0 (a row not made by initial_state): stream_pack takes the current weights[4]."""
+    return SS["PREV"] + 56 * N + 2
 
 
 def path_table(rp, entries=None):
@@ -76,6 +83,7 @@ def initial_state(mpc, N):
     s[SS["IWREF"]:SS["IWREF"] + 3] = mpc.iw_ref
     s[SS["PHIMAX"]] = mpc.phi_max[0]
     s[SS["W"]:SS["W"] + 15] = mpc.weights
+    s[ss_dphimax(N)] = mpc.dphi_max[0]
     if mpc.prev_solution is not None:
         s[SS["HASPREV"]] = 1.0
         s[SS["PREV"]:SS["PREV"] + 44 * N] = np.asarray(mpc.prev_solution, dtype=float).ravel()
@@ -89,7 +97,8 @@ def apply_update(ss, N, S, pos_points, rot_points, pos_lim, rot_lim, bp1, br1, s
     modified in place): new path table (returned, [entries][48]) and window start, path-parameter state projected onto the new first
     segment from the measured Cartesian state (p0, v, a, jerk), rotation reference, phi_max, weights, and the `updated` flag that
     switches the device's warm start to the re-projection branch of step() for good (the reference never clears it).  The previous
-    solution, its Cartesian derivatives and the error count stay, as in the reference -- with one exception: a stream that had LOST its plan
+    solution, its Cartesian derivatives, dphi_max (ss_dphimax: the constructor's weights[4], NOT the new one) and the error count stay, as in the
+    reference -- with one exception: a stream that had LOST its plan
     (error count >= N: the fused tick skips such a stream, status 3) is given a new attempt, its error count goes back to N - 1, so the tick after
     a re-planning solves it again on every launch shape (one more failure loses it again, a success resets the count as in BoundMPC.py:468)."""
     from .reference_path import ReferencePath
@@ -129,6 +138,11 @@ def replan_record(S, entries, pos_points, rot_points, pos_lim, rot_lim, bp1, br1
     """The re-plan record of one stream for bmpc_stream_update (StreamBatch.update_device): a numpy row [replan_len(S, entries)] with the flag
     raised.  Arguments as apply_update after (ss, N, S); rot_points are rotation matrices.  Limit and scalar lists shorter than the via-point list
     are extended by their last entry, as ReferencePath pads them; len(bp1) basis entries are computed on the device, the last one serves the rest.
+    Contract of the frames: every table entry's error-plane basis must be orthonormal to its own segment -- (bp1, bp2) to the segment's direction,
+    (br1, br2) to its rotation axis.  A basis entry that is replicated onto later segments (len(bp1) < n) is Gram-Schmidt'ed against ITS segment only:
+    on a later segment with another direction the frame [br2, d, br1] is then not orthogonal, stream_pack reads its zyx angles through a normalised
+    quaternion where the host mirror (scipy from_matrix) takes the nearest rotation, and v1..v3, ipar, io1, io2 of p differ between the two by
+    O(1).  Give one basis vector per via point unless the segments behind the last one share its direction and axis.
     Raises the ValueError of apply_update when the path does not fit into `entries`."""
     n, nb = len(pos_points), len(bp1)
     if n + S - 1 > entries:

@@ -221,7 +221,14 @@ int bmpc_graph_destroy(bmpc_graph *g);
  * DEVICE doubles, one row per stream, row lengths from bmpc_stream_lengths:
  *   path   [B][path_entries][path_entry]  static via-point table (layout: csrc/bmpc_stream.inl; builder: boundmpc_amd.stream.path_table)
  *   sstate [B][state]   [header 32: phi-state, rotation reference, sector, error count, weights | previous solution 44 N | Cartesian pos, vel,
- *                        acc, jerk of the previous plan 4 x 3 x N | updated flag, pad]
+ *                        acc, jerk of the previous plan 4 x 3 x N | updated flag | real-time continuation word (written by bmpc_stream_post, read by
+ *                        bmpc_stream_pack_rt) | dphi_max | pad].  dphi_max is the bound of the hard row dphi <= dphi_max: weights[4] as the stream was
+ *                        CREATED with (BoundMPC.py:77-79; builder: boundmpc_amd.stream.initial_state).  A re-plan replaces the weights and leaves this
+ *                        word, as the reference's update() does (:194).  A row that holds 0 there packs the current weights[4].
+ *                        Contract of the path table: every entry's error-plane bases are orthonormal to the entry's own direction (bp1, bp2) and rotation
+ *                        axis (br1, br2).  bmpc_stream_pack reads the zyx angles of the frame [br2, d, br1] through a normalised quaternion; for a frame
+ *                        that is not orthogonal (a basis vector replicated onto a segment with another axis, nb < n of a re-plan record) the reference's
+ *                        host code takes the nearest rotation instead, and the packed ipar, io1, io2, v1..v3 differ from it by O(1).
  *   robot  [B][robot]   q dq ddq p_lie v x_phi_d jerk = the arguments of step() (read; written when simulate)
  *   traj   [B][traj]    q dq ddq dddq (7 x N) | p v a (6 x N) | phi dphi ddphi dddphi (N) | n_valid using_previous success g_viol
  * Re-planning (BoundMPC.update, BoundMPC.py:163-217): bmpc_stream_update (below; one launch over the batch) or the host (one stream at a time,
@@ -333,7 +340,7 @@ int bmpc_stream_log(bmpc_handle *h, int B, const double *path, int path_entries,
  *   (builder: boundmpc_amd.stream.replan_record).  Written for a re-planned stream: its whole block of the path table (n + S - 1 slots as
  *   ReferencePath pads its lists, the rows behind them copy the last slot), and of its state row the window start (0), the path-parameter state
  *   projected onto the new first segment, the rotation reference, phi_max, the weights, the entry count and the `updated` flag; an error count
- *   >= N goes back to N - 1, so the next tick solves a stream that had lost its plan.  The previous solution and its Cartesian arrays stay.
+ *   >= N goes back to N - 1, so the next tick solves a stream that had lost its plan.  The previous solution, its Cartesian arrays and dphi_max stay.
  *   flags bit 0 (set_goal) with robot != NULL: also robot[x_phi_d] = (phi_max, 0, 0), what the node does right after update()
  *   (bound_mpc_node.py:164).
  *   flags bit 1 (splice; needs robot != NULL): the words the node takes from the plant (bound_mpc_node.py:121-137,158-162) are written into every

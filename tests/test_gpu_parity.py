@@ -666,7 +666,7 @@ def test_horizon_limits_of_the_handle():
         rc = s._lib.bmpc_stream_pack(s._h, 1, None, 5, vp, vp, vp, vp, None, None)    # missing buffer: refused
         assert rc == 1, rc
         lens = [ctypes.c_int() for _ in range(4)]
-        assert s._lib.bmpc_stream_lengths(s._h, *[ctypes.byref(v) for v in lens]) == 0 and lens[1].value == 32 + 56 * 40 + 2
+        assert s._lib.bmpc_stream_lengths(s._h, *[ctypes.byref(v) for v in lens]) == 0 and lens[1].value == 32 + 56 * 40 + 4      # (the row's tail: updated flag, continuation word, dphi_max, pad)
     finally:
         s.close()
 
