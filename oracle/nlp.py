@@ -309,10 +309,12 @@ def nlp_eval(x, p, N, S, h, stage_costs=False):
     return (fk if stage_costs else f), g.reshape(-1)
 
 
-def internal_ineq(x, p, N, S):
+def internal_ineq(x, p, N, S, bound_margin=0.0):
     """The build's internal inequality rows h[N][57] <= 0 (two-sided form of the reference's
     squared tube constraints plus the simple bounds), in the row order of oracle/bmpc_oracle.c.
-    Equivalent feasible set: l^2 - w^2 <= 0  <=>  -|w| <= l <= |w|."""
+    Equivalent feasible set: l^2 - w^2 <= 0  <=>  -|w| <= l <= |w|.
+    bound_margin m (include/boundmpc_hip.h bmpc_options; not in the reference): the joint position and
+    velocity rows 16:44 are those of the limits lim - m; jerk, phi and tube rows do not know it."""
     P = unpack_p(p, S)
     z = x.reshape(N, NZ)
     dt = np.result_type(x.dtype, p.dtype)
@@ -323,10 +325,10 @@ def internal_ineq(x, p, N, S):
         err = error_function(zk[IP:IP + 6], ref, P)
         H[k, 0:8] = zk[0:8] - U_LIM
         H[k, 8:16] = -zk[0:8] - U_LIM
-        H[k, 16:23] = zk[IQ:IQ + 7] - Q_LIM
-        H[k, 23:30] = -zk[IQ:IQ + 7] - Q_LIM
-        H[k, 30:37] = zk[IDQ:IDQ + 7] - DQ_LIM
-        H[k, 37:44] = -zk[IDQ:IDQ + 7] - DQ_LIM
+        H[k, 16:23] = zk[IQ:IQ + 7] - (Q_LIM - bound_margin)
+        H[k, 23:30] = -zk[IQ:IQ + 7] - (Q_LIM - bound_margin)
+        H[k, 30:37] = zk[IDQ:IDQ + 7] - (DQ_LIM - bound_margin)
+        H[k, 37:44] = -zk[IDQ:IDQ + 7] - (DQ_LIM - bound_margin)
         H[k, 44] = -zk[IPHI]
         H[k, 45] = zk[IPHI] - P["phi_max"][0]
         H[k, 46] = zk[IDPHI] - P["dphi_max"][0]

@@ -22,8 +22,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import nlp  # noqa: E402
 
 
-def solve(p, x0, N=10, S=4, h=0.1, maxiter=400, ftol=1e-14, verbose=True):
+def tighten(lbx, ubx, N, bound_margin):
+    """lbx / ubx with the joint position and velocity bounds of every stage moved inwards by bound_margin (the product's option of that name)"""
+    lb, ub = lbx.reshape(N, nlp.NZ).copy(), ubx.reshape(N, nlp.NZ).copy()
+    lb[:, nlp.IQ:nlp.IDDQ] += bound_margin; ub[:, nlp.IQ:nlp.IDDQ] -= bound_margin
+    return lb.ravel(), ub.ravel()
+
+
+def solve(p, x0, N=10, S=4, h=0.1, maxiter=400, ftol=1e-14, verbose=True, bound_margin=0.0):
     lbx, ubx, lbg, ubg = nlp.bounds(N)
+    lbx, ubx = tighten(lbx, ubx, N, bound_margin)
     cache = {}
 
     def ev(x):

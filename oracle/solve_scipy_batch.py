@@ -24,6 +24,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from oracle import nlp, c_oracle  # noqa: E402
+from oracle.solve_scipy import tighten  # noqa: E402
 from scipy.optimize import minimize  # noqa: E402
 
 
@@ -46,11 +47,12 @@ def jac_g_banded_fd(x, p, N, S=4, h=0.1, eps=1e-6):
     return Jg
 
 
-def solve(p, x0, N=10, S=4, h=0.1, maxiter=800, ftol=1e-14):
+def solve(p, x0, N=10, S=4, h=0.1, maxiter=800, ftol=1e-14, bound_margin=0.0):
     """SLSQP on the reference's NLP form (lbx <= x <= ubx, lbg <= g <= ubg with the squared tube rows), f and g from the C restatement,
     grad f analytic (bmpc_oracle_adjoint with zero multipliers; equal to the complex step through nlp.py to 1e-14), dg/dx by
     central differences.  The SOLVER is independent of the product's algorithm; the function evaluations are the oracle's."""
     lbx, ubx, lbg, ubg = nlp.bounds(N)
+    lbx, ubx = tighten(lbx, ubx, N, bound_margin)
     cache = {}
 
     def ev(x):

@@ -20,13 +20,13 @@ def _cap(v):
         return np.where(v > 0, np.minimum(v, NU_CAP), 0.0)      # (NaN -> 0)
 
 
-def nu_of(p, x, lam_g, lam_x, N, S):
+def nu_of(p, x, lam_g, lam_x, N, S, bound_margin=0.0):
     """One problem: nu [N][57] of the internal rows from multipliers in CasADi's convention (None = zeros), the rounding scale lam (|c| + wd)
     of its tube rows, c and wd [N][5] of the squared tube rows at x (from the oracle's internal rows h[47 + 2m] = c - wd, h[48 + 2m] = -c - wd)
-    and those rows H [N][57]."""
+    and those rows H [N][57] (of a handle with options.bound_margin = bound_margin)."""
     g = np.zeros((N, NG)) if lam_g is None else _fin(lam_g).reshape(N, NG)
     z = np.zeros((N, NZ)) if lam_x is None else _fin(lam_x).reshape(N, NZ)
-    H = internal_ineq(np.asarray(x, dtype=float), np.asarray(p, dtype=float), N, S).reshape(N, NI)
+    H = internal_ineq(np.asarray(x, dtype=float), np.asarray(p, dtype=float), N, S, bound_margin).reshape(N, NI)
     up, lo = H[:, 47::2], H[:, 48::2]
     c, wd = (up - lo) / 2, -(up + lo) / 2
     nu, sc = np.zeros((N, NI)), np.zeros((N, NI))

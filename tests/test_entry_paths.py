@@ -73,7 +73,7 @@ def test_team_and_pair_emulators_make_the_second_attempt(nw, mode):
 
 # what the library's option record (csrc/bmpc_wave.inl Opts, read through the emulator) and the oracle's (oracle/bmpc_oracle.c) both have
 SHARED_OPTION_FIELDS = ("tol", "max_iter", "mu_init", "mu_min_fac", "slack_push", "exact_hessian", "mu_warm", "stall_window", "restoration", "resto_short",
-                        "resto_cap", "start_rollout", "hold_mu", "retry_cap")
+                        "resto_cap", "start_rollout", "hold_mu", "retry_cap", "bound_margin")
 
 
 @pytest.mark.parametrize("N", [1, 11, 12, 40])

@@ -10,8 +10,8 @@ with nu = 10^U(-6, 2), mu = 0.05; solve_batch(p, x0, state=..., max_iter=K), K =
 TOLERANCE (measured on the CPU, never from the GPU's output).  Differences in x are taken relative to the row's max |x - x0| (the step), in nu
 relative to the row's max |nu|.  The FLOOR of a shape and K is the oracle-versus-emulator discrepancy on the same rows: two CPU implementations
 of the same iteration with different summation orders.  The GPU must agree with the emulator within FACTOR = 100 x floor: FMA contraction, the
-accumulation order of the matrix cores, the butterfly order.  bound_margin is not in the oracle's option record: that shape takes the floor of
-the same rows without the margin.  On these inputs the CPU builds take the same accept / reject decisions on every row (equal iteration counts;
+accumulation order of the matrix cores, the butterfly order.  The bound_margin shapes take their own floor like every other: the oracle's option
+record carries the margin (oracle/bmpc_oracle.c eval).  On these inputs the CPU builds take the same accept / reject decisions on every row (equal iteration counts;
 the team and pair emulators equal the one-wave emulator bit for bit): asserted below, on the CPU, before any GPU result is looked at.
 
 THE RESTORATION PHASE'S STEP (last test): set A of tests/entry_path_sets.py, restoration mode 1, one short step counts as a jam, iteration
@@ -47,7 +47,9 @@ SHAPES = {
     "slab_N6_S5_resto2":   dict(N=6, S=5, waves=None, nw=1, opts=dict(restoration=2)),
     "gauss_newton_one":    dict(N=10, S=4, waves=1, nw=1, opts=dict(exact_hessian=0)),
     "gauss_newton_team":   dict(N=10, S=4, waves=4, nw=4, opts=dict(exact_hessian=0)),
-    "bound_margin_one":    dict(N=10, S=4, waves=1, nw=1, opts=dict(bound_margin=0.05), floor_of="one_wave_N10"),
+    "bound_margin_one":    dict(N=10, S=4, waves=1, nw=1, opts=dict(bound_margin=0.05)),
+    "bound_margin_pair":   dict(N=10, S=4, waves=2, nw="pair", opts=dict(bound_margin=0.05)),
+    "bound_margin_team":   dict(N=10, S=4, waves=4, nw=4, opts=dict(bound_margin=0.05)),
 }
 
 
@@ -94,16 +96,12 @@ def cpu_side(name, K):
         one = emu.solve(P, x0, N, S, H_, opts=emu.opts_for(N, max_iter=K, **kw), nthreads=4, state=s1)
         assert np.array_equal(one["x"], e["x"]) and np.array_equal(s1, se) and np.array_equal(one["iters"], e["iters"]), (name, K)
     out = dict(x=e["x"], state=se, iters=e["iters"], status=e["status"], step=np.abs(e["x"] - x0).max(axis=1))
-    if "floor_of" in sh:
-        ref = cpu_side(sh["floor_of"], K)
-        out.update(floor_x=ref["floor_x"], floor_nu=ref["floor_nu"], oracle=None)
-    else:
-        so = st0.copy()
-        o = c_oracle.solve(P, x0, N, S, H_, opts=c_oracle.opts_for(N, max_iter=K, **kw), nthreads=4, state=so)
-        assert (o["status"] == 1).all() and (o["iters"] == K).all(), (name, K, o["status"], o["iters"])
-        assert np.array_equal(so[:, N * 57 + 1], se[:, N * 57 + 1])
-        out.update(floor_x=float(rel_x(o["x"], e["x"], x0).max()), floor_nu=float(rel_nu(so, se, N).max()),
-                   floor_mu=float(np.abs(so[:, N * 57] / se[:, N * 57] - 1).max()), oracle=dict(x=o["x"], state=so))
+    so = st0.copy()
+    o = c_oracle.solve(P, x0, N, S, H_, opts=c_oracle.opts_for(N, max_iter=K, **kw), nthreads=4, state=so)
+    assert (o["status"] == 1).all() and (o["iters"] == K).all(), (name, K, o["status"], o["iters"])
+    assert np.array_equal(so[:, N * 57 + 1], se[:, N * 57 + 1])
+    out.update(floor_x=float(rel_x(o["x"], e["x"], x0).max()), floor_nu=float(rel_nu(so, se, N).max()),
+               floor_mu=float(np.abs(so[:, N * 57] / se[:, N * 57] - 1).max()), oracle=dict(x=o["x"], state=so))
     return out
 
 

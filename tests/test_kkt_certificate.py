@@ -34,12 +34,12 @@ def _gap(given, own):
     return np.where(np.isfinite(d), d, np.inf)
 
 
-def checker(p, x, lam_g, lam_x, N, S, h=0.1):
-    """One problem.  Returns (record dict, tolerance dict, extras dict with g, lam_g (consistent), rj, nu)."""
+def checker(p, x, lam_g, lam_x, N, S, h=0.1, bound_margin=0.0):
+    """One problem (bound_margin: the handle's options.bound_margin, which tightens the joint rows of h).  Returns (record dict, tolerance dict, extras dict with g, lam_g (consistent), rj, nu)."""
     p, x = np.asarray(p, dtype=float), np.asarray(x, dtype=float)
     f, g = nlp.nlp_eval(x, p, N, S, h)
     g2 = g.reshape(N, NG)
-    nu, sc, c, wd, H = nu_of(p, x, lam_g, lam_x, N, S)
+    nu, sc, c, wd, H = nu_of(p, x, lam_g, lam_x, N, S, bound_margin)
     lam, rj, _ = c_oracle.adjoint(p, x, nu.ravel(), N, S, h)
     lam = lam.reshape(N, NE)
     slack, viol = np.maximum(-H, 0.0), np.maximum(H, 0.0)
@@ -81,9 +81,9 @@ def _emu():
     return emu.service_lib("kkt")
 
 
-def emu_cert(p, x, lam_g, lam_x, N, S, lane_order=0, poison=True, want=True):
+def emu_cert(p, x, lam_g, lam_x, N, S, lane_order=0, poison=True, want=True, bound_margin=0.0):
     from tests.emu import emu
-    o = emu.default_opts()
+    o = emu.default_opts(bound_margin=bound_margin)
     p, x = np.ascontiguousarray(np.atleast_2d(p), dtype=float), np.ascontiguousarray(np.atleast_2d(x), dtype=float)
     B = p.shape[0]
     arr = lambda a: None if a is None else np.ascontiguousarray(np.atleast_2d(a), dtype=float)

@@ -78,10 +78,10 @@ def small_problems(N, B=3, seed=5):
     return P, r["x"], r["lam_g"], r["lam_x"]
 
 
-def active_rows(p, x, lam_g, lam_x, N, mu=MU):
+def active_rows(p, x, lam_g, lam_x, N, mu=MU, bound_margin=0.0):
     """rows that carry the solution: nu_i s_i within 10 x mu (complementarity at the barrier level) with a multiplier above sqrt(mu) -- at the
     barrier level every row of an interior-point answer has nu s = mu; an ACTIVE one has the small slack"""
-    nu, _, _, _, Hv = nu_of(p, x, lam_g, lam_x, N, S_)
+    nu, _, _, _, Hv = nu_of(p, x, lam_g, lam_x, N, S_, bound_margin)
     Hv, nu = Hv.reshape(-1), nu.reshape(-1)
     s = np.maximum(-Hv, mu / np.maximum(nu, mu))
     return np.flatnonzero((nu * s <= 10 * mu) & (nu * s >= mu / 10) & (nu > np.sqrt(mu)))
@@ -98,10 +98,10 @@ _FD5 = lg.fd5      # five-point central difference of fun(t) at 0, step 1e-3 (te
 class Checker:
     """the system of one point (p, x, lam_g, lam_x, mu); tangent(dp) solves it"""
 
-    def __init__(self, p, x, lam_g, lam_x, N, mu=MU):
+    def __init__(self, p, x, lam_g, lam_x, N, mu=MU, bound_margin=0.0):
         self.p, self.x, self.N, self.mu = np.asarray(p, float), np.asarray(x, float), N, mu
         n = self.x.size
-        nu, _, _, _, Hv = nu_of(p, x, lam_g, lam_x, N, S_)
+        nu, _, _, _, Hv = nu_of(p, x, lam_g, lam_x, N, S_, bound_margin)      # (the margin shifts the rows' values, not their derivatives)
         self.nu, self.h = nu.reshape(-1), Hv.reshape(-1)
         gf, self.Jg, self.Jh = lg.jacobians(self.p, self.x, N, S_, H_)
         self.J, self.S = lg.column_split(n)
@@ -291,10 +291,10 @@ def full_size_points(B=2, seed=2, tol=TOL):
     return P, r["x"], r["lam_g"], r["lam_x"]
 
 
-def equation_residuals(p, x, lam_g, lam_x, dp, dx, dlam, dnu, N, mu=MU, S=S_, stationarity=True):
+def equation_residuals(p, x, lam_g, lam_x, dp, dx, dlam, dnu, N, mu=MU, S=S_, stationarity=True, bound_margin=0.0):
     """(residual, scale of the terms that cancel in it) of the three equations at one point, by complex step through oracle/nlp.py; the
     stationarity row by a central difference of the complex-step Lagrangian gradient (test_kkt_certificate.lagrangian_gradient)."""
-    nu, _, _, _, Hv = nu_of(p, x, lam_g, lam_x, N, S)
+    nu, _, _, _, Hv = nu_of(p, x, lam_g, lam_x, N, S, bound_margin)
     nu, hv = nu.reshape(-1), Hv.reshape(-1)
     lam = c_oracle.adjoint(p, x, nu, N, S, H_)[0]
     Sigma = nu / np.maximum(-hv, mu / np.maximum(nu, mu))
