@@ -45,6 +45,10 @@ SIGNATURES = {
     "bmpc_stream_rollout_plant": (_ci, _TICK[:2] + [_ci] + _TICK[2:] + [_cd, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _cd, _vp, _ci, _vp] + [_ci] + [_vp] * 14),      # ... tune_used, plant, plant_state, plant_info, plant_rec, stream
     "bmpc_stream_plant_len": (_ci, []), "bmpc_stream_plant_state_len": (_ci, []), "bmpc_stream_plant_rec_len": (_ci, []),
     "bmpc_stream_plant": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp]),      # handle, B, robot, sstate, plant, plant_state, plant_info, plant_rec, tick, stream
+    "bmpc_stream_rollout_sensor": (_ci, _TICK[:2] + [_ci] + _TICK[2:] + [_cd, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _cd, _vp, _ci, _vp] + [_ci] + [_vp] * 20),      # ... plant_rec, sensor, sensor_state, sensor_info, sensor_rec, sensor_noise, meas_hist, stream
+    "bmpc_stream_sensor_len": (_ci, []), "bmpc_stream_sensor_state_len": (_ci, []), "bmpc_stream_sensor_rec_len": (_ci, []),
+    "bmpc_stream_sense": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp]),      # handle, B, robot, sstate, sensor, sensor_state, sensor_info, sensor_rec, sensor_noise, meas, tick, stream
+    "bmpc_stream_unsense": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp]),      # handle, B, robot, sstate, sensor, sensor_state, stream
     "bmpc_stream_tune_len": (_ci, []), "bmpc_stream_tune_defaults": (_ci, [_vp, _ci, _vp]),
     "bmpc_stream_track_len": (_ci, []), "bmpc_stream_rollout_log_len": (_ci, [_vp, _ci]),
     "bmpc_stream_tube_len": (_ci, []), "bmpc_stream_tube": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp]),

@@ -21,7 +21,9 @@ SOURCES = [os.path.join(CSRC, "bmpc_hip.hip"), os.path.join(CSRC, "bmpc_wave.inl
            os.path.join(CSRC, "bmpc_stream_tube.inl"), os.path.join(CSRC, "bmpc_rollout_audit.hip"),
            os.path.join(CSRC, "bmpc_rollout_log.hip"), os.path.join(CSRC, "bmpc_team_rollout.hip"), os.path.join(CSRC, "bmpc_rollout_legs.hip"),
            os.path.join(CSRC, "bmpc_team_rollout_legs.hip"), os.path.join(CSRC, "bmpc_rollout_tune.hip"), os.path.join(CSRC, "bmpc_team_rollout_tune.hip"),
-           os.path.join(CSRC, "bmpc_stream_plant.inl"), os.path.join(CSRC, "bmpc_rollout_plant.hip"), os.path.join(CSRC, "bmpc_team_rollout_plant.hip")]
+           os.path.join(CSRC, "bmpc_stream_plant.inl"), os.path.join(CSRC, "bmpc_rollout_plant.hip"), os.path.join(CSRC, "bmpc_team_rollout_plant.hip"),
+           os.path.join(CSRC, "bmpc_rollout_body.inl"), os.path.join(CSRC, "bmpc_stream_sensor.inl"), os.path.join(CSRC, "bmpc_rollout_sensor.hip"),
+           os.path.join(CSRC, "bmpc_team_rollout_sensor.hip")]
 # translation units of the library: the one-wave batch kernels + C ABI, the team kernels (NW cooperating waves per problem), the restoration
 # kernels (the solver with the restoration phase, continuing what a batch kernel left jammed), the fused closed-loop tick kernels, the pair kernel
 # the rollout kernels (many ticks of every stream in one launch), the rollout kernels with events (disturbances, scheduled re-plans) and those with
@@ -29,12 +31,14 @@ SOURCES = [os.path.join(CSRC, "bmpc_hip.hip"), os.path.join(CSRC, "bmpc_wave.inl
 # records behind every tick's post, a tracking record per stream), the rollout kernels of the teams (plain and with everything on), the rollout
 # kernels with a queue of re-plan records per stream (fired by tick, goal or lost plan) on one wave and on teams, those with a table of controller
 # settings per stream on top (sweeps: a grid over settings as one launch) on one wave and on teams, those with a table of actuator models per stream
-# between the command and the plant on top of that on one wave and on teams: 16 units side by side
+# between the command and the plant on top of that on one wave and on teams, those with a table of measurement models per stream between the plant and
+# the controller on top of that on one wave and on teams: 18 units side by side
 UNITS = [os.path.join(CSRC, "bmpc_hip.hip"), os.path.join(CSRC, "bmpc_team.hip"), os.path.join(CSRC, "bmpc_resto.hip"), os.path.join(CSRC, "bmpc_tick.hip"),
          os.path.join(CSRC, "bmpc_pair.hip"), os.path.join(CSRC, "bmpc_rollout.hip"), os.path.join(CSRC, "bmpc_rollout_events.hip"),
          os.path.join(CSRC, "bmpc_rollout_audit.hip"), os.path.join(CSRC, "bmpc_rollout_log.hip"), os.path.join(CSRC, "bmpc_team_rollout.hip"),
          os.path.join(CSRC, "bmpc_rollout_legs.hip"), os.path.join(CSRC, "bmpc_team_rollout_legs.hip"), os.path.join(CSRC, "bmpc_rollout_tune.hip"),
-         os.path.join(CSRC, "bmpc_team_rollout_tune.hip"), os.path.join(CSRC, "bmpc_rollout_plant.hip"), os.path.join(CSRC, "bmpc_team_rollout_plant.hip")]
+         os.path.join(CSRC, "bmpc_team_rollout_tune.hip"), os.path.join(CSRC, "bmpc_rollout_plant.hip"), os.path.join(CSRC, "bmpc_team_rollout_plant.hip"),
+         os.path.join(CSRC, "bmpc_rollout_sensor.hip"), os.path.join(CSRC, "bmpc_team_rollout_sensor.hip")]
 
 
 def hipcc():

@@ -125,6 +125,16 @@ struct RArgs {
     int *plant_info;                 // [B] or NULL: the mask of the invalid slots of row b; 0 = the stream ran
     double *plant_rec;               // [B][bmpcpl::REC_LEN] or NULL, initialised by the kernel: what the plant did to the commands
 };
+// what a rollout with a measurement model adds (the SE kernels, bmpc_stream_rollout_sensor; bmpc_rollout_kernel.inl): a record of its own, the FOURTH
+// kernel argument of those kernels -- RArgs keeps its members, and the kernels without a sensor their three arguments
+struct NArgs {
+    const double *sensor;            // [B][bmpcse::LEN]: row b stands between the plant of stream b and what pack, solve and post of every tick read; a NaN slot is the identity
+    double *sensor_state;            // [B][bmpcse::ST_LEN], in and out: the held sample and the truth of a tick in flight; all zeros = fresh; required with sensor
+    int *sensor_info;                // [B] or NULL: the mask of the invalid slots of row b; 0 = the stream ran
+    double *sensor_rec;              // [B][bmpcse::REC_LEN] or NULL, initialised by the kernel: what the samples differed from the truth by
+    const double *sensor_noise;      // [ticks][B][bmpcs::DIST_LEN] or NULL: unit draws, scaled by the row's NQ, NDQ, NDDQ; a non-finite word counts as 0
+    double *meas_hist;               // [ticks][B][bmpcs::RB_LEN] or NULL: the robot record the pack of tick t read; NaN rows for the ticks not run
+};
 
 // ---- host and device: a row of per-stream controller settings (BMPC_TUNE_* of include/boundmpc_hip.h), what it resolves to and what is refused ----
 // The slots of a row; a slot holds NaN ("the launch's value") or the value of the option, setter or argument named behind it.
@@ -262,6 +272,45 @@ BMPC_ARGS_HD int bmpc_plant_check(const double *row, double *used) {
     return bad;
 }
 
+// ---- host and device: a row of a per-stream measurement model (BMPC_SENSOR_* of include/boundmpc_hip.h), its state and its record; the rule of the two
+// steps is stream_sense and stream_truth (bmpc_stream_sensor.inl) ----
+namespace bmpcse {
+enum { BIAS = 0,          // [7] encoder offset of joint j, rad                               identity 0, valid when finite
+       RES = 7,           // quantisation step of the joint positions, rad                   identity 0 (none), valid when finite and >= 0
+       NQ = 8, NDQ, NDDQ, // scale of the tick's noise row on q, dq, ddq                     identity 0, valid when finite and >= 0
+       HOLD = 11,         // 1: the controller sees the previous tick's sample              identity 0, valid when 0 or 1
+       SLOTS = 12,        // the slots that are looked at; the words behind them up to LEN are pad
+       LEN = 16 };
+// the state: the sample taken last [21], whether there is one, whether the sample handed out equals the truth, a pad word, the truth of a tick in flight
+// (the words RB_Q..RB_V of the robot record [33], then RB_JERK [7])
+enum { ST_HELD = 0, ST_HAS = 21, ST_SAME = 22, ST_TRUTH = 24, TRUTH_LEN = 40, ST_LEN = 64 };
+// the record: samples, largest |q_m - q| with its tick and joint, largest ||p_m - p|| (position part of p_lie, metres) with its tick, sum of squares of q_m - q, a pad word
+enum { REC_SAMPLES = 0, REC_MAX_DQ, REC_TICK_DQ, REC_JOINT_DQ, REC_MAX_DP, REC_TICK_DP, REC_SUMSQ_DQ, REC_LEN = 8 };
+}
+// what a NaN slot resolves to: the sensor that measures the plant exactly
+BMPC_ARGS_HD double bmpc_sensor_identity(int k) { return 0.0; }
+// THE validity rule of a slot that is not NaN, once (plain comparisons; the offsets within the bound bmpc_plant_slot_ok holds the gains to)
+BMPC_ARGS_HD bool bmpc_sensor_slot_ok(int k, double v) {
+    if (k < bmpcse::RES) return v >= -BMPC_TOL_MAX && v <= BMPC_TOL_MAX;
+    if (k < bmpcse::HOLD) return v >= 0.0 && v <= BMPC_TOL_MAX;
+    if (k == bmpcse::HOLD) return v == 0.0 || v == 1.0;
+    return true;      // (pad words: never looked at)
+}
+// Row `row`: the mask of its invalid slots, bit k = slot k; 0 = the stream runs.  used (or NULL): the row as resolved -- a NaN slot its identity value, a
+// refused value as it was given, pad words 0.
+BMPC_ARGS_HD int bmpc_sensor_check(const double *row, double *used) {
+    int bad = 0;
+    for (int k = 0; k < bmpcse::LEN; k++) {
+        double v = k < bmpcse::SLOTS ? row[k] : 0.0;
+        if (k < bmpcse::SLOTS) {
+            if (v != v) v = bmpc_sensor_identity(k);
+            else if (!bmpc_sensor_slot_ok(k, v)) bad |= 1 << k;
+        }
+        if (used) used[k] = v;
+    }
+    return bad;
+}
+
 // ---- host only: what the rollout entries of the C ABI refuse and which kernel they run, once (bmpc_hip.hip rollout_launch; the CPU build of the
 // rollout, tests/emu/bmpc_emu_rollout.cpp, asks the same function) ----
 // the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice (needs the robot records), bit 2 poor bounds (with bit 1 only)
@@ -300,3 +349,6 @@ inline int bmpc_rollout_level(int entry, const RArgs &r, int N, int flags, const
     if (entry == 2 && !r.tube_hist && !r.audit) entry = 1;
     return entry;
 }
+// What bmpc_stream_rollout_sensor refuses on top of what the plants' entry refuses (bmpc_rollout_level with entry 6 on its RArgs): a table without its
+// state.  Without a table it IS that entry, and no member of `n` is looked at.
+inline bool bmpc_rollout_sensor_ok(const NArgs &n) { return !n.sensor || n.sensor_state; }

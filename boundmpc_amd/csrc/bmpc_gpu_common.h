@@ -129,6 +129,12 @@ hipError_t bmpc_rollout_tune_launch(bool zlds, bool resto, const void *kargs, co
 hipError_t bmpc_rollout_plant_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // ---- the plant step on its own, one lane per stream of the batch (bmpc_rollout_plant.hip; bmpc_stream_plant.inl) ----
 hipError_t bmpc_stream_plant_launch(int N, int B, double h, double *rb, const double *ss, const double *plant, double *state, int *info, double *rec, int tick, hipStream_t st);
+// ---- the same with a table of measurement models per stream between the plant and the controller (bmpc_rollout_sensor.hip; everything on and SE) ----
+hipError_t bmpc_rollout_sensor_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, const NArgs *n, int grid, hipStream_t st);
+// ---- the sample and the way back to the truth on their own, one lane per stream of the batch (bmpc_rollout_sensor.hip; bmpc_stream_sensor.inl) ----
+hipError_t bmpc_stream_sense_launch(int N, int B, double *rb, const double *ss, const double *sensor, double *state, int *info, double *rec, const double *noise, double *meas,
+                                    int tick, hipStream_t st);
+hipError_t bmpc_stream_unsense_launch(int N, int B, double h, double *rb, const double *ss, const double *sensor, const double *state, hipStream_t st);
 // ---- the measurement on its own, one wave per stream of the batch (bmpc_rollout_audit.hip; bmpc_stream_tube.inl) ----
 hipError_t bmpc_stream_tube_launch(int N, int S, int B, const double *p, const double *ss, double *tube, hipStream_t st);
 
@@ -146,6 +152,8 @@ hipError_t bmpc_team_rollout_legs_launch(int nw, bool resto, const void *kargs, 
 hipError_t bmpc_team_rollout_tune_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // the same with the table of actuator models per stream (bmpc_team_rollout_plant.hip): the fully-featured kernel with QU, TU and PL
 hipError_t bmpc_team_rollout_plant_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
+// the same with the table of measurement models per stream (bmpc_team_rollout_sensor.hip): the fully-featured kernel with SE
+hipError_t bmpc_team_rollout_sensor_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, const NArgs *n, int grid, hipStream_t st);
 int bmpc_team_lds_bytes(int nw);
 int bmpc_team_nmax(int nw);      // longest horizon the team kernels take (their LDS holds most of the workspace)
 

@@ -71,15 +71,33 @@
 // treatment of an invalid settings row -- no tick, NaN history rows, its mask in r.plant_info[b], plant_state untouched.  Row, state (r.plant_state[b],
 // in and out: rollouts chain) and record (r.plant_rec[b]) live in global memory, behind opaque stream and tick indices: nothing of the plant is carried
 // in a register across the solve.  Without PL no plant line is compiled.
+// SENSORS (the kernels bmpc_stream_rollout_sensor_kernel, SE; bmpc_stream_rollout_sensor; bmpc_rollout_sensor.hip, bmpc_team_rollout_sensor.hip;
+// bmpc_stream_sensor.inl): a table n.sensor[b][bmpcse::LEN] of a measurement model per stream -- an encoder offset per joint, a quantisation step, noise on
+// q, dq and ddq scaled from the caller's unit draws n.sensor_noise[t][b], a sample one tick old -- between the plant and what pack, solve and post of a
+// tick read.  Every tick's pack reads the robot record, and the record IS the plant: the controller always measures the true state exactly, and a
+// disturbance cannot stand in for a sensor -- it moves the plant, and the next pack measures the moved plant perfectly.  Here the record is the SAMPLE from
+// stream_sense (behind the lost-plan test, ahead of the pack; the truth waits in n.sensor_state[b]) to stream_truth (behind the barrier behind
+// stream_post, ahead of the plant step), and the TRUTH everywhere else: in hist[t][b], in the caller's robot array behind the launch, for the disturbance,
+// the plant step, a spliced re-plan and a chained launch.  p, the audit row and the audit (taken from the pack's p), traj, the log and the tracking record
+// describe the MEASUREMENT and the plan made from it -- what the controller's own monitor would report; n.meas_hist[t][b] is the record the pack of tick t
+// read, and the record's largest ||p_m - p|| bounds what the audit's position excess can miss.  Where the sample equals the truth (SAME) the record keeps
+// every bit and the post steps the truth itself: an identity row leaves what the plants' entry leaves.  Else the truth takes the post's step under the
+// same planned jerk, or comes back as it was where the post exhausted the plan and did not step.  The barrier behind stream_truth is unconditional; EVERY
+// wave of a team reads SAME and the error count itself, from words that do not change between the barrier ahead and the first barrier behind, wave 0 does
+// the work.  The row is validated as a plant row is (bmpc_sensor_check; sensor_info, state untouched).  Row, state, record and noise live in global
+// memory behind opaque stream and tick indices, and the members of n are read through the kernel-argument segment (BMPCR_SENSOR_ARGS): nothing of the
+// sensor is carried in a register across the solve.  The SE kernels compile everything below them on and ask at run time whether there is a plant table.
+// The text of the stream and tick loops exists once, bmpc_rollout_body.inl; the kernels without a sensor expand it with BMPCR_SE 0 and hold no sensor line.
 // Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp:
-// one source and one entry for every variant, built once per BMPC_NW).  The eleven units (bmpc_rollout.hip,
-// bmpc_rollout_events.hip, bmpc_rollout_audit.hip, bmpc_rollout_log.hip, bmpc_rollout_legs.hip, bmpc_rollout_tune.hip, bmpc_rollout_plant.hip,
-// bmpc_team_rollout.hip, bmpc_team_rollout_legs.hip, bmpc_team_rollout_tune.hip, bmpc_team_rollout_plant.hip) and those builds launch through bmpc_rollout_run at the end of this file, the
-// one place that picks <ZLDS, RESTO>.
+// one source and one entry for every variant without a sensor, tests/emu/bmpc_emu_rollout_sensor.cpp for the sensor's, each built once per BMPC_NW).  The thirteen units (bmpc_rollout.hip,
+// bmpc_rollout_events.hip, bmpc_rollout_audit.hip, bmpc_rollout_log.hip, bmpc_rollout_legs.hip, bmpc_rollout_tune.hip, bmpc_rollout_plant.hip, bmpc_rollout_sensor.hip,
+// bmpc_team_rollout.hip, bmpc_team_rollout_legs.hip, bmpc_team_rollout_tune.hip, bmpc_team_rollout_plant.hip, bmpc_team_rollout_sensor.hip) and those builds launch through bmpc_rollout_run
+// and bmpc_rollout_sensor_run at the end of this file, the one place that picks <ZLDS, RESTO>.
 #pragma once
 
 #include "bmpc_stream_events.inl"
 #include "bmpc_stream_plant.inl"
+#include "bmpc_stream_sensor.inl"
 #include "bmpc_stream_tube.inl"
 #include "bmpc_stream_log.inl"
 
@@ -120,6 +138,27 @@ enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH
 #else
 #define BMPCR_PLANT_ARGS(pa_) const RArgs *pa_ = &r
 #endif
+// (SE) the members of the sensor kernels' fourth argument n, for the same reason read where they are consumed through the kernel-argument segment: it
+// lies behind r at its natural alignment.  No sensor line names `n`.  In the TEAM kernels the pointer, and with BMPCR_SENSOR_IDX the stream and tick indices
+// of the sensor lines, are made opaque in VECTOR registers: the members are then fetched by vector loads and every address the sensor lines form is vector
+// arithmetic, between two solves, where vector registers are idle -- as scalars they were thirteen more scalar spills in the team kernels, whose spill
+// registers then moved about at the join behind the tick loop (whole-wave copies, but the signature the build's ISA lint refuses).  The decisions taken from
+// them are made scalar again (BMPCK_UNIFORM).  The one-wave kernels keep the scalar form of the plant lines: there it is the vector form that moves a spill
+// register to a join inside the solve.  Both forms compute the same addresses; which one a unit takes is a matter of this toolchain's register allocation.
+#ifndef BMPC_EMU
+#define BMPCR_NARGS_AT ((BMPCR_RARGS_AT + sizeof(RArgs) + alignof(NArgs) - 1) / alignof(NArgs) * alignof(NArgs))
+#if BMPC_NW > 1
+#define BMPCR_SENSOR_IDX(i_) BMPCR_OPAQUE("+v"(i_))
+#else
+#define BMPCR_SENSOR_IDX(i_) BMPCR_OPAQUE("+s"(i_))
+#endif
+#define BMPCR_SENSOR_ARGS(na_) \
+    const NArgs *na_; \
+    { const char *k_ = (const char *)__builtin_amdgcn_kernarg_segment_ptr(); BMPCR_SENSOR_IDX(k_); na_ = (const NArgs *)(k_ + BMPCR_NARGS_AT); }
+#else
+#define BMPCR_SENSOR_ARGS(na_) const NArgs *na_ = &n
+#define BMPCR_SENSOR_IDX(i_)
+#endif
 // (the body of a tick in the kernel itself, as in bmpc_tick_kernel.inl: behind a function that takes `a` the argument loads lose their no-clobber
 // property -- bmpc_args.h, BMPC_PROBLEM)
 // (QT: the sixth argument counts what sits on top of the log -- 0 nothing, 1 the queue QU, 2 the queue and the table TU, 3 the queue, the table and the
@@ -128,211 +167,18 @@ enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH
 template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false, bool LG = false, int QT = 0>
 BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
     constexpr bool QU = QT >= 1, TU = QT >= 2, PL = QT == 3;
-    static_assert(BMPC_NW == 1 || ZLDS, "a team keeps the iterate in LDS");
-    BMPCK_LDS double lds[BMPC_NAMESPACE::L_SIZE];
-    BMPC_STRIDES(a);
-    const int wv = BMPCK_WAVE;
-    const bool w0 = BMPC_NW == 1 || wv == 0;      // the wave that runs the stream functions and stores the rows (a team: wave 0)
-    double *sh = lds + BMPC_NAMESPACE::L_RED;
-    static_assert(bmpcs::SH_LEN <= 6 * 64, "the stream functions' LDS words must fit into the solver's reduction area");
-    static_assert(bmpcs::TUBE_LEN <= 6 * 64, "and so must a tube row");
-    static_assert(bmpcs::LSH_LEN + bmpcs::LOG_STAGE + 4 <= 6 * 64, "and the log's LDS words with one stage row and its trailer behind them");
-    const int TRN = bmpcs::tr_len(a.N);
-    const double nan_ = __builtin_nan("");
-    for (int b = BMPCK_BLOCK; b < a.B; b += BMPCK_GRID) {
-        BMPC_STREAM_SLICES(a, s, b);
-        long long busy = 0;      // counts of the 100 MHz clock spent in the stream's solves
-        int t = 0;
-        if (EV && !QU) { if (r.replan_info && BMPCK_LANE == 0) r.replan_info[b] = -1; }
-        if (QU) {
-            // (the head of the queue lives in memory, legs_done[b]: wave 0 writes it here and behind a consumed record, every wave reads it behind the
-            // barrier of a tick's post; the per-record outputs start as "never")
-            if (r.replan && w0 && BMPCK_LANE == 0) {
-                r.legs_done[b] = 0;
-                for (int k = 0; k < r.legs; k++) {
-                    const long long q = (long long)b * r.legs + k;
-                    if (r.replan_info) r.replan_info[q] = -1;
-                    if (r.leg_fired) r.leg_fired[q] = -1;
-                    if (r.leg_why) r.leg_why[q] = 0;
-                }
-            }
-        }
-        if (AU) { if (r.audit && BMPCK_LANE == 0) bmpcs::stream_audit_init(r.audit + (long long)b * bmpcs::AUDIT_LEN); }
-        if (LG) { if (r.track && BMPCK_LANE == 0) bmpcs::stream_track_init(r.track + (long long)b * bmpcs::TRACK_LEN); }
-        int bad = 0;      // (TU) the invalid slots of the stream's row: such a stream runs no tick
-        if constexpr (TU) {
-            // (every wave reads the row and the kernel arguments itself; lane 0 of wave 0 stores the mask and the row as resolved)
-            if (r.tune) {
-                const bool out_ = w0 && BMPCK_LANE == 0;
-                bad = BMPCK_UNIFORM(bmpc_tune_check(r.tune + (long long)b * bmpctu::LEN, a.o, s, out_ && r.tune_used ? r.tune_used + (long long)b * bmpctu::LEN : nullptr));
-                if (out_ && r.tune_info) r.tune_info[b] = bad;
-            }
-        }
-        if constexpr (PL) {
-            // (a PL kernel is launched with a table only -- bmpc_rollout_level --, so no line here asks whether there is one.  Every wave reads the row
-            // itself; lane 0 of wave 0 stores the mask and starts the record)
-            BMPCR_PLANT_ARGS(pl_);
-            int b_ = b; BMPCR_OPAQUE("+s"(b_));
-            const int pbad = BMPCK_UNIFORM(bmpc_plant_check(pl_->plant + (long long)b_ * bmpcpl::LEN, nullptr));
-            if (w0 && BMPCK_LANE == 0) {
-                if (pl_->plant_info) pl_->plant_info[b_] = pbad;
-                if (pl_->plant_rec) bmpcs::stream_plant_init(pl_->plant_rec + (long long)b_ * bmpcpl::REC_LEN);
-            }
-            bad |= pbad;      // (an invalid plant row keeps the stream from running as an invalid settings row does: one word decides)
-        }
-        if (!TU || !bad) for (; t < r.ticks; t++) {
-            // (the lost-plan test of the fused tick: BoundMPC.step() returns five Nones there and the reference node stops)
-            if (BMPCK_UNIFORM((int)(ss[bmpcs::SS_ERRCNT] >= (double)a.N))) {
-                if (BMPCK_LANE == 0) { a.status[b] = 3; if (a.iters) a.iters[b] = 0; if (a.kkt) a.kkt[b] = 0.0; }
-                break;
-            }
-            int N_ = a.N, S_ = a.S;
-            BMPCR_OPAQUE("+s"(N_), "+s"(S_));      // (what the stream functions are given)
-            if constexpr (!TU) {
-                if (w0) bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCK_LANE, BMPCK_NL, s.lvl_c, s.lvl_lo, s.lvl_hi);
-            } else {
-                SArgs sp = s;      // (what the pack is given: the launch's level rule, or the stream's)
-                if (r.tune) { int b_ = b; BMPCR_OPAQUE("+s"(b_)); BMPCR_TUNE_ROW(tr_, b_); bmpc_tune_sargs(tr_, sp); }
-                if (w0) bmpcs::stream_pack(N_, S_, path, s.path_stride / bmpcs::PT_LEN, ss, rb, p, x0, dual, (s.flags & 2) ? a.x + (long long)b * nw : nullptr, sh, BMPCK_LANE, BMPCK_NL, sp.lvl_c, sp.lvl_lo, sp.lvl_hi);
-            }
-            BMPCK_SYNC();
-            if (AU) {
-                // (the stream and the tick opaque, as for the events: what the audit addresses is computed here and dead before the solve)
-                int b_ = b, t_ = t;
-                BMPCR_OPAQUE("+s"(b_), "+s"(t_), "+s"(N_), "+s"(S_));
-                double *row = r.tube_hist ? r.tube_hist + ((long long)t_ * a.B + b_) * bmpcs::TUBE_LEN : sh;
-                if (w0) bmpcs::stream_tube(N_, S_, p, nullptr, row, BMPCK_LANE, BMPCK_NL);      // (no state row: the lost-plan test has just passed)
-                if (r.audit && BMPCK_LANE == 0) bmpcs::stream_audit(row, r.audit + (long long)b_ * bmpcs::AUDIT_LEN, t_, r.audit_tol);
-                BMPCK_SYNC();      // the solver's reductions reuse the LDS words of the row
-            }
-            BMPC_WAVE_INIT(W, a, lds, a.scratch + (long long)BMPCK_BLOCK * a.scr_stride, wv); BMPCK_WAVE_HOOK(W);
-            if constexpr (TU) { if (r.tune) { int b_ = b; BMPCR_OPAQUE("+s"(b_)); BMPCR_TUNE_ROW(tr_, b_); bmpc_tune_opts(tr_, W.o); } }      // (W.o has just been rebuilt from a.o)
-            BMPC_TICK_PROBLEM(pr, a, b, p, x0, dual);
-            BMPCR_OPAQUE("+s"(W.N), "+s"(W.S), "+s"(W.h), "+s"(W.G.b), "+s"(pr.p), "+s"(pr.x0), "+s"(pr.x), "+s"(pr.g), "+s"(pr.state));
-            const long long t0_ = a.latency_us ? BMPC_NOW() : 0;
-            BMPC_NAMESPACE::wave_solve<ZLDS, true, RESTO>(W, pr);
-            BMPCK_SYNC();
-            if (a.latency_us) busy += BMPC_NOW() - t0_;
-            BMPCR_OPAQUE("+s"(N_), "+s"(S_));
-            if constexpr (!TU) {
-                if (w0) bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, s.rt_tol, sh, BMPCK_LANE, BMPCK_NL, s.rt_row_cap);
-            } else {
-                SArgs sq = s;      // (what the post is given: the launch's acceptance words, or the stream's, loaded here, behind the solve)
-                if (r.tune) { int b_ = b; BMPCR_OPAQUE("+s"(b_)); BMPCR_TUNE_ROW(tr_, b_); bmpc_tune_sargs(tr_, sq); }
-                if (w0) bmpcs::stream_post(N_, S_, a.h, path, s.path_stride / bmpcs::PT_LEN, ss, rb, pr.x, pr.g, a.status[b], traj, s.flags, sq.rt_tol, sh, BMPCK_LANE, BMPCK_NL, sq.rt_row_cap);
-            }
-            BMPCK_SYNC();      // the history and the next pack read ss, rb, x, traj and the dual state that other lanes have just stored
-            if constexpr (PL) {
-                // The drive between the command the post has just stored and the plant it has just stepped: only where it did step it (every wave reads the
-                // error count behind the post's barrier; the pack of the next tick does not write it).  The stream and the tick opaque, as for the events.
-                BMPCR_PLANT_ARGS(pl_);
-                int b_ = b, t_ = t;
-                BMPCR_OPAQUE("+s"(b_), "+s"(t_));
-                if (BMPCK_UNIFORM((int)(ss[bmpcs::SS_ERRCNT] < (double)N_))) {
-                    if (w0) bmpcs::stream_plant(a.h, pl_->plant + (long long)b_ * bmpcpl::LEN, pl_->plant_state + (long long)b_ * bmpcpl::ST_LEN, rb,
-                                                pl_->plant_rec ? pl_->plant_rec + (long long)b_ * bmpcpl::REC_LEN : nullptr, t_, BMPCK_LANE, BMPCK_NL);
-                }
-                BMPCK_SYNC();      // the rows, the events and the next pack read the TRUE plant
-            }
-            const long long row = (long long)t * a.B + b;
-            if (r.hist && w0) {
-                double *hr = r.hist + row * bmpcs::RH_LEN;
-                for (int i = BMPCK_LANE; i < bmpcs::RB_LEN; i += BMPCK_NL) hr[bmpcs::RH_ROBOT + i] = rb[i];
-                for (int i = BMPCK_LANE; i < 4; i += BMPCK_NL) hr[bmpcs::RH_NVALID + i] = traj[TRN - 4 + i];
-                if (BMPCK_LANE == 0) {
-                    hr[bmpcs::RH_PHI] = ss[bmpcs::SS_PHI]; hr[bmpcs::RH_ERRCNT] = ss[bmpcs::SS_ERRCNT]; hr[bmpcs::RH_STATUS] = (double)a.status[b];
-                    hr[bmpcs::RH_ITERS] = nan_; hr[bmpcs::RH_KKT] = nan_;
-                    if (a.iters) hr[bmpcs::RH_ITERS] = (double)a.iters[b];
-                    if (a.kkt) hr[bmpcs::RH_KKT] = a.kkt[b];
-                }
-            }
-            if (r.traj_hist && w0) { double *th = r.traj_hist + row * TRN; for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) th[i] = traj[i]; }
-            if (LG) {
-                // (the stream and the tick opaque, as for the audit: what the log addresses is computed here, behind the solve, and dead before the next one)
-                int b_ = b, t_ = t, cap_ = s.path_stride / bmpcs::PT_LEN;
-                BMPCR_OPAQUE("+s"(b_), "+s"(t_), "+s"(cap_), "+s"(N_), "+s"(S_));
-                // the row: the caller's, or stage 0 alone behind the log's own LDS words
-                const int K_ = r.log_hist ? r.log_stages : 1;
-                double *lrow = r.log_hist ? r.log_hist + ((long long)t_ * a.B + b_) * (K_ * bmpcs::LOG_STAGE + 4) : sh + bmpcs::LSH_LEN;
-                if (w0) bmpcs::stream_log_rows<true>(N_, S_, a.h, path, cap_, ss, p, traj, lrow, K_, sh, BMPCK_LANE, BMPCK_NL);
-                // (lane 0 wrote stage 0 and the trailer itself)
-                if (r.track && BMPCK_LANE == 0) bmpcs::stream_track(lrow, lrow[K_ * bmpcs::LOG_STAGE], traj[TRN - 3], r.track + (long long)b_ * bmpcs::TRACK_LEN, t_);
-                BMPCK_SYNC();      // the events and the next pack reuse the LDS words of the log
-            }
-            if (EV) {
-                // (the stream and the tick opaque: what the events address is computed here, behind the solve, not carried across it)
-                int b_ = b, t_ = t, cap_ = s.path_stride / bmpcs::PT_LEN;
-                BMPCR_OPAQUE("+s"(b_), "+s"(t_), "+s"(cap_), "+s"(S_));
-                if (r.disturb) {
-                    if (w0) bmpcs::stream_disturb(rb, r.disturb + ((long long)t_ * a.B + b_) * bmpcs::DIST_LEN, BMPCK_LANE, BMPCK_NL);
-                    BMPCK_SYNC();
-                }
-                if (!QU) {
-                    if (r.replan && BMPCK_UNIFORM((int)(r.replan_tick[b_] == t_))) {
-                        double *rec = r.replan + (long long)b_ * bmpcs::replan_len(S_, cap_);
-                        if (r.update_flags & 2) { if (w0) bmpcs::stream_splice(a.h, S_, cap_, rec, rb, r.update_flags, BMPCK_LANE, BMPCK_NL); BMPCK_SYNC(); }
-                        if (w0) bmpcs::stream_update(N_, S_, rec, const_cast<double *>(path), cap_, ss, rb, r.replan_info ? r.replan_info + b_ : nullptr, r.update_flags & 1,
-                                             BMPCK_LANE, BMPCK_NL);
-                        BMPCK_SYNC();      // the goal test, the lost-plan test and the next pack read what the re-plan stored
-                    }
-                } else if (r.replan) {
-                    // The head record of the stream's queue, legs_done[b], and whether it is due behind this tick: EVERY wave decides for itself, from words
-                    // that do not change between the barrier ahead (the post's, the log's or the disturbance's) and the first barrier behind the decision --
-                    // the three ss words the stops read, the read-only trigger arrays, and legs_done[b], which wave 0 writes at the start of the stream and
-                    // ahead of the last barrier of a consumed record.  Bit 0 of `why`: the record's goal, bit 1: the post of this tick exhausted the plan,
-                    // bit 2: at or after its tick.  A word with an unknown bit, or without any condition, is never due: it ends the queue.
-                    int L_ = r.legs;
-                    BMPCR_OPAQUE("+s"(L_));
-                    const int k_ = BMPCK_UNIFORM(r.legs_done[b_]);
-                    int why_ = 0;
-                    if (k_ < L_) {
-                        const long long q_ = (long long)b_ * L_ + k_;
-                        const int on_ = r.leg_on[q_], tk_ = r.leg_tick[q_];
-                        const double tol_ = r.leg_tol ? r.leg_tol[q_] : r.goal_tol;
-                        if (!(on_ & ~(bmpcs::LEG_AT_GOAL | bmpcs::LEG_ON_LOST))) {
-                            if ((on_ & bmpcs::LEG_AT_GOAL) && ss[bmpcs::SS_PHIMAX] - ss[bmpcs::SS_PHI] <= tol_) why_ |= bmpcs::LEG_WHY_GOAL;
-                            if ((on_ & bmpcs::LEG_ON_LOST) && ss[bmpcs::SS_ERRCNT] >= (double)a.N) why_ |= bmpcs::LEG_WHY_LOST;
-                            if (tk_ >= 0 && t_ >= tk_) why_ |= bmpcs::LEG_WHY_TICK;
-                        }
-                    }
-                    why_ = BMPCK_UNIFORM(why_);
-                    if (why_) {
-                        const long long q_ = (long long)b_ * L_ + k_;
-                        double *rec = r.replan + q_ * bmpcs::replan_len(S_, cap_);
-                        // (a barrier between the decision, which reads ss, and stream_update, which writes it: the splice's, or one of its own)
-                        if (r.update_flags & 2) { if (w0) bmpcs::stream_splice(a.h, S_, cap_, rec, rb, r.update_flags, BMPCK_LANE, BMPCK_NL); }
-                        BMPCK_SYNC();
-                        // (every wave has read the head ahead of that barrier: it advances here, ahead of the barrier behind stream_update)
-                        if (w0 && BMPCK_LANE == 0) {
-                            if (r.leg_fired) r.leg_fired[q_] = t_;
-                            if (r.leg_why) r.leg_why[q_] = why_;
-                            r.legs_done[b_] = k_ + 1;
-                        }
-                        if (w0) bmpcs::stream_update(N_, S_, rec, const_cast<double *>(path), cap_, ss, rb, r.replan_info ? r.replan_info + q_ : nullptr, r.update_flags & 1,
-                                             BMPCK_LANE, BMPCK_NL);
-                        BMPCK_SYNC();      // the goal test, the lost-plan test, the next tick's head and the next pack read what the re-plan stored
-                    }
-                }
-            }
-            if (BMPCK_UNIFORM((int)(r.goal_tol > 0.0 && ss[bmpcs::SS_PHIMAX] - ss[bmpcs::SS_PHI] <= r.goal_tol))) { t++; break; }
-        }
-        // t ticks were run; the rows behind them stay without a tick
-        for (int u = t; w0 && u < r.ticks; u++) {
-            const long long row = (long long)u * a.B + b;
-            if (r.hist) for (int i = BMPCK_LANE; i < bmpcs::RH_LEN; i += BMPCK_NL) r.hist[row * bmpcs::RH_LEN + i] = nan_;
-            if (r.traj_hist) for (int i = BMPCK_LANE; i < TRN; i += BMPCK_NL) r.traj_hist[row * TRN + i] = nan_;
-            if (AU) { if (r.tube_hist) for (int i = BMPCK_LANE; i < bmpcs::TUBE_LEN; i += BMPCK_NL) r.tube_hist[row * bmpcs::TUBE_LEN + i] = nan_; }
-            if (LG) {
-                const int LR = r.log_stages * bmpcs::LOG_STAGE + 4;
-                if (r.log_hist) for (int i = BMPCK_LANE; i < LR; i += BMPCK_NL) r.log_hist[row * LR + i] = nan_;
-            }
-        }
-        if (BMPCK_LANE == 0) {
-            if (r.ticks_run) r.ticks_run[b] = t;
-            if (a.latency_us) a.latency_us[b] = (double)busy * 0.01;
-        }
-        BMPCK_SYNC();      // the next stream's pack reuses the LDS words this stream's last phase read
-    }
+#define BMPCR_SE 0
+#include "bmpc_rollout_body.inl"
+#undef BMPCR_SE
+}
+// (SE: the same lines with the sensor's on, everything below it compiled on and the record of the sensor as a fourth argument; a kernel of its own, so
+// that the one above keeps its three arguments and its instantiations the code they had)
+template <bool ZLDS, bool RESTO>
+BMPCK_KERNEL bmpc_stream_rollout_sensor_kernel(KArgs a, SArgs s, RArgs r, NArgs n) {
+    constexpr bool EV = true, AU = true, LG = true, QU = true, TU = true, PL = true;
+#define BMPCR_SE 1
+#include "bmpc_rollout_body.inl"
+#undef BMPCR_SE
 }
 
 // Host: the one place that picks the instantiation <ZLDS, RESTO> of a unit's <EV, AU, LG, QU, TU, PL> (the kernel's sixth argument counts QU, TU and PL) and launches it on `grid` workgroups (BMPCK_LAUNCH: the GPU
@@ -352,3 +198,14 @@ static void bmpc_rollout_run(bool zlds, bool resto, const void *kargs, const SAr
     }
 }
 
+// the same for the kernels with a sensor table (SE): one pair, or two, of instantiations per unit
+template <class STREAM>
+static void bmpc_rollout_sensor_run(bool zlds, bool resto, const void *kargs, const SArgs &s, const RArgs &r, const NArgs &n, int grid, STREAM st) {
+    KArgs a; memcpy(&a, kargs, sizeof(a));
+    if (zlds && resto) BMPCK_LAUNCH((bmpc_stream_rollout_sensor_kernel<true, true>), grid, st, a, s, r, n);
+    else if (zlds) BMPCK_LAUNCH((bmpc_stream_rollout_sensor_kernel<true, false>), grid, st, a, s, r, n);
+    else if constexpr (BMPC_NW == 1) {
+        if (resto) BMPCK_LAUNCH((bmpc_stream_rollout_sensor_kernel<false, true>), grid, st, a, s, r, n);
+        else BMPCK_LAUNCH((bmpc_stream_rollout_sensor_kernel<false, false>), grid, st, a, s, r, n);
+    }
+}

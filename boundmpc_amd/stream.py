@@ -623,6 +623,134 @@ def unpack_plant_rec(row):
                 sumsq_du=float(row[PLANT_REC["SUMSQ_DU"]]), rms_du=float(np.sqrt(row[PLANT_REC["SUMSQ_DU"]] / (7 * n))) if n else None)
 
 
+# a sensor model (bmpc_stream_rollout_sensor, bmpc_stream_sense, bmpc_stream_unsense; BMPC_SENSOR_* of include/boundmpc_hip.h): the slots of a stream's row --
+# the measurement between the plant and what pack, solve and post of a tick read; NaN = the identity value, 0 --, of its state and of its record
+SENSOR = dict(BIAS=0, RES=7, NQ=8, NDQ=9, NDDQ=10, HOLD=11, LEN=16)
+SENSOR_STATE = dict(HELD=0, HAS=21, SAME=22, TRUTH=24, LEN=64)
+SENSOR_REC = dict(SAMPLES=0, MAX_DQ=1, TICK_DQ=2, JOINT_DQ=3, MAX_DP=4, TICK_DP=5, SUMSQ_DQ=6, LEN=8)
+_SENSOR_SLOTS = 12      # the slots that are looked at: BIAS[7], RES, NQ, NDQ, NDDQ, HOLD
+_TRUTH_HEAD = RB["XPHID"]      # the truth kept in the state: the words Q..V of the robot record, then JERK
+
+
+def sensor_check(row):
+    """What the device answers for `row` [SENSOR_LEN] in sensor_info (csrc/bmpc_args.h bmpc_sensor_check, restated): the bit mask of its invalid slots, bit k =
+    slot k.  A NaN slot is the identity and valid; BIAS must be finite, RES, NQ, NDQ and NDDQ finite and >= 0, HOLD 0 or 1; the pad words are never looked
+    at."""
+    row = np.asarray(row, dtype=np.float64)
+    assert row.shape == (SENSOR["LEN"],)
+    bad = 0
+    for k in range(_SENSOR_SLOTS):
+        v = float(row[k])
+        if np.isnan(v):
+            continue
+        if k < SENSOR["RES"]:
+            ok = np.isfinite(v)
+        elif k < SENSOR["HOLD"]:
+            ok = np.isfinite(v) and v >= 0.0
+        else:
+            ok = v == 0.0 or v == 1.0
+        if not ok:
+            bad |= 1 << k
+    return bad
+
+
+def sensor_table(B, bias=None, res=None, nq=None, ndq=None, nddq=None, hold=None):
+    """The table of sensor models, [B][SENSOR_LEN] float64 for StreamBatch.rollout(sensor=...), sense and unsense: bias a scalar, [7] or [B][7] (encoder
+    offsets, rad), res (the quantisation step of the joint positions, rad), nq, ndq, nddq (the scales of the noise rows) and hold a scalar or [B]; NaN (an
+    argument not given, or an entry of an array) is the identity, 0.  Raises ValueError on what the device would refuse (sensor_check)."""
+    B = int(B)
+    T = np.full((B, SENSOR["LEN"]), np.nan)
+    for name, col, at, w in (("bias", bias, SENSOR["BIAS"], 7), ("res", res, SENSOR["RES"], 1), ("nq", nq, SENSOR["NQ"], 1), ("ndq", ndq, SENSOR["NDQ"], 1),
+                             ("nddq", nddq, SENSOR["NDDQ"], 1), ("hold", hold, SENSOR["HOLD"], 1)):
+        if col is None:
+            continue
+        col = np.asarray(col, dtype=np.float64)
+        ok = (col.ndim == 0 or col.shape in ((7,), (B, 7))) if w == 7 else (col.ndim == 0 or col.shape == (B,))
+        if not ok:
+            raise ValueError(f"{name} must be a scalar, " + (f"[7] or [{B}][7]" if w == 7 else f"or [{B}]") + f", got {list(col.shape)}")
+        T[:, at:at + w] = col if w == 7 or col.ndim == 0 else col[:, None]
+    for b in range(B):
+        bad = sensor_check(T[b])
+        if bad:
+            raise ValueError(f"sensor row {b}: invalid slots {[k for k in range(_SENSOR_SLOTS) if bad >> k & 1]}")
+    return T
+
+
+def sense_robot(robot_row, sensor_row, state_row, noise_row=None):
+    """The device sample (stream_sense; bmpc_stream_sense) as numpy over `RobotModel`, the specification of one sample: robot_row is the TRUE record ahead of
+    a pack, noise_row [21] the tick's unit draws (None: zeros; a non-finite word counts as 0).  The truth (Q..V, JERK) goes into the state; per joint
+    m_q = (q + BIAS) + NQ n, with RES > 0 then RES rint(m_q / RES) (half to even), m_dq = dq + NDQ n, m_ddq = ddq + NDDQ n; out = HELD if HOLD and HAS else
+    m; HELD = m, HAS = 1; SAME = every word of out equals the truth's.  Where SAME is 0 the record's q, dq, ddq become out and p_lie and v are recomputed
+    from them; where it is 1 the record is returned unchanged.
+    -> (robot row: what the pack reads, state row, out - truth [21], ||p_m - p|| in metres) -- copies."""
+    from .robot_model import RobotModel
+    rb, st = np.array(robot_row, dtype=float), np.array(state_row, dtype=float)
+    w = np.asarray(sensor_row, dtype=float)
+    assert w.shape == (SENSOR["LEN"],) and st.shape == (SENSOR_STATE["LEN"],) and sensor_check(w) == 0
+    w = np.where(np.isnan(w), 0.0, w)
+    n = np.zeros(DIST_LEN) if noise_row is None else np.asarray(noise_row, dtype=float)
+    n = np.where(np.isfinite(n), n, 0.0)
+    T = SENSOR_STATE["TRUTH"]
+    st[T:T + _TRUTH_HEAD], st[T + _TRUTH_HEAD:T + _TRUTH_HEAD + 7] = rb[:_TRUTH_HEAD], rb[RB["JERK"]:RB["JERK"] + 7]
+    truth = rb[:DIST_LEN].copy()
+    m = truth.copy()
+    m[:7] = (truth[:7] + w[SENSOR["BIAS"]:SENSOR["BIAS"] + 7]) + w[SENSOR["NQ"]] * n[:7]
+    if w[SENSOR["RES"]] > 0.0:
+        m[:7] = w[SENSOR["RES"]] * np.rint(m[:7] / w[SENSOR["RES"]])
+    m[7:14] = truth[7:14] + w[SENSOR["NDQ"]] * n[7:14]
+    m[14:] = truth[14:] + w[SENSOR["NDDQ"]] * n[14:]
+    H = SENSOR_STATE["HELD"]
+    out = st[H:H + DIST_LEN].copy() if w[SENSOR["HOLD"]] == 1.0 and st[SENSOR_STATE["HAS"]] == 1.0 else m.copy()
+    st[H:H + DIST_LEN], st[SENSOR_STATE["HAS"]] = m, 1.0
+    same = bool((out == truth).all())
+    st[SENSOR_STATE["SAME"]] = 1.0 if same else 0.0
+    dp = 0.0
+    if not same:
+        p, J, _ = RobotModel().forward_kinematics(out[:7], out[7:14])
+        dp = float(np.linalg.norm(p[:3] - rb[RB["P"]:RB["P"] + 3]))
+        rb[:DIST_LEN] = out
+        rb[RB["P"]:RB["P"] + 6], rb[RB["V"]:RB["V"] + 6] = p, J @ out[7:14]
+    return rb, st, out - truth, dp
+
+
+def truth_robot(robot_row, state_row, h, stepped=True):
+    """The way back to the true plant behind a post (stream_truth; bmpc_stream_unsense) as numpy over `RobotModel`: robot_row is the record behind the post,
+    state_row what sense_robot left, stepped whether the post stepped the record (error count < N behind it).  SAME == 1: the record unchanged.  Else, where
+    stepped: with c the record's jerk (the first planned jerk), the TRUE q, dq, ddq take the model's chain step from the true jerk to c --
+    q += h dq + h^2/2 ddq + h^3/8 u_t + h^3/24 c, dq += h ddq + h^2/3 u_t + h^2/6 c, ddq += h/2 (u_t + c) --, p_lie and v are recomputed; else the words
+    Q..V are the truth's again.  -> the robot row, a copy."""
+    from .robot_model import RobotModel
+    rb, st = np.array(robot_row, dtype=float), np.asarray(state_row, dtype=float)
+    assert st.shape == (SENSOR_STATE["LEN"],)
+    if st[SENSOR_STATE["SAME"]] == 1.0:
+        return rb
+    tr = st[SENSOR_STATE["TRUTH"]:SENSOR_STATE["TRUTH"] + _TRUTH_HEAD + 7]
+    if not stepped:
+        rb[:_TRUTH_HEAD] = tr[:_TRUTH_HEAD]
+        return rb
+    q, dq, ddq, ut, c = tr[:7], tr[7:14], tr[14:21], tr[_TRUTH_HEAD:], rb[RB["JERK"]:RB["JERK"] + 7].copy()
+    qn = q + h * dq + h * h / 2 * ddq + h * h * h / 8 * ut + h * h * h / 24 * c
+    dqn = dq + h * ddq + h * h / 3 * ut + h * h / 6 * c
+    ddqn = ddq + h / 2 * (ut + c)
+    p, J, _ = RobotModel().forward_kinematics(qn, dqn)
+    rb[RB["Q"]:RB["Q"] + 7], rb[RB["DQ"]:RB["DQ"] + 7], rb[RB["DDQ"]:RB["DDQ"] + 7] = qn, dqn, ddqn
+    rb[RB["P"]:RB["P"] + 6], rb[RB["V"]:RB["V"] + 6] = p, J @ dqn
+    return rb
+
+
+def unpack_sensor_rec(row):
+    """A sensor record (rollout()["sensor_rec"][b], numpy) -> dict: samples, max_dq (the largest |q_m - q|; None without a sample), tick_dq and joint_dq (its
+    first tick and joint), max_dp (the largest ||p_m - p||, metres: what the audit's position excess can miss) and tick_dp, sumsq_dq, rms_dq (over
+    samples x 7)."""
+    row = np.asarray(row, dtype=np.float64)
+    assert row.shape == (SENSOR_REC["LEN"],)
+    n = int(row[SENSOR_REC["SAMPLES"]])
+    return dict(samples=n, max_dq=float(row[SENSOR_REC["MAX_DQ"]]) if n else None, tick_dq=int(row[SENSOR_REC["TICK_DQ"]]) if n else None,
+                joint_dq=int(row[SENSOR_REC["JOINT_DQ"]]) if n else None, max_dp=float(row[SENSOR_REC["MAX_DP"]]) if n else None,
+                tick_dp=int(row[SENSOR_REC["TICK_DP"]]) if n else None, sumsq_dq=float(row[SENSOR_REC["SUMSQ_DQ"]]),
+                rms_dq=float(np.sqrt(row[SENSOR_REC["SUMSQ_DQ"]] / (7 * n))) if n else None)
+
+
 def rollout_len():
     """[robot record 43 | phi | error count | iters | status | kkt | n_valid | using_previous | success | g_viol]"""
     return ROLL["LEN"]
@@ -778,6 +906,8 @@ class StreamBatch:
         self.tick_ms = None      # closed_loop(timed=True): HIP-event time of the tick just run
         self.plant_state = None  # plant_step(), rollout(plant=...): the drives' state [B][PLANT_STATE_LEN], created from the robot records on first use
         self.plant_info = self.plant_rec = None      # plant_step(): masks [B] and accumulated records [B][PLANT_REC_LEN], allocated on first use
+        self.sensor_state_ = None      # sense(), rollout(sensor=...): the sensors' state [B][SENSOR_STATE_LEN], zeros (fresh) on first use; read it with sensor_state()
+        self.sensor_info = self.sensor_rec = self.meas = None      # sense(): masks [B], accumulated records [B][SENSOR_REC_LEN] and the record the pack reads, allocated on first use
         solver._children.add(self)
 
     def update(self, b, *args, **kw):
@@ -894,6 +1024,58 @@ class StreamBatch:
                                                       _ptr(self.plant_rec), int(tick), self._stream(stream)), "bmpc_stream_plant")
         self._plant_input = plant      # the launch is asynchronous: its input lives until the next one replaces it
         return self.plant_info
+
+    def sensor_state(self, stream=None):
+        """the sensors' state on the device, [B][SENSOR_STATE_LEN] (slots SENSOR_STATE): the held sample, and the truth while a tick is in flight; zeros
+        (fresh: no sample held) on first use, then carried from launch to launch, so rollouts chain"""
+        import torch
+        if self.sensor_state_ is None:
+            lib = self.solver._lib
+            assert (lib.bmpc_stream_sensor_len(), lib.bmpc_stream_sensor_state_len(), lib.bmpc_stream_sensor_rec_len()) == (SENSOR["LEN"], SENSOR_STATE["LEN"], SENSOR_REC["LEN"])
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.path.device)):
+                self.sensor_state_ = torch.zeros((self.B, SENSOR_STATE["LEN"]), dtype=torch.float64, device=self.path.device)
+        return self.sensor_state_
+
+    def sensor_reset(self, stream=None):
+        """Start the sensors afresh: a state of zeros (no sample held) and an empty `self.sensor_rec`.  A per-tick loop that is to leave what
+        rollout(sensor=) leaves calls it where that launch would start."""
+        self.sensor_state_ = self.sensor_rec = self.sensor_info = self.meas = None
+        return self.sensor_state(stream)
+
+    def sense(self, sensor, noise=None, tick=0, stream=None):
+        """The sensors between the plants and the controller, the sample of one tick (bmpc_stream_sense): sensor [B][SENSOR_LEN] (`sensor_table(B, ...)`, an
+        array or a device tensor, taken as it is), row b the measurement model of stream b; noise [B][DIST_LEN] or None: the tick's unit draws.  Call it AHEAD
+        of tick() (or pack()) and unsense() with the same table behind it (behind post(), AHEAD of plant_step(), log(), disturb() and update_device()): in
+        between the robot records hold what the sensors hand out (`sense_robot` is the mirror), the truth waits in `self.sensor_state()`.  A stream without
+        a plan takes no sample; a stream with an invalid row is left alone, its mask in the result.  Accumulates `self.sensor_rec` [B][SENSOR_REC_LEN] (slots
+        SENSOR_REC; `tick` is what its TICK_* name), initialised on first use, and leaves in `self.meas` [B][RB_LEN] the records the pack will read.  One
+        launch, asynchronous on `stream`, capturable.  Returns the `sensor_info` tensor [B] (int32), valid once `stream` has run the launch."""
+        import torch
+        sensor = self._dev64(sensor, (self.B, SENSOR["LEN"]), "sensor", stream)
+        if noise is not None:
+            noise = self._dev64(noise, (self.B, DIST_LEN), "noise", stream)
+        state = self.sensor_state(stream)
+        if self.sensor_rec is None:
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.path.device)):
+                self.sensor_info = torch.zeros((self.B,), dtype=torch.int32, device=self.path.device)
+                rec0 = np.zeros(SENSOR_REC["LEN"])
+                rec0[[SENSOR_REC["MAX_DQ"], SENSOR_REC["MAX_DP"]]], rec0[[SENSOR_REC["TICK_DQ"], SENSOR_REC["JOINT_DQ"], SENSOR_REC["TICK_DP"]]] = -np.inf, -1.0
+                self.sensor_rec = torch.as_tensor(rec0).to(self.path.device).repeat(self.B, 1).contiguous()
+                self.meas = torch.full((self.B, RB["LEN"]), float("nan"), dtype=torch.float64, device=self.path.device)
+        _lib.check(self.solver._lib.bmpc_stream_sense(self.solver._h, self.B, _ptr(self.robot), _ptr(self.state), _ptr(sensor), _ptr(state), _ptr(self.sensor_info),
+                                                      _ptr(self.sensor_rec), None if noise is None else _ptr(noise), _ptr(self.meas), int(tick), self._stream(stream)),
+                   "bmpc_stream_sense")
+        self._sense_inputs = (sensor, noise)      # the launch is asynchronous: its inputs live until the next one replaces them
+        return self.sensor_info
+
+    def unsense(self, sensor, stream=None):
+        """The way back from the samples to the true plants behind a tick (bmpc_stream_unsense; `truth_robot` is the mirror): where the sample of sense()
+        differed from the truth, the true plant takes the step the post took on the sample, under the same planned jerk, or comes back as it was where the
+        post exhausted the plan.  sensor: the table sense() was given.  One launch, asynchronous on `stream`, capturable."""
+        sensor = self._dev64(sensor, (self.B, SENSOR["LEN"]), "sensor", stream)
+        _lib.check(self.solver._lib.bmpc_stream_unsense(self.solver._h, self.B, _ptr(self.robot), _ptr(self.state), _ptr(sensor), _ptr(self.sensor_state(stream)),
+                                                        self._stream(stream)), "bmpc_stream_unsense")
+        self._unsense_input = sensor
 
     def _dev64(self, a, shape, name, stream, dtype=None):
         """`a` as a contiguous device tensor of `shape` (float64 unless dtype), copied on `stream` when it is not one already"""
@@ -1018,7 +1200,7 @@ class StreamBatch:
     def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None,
                 replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None, audit=False, audit_tol=1e-6, want_tube=False,
                 want_log=False, log_stages=1, track=False, waves=None, legs=None, leg_tick=None, leg_on=None, leg_tol=None, tune=None, want_tune_used=False,
-                plant=None, want_plant_rec=False):
+                plant=None, want_plant_rec=False, sensor=None, sensor_noise=None, want_meas=False, want_sensor_rec=False):
         """`ticks` closed-loop ticks (plant simulation on) of every stream in ONE launch (bmpc_stream_rollout): each stream runs at its own pace, so
         the launch lasts as long as the slowest stream's SUM of solves, where a loop of tick() / tick_graph() pays the slowest stream of every tick.
         For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, a time
@@ -1088,7 +1270,22 @@ class StreamBatch:
         The drives' state is `self.plant_state` [B][PLANT_STATE_LEN], created from the robot records on first use (plant_state_of) and carried from launch to
         launch, so rollouts chain.  The rows are validated on the device; a row with an invalid slot does not run, as an invalid tune row.
           plant_info [B] int32             0: the row was valid and the stream ran; else the bit mask of its invalid slots -- READ IT
-          plant_rec [B][PLANT_REC_LEN]     want_plant_rec: what the drives did to the commands (slots PLANT_REC, unpack_plant_rec)."""
+          plant_rec [B][PLANT_REC_LEN]     want_plant_rec: what the drives did to the commands (slots PLANT_REC, unpack_plant_rec).
+        SENSORS (bmpc_stream_rollout_sensor; with or without `legs`, `tune` and `plant`, not with replan / replan_tick; without `sensor` nothing changes): a
+        measurement model per stream between the plant and what the pack, the solve and the post of every tick read, which otherwise IS the plant --
+        "encoder resolution x lag x margin" is one launch.
+          sensor [B][SENSOR_LEN]           `sensor_table(B, bias=, res=, nq=, ndq=, nddq=, hold=)`, an array or a device tensor (taken as it is): row b,
+                                           slots SENSOR; a NaN slot is the identity.  The sample (`sense_robot` is the mirror) is taken ahead of every pack,
+                                           the way back to the truth (`truth_robot`) sits behind the post, ahead of the plant step.
+          sensor_noise [ticks][B][DIST_LEN]   unit draws made by the caller, scaled by the row's NQ, NDQ, NDDQ; None: zeros
+        WHAT EACH OUTPUT THEN DESCRIBES.  hist, `self.robot` behind the launch, what disturb acts on, what the plant step corrects, what a spliced re-plan
+        takes and what the next launch starts from: the TRUTH.  `self.p`, tube_hist and audit (taken from the pack's p), traj_hist, log_hist and track: the
+        MEASUREMENT and the plan made from it -- what the controller's own monitor would report.
+          meas_hist [ticks][B][RB_LEN]     want_meas: the robot record the pack of tick t read; NaN for a tick the stream did not run
+          sensor_info [B] int32            0: the row was valid and the stream ran; else the bit mask of its invalid slots -- READ IT
+          sensor_rec [B][SENSOR_REC_LEN]   want_sensor_rec: what the samples differed from the truth by (slots SENSOR_REC, unpack_sensor_rec); its max_dp
+                                           bounds what the audit's position excess can miss.
+        The sensors' state is `self.sensor_state()` [B][SENSOR_STATE_LEN], zeros on first use and carried from launch to launch, so rollouts chain."""
         import torch
         former = self.solver.rollout_waves
         if waves is not None:
@@ -1108,6 +1305,10 @@ class StreamBatch:
                 raise ValueError("want_plant_rec goes with plant")
             if plant is not None and scheduled:
                 raise ValueError("plant goes with legs, the queue of re-plan records: it does not go with replan / replan_tick")
+            if sensor is None and (sensor_noise is not None or want_meas or want_sensor_rec):
+                raise ValueError("sensor_noise, want_meas and want_sensor_rec go with sensor")
+            if sensor is not None and scheduled:
+                raise ValueError("sensor goes with legs, the queue of re-plan records: it does not go with replan / replan_tick")
             if legs is not None and scheduled:
                 raise ValueError("legs is the queue of re-plan records: it does not go with replan / replan_tick")
             if legs is None and (leg_tick is not None or leg_on is not None or leg_tol is not None):
@@ -1117,12 +1318,14 @@ class StreamBatch:
             name = rollout_entry(replan=replan is not None, replan_tick=replan_tick is not None, disturb=disturb is not None, audit=bool(audit), want_tube=bool(want_tube),
                                  want_log=bool(want_log), track=bool(track), legs=legs is not None, tune=tune is not None, plant=plant is not None)
             entry = ROLLOUT_ENTRIES.index(name)
+            if sensor is not None:      # (the sensor's entry, chosen here: it takes every group of the plants' entry and the sensor's behind them)
+                name, entry = "bmpc_stream_rollout_sensor", len(ROLLOUT_ENTRIES)
             flags = self._update_flags(set_goal, splice, poor_bounds) if entry else 0      # (the plain rollout has no events: their words are not looked at)
             lib, B, n, dev = self.solver._lib, self.B, max(int(ticks), 0), self.path.device
             assert lib.bmpc_stream_rollout_len() == ROLL["LEN"] and (not track or lib.bmpc_stream_track_len() == TRACK["LEN"]) and (tune is None or lib.bmpc_stream_tune_len() == TUNE["LEN"])
             assert not want_log or lib.bmpc_stream_rollout_log_len(self.solver._h, int(log_stages)) == rollout_log_len(log_stages)
             # 2. every input on the device, once
-            record = state = None
+            record = state = sstate = None
             K = 0
             if replan is not None:
                 record = self._replan_buffer(replan, stream)
@@ -1140,14 +1343,20 @@ class StreamBatch:
                 tune = self._dev64(tune, (B, TUNE["LEN"]), "tune", stream)
             if plant is not None:
                 plant, state = self._dev64(plant, (B, PLANT["LEN"]), "plant", stream), self._plant_state(stream)
+            if sensor is not None:
+                assert lib.bmpc_stream_sensor_len() == SENSOR["LEN"]
+                sensor, sstate = self._dev64(sensor, (B, SENSOR["LEN"]), "sensor", stream), self.sensor_state(stream)
+                if sensor_noise is not None:
+                    sensor_noise = self._dev64(sensor_noise, (n, B, DIST_LEN), "sensor_noise", stream)
             # 3. every output, once
             out = {"hist": torch.empty((n, B, ROLL["LEN"]), dtype=torch.float64, device=dev), "ticks_run": torch.zeros((B,), dtype=torch.int32, device=dev)}
             for key, want, shape in (("traj_hist", want_traj, (n, B, self.tr_len)), ("audit", audit, (B, AUDIT["LEN"])), ("tube_hist", want_tube, (n, B, TUBE["LEN"])),
                                      ("log_hist", want_log, (n, B, rollout_log_len(log_stages) if want_log else 0)), ("track", track, (B, TRACK["LEN"])),
-                                     ("tune_used", want_tune_used, (B, TUNE["LEN"])), ("plant_rec", want_plant_rec, (B, PLANT_REC["LEN"]))):
+                                     ("tune_used", want_tune_used, (B, TUNE["LEN"])), ("plant_rec", want_plant_rec, (B, PLANT_REC["LEN"])),
+                                     ("meas_hist", want_meas, (n, B, RB["LEN"])), ("sensor_rec", want_sensor_rec, (B, SENSOR_REC["LEN"]))):
                 if want:
                     out[key] = torch.empty(shape, dtype=torch.float64, device=dev)
-            for key, want, shape, fill in (("tune_info", tune is not None, (B,), -1), ("plant_info", plant is not None, (B,), -1), ("legs_done", K, (B,), 0), ("leg_fired", K, (B, K), -1),
+            for key, want, shape, fill in (("tune_info", tune is not None, (B,), -1), ("plant_info", plant is not None, (B,), -1), ("sensor_info", sensor is not None, (B,), -1), ("legs_done", K, (B,), 0), ("leg_fired", K, (B, K), -1),
                                            ("leg_why", K, (B, K), 0), ("replan_info", K or 1 <= entry <= 3, (B, K) if K else (B,), -1)):
                 if want:
                     out[key] = torch.full(shape, fill, dtype=torch.int32, device=dev)
@@ -1161,10 +1370,11 @@ class StreamBatch:
                       (o("log_hist"), int(log_stages), o("track")),                                                            # log
                       (K, at(leg_tick), at(leg_on), at(leg_tol), o("legs_done"), o("leg_fired"), o("leg_why")),                 # queue
                       (at(tune), o("tune_info"), o("tune_used")),                                                              # table
-                      (at(plant), at(state), o("plant_info"), o("plant_rec")))                                                 # plant
+                      (at(plant), at(state), o("plant_info"), o("plant_rec")),                                                 # plant
+                      (at(sensor), at(sstate), o("sensor_info"), o("sensor_rec"), at(sensor_noise), o("meas_hist")))             # sensor
             _lib.check(getattr(lib, name)(*prefix, *(a for group in groups[:entry] for a in group), self._stream(stream)), name)
             if entry:
-                self._event_inputs = (replan_tick, leg_tick, leg_on, leg_tol, disturb, tune, plant)      # the launch is asynchronous: its inputs live until the next one replaces them
+                self._event_inputs = (replan_tick, leg_tick, leg_on, leg_tol, disturb, tune, plant, sensor, sensor_noise)      # the launch is asynchronous: its inputs live until the next one replaces them
             return out
         finally:
             if waves is not None:

@@ -617,6 +617,82 @@ int bmpc_stream_rollout_plant(bmpc_handle *h, int B, int ticks, const double *pa
 int bmpc_stream_plant(bmpc_handle *h, int B, double *robot, const double *sstate, const double *plant /* [B][BMPC_PLANT_LEN] */,
                       double *plant_state /* [B][BMPC_PLANT_STATE_LEN] */, int *plant_info /* [B] or NULL */,
                       double *plant_rec /* [B][BMPC_PLANT_REC_LEN] or NULL, accumulated, not initialised */, int tick, void *hip_stream);
+/* Rollout with a SENSOR MODEL: bmpc_stream_rollout_plant (its arguments in their order up to and including plant_rec, their meaning, tests and contract;
+ * NULL event, audit, log, queue, settings and plant pointers switch those off) with a TABLE of measurement models per stream.  In every other rollout the
+ * pack of a tick reads the robot record, and the record IS the plant: the controller measures the true state exactly.  The disturb table cannot stand in
+ * for a sensor: it moves the plant, and the next pack measures the moved plant exactly.  Here a sensor stands between the plant and what the pack, the
+ * solve and the post of a tick read:
+ *   sensor       [B][BMPC_SENSOR_LEN] or NULL, DEVICE: row b, slots BMPC_SENSOR_*; the four words behind BMPC_SENSOR_HOLD are pad and never looked at
+ *                  BIAS[7]          encoder offset of joint j, rad                          identity 0       valid when finite
+ *                  RES              quantisation step of the joint positions, rad           identity 0       valid when finite and >= 0 (0: none)
+ *                  NQ, NDQ, NDDQ    scale of the tick's noise row on q, dq, ddq             identity 0       valid when finite and >= 0
+ *                  HOLD             1: the controller sees the previous tick's sample       identity 0       valid when 0 or 1
+ *                a NaN slot takes its identity value
+ *   sensor_state [B][BMPC_SENSOR_STATE_LEN], required with sensor, IN AND OUT so that rollouts chain; all zeros = fresh: HELD[21] the sample taken last
+ *                (q, dq, ddq), HAS 1 once there is one, SAME 1 where the sample handed out last equalled the truth, a pad word, TRUTH[40] the words q..v
+ *                [33] and jerk [7] of the robot record while a tick is in flight
+ *   sensor_info  [B] or NULL: 0 = row b was valid and the stream ran; else the bit mask of its invalid slots (bit k = slot k)
+ *   sensor_rec   [B][BMPC_SENSOR_REC_LEN] or NULL, initialised by the call: SAMPLES the samples taken, MAX_DQ the largest |q_m - q| with TICK_DQ and
+ *                JOINT_DQ its first tick and joint, MAX_DP the largest ||p_m - p|| (metres, position part of p_lie) with TICK_DP its first tick, SUMSQ_DQ
+ *                the sum of (q_m - q)^2 in tick order, joints 0..6 inside a tick, a pad word; q_m, p_m: what the controller was handed (under HOLD the
+ *                sample of the tick before); a stream without a sample: SAMPLES 0, MAX_* -inf, TICK_* and JOINT_DQ -1, sum 0; a non-finite
+ *                difference makes its MAX NaN for good
+ *   sensor_noise [ticks][B][21] or NULL (zeros), DEVICE: unit draws made by the caller, delta q 7 | delta dq 7 | delta ddq 7 of tick t of stream b; a
+ *                non-finite word counts as 0, as in bmpc_stream_disturb
+ *   meas_hist    [ticks][B][robot record] or NULL: the robot record the pack of tick t read; NaN rows for the ticks a stream did not run
+ * The sample of tick t, behind the lost-plan test and ahead of the pack, per joint j with n the tick's noise row:
+ *   m_q = (q_j + BIAS_j) + NQ n_j;  RES > 0: m_q = RES rint(m_q / RES) (half to even);  m_dq = dq_j + NDQ n_{7+j};  m_ddq = ddq_j + NDDQ n_{14+j};
+ *   out = (HOLD == 1 and HAS) ? HELD : m;  HELD = m;  HAS = 1;  SAME = every word of out compares equal to the truth's
+ * Where SAME == 0 the robot record's q, dq, ddq become out and its p_lie and v are recomputed from them as bmpc_stream_disturb does (jerk and x_phi_d are
+ * kept); where SAME == 1 the record keeps every bit.  The way back, behind the post and ahead of the plant step: SAME == 1: nothing, the post has
+ * stepped the truth itself.  Else, where the post stepped the record (error count < N behind it): the TRUE q, dq, ddq take the model's chain step from
+ * the true jerk to the first planned jerk c the post has stored, p_lie and v follow, the jerk is c -- the post's step on the true plant.  Else (the post
+ * exhausted the plan and did not step) the words q..v are the truth's again.
+ * WHAT EACH OUTPUT THEN DESCRIBES.  hist, robot behind the call, what disturb acts on, what the plant step corrects, what a spliced re-plan takes and what
+ * the next launch starts from: the TRUTH.  p, the tube rows and the audit (taken from the pack's p), traj, the log rows and the tracking record: the
+ * MEASUREMENT and the plan made from it -- what the controller's own monitor would report.  meas_hist is the measurement itself, and MAX_DP of the record
+ * bounds what the audit's position excess can miss.  An audit of the truth's orientation rows would need the pack's orientation decomposition at the true
+ * pose, and a splice from the measurement instead of the truth is not offered either.
+ * An invalid row gets the treatment of an invalid plant row: no tick, NaN history rows, its mask in sensor_info[b], sensor_state untouched.
+ * With sensor == NULL the call IS bmpc_stream_rollout_plant, and no sensor argument is looked at.  With a table of NaN or of identity values every array
+ * that entry names holds what it leaves, bit for bit.  With goal_tol = 0 every array, sensor_state and sensor_rec hold what this loop leaves, bit for bit:
+ *   for t in 0..ticks-1: bmpc_stream_sense(tick t, noise rows of tick t); bmpc_stream_tick on one wave per stream; bmpc_stream_unsense;
+ *                        bmpc_stream_plant(tick t); bmpc_stream_log; bmpc_stream_disturb(rows of tick t); bmpc_stream_update of the head records due
+ * bmpc_stream_sense and bmpc_stream_unsense are the two steps on their own, one launch over the batch each, for per-tick loops: around a tick (or pack ..
+ * post).  The sample: for an invalid row it writes the mask and touches nothing; a stream whose sstate error count is >= N (the tick will skip it) takes no
+ * sample, and SAME = 1 is written so that the way back leaves it alone; sensor_noise is ONE row per stream [B][21]; meas (or NULL) [B][robot record] is
+ * the record the pack will read; sensor_rec (or NULL) is ACCUMULATED, not initialised.  Neither uses workspace of the handle; both may sit inside a
+ * capture of the caller's stream, like bmpc_stream_plant.
+ * BMPC_ERR_ARG, nothing launched: what bmpc_stream_rollout_plant refuses, and sensor without sensor_state; the two steps: no handle, B < 1, no robot,
+ * sstate, sensor or sensor_state. */
+enum { BMPC_SENSOR_BIAS = 0, BMPC_SENSOR_RES = 7, BMPC_SENSOR_NQ = 8, BMPC_SENSOR_NDQ = 9, BMPC_SENSOR_NDDQ = 10, BMPC_SENSOR_HOLD = 11, BMPC_SENSOR_LEN = 16 };      /* four pad words */
+enum { BMPC_SENSOR_STATE_HELD = 0, BMPC_SENSOR_STATE_HAS = 21, BMPC_SENSOR_STATE_SAME = 22, BMPC_SENSOR_STATE_TRUTH = 24, BMPC_SENSOR_STATE_LEN = 64 };              /* one pad word */
+enum { BMPC_SENSOR_REC_SAMPLES = 0, BMPC_SENSOR_REC_MAX_DQ, BMPC_SENSOR_REC_TICK_DQ, BMPC_SENSOR_REC_JOINT_DQ, BMPC_SENSOR_REC_MAX_DP, BMPC_SENSOR_REC_TICK_DP,
+       BMPC_SENSOR_REC_SUMSQ_DQ, BMPC_SENSOR_REC_LEN = 8 };                                                                                                        /* one pad word */
+int bmpc_stream_sensor_len(void);
+int bmpc_stream_sensor_state_len(void);
+int bmpc_stream_sensor_rec_len(void);
+int bmpc_stream_rollout_sensor(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                               double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                               double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan /* [B][legs][len] or NULL */,
+                               int *replan_info /* [B][legs] or NULL */, int update_flags, const double *disturb /* [ticks][B][21] or NULL */,
+                               double *tube_hist /* [ticks][B][16] or NULL */, double *audit /* [B][12] or NULL */, double audit_tol,
+                               double *log_hist /* [ticks][B][88 log_stages + 4] or NULL */, int log_stages, double *track /* [B][12] or NULL */,
+                               int legs, const int *leg_tick /* [B][legs] */, const int *leg_on /* [B][legs] */, const double *leg_tol /* [B][legs] or NULL */,
+                               int *legs_done /* [B] */, int *leg_fired /* [B][legs] or NULL */, int *leg_why /* [B][legs] or NULL */,
+                               const double *tune /* [B][BMPC_TUNE_LEN] or NULL */, int *tune_info /* [B] or NULL */,
+                               double *tune_used /* [B][BMPC_TUNE_LEN] or NULL */, const double *plant /* [B][BMPC_PLANT_LEN] or NULL */,
+                               double *plant_state /* [B][BMPC_PLANT_STATE_LEN] */, int *plant_info /* [B] or NULL */,
+                               double *plant_rec /* [B][BMPC_PLANT_REC_LEN] or NULL */, const double *sensor /* [B][BMPC_SENSOR_LEN] or NULL */,
+                               double *sensor_state /* [B][BMPC_SENSOR_STATE_LEN] */, int *sensor_info /* [B] or NULL */,
+                               double *sensor_rec /* [B][BMPC_SENSOR_REC_LEN] or NULL */, const double *sensor_noise /* [ticks][B][21] or NULL */,
+                               double *meas_hist /* [ticks][B][robot record] or NULL */, void *hip_stream);
+int bmpc_stream_sense(bmpc_handle *h, int B, double *robot, const double *sstate, const double *sensor /* [B][BMPC_SENSOR_LEN] */,
+                      double *sensor_state /* [B][BMPC_SENSOR_STATE_LEN] */, int *sensor_info /* [B] or NULL */,
+                      double *sensor_rec /* [B][BMPC_SENSOR_REC_LEN] or NULL, accumulated, not initialised */, const double *sensor_noise /* [B][21] or NULL */,
+                      double *meas /* [B][robot record] or NULL */, int tick, void *hip_stream);
+int bmpc_stream_unsense(bmpc_handle *h, int B, double *robot, const double *sstate, const double *sensor /* [B][BMPC_SENSOR_LEN] */,
+                        const double *sensor_state /* [B][BMPC_SENSOR_STATE_LEN] */, void *hip_stream);
 
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
