@@ -9,9 +9,10 @@ from ._lib import BoundMPCHipError, LIB_PATH  # noqa: F401
 
 __all__ = ["BatchedOCPSolver", "NlpSolverShim", "BoundMPCHipError", "LIB_PATH"]
 
-# the plant and sensor models of a rollout (boundmpc_amd.stream), re-exported on first use: importing the package does not import the stream module
+# the plant, sensor and observer models of a rollout (boundmpc_amd.stream), re-exported on first use: importing the package does not import the stream module
 _PLANT = ("PLANT", "PLANT_STATE", "PLANT_REC", "plant_table", "plant_check", "plant_state_of", "plant_robot", "unpack_plant_rec",
-          "SENSOR", "SENSOR_STATE", "SENSOR_REC", "sensor_table", "sensor_check", "sense_robot", "truth_robot", "unpack_sensor_rec")
+          "SENSOR", "SENSOR_STATE", "SENSOR_REC", "sensor_table", "sensor_check", "sense_robot", "truth_robot", "unpack_sensor_rec",
+          "OBSERVER", "OBSERVER_STATE", "OBSERVER_REC", "observer_table", "observer_check", "observe_robot", "unpack_observer_rec")
 
 
 def __getattr__(name):

@@ -49,6 +49,9 @@ SIGNATURES = {
     "bmpc_stream_sensor_len": (_ci, []), "bmpc_stream_sensor_state_len": (_ci, []), "bmpc_stream_sensor_rec_len": (_ci, []),
     "bmpc_stream_sense": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp]),      # handle, B, robot, sstate, sensor, sensor_state, sensor_info, sensor_rec, sensor_noise, meas, tick, stream
     "bmpc_stream_unsense": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp]),      # handle, B, robot, sstate, sensor, sensor_state, stream
+    "bmpc_stream_rollout_observer": (_ci, _TICK[:2] + [_ci] + _TICK[2:] + [_cd, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _cd, _vp, _ci, _vp] + [_ci] + [_vp] * 25),      # ... meas_hist, observer, observer_state, observer_info, observer_rec, sample_hist, stream
+    "bmpc_stream_observer_len": (_ci, []), "bmpc_stream_observer_state_len": (_ci, []), "bmpc_stream_observer_rec_len": (_ci, []),
+    "bmpc_stream_observe": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _vp]),      # the arguments of bmpc_stream_sense up to tick, observer, observer_state, observer_info, observer_rec, sample, stream
     "bmpc_stream_tune_len": (_ci, []), "bmpc_stream_tune_defaults": (_ci, [_vp, _ci, _vp]),
     "bmpc_stream_track_len": (_ci, []), "bmpc_stream_rollout_log_len": (_ci, [_vp, _ci]),
     "bmpc_stream_tube_len": (_ci, []), "bmpc_stream_tube": (_ci, [_vp, _ci, _vp, _vp, _vp, _vp]),

@@ -23,7 +23,8 @@ SOURCES = [os.path.join(CSRC, "bmpc_hip.hip"), os.path.join(CSRC, "bmpc_wave.inl
            os.path.join(CSRC, "bmpc_team_rollout_legs.hip"), os.path.join(CSRC, "bmpc_rollout_tune.hip"), os.path.join(CSRC, "bmpc_team_rollout_tune.hip"),
            os.path.join(CSRC, "bmpc_stream_plant.inl"), os.path.join(CSRC, "bmpc_rollout_plant.hip"), os.path.join(CSRC, "bmpc_team_rollout_plant.hip"),
            os.path.join(CSRC, "bmpc_rollout_body.inl"), os.path.join(CSRC, "bmpc_stream_sensor.inl"), os.path.join(CSRC, "bmpc_rollout_sensor.hip"),
-           os.path.join(CSRC, "bmpc_team_rollout_sensor.hip")]
+           os.path.join(CSRC, "bmpc_team_rollout_sensor.hip"), os.path.join(CSRC, "bmpc_stream_observer.inl"), os.path.join(CSRC, "bmpc_rollout_observer.hip"),
+           os.path.join(CSRC, "bmpc_team_rollout_observer.hip")]
 # translation units of the library: the one-wave batch kernels + C ABI, the team kernels (NW cooperating waves per problem), the restoration
 # kernels (the solver with the restoration phase, continuing what a batch kernel left jammed), the fused closed-loop tick kernels, the pair kernel
 # the rollout kernels (many ticks of every stream in one launch), the rollout kernels with events (disturbances, scheduled re-plans) and those with
@@ -32,13 +33,15 @@ SOURCES = [os.path.join(CSRC, "bmpc_hip.hip"), os.path.join(CSRC, "bmpc_wave.inl
 # kernels with a queue of re-plan records per stream (fired by tick, goal or lost plan) on one wave and on teams, those with a table of controller
 # settings per stream on top (sweeps: a grid over settings as one launch) on one wave and on teams, those with a table of actuator models per stream
 # between the command and the plant on top of that on one wave and on teams, those with a table of measurement models per stream between the plant and
-# the controller on top of that on one wave and on teams: 18 units side by side
+# the controller on top of that on one wave and on teams, those with a table of state observers per stream between the sensor's sample and the pack on top
+# of that on one wave and on teams: 20 units side by side
 UNITS = [os.path.join(CSRC, "bmpc_hip.hip"), os.path.join(CSRC, "bmpc_team.hip"), os.path.join(CSRC, "bmpc_resto.hip"), os.path.join(CSRC, "bmpc_tick.hip"),
          os.path.join(CSRC, "bmpc_pair.hip"), os.path.join(CSRC, "bmpc_rollout.hip"), os.path.join(CSRC, "bmpc_rollout_events.hip"),
          os.path.join(CSRC, "bmpc_rollout_audit.hip"), os.path.join(CSRC, "bmpc_rollout_log.hip"), os.path.join(CSRC, "bmpc_team_rollout.hip"),
          os.path.join(CSRC, "bmpc_rollout_legs.hip"), os.path.join(CSRC, "bmpc_team_rollout_legs.hip"), os.path.join(CSRC, "bmpc_rollout_tune.hip"),
          os.path.join(CSRC, "bmpc_team_rollout_tune.hip"), os.path.join(CSRC, "bmpc_rollout_plant.hip"), os.path.join(CSRC, "bmpc_team_rollout_plant.hip"),
-         os.path.join(CSRC, "bmpc_rollout_sensor.hip"), os.path.join(CSRC, "bmpc_team_rollout_sensor.hip")]
+         os.path.join(CSRC, "bmpc_rollout_sensor.hip"), os.path.join(CSRC, "bmpc_team_rollout_sensor.hip"), os.path.join(CSRC, "bmpc_rollout_observer.hip"),
+         os.path.join(CSRC, "bmpc_team_rollout_observer.hip")]
 
 
 def hipcc():
@@ -123,11 +126,17 @@ def read_listing(asm_path):
             if text and text[0] != "." and text[-1] != ":":
                 funcs[-1].blocks[-1].insns.append(Ins(n, text, note.strip()))
     by_name = {fn.name: fn for fn in funcs}
+    kernels = set()
     # the metadata (YAML): one `  - .key: value` entry per kernel, its own keys at indent 4, those of its arguments deeper
     for entry in re.split(r"\n  - (?=\.)", listing.partition("\namdhsa.kernels:")[2].partition("\namdhsa.target:")[0])[1:]:
         fields = dict(re.findall(r"^(?:    )?\.(\w+): +(\S+)$", entry, re.M))
         if fields.get("name") in by_name:
             by_name[fields["name"]].resources.update((k, int(v)) for k, v in fields.items() if v.isdigit())
+            kernels.add(fields["name"])
+    # (a function the kernels CALL -- stream_observe of the observer units -- has a `; Function info:` trailer and no metadata entry: no kernel, no record)
+    for fn in funcs:
+        if fn.name not in kernels:
+            fn.resources.clear()
     return funcs
 
 

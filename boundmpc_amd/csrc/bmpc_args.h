@@ -135,6 +135,15 @@ struct NArgs {
     const double *sensor_noise;      // [ticks][B][bmpcs::DIST_LEN] or NULL: unit draws, scaled by the row's NQ, NDQ, NDDQ; a non-finite word counts as 0
     double *meas_hist;               // [ticks][B][bmpcs::RB_LEN] or NULL: the robot record the pack of tick t read; NaN rows for the ticks not run
 };
+// what a rollout with a state observer adds (the OB kernels, bmpc_stream_rollout_observer; bmpc_rollout_kernel.inl): a record of its own, the FIFTH kernel
+// argument of those kernels -- RArgs and NArgs keep their members, and the other kernels their arguments
+struct OArgs {
+    const double *observer;          // [B][bmpcob::LEN]: row b stands between the sample of stream b's sensor and the pack; a NaN slot is the identity
+    double *observer_state;          // [B][bmpcob::ST_LEN], in and out: the last posterior and the jerks that advance it; all zeros = fresh; required with observer
+    int *observer_info;              // [B] or NULL: the mask of the invalid slots of row b; 0 = the stream ran
+    double *observer_rec;            // [B][bmpcob::REC_LEN] or NULL, initialised by the kernel: what the estimates differed from the truth by
+    double *sample_hist;             // [ticks][B][bmpcs::DIST_LEN] or NULL: the raw sample the sensor handed the observer at tick t; NaN rows for the ticks not run
+};
 
 // ---- host and device: a row of per-stream controller settings (BMPC_TUNE_* of include/boundmpc_hip.h), what it resolves to and what is refused ----
 // The slots of a row; a slot holds NaN ("the launch's value") or the value of the option, setter or argument named behind it.
@@ -311,6 +320,45 @@ BMPC_ARGS_HD int bmpc_sensor_check(const double *row, double *used) {
     return bad;
 }
 
+// ---- host and device: a row of a per-stream state observer (BMPC_OBSERVER_* of include/boundmpc_hip.h), its state and its record; the rule of the step is
+// stream_observe (bmpc_stream_observer.inl) ----
+namespace bmpcob {
+enum { LQ = 0, LDQ, LDDQ, // correction gain on q, dq, ddq                                   identity 1 (the estimate is the sample), valid when 0 < v <= 1
+       LEAD = 3,          // 1: the sample is one tick old, the estimate is advanced a step  identity 0, valid when 0 or 1
+       GATE = 4,          // innovation gate on the joint positions, rad                     identity +inf (none), valid when > 0, +inf allowed
+       SLOTS = 5,         // the slots that are looked at; the words behind them up to LEN are pad
+       LEN = 8 };
+// the state: the last posterior [21], the record's jerk at the posterior's time [7], the record's jerk read at the last call [7], whether there is a
+// posterior, whether it is one tick behind the last call, three pad words
+enum { ST_POST = 0, ST_JP = 21, ST_JL = 28, ST_HAS = 35, ST_LAGS = 36, ST_LEN = 40 };
+// the record: estimates, gate rejections, largest |q_est - q| with its tick and joint, largest ||p_est - p|| (position part of p_lie, metres) with its tick,
+// sum of squares of q_est - q
+enum { REC_SAMPLES = 0, REC_N_REJ, REC_MAX_DQ, REC_TICK_DQ, REC_JOINT_DQ, REC_MAX_DP, REC_TICK_DP, REC_SUMSQ_DQ, REC_LEN = 8 };
+}
+// what a NaN slot resolves to: the observer that hands the sample on
+BMPC_ARGS_HD double bmpc_observer_identity(int k) { return k < bmpcob::LEAD ? 1.0 : k == bmpcob::GATE ? __builtin_inf() : 0.0; }
+// THE validity rule of a slot that is not NaN, once (plain comparisons)
+BMPC_ARGS_HD bool bmpc_observer_slot_ok(int k, double v) {
+    if (k < bmpcob::LEAD) return v > 0.0 && v <= 1.0;
+    if (k == bmpcob::LEAD) return v == 0.0 || v == 1.0;
+    if (k == bmpcob::GATE) return v > 0.0;      // (+inf: no gate)
+    return true;      // (pad words: never looked at)
+}
+// Row `row`: the mask of its invalid slots, bit k = slot k; 0 = the stream runs.  used (or NULL): the row as resolved -- a NaN slot its identity value, a
+// refused value as it was given, pad words 0.
+BMPC_ARGS_HD int bmpc_observer_check(const double *row, double *used) {
+    int bad = 0;
+    for (int k = 0; k < bmpcob::LEN; k++) {
+        double v = k < bmpcob::SLOTS ? row[k] : 0.0;
+        if (k < bmpcob::SLOTS) {
+            if (v != v) v = bmpc_observer_identity(k);
+            else if (!bmpc_observer_slot_ok(k, v)) bad |= 1 << k;
+        }
+        if (used) used[k] = v;
+    }
+    return bad;
+}
+
 // ---- host only: what the rollout entries of the C ABI refuse and which kernel they run, once (bmpc_hip.hip rollout_launch; the CPU build of the
 // rollout, tests/emu/bmpc_emu_rollout.cpp, asks the same function) ----
 // the flags of bmpc_stream_update: bit 0 set_goal, bit 1 splice (needs the robot records), bit 2 poor bounds (with bit 1 only)
@@ -352,3 +400,6 @@ inline int bmpc_rollout_level(int entry, const RArgs &r, int N, int flags, const
 // What bmpc_stream_rollout_sensor refuses on top of what the plants' entry refuses (bmpc_rollout_level with entry 6 on its RArgs): a table without its
 // state.  Without a table it IS that entry, and no member of `n` is looked at.
 inline bool bmpc_rollout_sensor_ok(const NArgs &n) { return !n.sensor || n.sensor_state; }
+// What bmpc_stream_rollout_observer refuses on top of what the sensors' entry refuses: an observer without a sensor table -- there is no sample to
+// filter -- and an observer without its state.  Without an observer table it IS that entry, and no member of `o` is looked at.
+inline bool bmpc_rollout_observer_ok(const NArgs &n, const OArgs &o) { return !o.observer || (n.sensor && o.observer_state); }

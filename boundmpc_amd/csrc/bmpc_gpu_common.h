@@ -135,6 +135,11 @@ hipError_t bmpc_rollout_sensor_launch(bool zlds, bool resto, const void *kargs, 
 hipError_t bmpc_stream_sense_launch(int N, int B, double *rb, const double *ss, const double *sensor, double *state, int *info, double *rec, const double *noise, double *meas,
                                     int tick, hipStream_t st);
 hipError_t bmpc_stream_unsense_launch(int N, int B, double h, double *rb, const double *ss, const double *sensor, const double *state, hipStream_t st);
+// ---- the same with a table of state observers per stream between the sensor's sample and the pack (bmpc_rollout_observer.hip; everything on, SE and OB) ----
+hipError_t bmpc_rollout_observer_launch(bool zlds, bool resto, const void *kargs, const SArgs *s, const RArgs *r, const NArgs *n, const OArgs *o, int grid, hipStream_t st);
+// ---- the sample and the estimate on their own, one lane per stream of the batch (bmpc_rollout_observer.hip; bmpc_stream_observer.inl) ----
+hipError_t bmpc_stream_observe_launch(int N, int B, double h, double *rb, const double *ss, const double *sensor, double *state, int *info, double *rec, const double *noise,
+                                      double *meas, int tick, const double *observer, double *ostate, int *oinfo, double *orec, double *sample, hipStream_t st);
 // ---- the measurement on its own, one wave per stream of the batch (bmpc_rollout_audit.hip; bmpc_stream_tube.inl) ----
 hipError_t bmpc_stream_tube_launch(int N, int S, int B, const double *p, const double *ss, double *tube, hipStream_t st);
 
@@ -154,6 +159,8 @@ hipError_t bmpc_team_rollout_tune_launch(int nw, bool resto, const void *kargs, 
 hipError_t bmpc_team_rollout_plant_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, int grid, hipStream_t st);
 // the same with the table of measurement models per stream (bmpc_team_rollout_sensor.hip): the fully-featured kernel with SE
 hipError_t bmpc_team_rollout_sensor_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, const NArgs *n, int grid, hipStream_t st);
+// the same with the table of state observers per stream (bmpc_team_rollout_observer.hip): the fully-featured kernel with SE and OB
+hipError_t bmpc_team_rollout_observer_launch(int nw, bool resto, const void *kargs, const SArgs *s, const RArgs *r, const NArgs *n, const OArgs *o, int grid, hipStream_t st);
 int bmpc_team_lds_bytes(int nw);
 int bmpc_team_nmax(int nw);      // longest horizon the team kernels take (their LDS holds most of the workspace)
 

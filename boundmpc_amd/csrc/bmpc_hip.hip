@@ -863,10 +863,12 @@ extern "C" int bmpc_stream_rollout_len(void) { return BMPC_ROLL_LEN; }
 // event and the audit code (2), with the log code on top of both (3), with the queue of re-plan records on top of all (4), with the table of per-stream
 // settings on top of that (5), with the table of per-stream actuator models on top of that (6) -- are bmpc_rollout_level's (bmpc_args.h).
 // n: the record of the sensor entry WITH a table (the SE kernels, which serve whatever level the other arguments name), else NULL.
-static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, const RArgs &r, int entry, hipStream_t st, const NArgs *n = nullptr) {
+// o: the record of the observer entry WITH a table (the OB kernels: the SE kernels with the estimate between the sample and the pack), else NULL; with n only.
+static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const StreamIO &t, const RArgs &r, int entry, hipStream_t st, const NArgs *n = nullptr,
+                          const OArgs *o = nullptr) {
     if (!tick_args_ok(h, B, io, t)) return BMPC_ERR_ARG;
     const int level = bmpc_rollout_level(entry, r, h->N, t.flags, t.robot);
-    if (level == BMPC_ROLLOUT_REFUSED || (n && !bmpc_rollout_sensor_ok(*n))) return BMPC_ERR_ARG;
+    if (level == BMPC_ROLLOUT_REFUSED || (n && !bmpc_rollout_sensor_ok(*n)) || (o && !(n && bmpc_rollout_observer_ok(*n, *o)))) return BMPC_ERR_ARG;
     if (h->rt_budget_us > 0.0) return BMPC_ERR_ARG;                   // a rollout is not real time, and budgeted results depend on the clock
     if (h->closed || caller_is_capturing(st)) return BMPC_ERR_ARG;    // (a direct launch: the workspace may grow, and the ordering events are recorded)
     if (B == 0) return BMPC_OK;
@@ -883,7 +885,9 @@ static int rollout_launch(bmpc_handle *h, int B, const SolveIO &io, const Stream
     hipEvent_t *pair = nullptr;
     if (h->timing) { int rc = timing_slot(h, &pair); if (rc != BMPC_OK) return rc; HIPCHK(hipEventRecord(pair[0], st)); }
     // (teams at levels 1 and 2 hand the LG text the caller's log_stages UNCHECKED, with log_hist and track NULL: the kernel reads it behind r.log_hist only)
-    if (team && n) HIPCHK(bmpc_team_rollout_sensor_launch(BMPC_TEAM_NW, resto, &a, &s, &r, n, grid, st));
+    if (team && o) HIPCHK(bmpc_team_rollout_observer_launch(BMPC_TEAM_NW, resto, &a, &s, &r, n, o, grid, st));
+    else if (o) HIPCHK(bmpc_rollout_observer_launch(handle_zlds(h), resto, &a, &s, &r, n, o, grid, st));
+    else if (team && n) HIPCHK(bmpc_team_rollout_sensor_launch(BMPC_TEAM_NW, resto, &a, &s, &r, n, grid, st));
     else if (n) HIPCHK(bmpc_rollout_sensor_launch(handle_zlds(h), resto, &a, &s, &r, n, grid, st));
     else if (team && level == 6) HIPCHK(bmpc_team_rollout_plant_launch(BMPC_TEAM_NW, resto, &a, &s, &r, grid, st));
     else if (team && level == 5) HIPCHK(bmpc_team_rollout_tune_launch(BMPC_TEAM_NW, resto, &a, &s, &r, grid, st));
@@ -1035,6 +1039,38 @@ extern "C" int bmpc_stream_sense(bmpc_handle *h, int B, double *robot, const dou
 extern "C" int bmpc_stream_unsense(bmpc_handle *h, int B, double *robot, const double *sstate, const double *sensor, const double *sensor_state, void *hip_stream) {
     if (!h || B < 1 || !robot || !sstate || !sensor || !sensor_state || h->N > bmpcs::STREAM_NMAX) return BMPC_ERR_ARG;
     HIPCHK(bmpc_stream_unsense_launch(h->N, B, h->h, robot, sstate, sensor, sensor_state, (hipStream_t)hip_stream));
+    return BMPC_OK;
+}
+// with a table of state observers per stream between the sensor's sample and the pack on top (bmpc_rollout_observer.hip, bmpc_team_rollout_observer.hip): the
+// rows live on the device and are validated there, by the rule of bmpc_args.h; without a table it IS the entry above
+extern "C" int bmpc_stream_observer_len(void) { return BMPC_OBSERVER_LEN; }
+extern "C" int bmpc_stream_observer_state_len(void) { return BMPC_OBSERVER_STATE_LEN; }
+extern "C" int bmpc_stream_observer_rec_len(void) { return BMPC_OBSERVER_REC_LEN; }
+extern "C" int bmpc_stream_rollout_observer(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                                            double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                                            double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan, int *replan_info, int update_flags,
+                                            const double *disturb, double *tube_hist, double *audit, double audit_tol, double *log_hist, int log_stages, double *track,
+                                            int legs, const int *leg_tick, const int *leg_on, const double *leg_tol, int *legs_done, int *leg_fired, int *leg_why,
+                                            const double *tune, int *tune_info, double *tune_used, const double *plant, double *plant_state, int *plant_info,
+                                            double *plant_rec, const double *sensor, double *sensor_state, int *sensor_info, double *sensor_rec,
+                                            const double *sensor_noise, double *meas_hist, const double *observer, double *observer_state, int *observer_info,
+                                            double *observer_rec, double *sample_hist, void *hip_stream) {
+    const SolveIO io{p, x0, dual_state, max_iter, x, g, nullptr, nullptr, nullptr, iters, status, kkt};
+    const StreamIO t{path, path_entries, sstate, robot, traj, flags};
+    const RArgs r{ticks, goal_tol, hist, traj_hist, ticks_run, replan, nullptr, replan_info, update_flags, disturb, tube_hist, audit, audit_tol, log_hist, log_stages, track,
+                  legs, leg_tick, leg_on, leg_tol, legs_done, leg_fired, leg_why, tune, tune_info, tune_used, plant, plant_state, plant_info, plant_rec};
+    const NArgs n{sensor, sensor_state, sensor_info, sensor_rec, sensor_noise, meas_hist};
+    const OArgs o{observer, observer_state, observer_info, observer_rec, sample_hist};
+    if (!bmpc_rollout_observer_ok(n, o)) return BMPC_ERR_ARG;      // (an observer without a sensor table or without its state)
+    return rollout_launch(h, B, io, t, r, 6, (hipStream_t)hip_stream, sensor ? &n : nullptr, observer ? &o : nullptr);
+}
+// the sample and the estimate on their own, for per-tick loops in the place of bmpc_stream_sense (no workspace of the handle: may sit inside a capture)
+extern "C" int bmpc_stream_observe(bmpc_handle *h, int B, double *robot, const double *sstate, const double *sensor, double *sensor_state, int *sensor_info, double *sensor_rec,
+                                   const double *sensor_noise, double *meas, int tick, const double *observer, double *observer_state, int *observer_info,
+                                   double *observer_rec, double *sample, void *hip_stream) {
+    if (!h || B < 1 || !robot || !sstate || !sensor || !sensor_state || !observer || !observer_state || h->N > bmpcs::STREAM_NMAX) return BMPC_ERR_ARG;
+    HIPCHK(bmpc_stream_observe_launch(h->N, B, h->h, robot, sstate, sensor, sensor_state, sensor_info, sensor_rec, sensor_noise, meas, tick, observer, observer_state,
+                                      observer_info, observer_rec, sample, (hipStream_t)hip_stream));
     return BMPC_OK;
 }
 

@@ -3,6 +3,8 @@
 // include guard.  The expanding function declares the constants EV, AU, LG, QU, TU, PL and ZLDS, RESTO; the lines under `#if BMPCR_SE` -- the sample ahead
 // of the pack, the way back to the truth behind the post, the meas_hist rows -- exist in the sensor kernels only, and `!BMPCR_SE ||` ahead of a test of the
 // plant table is a constant true in the others: a PL kernel without a sensor is launched with a plant table only, an SE kernel asks at run time.
+// The lines under `#if BMPCR_OB` (with BMPCR_SE 1 only: bmpc_stream_rollout_observer_kernel, a fifth argument of type OArgs) -- the observer row's validation,
+// stream_observe in the place of stream_sense, the sample_hist rows -- exist in the observer kernels only; the others expand the body with BMPCR_OB 0.
 // Rationale of every section: the file comment of bmpc_rollout_kernel.inl.
     static_assert(BMPC_NW == 1 || ZLDS, "a team keeps the iterate in LDS");
     BMPCK_LDS double lds[BMPC_NAMESPACE::L_SIZE];
@@ -70,6 +72,17 @@
                 if (se_->sensor_rec) bmpcs::stream_sensor_init(se_->sensor_rec + (long long)b_ * bmpcse::REC_LEN);
             }
             bad |= sbad;
+#if BMPCR_OB
+            // (an OB kernel is launched with an observer table only -- bmpc_rollout_observer_ok and the entry.  Every wave reads the row itself; lane 0 of wave 0
+            // stores the mask and starts the record.  An invalid row: as an invalid sensor row, both states untouched)
+            BMPCR_OBSERVER_FROM(ob_, se_);
+            const int obad = BMPCK_UNIFORM(bmpc_observer_check(ob_->observer + (long long)b_ * bmpcob::LEN, nullptr));
+            if (w0 && BMPCK_LANE == 0) {
+                if (ob_->observer_info) ob_->observer_info[b_] = obad;
+                if (ob_->observer_rec) bmpcs::stream_observer_init(ob_->observer_rec + (long long)b_ * bmpcob::REC_LEN);
+            }
+            bad |= obad;
+#endif
         }
 #endif
         if (!TU || !bad) for (; t < r.ticks; t++) {
@@ -86,9 +99,20 @@
                 int b_ = b, t_ = t;
                 BMPCR_SENSOR_IDX(b_); BMPCR_SENSOR_IDX(t_);
                 const long long row_ = (long long)t_ * a.B + b_;
+#if !BMPCR_OB
                 if (w0) bmpcs::stream_sense(se_->sensor + (long long)b_ * bmpcse::LEN, se_->sensor_noise ? se_->sensor_noise + row_ * bmpcs::DIST_LEN : nullptr,
                                             se_->sensor_state + (long long)b_ * bmpcse::ST_LEN, rb, se_->sensor_rec ? se_->sensor_rec + (long long)b_ * bmpcse::REC_LEN : nullptr,
                                             t_, BMPCK_LANE, BMPCK_NL);
+#else
+                // (the sample followed by the estimate in the same lane-0 section: what the record holds from here to the way back is the observer's estimate,
+                // meas_hist the record of it; sample_hist: the raw sample, stored by the lane that made it)
+                BMPCR_OBSERVER_FROM(ob_, se_);
+                if (w0) bmpcs::stream_observe(a.h, se_->sensor + (long long)b_ * bmpcse::LEN, se_->sensor_noise ? se_->sensor_noise + row_ * bmpcs::DIST_LEN : nullptr,
+                                              se_->sensor_state + (long long)b_ * bmpcse::ST_LEN, ob_->observer + (long long)b_ * bmpcob::LEN,
+                                              ob_->observer_state + (long long)b_ * bmpcob::ST_LEN, rb, se_->sensor_rec ? se_->sensor_rec + (long long)b_ * bmpcse::REC_LEN : nullptr,
+                                              ob_->observer_rec ? ob_->observer_rec + (long long)b_ * bmpcob::REC_LEN : nullptr,
+                                              ob_->sample_hist ? ob_->sample_hist + row_ * bmpcs::DIST_LEN : nullptr, t_, BMPCK_LANE, BMPCK_NL);
+#endif
                 BMPCK_SYNC();      // the pack and the row read the record lane 0 has just stored
                 if (se_->meas_hist && w0) { double *mr = se_->meas_hist + row_ * bmpcs::RB_LEN; for (int i = BMPCK_LANE; i < bmpcs::RB_LEN; i += BMPCK_NL) mr[i] = rb[i]; }
             }
@@ -261,6 +285,17 @@
                     for (int i = BMPCK_LANE; i < bmpcs::RB_LEN; i += BMPCK_NL) mr[i] = nan_;
                 }
             }
+#if BMPCR_OB
+            BMPCR_OBSERVER_FROM(ob_, se_);
+            if (ob_->sample_hist && w0) {
+                // (ONE loop over the words from row t of the stream to its last row, those of the other streams' rows skipped: as a second nest of two loops
+                // here the team kernel with the restoration phase moved a scalar-spill register at the join behind the tick loop, the signature the build's
+                // ISA lint refuses.  The last word touched is word DIST_LEN - 1 of row ticks - 1; a stream that ran every tick has n_ <= 0)
+                double *sr = ob_->sample_hist + ((long long)t * a.B + b_) * bmpcs::DIST_LEN;
+                const long long n_ = (long long)(r.ticks - t - 1) * a.B * bmpcs::DIST_LEN + bmpcs::DIST_LEN;
+                for (long long i = BMPCK_LANE; i < n_; i += BMPCK_NL) if (i % ((long long)a.B * bmpcs::DIST_LEN) < bmpcs::DIST_LEN) sr[i] = nan_;
+            }
+#endif
         }
 #endif
         if (BMPCK_LANE == 0) {

@@ -87,17 +87,30 @@
 // the work.  The row is validated as a plant row is (bmpc_sensor_check; sensor_info, state untouched).  Row, state, record and noise live in global
 // memory behind opaque stream and tick indices, and the members of n are read through the kernel-argument segment (BMPCR_SENSOR_ARGS): nothing of the
 // sensor is carried in a register across the solve.  The SE kernels compile everything below them on and ask at run time whether there is a plant table.
-// The text of the stream and tick loops exists once, bmpc_rollout_body.inl; the kernels without a sensor expand it with BMPCR_SE 0 and hold no sensor line.
+// OBSERVERS (the kernels bmpc_stream_rollout_observer_kernel, OB; bmpc_stream_rollout_observer; bmpc_rollout_observer.hip, bmpc_team_rollout_observer.hip;
+// bmpc_stream_observer.inl): a table o.observer[b][bmpcob::LEN] of a state estimator per stream -- a correction gain on q, dq and ddq, one step of lead for a
+// sample that is one tick old, an innovation gate -- between the sensor's sample and the pack, which without it takes the noisy sample unfiltered.  The
+// estimate is made in the lane-0 section of the sample (stream_observe in the place of stream_sense: the tick gains no barrier) and installed where the
+// sample is installed; SAME of the sensor state is decided on the estimate, so the way back, the plant step, the rows and the events stay the lines they
+// are.  n.meas_hist[t][b] is then the estimate's record, o.sample_hist[t][b] the raw sample, n.sensor_rec the sample against the truth and o.observer_rec
+// the estimate against the truth.  The row is validated as a sensor row is (bmpc_observer_check; observer_info, both states untouched).  The observer does
+// not see a disturbance, a spliced re-plan or a post that exhausted the plan: the innovation pulls it back, the state is not reset.  Row, state and
+// record live in global memory behind opaque indices, the members of o are read through the kernel-argument segment (BMPCR_OBSERVER_FROM): nothing of
+// the observer is carried in a register across the solve.
+// The text of the stream and tick loops exists once, bmpc_rollout_body.inl; the kernels without a sensor expand it with BMPCR_SE 0 and hold no sensor line,
+// those without an observer with BMPCR_OB 0 and hold no observer line.
 // Written in the entry words of bmpc_gpu_common.h (BMPCK_*): g++ compiles the same text for the CPU tests (tests/emu/bmpc_emu_rollout.cpp:
-// one source and one entry for every variant without a sensor, tests/emu/bmpc_emu_rollout_sensor.cpp for the sensor's, each built once per BMPC_NW).  The thirteen units (bmpc_rollout.hip,
+// one source and one entry for every variant without a sensor, tests/emu/bmpc_emu_rollout_sensor.cpp for the sensor's, tests/emu/bmpc_emu_rollout_observer.cpp for the observer's, each built
+// once per BMPC_NW).  The fifteen units (bmpc_rollout_observer.hip, bmpc_team_rollout_observer.hip, bmpc_rollout.hip,
 // bmpc_rollout_events.hip, bmpc_rollout_audit.hip, bmpc_rollout_log.hip, bmpc_rollout_legs.hip, bmpc_rollout_tune.hip, bmpc_rollout_plant.hip, bmpc_rollout_sensor.hip,
 // bmpc_team_rollout.hip, bmpc_team_rollout_legs.hip, bmpc_team_rollout_tune.hip, bmpc_team_rollout_plant.hip, bmpc_team_rollout_sensor.hip) and those builds launch through bmpc_rollout_run
-// and bmpc_rollout_sensor_run at the end of this file, the one place that picks <ZLDS, RESTO>.
+// bmpc_rollout_sensor_run and bmpc_rollout_observer_run at the end of this file, the one place that picks <ZLDS, RESTO>.
 #pragma once
 
 #include "bmpc_stream_events.inl"
 #include "bmpc_stream_plant.inl"
 #include "bmpc_stream_sensor.inl"
+#include "bmpc_stream_observer.inl"
 #include "bmpc_stream_tube.inl"
 #include "bmpc_stream_log.inl"
 
@@ -159,6 +172,15 @@ enum { RH_ROBOT = 0, RH_PHI = RB_LEN, RH_ERRCNT, RH_ITERS, RH_STATUS, RH_KKT, RH
 #define BMPCR_SENSOR_ARGS(na_) const NArgs *na_ = &n
 #define BMPCR_SENSOR_IDX(i_)
 #endif
+// (OB) the members of the observer kernels' fifth argument o, read the same way: it lies behind n at its natural alignment, and no observer line names
+// `o`.  Every observer line sits in a block that has the sensor's pointer na_ (BMPCR_SENSOR_ARGS), and takes its own from it: one opaque pointer per block,
+// in the sensor lines' form -- scalar on one wave, vector on teams, for the reasons written there.
+#ifndef BMPC_EMU
+#define BMPCR_OARGS_AT ((BMPCR_NARGS_AT + sizeof(NArgs) + alignof(OArgs) - 1) / alignof(OArgs) * alignof(OArgs))
+#define BMPCR_OBSERVER_FROM(oa_, na_) const OArgs *oa_ = (const OArgs *)((const char *)(na_) + (BMPCR_OARGS_AT - BMPCR_NARGS_AT))
+#else
+#define BMPCR_OBSERVER_FROM(oa_, na_) const OArgs *oa_ = &o
+#endif
 // (the body of a tick in the kernel itself, as in bmpc_tick_kernel.inl: behind a function that takes `a` the argument loads lose their no-clobber
 // property -- bmpc_args.h, BMPC_PROBLEM)
 // (QT: the sixth argument counts what sits on top of the log -- 0 nothing, 1 the queue QU, 2 the queue and the table TU, 3 the queue, the table and the
@@ -168,7 +190,9 @@ template <bool ZLDS, bool RESTO, bool EV = false, bool AU = false, bool LG = fal
 BMPCK_KERNEL bmpc_stream_rollout_kernel(KArgs a, SArgs s, RArgs r) {
     constexpr bool QU = QT >= 1, TU = QT >= 2, PL = QT == 3;
 #define BMPCR_SE 0
+#define BMPCR_OB 0
 #include "bmpc_rollout_body.inl"
+#undef BMPCR_OB
 #undef BMPCR_SE
 }
 // (SE: the same lines with the sensor's on, everything below it compiled on and the record of the sensor as a fourth argument; a kernel of its own, so
@@ -177,7 +201,20 @@ template <bool ZLDS, bool RESTO>
 BMPCK_KERNEL bmpc_stream_rollout_sensor_kernel(KArgs a, SArgs s, RArgs r, NArgs n) {
     constexpr bool EV = true, AU = true, LG = true, QU = true, TU = true, PL = true;
 #define BMPCR_SE 1
+#define BMPCR_OB 0
 #include "bmpc_rollout_body.inl"
+#undef BMPCR_OB
+#undef BMPCR_SE
+}
+// (OB: the sensor kernel's lines with the observer's on and the record of the observer as a fifth argument; a kernel of its own, so that the two above
+// keep their arguments and their instantiations the code they had)
+template <bool ZLDS, bool RESTO>
+BMPCK_KERNEL bmpc_stream_rollout_observer_kernel(KArgs a, SArgs s, RArgs r, NArgs n, OArgs o) {
+    constexpr bool EV = true, AU = true, LG = true, QU = true, TU = true, PL = true;
+#define BMPCR_SE 1
+#define BMPCR_OB 1
+#include "bmpc_rollout_body.inl"
+#undef BMPCR_OB
 #undef BMPCR_SE
 }
 
@@ -207,5 +244,17 @@ static void bmpc_rollout_sensor_run(bool zlds, bool resto, const void *kargs, co
     else if constexpr (BMPC_NW == 1) {
         if (resto) BMPCK_LAUNCH((bmpc_stream_rollout_sensor_kernel<false, true>), grid, st, a, s, r, n);
         else BMPCK_LAUNCH((bmpc_stream_rollout_sensor_kernel<false, false>), grid, st, a, s, r, n);
+    }
+}
+
+// the same for the kernels with an observer table (OB)
+template <class STREAM>
+static void bmpc_rollout_observer_run(bool zlds, bool resto, const void *kargs, const SArgs &s, const RArgs &r, const NArgs &n, const OArgs &o, int grid, STREAM st) {
+    KArgs a; memcpy(&a, kargs, sizeof(a));
+    if (zlds && resto) BMPCK_LAUNCH((bmpc_stream_rollout_observer_kernel<true, true>), grid, st, a, s, r, n, o);
+    else if (zlds) BMPCK_LAUNCH((bmpc_stream_rollout_observer_kernel<true, false>), grid, st, a, s, r, n, o);
+    else if constexpr (BMPC_NW == 1) {
+        if (resto) BMPCK_LAUNCH((bmpc_stream_rollout_observer_kernel<false, true>), grid, st, a, s, r, n, o);
+        else BMPCK_LAUNCH((bmpc_stream_rollout_observer_kernel<false, false>), grid, st, a, s, r, n, o);
     }
 }

@@ -751,6 +751,133 @@ def unpack_sensor_rec(row):
                 rms_dq=float(np.sqrt(row[SENSOR_REC["SUMSQ_DQ"]] / (7 * n))) if n else None)
 
 
+# a state observer (bmpc_stream_rollout_observer, bmpc_stream_observe; BMPC_OBSERVER_* of include/boundmpc_hip.h): the slots of a stream's row -- the
+# predictor-corrector between the sensor's sample and what pack, solve and post of a tick read; NaN = the identity value --, of its state and of its record
+OBSERVER = dict(LQ=0, LDQ=1, LDDQ=2, LEAD=3, GATE=4, LEN=8)
+OBSERVER_STATE = dict(POST=0, JP=21, JL=28, HAS=35, LAGS=36, LEN=40)
+OBSERVER_REC = dict(SAMPLES=0, N_REJ=1, MAX_DQ=2, TICK_DQ=3, JOINT_DQ=4, MAX_DP=5, TICK_DP=6, SUMSQ_DQ=7, LEN=8)
+_OBSERVER_SLOTS = 5      # the slots that are looked at: LQ, LDQ, LDDQ, LEAD, GATE
+_OBSERVER_IDENTITY = (1.0, 1.0, 1.0, 0.0, np.inf)
+
+
+def observer_check(row):
+    """What the device answers for `row` [OBSERVER_LEN] in observer_info (csrc/bmpc_args.h bmpc_observer_check, restated): the bit mask of its invalid slots,
+    bit k = slot k.  A NaN slot is the identity and valid; the gains LQ, LDQ, LDDQ must lie in (0, 1], LEAD be 0 or 1, GATE be > 0 (+inf: no gate); the pad
+    words are never looked at."""
+    row = np.asarray(row, dtype=np.float64)
+    assert row.shape == (OBSERVER["LEN"],)
+    bad = 0
+    for k in range(_OBSERVER_SLOTS):
+        v = float(row[k])
+        if np.isnan(v):
+            continue
+        if k < OBSERVER["LEAD"]:
+            ok = 0.0 < v <= 1.0
+        elif k == OBSERVER["LEAD"]:
+            ok = v == 0.0 or v == 1.0
+        else:
+            ok = v > 0.0
+        if not ok:
+            bad |= 1 << k
+    return bad
+
+
+def observer_table(B, lq=None, ldq=None, lddq=None, lead=None, gate=None):
+    """The table of state observers, [B][OBSERVER_LEN] float64 for StreamBatch.rollout(observer=...) and observe: lq, ldq, lddq (the correction gains on q, dq
+    and ddq, in (0, 1]; 1: the estimate is the sample), lead (1: the sample is one tick old, the sensor's HOLD, and the corrected estimate is advanced one
+    chain step) and gate (the innovation gate on the joint positions, rad; +inf: none) a scalar or [B]; NaN (an argument not given, or an entry of an array)
+    is the identity.  Raises ValueError on what the device would refuse (observer_check)."""
+    B = int(B)
+    T = np.full((B, OBSERVER["LEN"]), np.nan)
+    for name, col, at in (("lq", lq, OBSERVER["LQ"]), ("ldq", ldq, OBSERVER["LDQ"]), ("lddq", lddq, OBSERVER["LDDQ"]), ("lead", lead, OBSERVER["LEAD"]), ("gate", gate, OBSERVER["GATE"])):
+        if col is None:
+            continue
+        col = np.asarray(col, dtype=np.float64)
+        if not (col.ndim == 0 or col.shape == (B,)):
+            raise ValueError(f"{name} must be a scalar or [{B}], got {list(col.shape)}")
+        T[:, at] = col
+    for b in range(B):
+        bad = observer_check(T[b])
+        if bad:
+            raise ValueError(f"observer row {b}: invalid slots {[k for k in range(_OBSERVER_SLOTS) if bad >> k & 1]}")
+    return T
+
+
+def _observer_step(x, up, u, h):
+    """the model's chain step (csrc/bmpc_stream.inl chain_step) of the 21 words q | dq | ddq from the jerk `up` to the jerk `u`, in its order of operations"""
+    q, dq, ddq = x[:7], x[7:14], x[14:21]
+    return np.concatenate((q + h * dq + h * h / 2 * ddq + h * h * h / 8 * up + h * h * h / 24 * u, dq + h * ddq + h * h / 3 * up + h * h / 6 * u, ddq + h / 2 * (up + u)))
+
+
+def observe_robot(robot_row, sensor_row, state_row, observer_row, ostate_row, h, noise_row=None):
+    """The device sample and estimate (stream_observe; bmpc_stream_observe) as numpy over `sense_robot`, THE SPECIFICATION of one observer step: robot_row is the
+    TRUE record ahead of a pack, sensor_row, state_row and noise_row the arguments of sense_robot, which makes the sample m (behind the sensor's HOLD);
+    observer_row [OBSERVER_LEN] and ostate_row [OBSERVER_STATE_LEN] the stream's observer row and state, h the handle's step.  With J the record's jerk and
+    step = the model's chain step per joint:
+      fresh (HAS == 0)   post = out = m;  POST = m, JP = JL = J, HAS = 1, LAGS = 0; no gate
+      LEAD == 0          prior = step(POST, JP, J);  post = prior + L (m - prior), the word m itself where L == 1; a sample with any |m_q - prior_q| not <= GATE
+                         (a NaN among them) is rejected: post = prior;  out = post;  POST = post, JP = JL = J, LAGS = 0
+      LEAD == 1          prior = step(POST, JP, JL) if LAGS else POST (the sample's own time);  post as above;  out = step(post, JL if LAGS else JP, J);
+                         POST = post, where LAGS was 1 JP = the old JL, then JL = J, LAGS = 1
+    SAME of the sensor state is decided on out against the truth over all 21 words; where it is 0 the record's q, dq, ddq become out and p_lie and v are
+    recomputed from them, where it is 1 the record is returned unchanged.  The observer is not told of a disturbance, a spliced re-plan or a post that exhausted
+    the plan: the innovation pulls it back, the state is never reset.
+    -> (robot row: what the pack reads, sensor state row, observer state row, m [21], out - truth [21], ||p_est - p|| in metres, m - truth [21],
+        ||p_m - p||, rejected) -- copies."""
+    from .robot_model import RobotModel
+    rb = np.array(robot_row, dtype=float)
+    o, ost = np.asarray(observer_row, dtype=float), np.array(ostate_row, dtype=float)
+    assert o.shape == (OBSERVER["LEN"],) and ost.shape == (OBSERVER_STATE["LEN"],) and observer_check(o) == 0
+    o = np.where(np.isnan(o[:_OBSERVER_SLOTS]), _OBSERVER_IDENTITY, o[:_OBSERVER_SLOTS])
+    rb_s, st, d_s, dp_s = sense_robot(robot_row, sensor_row, state_row, noise_row)
+    truth, J = rb[:DIST_LEN].copy(), rb[RB["JERK"]:RB["JERK"] + 7].copy()
+    m = rb_s[:DIST_LEN].copy()      # (where the sample equals the truth sense_robot returns the record unchanged: its words ARE the sample)
+    P, JP, JL, HAS, LAGS = (OBSERVER_STATE[k] for k in ("POST", "JP", "JL", "HAS", "LAGS"))
+    rejected = False
+    if ost[HAS] != 1.0:
+        post = out = m.copy()
+        ost[JP:JP + 7], ost[JL:JL + 7], ost[HAS], ost[LAGS] = J, J, 1.0, 0.0
+    else:
+        lead, lags = o[OBSERVER["LEAD"]] == 1.0, ost[LAGS] == 1.0
+        jp, jl = ost[JP:JP + 7].copy(), ost[JL:JL + 7].copy()
+        prior = ost[P:P + DIST_LEN].copy() if lead and not lags else _observer_step(ost[P:P + DIST_LEN], jp, jl if lead else J, h)
+        rejected = not bool((np.abs(m[:7] - prior[:7]) <= o[OBSERVER["GATE"]]).all())
+        L = np.repeat(o[:3], 7)
+        with np.errstate(invalid="ignore"):
+            post = prior.copy() if rejected else np.where(L == 1.0, m, prior + L * (m - prior))
+        if not lead:
+            out = post.copy()
+            ost[JP:JP + 7], ost[JL:JL + 7], ost[LAGS] = J, J, 0.0
+        else:
+            out = _observer_step(post, jl if lags else jp, J, h)
+            if lags:
+                ost[JP:JP + 7] = jl
+            ost[JL:JL + 7], ost[LAGS] = J, 1.0
+    ost[P:P + DIST_LEN] = post
+    same = bool((out == truth).all())
+    st[SENSOR_STATE["SAME"]] = 1.0 if same else 0.0
+    dp = 0.0
+    if not same:
+        p, Jac, _ = RobotModel().forward_kinematics(out[:7], out[7:14])
+        dp = float(np.linalg.norm(p[:3] - rb[RB["P"]:RB["P"] + 3]))
+        rb[:DIST_LEN] = out
+        rb[RB["P"]:RB["P"] + 6], rb[RB["V"]:RB["V"] + 6] = p, Jac @ out[7:14]
+    return rb, st, ost, m, out - truth, dp, d_s, dp_s, rejected
+
+
+def unpack_observer_rec(row):
+    """An observer record (rollout()["observer_rec"][b], numpy) -> dict: samples (the estimates made), n_rej (the samples the gate rejected), max_dq (the largest
+    |q_est - q|; None without an estimate), tick_dq and joint_dq (its first tick and joint), max_dp (the largest ||p_est - p||, metres) and tick_dp, sumsq_dq,
+    rms_dq (over samples x 7)."""
+    row = np.asarray(row, dtype=np.float64)
+    assert row.shape == (OBSERVER_REC["LEN"],)
+    n = int(row[OBSERVER_REC["SAMPLES"]])
+    return dict(samples=n, n_rej=int(row[OBSERVER_REC["N_REJ"]]), max_dq=float(row[OBSERVER_REC["MAX_DQ"]]) if n else None, tick_dq=int(row[OBSERVER_REC["TICK_DQ"]]) if n else None,
+                joint_dq=int(row[OBSERVER_REC["JOINT_DQ"]]) if n else None, max_dp=float(row[OBSERVER_REC["MAX_DP"]]) if n else None,
+                tick_dp=int(row[OBSERVER_REC["TICK_DP"]]) if n else None, sumsq_dq=float(row[OBSERVER_REC["SUMSQ_DQ"]]),
+                rms_dq=float(np.sqrt(row[OBSERVER_REC["SUMSQ_DQ"]] / (7 * n))) if n else None)
+
+
 def rollout_len():
     """[robot record 43 | phi | error count | iters | status | kkt | n_valid | using_previous | success | g_viol]"""
     return ROLL["LEN"]
@@ -908,6 +1035,8 @@ class StreamBatch:
         self.plant_info = self.plant_rec = None      # plant_step(): masks [B] and accumulated records [B][PLANT_REC_LEN], allocated on first use
         self.sensor_state_ = None      # sense(), rollout(sensor=...): the sensors' state [B][SENSOR_STATE_LEN], zeros (fresh) on first use; read it with sensor_state()
         self.sensor_info = self.sensor_rec = self.meas = None      # sense(): masks [B], accumulated records [B][SENSOR_REC_LEN] and the record the pack reads, allocated on first use
+        self.observer_state_ = None      # observe(), rollout(observer=...): the observers' state [B][OBSERVER_STATE_LEN], zeros (fresh) on first use; read it with observer_state()
+        self.observer_info = self.observer_rec = self.sample = None      # observe(): masks [B], accumulated records [B][OBSERVER_REC_LEN] and the raw samples, allocated on first use
         solver._children.add(self)
 
     def update(self, b, *args, **kw):
@@ -1077,6 +1206,60 @@ class StreamBatch:
                                                         self._stream(stream)), "bmpc_stream_unsense")
         self._unsense_input = sensor
 
+    def observer_state(self, stream=None):
+        """the observers' state on the device, [B][OBSERVER_STATE_LEN] (slots OBSERVER_STATE): the last posterior and the jerks that advance it; zeros (fresh:
+        the first sample is taken as it is) on first use, then carried from launch to launch, so rollouts chain"""
+        import torch
+        if self.observer_state_ is None:
+            lib = self.solver._lib
+            assert (lib.bmpc_stream_observer_len(), lib.bmpc_stream_observer_state_len(), lib.bmpc_stream_observer_rec_len()) == (OBSERVER["LEN"], OBSERVER_STATE["LEN"], OBSERVER_REC["LEN"])
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(self.path.device)):
+                self.observer_state_ = torch.zeros((self.B, OBSERVER_STATE["LEN"]), dtype=torch.float64, device=self.path.device)
+        return self.observer_state_
+
+    def observer_reset(self, stream=None):
+        """Start the observers afresh: a state of zeros (no posterior) and an empty `self.observer_rec`.  A per-tick loop that is to leave what
+        rollout(observer=) leaves calls it, and sensor_reset(), where that launch would start.  Nothing else resets the state: not a disturbance, not a
+        re-plan, not a lost plan."""
+        self.observer_state_ = self.observer_rec = self.observer_info = self.sample = None
+        return self.observer_state(stream)
+
+    def observe(self, sensor, observer, noise=None, tick=0, stream=None):
+        """The sensors and the observers between the plants and the controller, the sample of one tick and the estimate made from it (bmpc_stream_observe): sense()
+        with observer [B][OBSERVER_LEN] (`observer_table(B, ...)`, an array or a device tensor, taken as it is), row b the state estimator of stream b, between
+        the sample and the robot records.  Call it IN THE PLACE of sense(), ahead of tick() (or pack()), and unsense() with the same sensor table behind the
+        tick: in between the robot records hold the estimates (`observe_robot` is the mirror and the specification), the truth waits in
+        `self.sensor_state()`.  A stream without a plan takes no sample and makes no estimate; a stream with an invalid sensor or observer row is left alone,
+        its masks in `self.sensor_info` and the result.  Accumulates `self.sensor_rec` (the samples against the truth) and `self.observer_rec`
+        [B][OBSERVER_REC_LEN] (the estimates against the truth; slots OBSERVER_REC), initialised on first use, and leaves in `self.meas` [B][RB_LEN] the records
+        the pack will read and in `self.sample` [B][DIST_LEN] the raw samples.  One launch, asynchronous on `stream`, capturable.  Returns the `observer_info`
+        tensor [B] (int32), valid once `stream` has run the launch."""
+        import torch
+        sensor = self._dev64(sensor, (self.B, SENSOR["LEN"]), "sensor", stream)
+        observer = self._dev64(observer, (self.B, OBSERVER["LEN"]), "observer", stream)
+        if noise is not None:
+            noise = self._dev64(noise, (self.B, DIST_LEN), "noise", stream)
+        state, ostate = self.sensor_state(stream), self.observer_state(stream)
+        dev = self.path.device
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream(dev)):
+            if self.sensor_rec is None:
+                self.sensor_info = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+                rec0 = np.zeros(SENSOR_REC["LEN"])
+                rec0[[SENSOR_REC["MAX_DQ"], SENSOR_REC["MAX_DP"]]], rec0[[SENSOR_REC["TICK_DQ"], SENSOR_REC["JOINT_DQ"], SENSOR_REC["TICK_DP"]]] = -np.inf, -1.0
+                self.sensor_rec = torch.as_tensor(rec0).to(dev).repeat(self.B, 1).contiguous()
+                self.meas = torch.full((self.B, RB["LEN"]), float("nan"), dtype=torch.float64, device=dev)
+            if self.observer_rec is None:
+                self.observer_info = torch.zeros((self.B,), dtype=torch.int32, device=dev)
+                rec0 = np.zeros(OBSERVER_REC["LEN"])
+                rec0[[OBSERVER_REC["MAX_DQ"], OBSERVER_REC["MAX_DP"]]], rec0[[OBSERVER_REC["TICK_DQ"], OBSERVER_REC["JOINT_DQ"], OBSERVER_REC["TICK_DP"]]] = -np.inf, -1.0
+                self.observer_rec = torch.as_tensor(rec0).to(dev).repeat(self.B, 1).contiguous()
+                self.sample = torch.full((self.B, DIST_LEN), float("nan"), dtype=torch.float64, device=dev)
+        _lib.check(self.solver._lib.bmpc_stream_observe(self.solver._h, self.B, _ptr(self.robot), _ptr(self.state), _ptr(sensor), _ptr(state), _ptr(self.sensor_info),
+                                                        _ptr(self.sensor_rec), None if noise is None else _ptr(noise), _ptr(self.meas), int(tick), _ptr(observer), _ptr(ostate),
+                                                        _ptr(self.observer_info), _ptr(self.observer_rec), _ptr(self.sample), self._stream(stream)), "bmpc_stream_observe")
+        self._observe_inputs = (sensor, observer, noise)      # the launch is asynchronous: its inputs live until the next one replaces them
+        return self.observer_info
+
     def _dev64(self, a, shape, name, stream, dtype=None):
         """`a` as a contiguous device tensor of `shape` (float64 unless dtype), copied on `stream` when it is not one already"""
         import torch
@@ -1200,7 +1383,8 @@ class StreamBatch:
     def rollout(self, ticks, max_iter=0, warm_dual=False, accept_capped=False, goal_tol=0.0, want_traj=False, stream=None,
                 replan=None, replan_tick=None, splice=True, poor_bounds=False, set_goal=True, disturb=None, audit=False, audit_tol=1e-6, want_tube=False,
                 want_log=False, log_stages=1, track=False, waves=None, legs=None, leg_tick=None, leg_on=None, leg_tol=None, tune=None, want_tune_used=False,
-                plant=None, want_plant_rec=False, sensor=None, sensor_noise=None, want_meas=False, want_sensor_rec=False):
+                plant=None, want_plant_rec=False, sensor=None, sensor_noise=None, want_meas=False, want_sensor_rec=False, observer=None, want_sample=False,
+                want_observer_rec=False):
         """`ticks` closed-loop ticks (plant simulation on) of every stream in ONE launch (bmpc_stream_rollout): each stream runs at its own pace, so
         the launch lasts as long as the slowest stream's SUM of solves, where a loop of tick() / tick_graph() pays the slowest stream of every tick.
         For closed loops run in bulk -- whole-loop throughput, any B; where a host reads or acts between ticks (a real plant, a time
@@ -1285,7 +1469,23 @@ class StreamBatch:
           sensor_info [B] int32            0: the row was valid and the stream ran; else the bit mask of its invalid slots -- READ IT
           sensor_rec [B][SENSOR_REC_LEN]   want_sensor_rec: what the samples differed from the truth by (slots SENSOR_REC, unpack_sensor_rec); its max_dp
                                            bounds what the audit's position excess can miss.
-        The sensors' state is `self.sensor_state()` [B][SENSOR_STATE_LEN], zeros on first use and carried from launch to launch, so rollouts chain."""
+        The sensors' state is `self.sensor_state()` [B][SENSOR_STATE_LEN], zeros on first use and carried from launch to launch, so rollouts chain.
+        OBSERVERS (bmpc_stream_rollout_observer; with `sensor` only; without `observer` nothing changes): a state estimator per stream between the sensor's
+        sample and what the pack, the solve and the post of every tick read, which otherwise IS the noisy sample -- "encoder resolution x lag x margin x
+        filter" is one launch.
+          observer [B][OBSERVER_LEN]       `observer_table(B, lq=, ldq=, lddq=, lead=, gate=)`, an array or a device tensor (taken as it is): row b, slots
+                                           OBSERVER; a NaN slot is the identity.  A predictor-corrector on the model's own jerk-integrator chain
+                                           (`observe_robot` is the mirror and the specification): gains on q, dq, ddq, one step of lead for a sample that is
+                                           one tick old (the sensor's HOLD), an innovation gate.  The estimate is installed where the sample is.
+          meas_hist                        keeps its meaning, the record the pack of tick t read: it is now the ESTIMATE's record
+          sensor_rec                       keeps its meaning: the samples against the truth
+          sample_hist [ticks][B][DIST_LEN]   want_sample: the raw sample of tick t; NaN for a tick the stream did not run
+          observer_info [B] int32          0: the row was valid and the stream ran; else the bit mask of its invalid slots -- READ IT
+          observer_rec [B][OBSERVER_REC_LEN]   want_observer_rec: what the estimates differed from the truth by and how many samples the gate rejected
+                                           (slots OBSERVER_REC, unpack_observer_rec)
+        The observers' state is `self.observer_state()` [B][OBSERVER_STATE_LEN], zeros on first use and carried from launch to launch, so rollouts chain.  The
+        observer is not told of a disturbance, a spliced re-plan or a post that exhausted the plan: its prediction is then off, the innovation pulls it back
+        as a real filter's would, and the state is not reset."""
         import torch
         former = self.solver.rollout_waves
         if waves is not None:
@@ -1309,6 +1509,10 @@ class StreamBatch:
                 raise ValueError("sensor_noise, want_meas and want_sensor_rec go with sensor")
             if sensor is not None and scheduled:
                 raise ValueError("sensor goes with legs, the queue of re-plan records: it does not go with replan / replan_tick")
+            if observer is None and (want_sample or want_observer_rec):
+                raise ValueError("want_sample and want_observer_rec go with observer")
+            if observer is not None and sensor is None:
+                raise ValueError("observer goes with sensor: there is no sample to filter without one")
             if legs is not None and scheduled:
                 raise ValueError("legs is the queue of re-plan records: it does not go with replan / replan_tick")
             if legs is None and (leg_tick is not None or leg_on is not None or leg_tol is not None):
@@ -1320,12 +1524,14 @@ class StreamBatch:
             entry = ROLLOUT_ENTRIES.index(name)
             if sensor is not None:      # (the sensor's entry, chosen here: it takes every group of the plants' entry and the sensor's behind them)
                 name, entry = "bmpc_stream_rollout_sensor", len(ROLLOUT_ENTRIES)
+            if observer is not None:      # (the observer's entry: the groups of the sensor's entry and the observer's behind them)
+                name, entry = "bmpc_stream_rollout_observer", len(ROLLOUT_ENTRIES) + 1
             flags = self._update_flags(set_goal, splice, poor_bounds) if entry else 0      # (the plain rollout has no events: their words are not looked at)
             lib, B, n, dev = self.solver._lib, self.B, max(int(ticks), 0), self.path.device
             assert lib.bmpc_stream_rollout_len() == ROLL["LEN"] and (not track or lib.bmpc_stream_track_len() == TRACK["LEN"]) and (tune is None or lib.bmpc_stream_tune_len() == TUNE["LEN"])
             assert not want_log or lib.bmpc_stream_rollout_log_len(self.solver._h, int(log_stages)) == rollout_log_len(log_stages)
             # 2. every input on the device, once
-            record = state = sstate = None
+            record = state = sstate = ostate = None
             K = 0
             if replan is not None:
                 record = self._replan_buffer(replan, stream)
@@ -1348,15 +1554,19 @@ class StreamBatch:
                 sensor, sstate = self._dev64(sensor, (B, SENSOR["LEN"]), "sensor", stream), self.sensor_state(stream)
                 if sensor_noise is not None:
                     sensor_noise = self._dev64(sensor_noise, (n, B, DIST_LEN), "sensor_noise", stream)
+            if observer is not None:
+                assert lib.bmpc_stream_observer_len() == OBSERVER["LEN"]
+                observer, ostate = self._dev64(observer, (B, OBSERVER["LEN"]), "observer", stream), self.observer_state(stream)
             # 3. every output, once
             out = {"hist": torch.empty((n, B, ROLL["LEN"]), dtype=torch.float64, device=dev), "ticks_run": torch.zeros((B,), dtype=torch.int32, device=dev)}
             for key, want, shape in (("traj_hist", want_traj, (n, B, self.tr_len)), ("audit", audit, (B, AUDIT["LEN"])), ("tube_hist", want_tube, (n, B, TUBE["LEN"])),
                                      ("log_hist", want_log, (n, B, rollout_log_len(log_stages) if want_log else 0)), ("track", track, (B, TRACK["LEN"])),
                                      ("tune_used", want_tune_used, (B, TUNE["LEN"])), ("plant_rec", want_plant_rec, (B, PLANT_REC["LEN"])),
-                                     ("meas_hist", want_meas, (n, B, RB["LEN"])), ("sensor_rec", want_sensor_rec, (B, SENSOR_REC["LEN"]))):
+                                     ("meas_hist", want_meas, (n, B, RB["LEN"])), ("sensor_rec", want_sensor_rec, (B, SENSOR_REC["LEN"])),
+                                     ("sample_hist", want_sample, (n, B, DIST_LEN)), ("observer_rec", want_observer_rec, (B, OBSERVER_REC["LEN"]))):
                 if want:
                     out[key] = torch.empty(shape, dtype=torch.float64, device=dev)
-            for key, want, shape, fill in (("tune_info", tune is not None, (B,), -1), ("plant_info", plant is not None, (B,), -1), ("sensor_info", sensor is not None, (B,), -1), ("legs_done", K, (B,), 0), ("leg_fired", K, (B, K), -1),
+            for key, want, shape, fill in (("tune_info", tune is not None, (B,), -1), ("plant_info", plant is not None, (B,), -1), ("sensor_info", sensor is not None, (B,), -1), ("observer_info", observer is not None, (B,), -1), ("legs_done", K, (B,), 0), ("leg_fired", K, (B, K), -1),
                                            ("leg_why", K, (B, K), 0), ("replan_info", K or 1 <= entry <= 3, (B, K) if K else (B,), -1)):
                 if want:
                     out[key] = torch.full(shape, fill, dtype=torch.int32, device=dev)
@@ -1371,10 +1581,11 @@ class StreamBatch:
                       (K, at(leg_tick), at(leg_on), at(leg_tol), o("legs_done"), o("leg_fired"), o("leg_why")),                 # queue
                       (at(tune), o("tune_info"), o("tune_used")),                                                              # table
                       (at(plant), at(state), o("plant_info"), o("plant_rec")),                                                 # plant
-                      (at(sensor), at(sstate), o("sensor_info"), o("sensor_rec"), at(sensor_noise), o("meas_hist")))             # sensor
+                      (at(sensor), at(sstate), o("sensor_info"), o("sensor_rec"), at(sensor_noise), o("meas_hist")),             # sensor
+                      (at(observer), at(ostate), o("observer_info"), o("observer_rec"), o("sample_hist")))                        # observer
             _lib.check(getattr(lib, name)(*prefix, *(a for group in groups[:entry] for a in group), self._stream(stream)), name)
             if entry:
-                self._event_inputs = (replan_tick, leg_tick, leg_on, leg_tol, disturb, tune, plant, sensor, sensor_noise)      # the launch is asynchronous: its inputs live until the next one replaces them
+                self._event_inputs = (replan_tick, leg_tick, leg_on, leg_tol, disturb, tune, plant, sensor, sensor_noise, observer)      # the launch is asynchronous: its inputs live until the next one replaces them
             return out
         finally:
             if waves is not None:

@@ -693,6 +693,83 @@ int bmpc_stream_sense(bmpc_handle *h, int B, double *robot, const double *sstate
                       double *meas /* [B][robot record] or NULL */, int tick, void *hip_stream);
 int bmpc_stream_unsense(bmpc_handle *h, int B, double *robot, const double *sstate, const double *sensor /* [B][BMPC_SENSOR_LEN] */,
                         const double *sensor_state /* [B][BMPC_SENSOR_STATE_LEN] */, void *hip_stream);
+/* Rollout with a STATE OBSERVER: bmpc_stream_rollout_sensor (its arguments in their order up to and including meas_hist, their meaning, tests and contract)
+ * with a TABLE of state estimators per stream.  The sensor hands its sample straight to the pack: offsets, quantisation and noise on q, dq and ddq, and under
+ * BMPC_SENSOR_HOLD a sample that is one tick old.  Here an observer stands between the sample and what the pack, the solve and the post of a tick read: a
+ * predictor-corrector on the model's own jerk-integrator chain.
+ *   observer       [B][BMPC_OBSERVER_LEN] or NULL, DEVICE: row b, slots BMPC_OBSERVER_*; the three words behind BMPC_OBSERVER_GATE are pad and never looked at
+ *                    LQ, LDQ, LDDQ    correction gain on q, dq, ddq                                          identity 1       valid when 0 < v <= 1
+ *                    LEAD             1: the sample is one tick old (the sensor's HOLD): the corrected       identity 0       valid when 0 or 1
+ *                                     estimate is advanced one chain step before it is handed out
+ *                    GATE             innovation gate, rad: a sample with any |m_q,j - prior_q,j| not        identity +inf    valid when > 0 (+inf: none)
+ *                                     <= GATE is rejected and the posterior is the prior (NaN is rejected)
+ *                  a NaN slot takes its identity value
+ *   observer_state [B][BMPC_OBSERVER_STATE_LEN], required with observer, IN AND OUT so that rollouts chain; all zeros = fresh: POST[21] the last posterior
+ *                  (q, dq, ddq), JP[7] the record's jerk at the posterior's time, JL[7] the record's jerk read at the last call, HAS 1 once there is a
+ *                  posterior, LAGS 1 where POST is one tick behind the last call, three pad words
+ *   observer_info  [B] or NULL: 0 = row b was valid and the stream ran; else the bit mask of its invalid slots (bit k = slot k)
+ *   observer_rec   [B][BMPC_OBSERVER_REC_LEN] or NULL, initialised by the call: SAMPLES the estimates made, N_REJ the samples the gate rejected, MAX_DQ the
+ *                  largest |q_est - q| with TICK_DQ and JOINT_DQ its first tick and joint, MAX_DP the largest ||p_est - p|| (metres, position part of p_lie)
+ *                  with TICK_DP its first tick, SUMSQ_DQ the sum of (q_est - q)^2 in tick order, joints 0..6 inside a tick; the conventions of sensor_rec
+ *   sample_hist    [ticks][B][21] or NULL: the raw sample m (q | dq | ddq) the sensor handed the observer at tick t; NaN rows for the ticks not run
+ * The estimate of tick t, right behind the sample and ahead of the pack, with m the sample (behind the sensor's HOLD), J the jerk the robot record carries at
+ * this tick (the sensor keeps it; behind a plant step it is the jerk the drive delivered) and step(x, up, u) the model's chain step per joint from the jerk
+ * up to the jerk u with the handle's h:
+ *   fresh (HAS == 0)   post = out = m;  POST = m, JP = JL = J, HAS = 1, LAGS = 0; no gate is applied
+ *   LEAD == 0          prior = step(POST, JP, J);  post = prior + L (m - prior) per word with the gain of its derivative, the word m itself where L == 1;
+ *                      a rejected sample: post = prior;  out = post;  POST = post, JP = JL = J, LAGS = 0
+ *   LEAD == 1          prior = LAGS ? step(POST, JP, JL) : POST (the sample's own time);  post as above;  out = step(post, LAGS ? JL : JP, J);
+ *                      POST = post, where LAGS was 1 JP = the old JL, then JL = J, LAGS = 1
+ * out replaces the sample where bmpc_stream_rollout_sensor installs the sample: SAME of the sensor state is decided on out against the truth over all 21
+ * words; where it is 0 the record's q, dq, ddq become out and p_lie and v are recomputed from them, where it is 1 the record keeps every bit.  The way back
+ * to the truth, the plant step, the rows and the events are that entry's.  meas_hist keeps its meaning, the record the pack of tick t read: it is now the
+ * ESTIMATE's record.  sensor_rec keeps its meaning, the sample against the truth; observer_rec is the estimate against the truth.
+ * KNOWN BLIND SPOT.  The observer is not told of a disturbance, a spliced re-plan or a post that exhausted the plan (the plant did not step): its prediction
+ * is then off by what happened and the innovation pulls it back over the next samples, as a real filter's would.  The state is not reset.
+ * An invalid row gets the treatment of an invalid sensor row: no tick, NaN history rows, its mask in observer_info[b], sensor_state and observer_state
+ * untouched.  With observer == NULL the call IS bmpc_stream_rollout_sensor, and no observer argument is looked at.  With a table of NaN or of identity
+ * values every array that entry names holds what it leaves, bit for bit.  With goal_tol = 0 every array, the states and the records hold what this loop
+ * leaves, bit for bit:
+ *   for t in 0..ticks-1: bmpc_stream_observe(tick t, noise rows of tick t); bmpc_stream_tick on one wave per stream; bmpc_stream_unsense;
+ *                        bmpc_stream_plant(tick t); bmpc_stream_log; bmpc_stream_disturb(rows of tick t); bmpc_stream_update of the head records due
+ * bmpc_stream_observe is the sample and the estimate on their own, one launch over the batch, for per-tick loops in the place of bmpc_stream_sense (its
+ * arguments with their meaning, then the observer's): for an invalid sensor or observer row it writes the masks and touches nothing; a stream whose sstate
+ * error count is >= N takes no sample and makes no estimate, SAME = 1 is written; observer_rec (or NULL) is ACCUMULATED, not initialised; sample (or NULL)
+ * [B][21] is the raw sample.  It uses no workspace of the handle and may sit inside a capture of the caller's stream.
+ * BMPC_ERR_ARG, nothing launched: what bmpc_stream_rollout_sensor refuses, observer without sensor, and observer without observer_state; the step: what
+ * bmpc_stream_sense refuses, and no observer or observer_state. */
+enum { BMPC_OBSERVER_LQ = 0, BMPC_OBSERVER_LDQ = 1, BMPC_OBSERVER_LDDQ = 2, BMPC_OBSERVER_LEAD = 3, BMPC_OBSERVER_GATE = 4, BMPC_OBSERVER_LEN = 8 };      /* three pad words */
+enum { BMPC_OBSERVER_STATE_POST = 0, BMPC_OBSERVER_STATE_JP = 21, BMPC_OBSERVER_STATE_JL = 28, BMPC_OBSERVER_STATE_HAS = 35, BMPC_OBSERVER_STATE_LAGS = 36,
+       BMPC_OBSERVER_STATE_LEN = 40 };                                                                                                                     /* three pad words */
+enum { BMPC_OBSERVER_REC_SAMPLES = 0, BMPC_OBSERVER_REC_N_REJ, BMPC_OBSERVER_REC_MAX_DQ, BMPC_OBSERVER_REC_TICK_DQ, BMPC_OBSERVER_REC_JOINT_DQ, BMPC_OBSERVER_REC_MAX_DP,
+       BMPC_OBSERVER_REC_TICK_DP, BMPC_OBSERVER_REC_SUMSQ_DQ, BMPC_OBSERVER_REC_LEN = 8 };
+int bmpc_stream_observer_len(void);
+int bmpc_stream_observer_state_len(void);
+int bmpc_stream_observer_rec_len(void);
+int bmpc_stream_rollout_observer(bmpc_handle *h, int B, int ticks, const double *path, int path_entries, double *sstate, double *robot, double *p, double *x0,
+                                 double *dual_state, int max_iter, double *x, double *g, int *iters, int *status, double *kkt, double *traj, int flags,
+                                 double goal_tol, double *hist, double *traj_hist, int *ticks_run, double *replan /* [B][legs][len] or NULL */,
+                                 int *replan_info /* [B][legs] or NULL */, int update_flags, const double *disturb /* [ticks][B][21] or NULL */,
+                                 double *tube_hist /* [ticks][B][16] or NULL */, double *audit /* [B][12] or NULL */, double audit_tol,
+                                 double *log_hist /* [ticks][B][88 log_stages + 4] or NULL */, int log_stages, double *track /* [B][12] or NULL */,
+                                 int legs, const int *leg_tick /* [B][legs] */, const int *leg_on /* [B][legs] */, const double *leg_tol /* [B][legs] or NULL */,
+                                 int *legs_done /* [B] */, int *leg_fired /* [B][legs] or NULL */, int *leg_why /* [B][legs] or NULL */,
+                                 const double *tune /* [B][BMPC_TUNE_LEN] or NULL */, int *tune_info /* [B] or NULL */,
+                                 double *tune_used /* [B][BMPC_TUNE_LEN] or NULL */, const double *plant /* [B][BMPC_PLANT_LEN] or NULL */,
+                                 double *plant_state /* [B][BMPC_PLANT_STATE_LEN] */, int *plant_info /* [B] or NULL */,
+                                 double *plant_rec /* [B][BMPC_PLANT_REC_LEN] or NULL */, const double *sensor /* [B][BMPC_SENSOR_LEN] or NULL */,
+                                 double *sensor_state /* [B][BMPC_SENSOR_STATE_LEN] */, int *sensor_info /* [B] or NULL */,
+                                 double *sensor_rec /* [B][BMPC_SENSOR_REC_LEN] or NULL */, const double *sensor_noise /* [ticks][B][21] or NULL */,
+                                 double *meas_hist /* [ticks][B][robot record] or NULL */, const double *observer /* [B][BMPC_OBSERVER_LEN] or NULL */,
+                                 double *observer_state /* [B][BMPC_OBSERVER_STATE_LEN] */, int *observer_info /* [B] or NULL */,
+                                 double *observer_rec /* [B][BMPC_OBSERVER_REC_LEN] or NULL */, double *sample_hist /* [ticks][B][21] or NULL */, void *hip_stream);
+int bmpc_stream_observe(bmpc_handle *h, int B, double *robot, const double *sstate, const double *sensor /* [B][BMPC_SENSOR_LEN] */,
+                        double *sensor_state /* [B][BMPC_SENSOR_STATE_LEN] */, int *sensor_info /* [B] or NULL */,
+                        double *sensor_rec /* [B][BMPC_SENSOR_REC_LEN] or NULL, accumulated, not initialised */, const double *sensor_noise /* [B][21] or NULL */,
+                        double *meas /* [B][robot record] or NULL */, int tick, const double *observer /* [B][BMPC_OBSERVER_LEN] */,
+                        double *observer_state /* [B][BMPC_OBSERVER_STATE_LEN] */, int *observer_info /* [B] or NULL */,
+                        double *observer_rec /* [B][BMPC_OBSERVER_REC_LEN] or NULL, accumulated, not initialised */, double *sample /* [B][21] or NULL */,
+                        void *hip_stream);
 
 /* HOST pointers; one staged copy each way on a stream of the handle, then a stream synchronisation (the single-problem solver(...) call) */
 int bmpc_solve_batch_host(bmpc_handle *h, int B, const double *p, const double *x0, double *x, double *g, double *lam_g, double *lam_x,
